@@ -2,8 +2,13 @@
 """bench.py -- slider train-steps/sec (BASELINE.json metric) on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config sdxl_1024_b2_r4|sd15_512_b4_r4|...]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline JSON line (`value`, `ms_per_step`, ...).
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (see dump_outputs); every input is seeded,
+so two builds run with the same arguments can be compared output for output.
 
 One "step" = one pass of the hot path over one batch of synthetic input: 3 frozen UNet
 forwards + 1 LoRA-adapted forward + backward + guidance loss + global-norm clip + AdamW (+ all-reduce of the flat
@@ -12,7 +17,10 @@ LoRA gradient when N > 1), all on the CFG-doubled UNet batch 2B exactly as the r
 supplied directly, resident in HBM before the timed region.  Weights are random-init of the real architecture
 (no checkpoints offline) -- "data": "synthetic".
 
-Extra objects on the JSON line:
+Extra objects on the JSON line with --full (each takes work of its own after the timed steps):
+  allreduce    -- (N > 1) the step's one collective timed on its own
+  preroll      -- the no-grad pre-roll the reference runs before every step, timed separately
+  kernel_classes -- per-kernel-class device time of one separately profiled step (HIP events around every launch)
   roofline     -- dominant kernel class (the MFMA GEMM kernels gemm_5ph_kernel / gemm_8ph_kernel / gemm_glds_kernel: Linear + implicit-GEMM conv launches), algorithmic
                   FLOPs / device time measured with HIP events on the launch stream in a separate profiled step
   cpu_baseline -- the CPU oracle (oracle/unet_ref.py, kind "port") timed on this box's host cores on a bounded sample
@@ -93,6 +101,26 @@ def init_synthetic_on_device(module, seed):
         else:
             w = 0.02 * torch.randn(p.shape, generator=g, device="cuda")
         p.copy_(w.to(p.dtype))
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes {name: tensor} as out_dir/<name>.npy in float32 (float64 stays float64).  An array that would not fit its
+    share of DUMP_BUDGET_BYTES is written as a fixed, seeded sample of its flattened elements (sorted indices, so the
+    sample is the same from run to run and build to build)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        limit = share // t.element_size()
+        if t.numel() > limit:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:limit].sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def algorithmic_step_flops(engine_profile):
@@ -342,6 +370,7 @@ def image_workload(args, world, rank, rank_devices, unet, net, sched, cfg, model
         losses = one_step()
     sync()
     elapsed = time.perf_counter() - t0
+    losses = losses.clone()  # step.losses is a view into the step's message: a --full profiled step below overwrites it
     rank_ms = [elapsed / args.steps * 1e3]
     if world > 1:
         te = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
@@ -349,18 +378,16 @@ def image_workload(args, world, rank, rank_devices, unet, net, sched, cfg, model
         torch.distributed.all_gather(tl, te)
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in tl]
         elapsed = max(float(x.item()) for x in tl)
-    engine = unet._engine
-    engine.profile_enable(True)
-    one_step(timed_vae=True)
-    prof = engine.profile_read()
-    engine.profile_enable(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"losses_high_low": losses, "lora_weights": net.flat, "lora_grad": step.grad})
+    if args.full:
+        engine = unet._engine
+        engine.profile_enable(True)
+        one_step(timed_vae=True)
+        prof = engine.profile_read()
+        engine.profile_enable(False)
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        step_flops = algorithmic_step_flops(prof)
-        mm_ms = prof["gemm"]["ms"] + prof["conv"]["ms"]
-        mm_fl = prof["gemm"]["flops"] + prof["conv"]["flops"]
-        mm_la = prof["gemm"]["launches"] + prof["conv"]["launches"]
-        achieved = mm_fl / (mm_ms * 1e-3) / 1e12 if mm_ms > 0 else 0.0
         out = {
             "metric": "slider train-steps/sec (image slider: 2 adapted UNet fwd+bwd + 2 VAE encodes)",
             "value": world * args.steps / elapsed, "unit": "steps/s", "n_gpus": world, "steps": args.steps,
@@ -375,20 +402,28 @@ def image_workload(args, world, rank, rank_devices, unet, net, sched, cfg, model
             "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
             "rccl_world_size": world, "rank_devices": rank_devices,
             "losses_high_low": [float(v) for v in losses.tolist()],
-            "vae_encode_and_noise_ms": t_vae[0],
-            "step_algorithmic_tflop_unet": step_flops / 1e12,
-            "roofline": {"kernel": "gemm_5ph_kernel + gemm_8ph_kernel + gemm_glds_kernel (UNet Linear GEMMs + implicit-GEMM 3x3 convs)",
-                         "bound": "mfma", "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": None,
-                         "launches_per_step": int(mm_la), "avg_launch_us": mm_ms * 1e3 / max(mm_la, 1),
-                         "algorithmic_tflop_per_step": mm_fl / 1e12},
-            "kernel_classes": {k: {"ms": round(v["ms"], 3), "launches": int(v["launches"]),
-                                   "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 and v["flops"] else None,
-                                   "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 and v["bytes"] else None}
-                               for k, v in prof.items()},
-            "cpu_baseline": None,
-            "cpu_baseline_note": "the CPU oracle step is timed on the text-slider workloads (sd14_512_b1_r4 at the same size)",
         }
+        if args.full:
+            step_flops = algorithmic_step_flops(prof)
+            mm_ms = prof["gemm"]["ms"] + prof["conv"]["ms"]
+            mm_fl = prof["gemm"]["flops"] + prof["conv"]["flops"]
+            mm_la = prof["gemm"]["launches"] + prof["conv"]["launches"]
+            achieved = mm_fl / (mm_ms * 1e-3) / 1e12 if mm_ms > 0 else 0.0
+            out.update({
+                "vae_encode_and_noise_ms": t_vae[0],
+                "step_algorithmic_tflop_unet": step_flops / 1e12,
+                "roofline": {"kernel": "gemm_5ph_kernel + gemm_8ph_kernel + gemm_glds_kernel (UNet Linear GEMMs + implicit-GEMM 3x3 convs)",
+                             "bound": "mfma", "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": None,
+                             "launches_per_step": int(mm_la), "avg_launch_us": mm_ms * 1e3 / max(mm_la, 1),
+                             "algorithmic_tflop_per_step": mm_fl / 1e12},
+                "kernel_classes": {k: {"ms": round(v["ms"], 3), "launches": int(v["launches"]),
+                                       "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 and v["flops"] else None,
+                                       "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 and v["bytes"] else None}
+                                   for k, v in prof.items()},
+                "cpu_baseline": None,
+                "cpu_baseline_note": "the CPU oracle step is timed on the text-slider workloads (sd14_512_b1_r4 at the same size)",
+            })
         print(json.dumps(out))
     if world > 1:
         torch.distributed.barrier()
@@ -410,13 +445,21 @@ def main():
                          "three frozen passes): identical results, 8B -> 5B UNet samples per step")
     ap.add_argument("--skip-dead-cfg-half", action="store_true",
                     help="drop the algebraically dead unconditional half (CFG scale 1); reported separately")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what the headline does not need: the all-reduce on its own "
+                         "(N > 1), the pre-roll, one HIP-event profiled step (kernel_classes, roofline) and the CPU oracle "
+                         "baseline (N = 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss, LoRA weights, LoRA gradient) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle baseline")
     ap.add_argument("--timed-only", action="store_true",
                     help="counter-collection passes (tools/collect_profiles.sh): warm-up + timed steps only -- no pre-roll, no "
                          "HIP-event profiled step (two event packets around every launch), no CPU baseline, no JSON line")
     ap.add_argument("--separate-passes", action="store_true",
                     help="run the four guidance passes as four UNet calls instead of one batched pass")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -532,27 +575,15 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     rank_ms = [elapsed / args.steps * 1e3]
-    allreduce_us = None
     if world > 1:
         te = torch.tensor([elapsed], device="cuda", dtype=torch.float64)
         tl = [torch.zeros_like(te) for _ in range(world)]
         torch.distributed.all_gather(tl, te)
         rank_ms = [float(x.item()) / args.steps * 1e3 for x in tl]
         elapsed = max(float(x.item()) for x in tl)  # MAX over ranks
-        # the step's one collective on its own: HIP events around the flat fp32 LoRA-gradient all-reduce
-        from sliders_conceptmod_amd import parallel
-        buf = step.msg.clone()  # [gradient | loss scalar]: the step's one message
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        parallel.allreduce_mean_(buf)
-        torch.cuda.synchronize()
-        torch.distributed.barrier()
-        ev[0].record()
-        for _ in range(10):
-            parallel.allreduce_mean_(buf)
-        ev[1].record()
-        torch.cuda.synchronize()
-        allreduce_us = ev[0].elapsed_time(ev[1]) * 1e3 / 10
     loss_val = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": loss, "lora_weights": net.flat, "lora_grad": step.grad})
     if args.timed_only:
         if rank == 0:
             log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.1f} ms/step (--timed-only: done)")
@@ -561,55 +592,67 @@ def main():
             torch.distributed.destroy_process_group()
         return
     if rank == 0:
-        log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.1f} ms/step; profiling one step")
+        log(f"timed {args.steps} steps: {elapsed / args.steps * 1e3:.1f} ms/step" + ("; profiling one step" if args.full else ""))
 
-    # ---- second number: the no-grad pre-roll the reference runs before every step
-    # (diffusion / diffusion_xl, adaptor on, CFG batch 2B), with timesteps_to fixed at its mean
-    n_pre = 6 if xl else 25
-    pre_sched = MU.create_noise_scheduler(sched_name)
-    pre_sched.set_timesteps(12 if xl else 50)
-    pre_step = SliderStep(unet, net, pre_sched, cfg_scale=1.0)
-    torch.manual_seed(7)
-    pre_step.preroll(denoised, cond, 1, 3.0)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    pre_step.preroll(denoised, cond, n_pre, 3.0)
-    torch.cuda.synchronize()
-    preroll_ms = (time.perf_counter() - t0) * 1e3
-    # the SD-XL trainer's DEFAULT pre-roll runs at guidance scale train.cfg = 1.0 (T/config_util.py:41), where the
-    # unconditional half of the doubled batch is algebraically dead and SliderStep.preroll runs the conditional half alone
-    preroll_cfg1_ms = None
-    if xl:
-        pre_step.preroll(denoised, cond, 1, 1.0)
+    allreduce_us = None
+    if args.full:
+        if world > 1:
+            # the step's one collective on its own: HIP events around the flat fp32 LoRA-gradient all-reduce
+            from sliders_conceptmod_amd import parallel
+            buf = step.msg.clone()  # [gradient | loss scalar]: the step's one message
+            ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+            parallel.allreduce_mean_(buf)
+            torch.cuda.synchronize()
+            torch.distributed.barrier()
+            ev[0].record()
+            for _ in range(10):
+                parallel.allreduce_mean_(buf)
+            ev[1].record()
+            torch.cuda.synchronize()
+            allreduce_us = ev[0].elapsed_time(ev[1]) * 1e3 / 10
+
+        # ---- second number: the no-grad pre-roll the reference runs before every step
+        # (diffusion / diffusion_xl, adaptor on, CFG batch 2B), with timesteps_to fixed at its mean
+        n_pre = 6 if xl else 25
+        pre_sched = MU.create_noise_scheduler(sched_name)
+        pre_sched.set_timesteps(12 if xl else 50)
+        pre_step = SliderStep(unet, net, pre_sched, cfg_scale=1.0)
+        torch.manual_seed(7)
+        pre_step.preroll(denoised, cond, 1, 3.0)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        pre_step.preroll(denoised, cond, n_pre, 1.0)
+        pre_step.preroll(denoised, cond, n_pre, 3.0)
         torch.cuda.synchronize()
-        preroll_cfg1_ms = (time.perf_counter() - t0) * 1e3
-    if os.environ.get("SMI_BENCH_PROFILE_PREROLL") in ("1", "g1"):  # per-shape table of ONE pre-roll forward (with SMI_PROF_DUMP=1)
-        unet._engine.profile_enable(True)                             # "g1": at guidance 1 (the conditional half alone)
-        pre_step.preroll(denoised, cond, 1, 1.0 if os.environ["SMI_BENCH_PROFILE_PREROLL"] == "g1" else 3.0)
-        pp = unet._engine.profile_read()
-        unet._engine.profile_enable(False)
+        preroll_ms = (time.perf_counter() - t0) * 1e3
+        # the SD-XL trainer's DEFAULT pre-roll runs at guidance scale train.cfg = 1.0 (T/config_util.py:41), where the
+        # unconditional half of the doubled batch is algebraically dead and SliderStep.preroll runs the conditional half alone
+        preroll_cfg1_ms = None
+        if xl:
+            pre_step.preroll(denoised, cond, 1, 1.0)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            pre_step.preroll(denoised, cond, n_pre, 1.0)
+            torch.cuda.synchronize()
+            preroll_cfg1_ms = (time.perf_counter() - t0) * 1e3
+        if os.environ.get("SMI_BENCH_PROFILE_PREROLL") in ("1", "g1"):  # per-shape table of ONE pre-roll forward (with SMI_PROF_DUMP=1)
+            unet._engine.profile_enable(True)                             # "g1": at guidance 1 (the conditional half alone)
+            pre_step.preroll(denoised, cond, 1, 1.0 if os.environ["SMI_BENCH_PROFILE_PREROLL"] == "g1" else 3.0)
+            pp = unet._engine.profile_read()
+            unet._engine.profile_enable(False)
+            if rank == 0:
+                log("one pre-roll forward by class: " + json.dumps({k: round(v["ms"], 3) for k, v in pp.items()}))
         if rank == 0:
-            log("one pre-roll forward by class: " + json.dumps({k: round(v["ms"], 3) for k, v in pp.items()}))
-    if rank == 0:
-        log(f"pre-roll of {n_pre} forwards: {preroll_ms:.1f} ms")
+            log(f"pre-roll of {n_pre} forwards: {preroll_ms:.1f} ms")
 
-    # ---- separate profiled step: per-kernel-class device time from HIP events on the launch stream
-    engine = unet._engine
-    engine.profile_enable(True)
-    step.train_step(denoised, timestep, cond, "enhance", 4.0)
-    prof = engine.profile_read()
-    engine.profile_enable(False)
+        # ---- separate profiled step: per-kernel-class device time from HIP events on the launch stream
+        engine = unet._engine
+        engine.profile_enable(True)
+        step.train_step(denoised, timestep, cond, "enhance", 4.0)
+        prof = engine.profile_read()
+        engine.profile_enable(False)
 
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
-        step_flops = algorithmic_step_flops(prof)
-        mm_ms = prof["gemm"]["ms"] + prof["conv"]["ms"]
-        mm_fl = prof["gemm"]["flops"] + prof["conv"]["flops"]
-        mm_la = prof["gemm"]["launches"] + prof["conv"]["launches"]
-        achieved = mm_fl / (mm_ms * 1e-3) / 1e12 if mm_ms > 0 else 0.0
         out = {
             "metric": "slider train-steps/sec (4-pass UNet fwd+bwd)",
             "value": world * args.steps / elapsed,
@@ -628,42 +671,50 @@ def main():
             "samples_per_s": args.steps * B * world / elapsed,
             "per_rank_ms_per_step": {"min": min(rank_ms), "max": max(rank_ms)},
             "rccl_world_size": seen_world, "rank_devices": rank_devices,
-            "allreduce": None if allreduce_us is None else {
-                "us": allreduce_us, "bytes": int(step.msg.numel() * 4),
-                "what": "flat fp32 LoRA gradient + the loss scalar in ONE message, all-reduce(sum) + divide, on the compute stream (RCCL), issued after "
-                        "the deferred grouped weight-gradient launches of the backward: nothing overlaps it (it is "
-                        "~0.1 % of a step)"},
             "loss": loss_val,
-            "preroll": {"forwards": n_pre, "ms": preroll_ms, "unet_batch": 2 * B,
-                        "note": "no-grad diffusion(_xl) pre-roll at its mean length, adaptor on, guidance scale 3 (doubled "
-                                "batch); NOT part of `value`",
-                        "ms_at_guidance_1": preroll_cfg1_ms,
-                        "note_guidance_1": "the SD-XL trainer's default train.cfg = 1.0: the conditional half alone "
-                                           "(UNet batch B), the unconditional half being algebraically dead there",
-                        "steps_per_s_with_preroll": world / ((ms_per_step + preroll_ms) * 1e-3)},
-            "step_algorithmic_tflop": step_flops / 1e12,
-            "step_tflops_achieved": step_flops / 1e12 / (ms_per_step * 1e-3),
-            "step_frac_of_mfma_peak": step_flops / 1e12 / (ms_per_step * 1e-3) / MFMA_PEAK_TFLOPS,
-            "roofline": {"kernel": "gemm_5ph_kernel + gemm_8ph_kernel + gemm_glds_kernel (Linear GEMMs + implicit-GEMM 3x3 convs)",
-                         "bound": "mfma",
-                         "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
-                         "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": pmc_traffic(args.config),
-                         "traffic_note": "bytes/launch at the L2's memory side (FETCH_SIZE x2 + WRITE_SIZE, KiB -> B), "
-                                         "launch-weighted over the GEMM kernels; from the committed rocprofv3 --pmc "
-                                         "passes in profiles/ (not collected live)",
-                         "launches_per_step": int(mm_la), "avg_launch_us": mm_ms * 1e3 / max(mm_la, 1),
-                         "algorithmic_tflop_per_step": mm_fl / 1e12,
-                         "share_of_step_device_time": mm_ms / max(sum(v["ms"] for v in prof.values()), 1e-9)},
-            "kernel_classes": {k: {"ms": round(v["ms"], 3), "launches": int(v["launches"]),
-                                   "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 and v["flops"] else None,
-                                   "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 and v["bytes"] else None}
-                               for k, v in prof.items()},
-            "kernel_classes_note": "HIP events around every launch of ONE separately profiled step: the events add about 2 % "
-                                   "(the classes sum to more than ms_per_step); the rocprofv3 kernel trace cut into "
-                                   "steady-state steps (profiles/r*_trace_steps_*.json) is the better per-class source",
         }
+        if args.full:
+            step_flops = algorithmic_step_flops(prof)
+            mm_ms = prof["gemm"]["ms"] + prof["conv"]["ms"]
+            mm_fl = prof["gemm"]["flops"] + prof["conv"]["flops"]
+            mm_la = prof["gemm"]["launches"] + prof["conv"]["launches"]
+            achieved = mm_fl / (mm_ms * 1e-3) / 1e12 if mm_ms > 0 else 0.0
+            out.update({
+                "allreduce": None if allreduce_us is None else {
+                    "us": allreduce_us, "bytes": int(step.msg.numel() * 4),
+                    "what": "flat fp32 LoRA gradient + the loss scalar in ONE message, all-reduce(sum) + divide, on the compute stream (RCCL), issued after "
+                            "the deferred grouped weight-gradient launches of the backward: nothing overlaps it (it is "
+                            "~0.1 % of a step)"},
+                "preroll": {"forwards": n_pre, "ms": preroll_ms, "unet_batch": 2 * B,
+                            "note": "no-grad diffusion(_xl) pre-roll at its mean length, adaptor on, guidance scale 3 (doubled "
+                                    "batch); NOT part of `value`",
+                            "ms_at_guidance_1": preroll_cfg1_ms,
+                            "note_guidance_1": "the SD-XL trainer's default train.cfg = 1.0: the conditional half alone "
+                                               "(UNet batch B), the unconditional half being algebraically dead there",
+                            "steps_per_s_with_preroll": world / ((ms_per_step + preroll_ms) * 1e-3)},
+                "step_algorithmic_tflop": step_flops / 1e12,
+                "step_tflops_achieved": step_flops / 1e12 / (ms_per_step * 1e-3),
+                "step_frac_of_mfma_peak": step_flops / 1e12 / (ms_per_step * 1e-3) / MFMA_PEAK_TFLOPS,
+                "roofline": {"kernel": "gemm_5ph_kernel + gemm_8ph_kernel + gemm_glds_kernel (Linear GEMMs + implicit-GEMM 3x3 convs)",
+                             "bound": "mfma",
+                             "achieved": achieved, "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s",
+                             "frac": achieved / MFMA_PEAK_TFLOPS, "traffic": pmc_traffic(args.config),
+                             "traffic_note": "bytes/launch at the L2's memory side (FETCH_SIZE x2 + WRITE_SIZE, KiB -> B), "
+                                             "launch-weighted over the GEMM kernels; from the committed rocprofv3 --pmc "
+                                             "passes in profiles/ (not collected live)",
+                             "launches_per_step": int(mm_la), "avg_launch_us": mm_ms * 1e3 / max(mm_la, 1),
+                             "algorithmic_tflop_per_step": mm_fl / 1e12,
+                             "share_of_step_device_time": mm_ms / max(sum(v["ms"] for v in prof.values()), 1e-9)},
+                "kernel_classes": {k: {"ms": round(v["ms"], 3), "launches": int(v["launches"]),
+                                       "tflops": (v["flops"] / (v["ms"] * 1e-3) / 1e12) if v["ms"] > 0 and v["flops"] else None,
+                                       "gbs": (v["bytes"] / (v["ms"] * 1e-3) / 1e9) if v["ms"] > 0 and v["bytes"] else None}
+                                   for k, v in prof.items()},
+                "kernel_classes_note": "HIP events around every launch of ONE separately profiled step: the events add about 2 % "
+                                       "(the classes sum to more than ms_per_step); the rocprofv3 kernel trace cut into "
+                                       "steady-state steps (profiles/r*_trace_steps_*.json) is the better per-class source",
+            })
         # weak scaling: a unit is one 4-pass step on one per-GPU batch B; all ranks together process world*steps units
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("GPU part done; timing the CPU oracle sample: " + json.dumps({k: out[k] for k in ("value", "ms_per_step")}))
             try:
                 out["cpu_baseline"] = cpu_baseline(model, lrank, step_flops, res, B)

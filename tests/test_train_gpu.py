@@ -397,8 +397,9 @@ def test_native_preroll_matches_the_drop_in_diffusion_xl():
 
 def test_two_rank_bench_flow_on_one_gpu():
     """The N > 1 path of bench.py (one process per rank, barrier + max-over-ranks timing, LoRA-gradient all-reduce before
-    the clip, rank 0 prints the JSON line) rehearsed with two ranks sharing this box's single GPU over gloo
-    (SMI_BENCH_ONE_DEVICE=1; RCCL refuses two ranks on one device).  The measured path is one rank per GPU over RCCL."""
+    the clip, rank 0 prints the JSON line, the --full measurements after the timed steps) rehearsed with two ranks
+    sharing this box's single GPU over gloo (SMI_BENCH_ONE_DEVICE=1; RCCL refuses two ranks on one device).  The
+    measured path is one rank per GPU over RCCL."""
     import json
     import os
     import subprocess
@@ -407,7 +408,7 @@ def test_two_rank_bench_flow_on_one_gpu():
     env = dict(os.environ, SMI_BENCH_ONE_DEVICE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", "29533", os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2",
-           "--warmup", "1", "--config", "tiny_sdxl", "--no-cpu-baseline"]
+           "--warmup", "1", "--config", "tiny_sdxl", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-1500:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -416,6 +417,8 @@ def test_two_rank_bench_flow_on_one_gpu():
     assert d["n_gpus"] == 2 and d["steps"] == 2 and d["scaling"] == "weak" and d["value"] > 0
     assert abs(d["value"] - 2 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]  # whole-job aggregate: world / step time
     assert d["config"]["global_batch"] == 2 * d["config"]["per_gpu_batch"]
+    # --full: the stand-alone all-reduce timing, the pre-roll and the profiled step ran on both ranks
+    assert d["allreduce"]["us"] > 0 and d["preroll"]["ms"] > 0 and d["kernel_classes"]
 
 
 def test_cli_main_runs_the_shipped_c3lier_config_end_to_end(tmp_path, monkeypatch):

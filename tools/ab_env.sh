@@ -9,7 +9,7 @@ for r in $(seq 1 $ROUNDS); do
   i=0
   for arm in "$@"; do
     i=$((i+1))
-    env $arm python3 bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline > $OUT/abenv_$i.json 2> $OUT/abenv_$i.err || { tail -20 $OUT/abenv_$i.err; exit 1; }
+    env $arm python3 bench.py --config $CFG --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/abenv_$i.json 2> $OUT/abenv_$i.err || { tail -20 $OUT/abenv_$i.err; exit 1; }
     python3 - "$arm" $OUT/abenv_$i.json <<'P'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

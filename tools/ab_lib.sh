@@ -7,7 +7,7 @@ OUT=gpurun_out; mkdir -p $OUT
 for r in $(seq 1 $ROUNDS); do
   for arm in base new; do
     if [ $arm = base ]; then export SMI_LIB=$BASE; else unset SMI_LIB; fi
-    python3 bench.py --config $CFG --steps 5 --warmup 2 --no-cpu-baseline > $OUT/ab_$arm.json 2> $OUT/ab_$arm.err || { tail -20 $OUT/ab_$arm.err; exit 1; }
+    python3 bench.py --config $CFG --steps 5 --warmup 2 --full --no-cpu-baseline > $OUT/ab_$arm.json 2> $OUT/ab_$arm.err || { tail -20 $OUT/ab_$arm.err; exit 1; }
     python3 - $arm $OUT/ab_$arm.json <<'P'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])

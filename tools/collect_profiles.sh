@@ -12,11 +12,11 @@ export TMPDIR=/tmp
 export SMI_TUNE_FILE=/tmp/smi_tune_${CFG}.txt
 OUT=gpurun_out
 mkdir -p $OUT
-SMI_PROF_DUMP=1 python3 bench.py --config $CFG --steps 6 --warmup 2 > $OUT/${TAG}_bench_default_${CFG}.json 2> $OUT/${TAG}_bench_default_${CFG}.err
+SMI_PROF_DUMP=1 python3 bench.py --config $CFG --steps 6 --warmup 2 --full > $OUT/${TAG}_bench_default_${CFG}.json 2> $OUT/${TAG}_bench_default_${CFG}.err
 cp $SMI_TUNE_FILE $OUT/${TAG}_tune_${CFG}.txt
 echo "bench done: $(wc -l < $SMI_TUNE_FILE) tuned keys"
 rm -rf $OUT/${TAG}_trace
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 bench.py --config $CFG --steps 8 --warmup 2 --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof_${CFG}.json 2> $OUT/${TAG}_trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${TAG}_trace -- python3 bench.py --config $CFG --steps 8 --warmup 2 --full --no-cpu-baseline > $OUT/${TAG}_bench_under_rocprof_${CFG}.json 2> $OUT/${TAG}_trace.err
 find $OUT/${TAG}_trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_rocprofv3_kernel_stats_${CFG}.csv
 KT=$(find $OUT/${TAG}_trace -name "*kernel_trace.csv" | head -1)
 python3 tools/trace_steps.py $KT $OUT/${TAG}_bench_under_rocprof_${CFG}.json $OUT/${TAG}_trace_steps_${CFG}.json

@@ -12,7 +12,7 @@ if [ "$PART" = "1" ]; then
   tail -4 $OUT/${TAG}_collect.log
   for c in sdxl_1024_b2_r8 sdxl_1024_b2_r4_dora sd15_512_b4_r4 sd14_512_b1_r4 sd14_512_b1_r4_c3lier image_sdxl_1024_b1_r4; do
     extra=""; [ "$c" != "sd14_512_b1_r4" ] && extra="--no-cpu-baseline"
-    python3 bench.py --config $c --steps 8 --warmup 2 $extra > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err || { tail -30 $OUT/${TAG}_bench_$c.err; exit 1; }
+    python3 bench.py --config $c --steps 8 --warmup 2 --full $extra > $OUT/${TAG}_bench_$c.json 2> $OUT/${TAG}_bench_$c.err || { tail -30 $OUT/${TAG}_bench_$c.err; exit 1; }
   done
   python3 - <<P
 import json
