@@ -152,6 +152,22 @@ int smi_vae_create(const smi_vae_config* cfg, const smi_weight* weights, int n_w
                    void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
 int smi_vae_encode(smi_engine* e, int n, const float* image, float* moments_out);
 
+/* ---- AutoencoderKL decoder (looking at a trained slider) ---------------------------------------------------------------
+ * image = decoder(post_quant_conv(latents)): replaces `vae.decode(latents / scaling_factor).sample` and the eval scripts'
+ * post-processing (eval-scripts/generate_images_sd1.py:195-200).
+ *   weights  diffusers AutoencoderKL state_dict entries `decoder.*` and `post_quant_conv.*`, dtype T (same size rule as
+ *            the encoder: h, w multiples of f = 2^(n_levels-1); w also a multiple of 4; in_channels <= 4)
+ *   latents  f32 [n, latent_channels, h/f, w/f]: what `vae.decode(z)` receives, i.e. ALREADY divided by scaling_factor
+ *   image    f32 [n, in_channels, h, w]: `vae.decode(z).sample`, unclamped
+ *   rgb8     optional (NULL: skipped) uint8 [n, h, w, in_channels] = round_half_even(clamp(sample/2 + 0.5, 0, 1) * 255)
+ * Creation refuses a batch whose largest conv operand would cross the GEMM's 4 GiB limit (SD config: 7 images at 1024^2,
+ * 31 at 512^2); the message names the largest batch that fits.  smi_vae_encode refuses a decoder engine, smi_vae_decode
+ * an encoder engine, and every UNet entry point both.  SMI_VAE_DEC_TAIL=0 (read at creation): the unfused tail. */
+int smi_vae_decoder_workspace_bytes(const smi_vae_config* cfg, int batch, int h, int w, size_t* bytes);
+int smi_vae_decoder_create(const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch, int h, int w,
+                           void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_vae_decode(smi_engine* e, int n, const float* latents, float* image_out, uint8_t* rgb8_out);
+
 /* ---- CLIP text encoder (prompt front end) -----------------------------------------------------------------------------
  * Replaces `text_encoder(tokens)[0]` (train_util.py:119-120) and `text_encoder(tokens, output_hidden_states=True)`
  * -> `[0]`, `.hidden_states[-2]` (train_util.py:139-144).  Causal self-attention, pre-LayerNorm blocks.

@@ -75,6 +75,11 @@ _SIGS = {
     "smi_vae_create": (C.c_int, [C.POINTER(VaeConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_int, C.c_int,
                                  C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_vae_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "smi_vae_decoder_workspace_bytes": (C.c_int, [C.POINTER(VaeConfigC), C.c_int, C.c_int, C.c_int,
+                                                  C.POINTER(C.c_size_t)]),
+    "smi_vae_decoder_create": (C.c_int, [C.POINTER(VaeConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_vae_decode": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smi_clip_workspace_bytes": (C.c_int, [C.POINTER(ClipConfigC), C.c_int, C.POINTER(C.c_size_t)]),
     "smi_clip_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -375,6 +380,66 @@ class VaeEngine:
                           device=image.device)
         check(lib().smi_vae_encode(self.handle, n, ptr(image), ptr(out)), "smi_vae_encode")
         return out
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().smi_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def vae_config_c(cfg, dtype: torch.dtype) -> VaeConfigC:
+    c = VaeConfigC()
+    c.dtype = DTYPE_CODE[dtype]
+    c.in_channels, c.latent_channels = cfg.in_channels, cfg.latent_channels
+    c.n_levels = len(cfg.block_out_channels)
+    for i, v in enumerate(cfg.block_out_channels):
+        c.block_out_channels[i] = v
+    c.layers_per_block, c.norm_num_groups = cfg.layers_per_block, cfg.norm_num_groups
+    return c
+
+
+def vae_decoder_workspace_bytes(cfg, dtype: torch.dtype, batch: int, h: int, w: int) -> int:
+    """smi_vae_decoder_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on a refused shape."""
+    out = C.c_size_t(0)
+    check(lib().smi_vae_decoder_workspace_bytes(C.byref(vae_config_c(cfg, dtype)), batch, h, w, C.byref(out)),
+          "smi_vae_decoder_workspace_bytes")
+    return out.value
+
+
+class VaeDecoderEngine:
+    """AutoencoderKL decoder on the HIP engine for one image size (smi_vae_decoder_*): latents -> image (+ uint8)."""
+
+    def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, h: int, w: int, device):
+        c = vae_config_c(cfg, dtype)
+        self.cfg_c, self.batch, self.h, self.w = c, batch, h, w
+        self.latent_channels, self.out_channels = cfg.latent_channels, cfg.in_channels
+        self.down = 2 ** (len(cfg.block_out_channels) - 1)
+        nbytes = vae_decoder_workspace_bytes(cfg, dtype, batch, h, w)
+        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.workspace.device):
+            check(lib().smi_vae_decoder_create(C.byref(c), warr, len(state), batch, h, w, ptr(self.workspace), nbytes,
+                                               stream_ptr(), C.byref(handle)), "smi_vae_decoder_create")
+        self.handle = handle
+
+    def decode(self, latents: torch.Tensor, want_rgb8: bool = False):
+        """latents f32 [n, latent, h/f, w/f] on the engine's device -> (sample f32 [n, C, h, w], uint8 [n, h, w, C] or None)"""
+        n = latents.shape[0]
+        if tuple(latents.shape[1:]) != (self.latent_channels, self.h // self.down, self.w // self.down):
+            raise SmiError(f"latents {tuple(latents.shape)} do not match the engine's {self.h}x{self.w} image")
+        latents = latents.to(torch.float32).contiguous()
+        out = torch.empty((n, self.out_channels, self.h, self.w), dtype=torch.float32, device=latents.device)
+        rgb = (torch.empty((n, self.h, self.w, self.out_channels), dtype=torch.uint8, device=latents.device)
+               if want_rgb8 else None)
+        check(lib().smi_vae_decode(self.handle, n, ptr(latents), ptr(out), ptr(rgb)), "smi_vae_decode")
+        return out, rgb
 
     def close(self):
         if getattr(self, "handle", None):

@@ -1747,6 +1747,23 @@ struct smi_engine {
   const void* v_quant_w = nullptr;
   const void* v_quant_b = nullptr;
 
+  // the mid block's single-head attention: its GroupNorm, fused q|k|v (+ fused bias), to_out.0
+  void build_vae_attn(const std::string& pre, int ch) {
+    v_attn_norm = make_norm(pre + ".group_norm", ch, 1e-6f);
+    v_qkv = make_fused(pre, {"to_q", "to_k", "to_v"}, ch, ch, false);
+    {  // fused q|k|v bias
+      char* bq = (char*)pack_alloc((size_t)3 * ch * esz());
+      const char* parts[3] = {"to_q", "to_k", "to_v"};
+      for (int i = 0; i < 3; ++i) {
+        const void* src = Wd(pre + "." + parts[i] + ".bias");
+        if (!dry && !err && src)
+          (void)hipMemcpyAsync(bq + (size_t)i * ch * esz(), src, (size_t)ch * esz(), hipMemcpyDeviceToDevice, stream);
+      }
+      v_qkv.b = bq;
+    }
+    v_o = make_lin(pre + ".to_out.0", ch, ch, true, false);
+  }
+
   void build_vae() {
     const int L = vcfg.n_levels;
     const int* boc = vcfg.block_out_channels;
@@ -1773,19 +1790,7 @@ struct smi_engine {
       }
     }
     v_mid0 = make_resnet("encoder.mid_block.resnets.0", ch, ch, false, 1e-6f, false);
-    v_attn_norm = make_norm("encoder.mid_block.attentions.0.group_norm", ch, 1e-6f);
-    v_qkv = make_fused("encoder.mid_block.attentions.0", {"to_q", "to_k", "to_v"}, ch, ch, false);
-    {  // fused q|k|v bias
-      char* bq = (char*)pack_alloc((size_t)3 * ch * esz());
-      const char* parts[3] = {"to_q", "to_k", "to_v"};
-      for (int i = 0; i < 3; ++i) {
-        const void* src = Wd(std::string("encoder.mid_block.attentions.0.") + parts[i] + ".bias");
-        if (!dry && !err && src)
-          (void)hipMemcpyAsync(bq + (size_t)i * ch * esz(), src, (size_t)ch * esz(), hipMemcpyDeviceToDevice, stream);
-      }
-      v_qkv.b = bq;
-    }
-    v_o = make_lin("encoder.mid_block.attentions.0.to_out.0", ch, ch, true, false);
+    build_vae_attn("encoder.mid_block.attentions.0", ch);
     v_mid1 = make_resnet("encoder.mid_block.resnets.1", ch, ch, false, 1e-6f, false);
     v_norm_out = make_norm("encoder.conv_norm_out", ch, 1e-6f);
     v_conv_out = make_conv("encoder.conv_out", ch, 2 * vcfg.latent_channels, 0, false);
@@ -1794,6 +1799,66 @@ struct smi_engine {
     check_shape("quant_conv.weight", {2 * vcfg.latent_channels, 2 * vcfg.latent_channels, 1, 1});
     gscale = (float*)pack_alloc(256 * sizeof(float));
     finish_lora();
+  }
+
+  // single-head attention over the pixels, with its own GroupNorm and residual.  Materialised per image: S = Q K^T (fp32),
+  // P = softmax(S / sqrt(C)), O = P V.  `hoist`: one set of per-image buffers (S, P, K, V^T) for all images (the decoder);
+  // otherwise each image allocates its own (the encoder's layout, kept as it was)
+  Ten* vae_attn(Ten* h, bool hoist) {
+    const int n = h->n;
+    const int C = h->cols, N = h->H * h->W;
+    Ten* nrm = groupnorm(h, v_attn_norm, false);
+    Ten* qkv = linear(nrm, v_qkv);
+    Ten* o = new_ten(h->rows, C, h->n, h->H, h->W);
+    const float sc = 1.f / sqrtf((float)C);
+    float* S = nullptr;
+    void *P = nullptr, *Vt = nullptr, *Kd = nullptr, *Vd = nullptr;
+    if (hoist) {
+      S = alloc_f32((size_t)N * N);
+      P = alloc_t(N, N);
+      Vt = alloc_t(C, N);
+      Kd = alloc_t(N, C);
+      Vd = alloc_t(N, C);
+    }
+    for (int i = 0; i < n; ++i) {
+      const char* base = (const char*)qkv->p + (size_t)i * N * 3 * C * esz();
+      if (!hoist) {
+        S = alloc_f32((size_t)N * N);
+        P = alloc_t(N, N);
+        Vt = alloc_t(C, N);
+      }
+      GemmParams g;
+      g.dtype = dtype;
+      g.A = base;
+      g.lda = 3 * C;
+      // the GEMM's W operand is dense [N_out, K]: K (and V) are column blocks of the fused tensor, so stage them
+      if (!hoist) Kd = alloc_t(N, C);
+      RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)C * esz(), 3 * C, Kd, C, 0, N, C, stream));
+      g.W = Kd;
+      g.C = S;
+      g.ldc = N;
+      g.out_f32 = 1;
+      g.M = N;
+      g.N = N;
+      g.K = C;
+      RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(g, stream));
+      RUNP(SMI_PROF_ATTN, 0.0, 0.0, launch_softmax_rows(dtype, S, P, N, N, sc, stream));
+      if (!hoist) Vd = alloc_t(N, C);
+      RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)2 * C * esz(), 3 * C, Vd, C, 0, N, C, stream));
+      transpose_into(Vd, Vt, N, C, N, 0, false);
+      GemmParams pv;
+      pv.dtype = dtype;
+      pv.A = P;
+      pv.lda = N;
+      pv.W = Vt;
+      pv.C = (char*)o->p + (size_t)i * N * C * esz();
+      pv.ldc = C;
+      pv.M = N;
+      pv.N = C;
+      pv.K = N;
+      RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(pv, stream));
+    }
+    return linear(o, v_o, h);
   }
 
   // image f32 [n, 3, h, w] in [-1, 1]  ->  moments f32 [n, 2 * latent, h/8, w/8] (mean | logvar, before the clamp)
@@ -1815,51 +1880,7 @@ struct smi_engine {
       if (lv.has_samp) h = conv3x3(h, lv.samp, nullptr, nullptr);
     }
     h = resnet(h, v_mid0, nullptr);
-    {  // single-head attention over the pixels, with its own GroupNorm and residual
-      const int C = h->cols, N = h->H * h->W;
-      Ten* nrm = groupnorm(h, v_attn_norm, false);
-      Ten* qkv = linear(nrm, v_qkv);
-      Ten* o = new_ten(h->rows, C, h->n, h->H, h->W);
-      const float sc = 1.f / sqrtf((float)C);
-      for (int i = 0; i < n; ++i) {
-        const char* base = (const char*)qkv->p + (size_t)i * N * 3 * C * esz();
-        float* S = alloc_f32((size_t)N * N);
-        void* P = alloc_t(N, N);
-        void* Vt = alloc_t(C, N);
-        GemmParams g;
-        g.dtype = dtype;
-        g.A = base;
-        g.lda = 3 * C;
-        g.W = base + (size_t)C * esz();  // K rows, row stride 3C: not a dense [N, C] operand -> copy below
-        // the GEMM's W operand is dense [N_out, K]: K (and V) are column blocks of the fused tensor, so stage them
-        void* Kd = alloc_t(N, C);
-        RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)C * esz(), 3 * C, Kd, C, 0, N, C, stream));
-        g.W = Kd;
-        g.C = S;
-        g.ldc = N;
-        g.out_f32 = 1;
-        g.M = N;
-        g.N = N;
-        g.K = C;
-        RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(g, stream));
-        RUNP(SMI_PROF_ATTN, 0.0, 0.0, launch_softmax_rows(dtype, S, P, N, N, sc, stream));
-        void* Vd = alloc_t(N, C);
-        RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)2 * C * esz(), 3 * C, Vd, C, 0, N, C, stream));
-        transpose_into(Vd, Vt, N, C, N, 0, false);
-        GemmParams pv;
-        pv.dtype = dtype;
-        pv.A = P;
-        pv.lda = N;
-        pv.W = Vt;
-        pv.C = (char*)o->p + (size_t)i * N * C * esz();
-        pv.ldc = C;
-        pv.M = N;
-        pv.N = C;
-        pv.K = N;
-        RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(pv, stream));
-      }
-      h = linear(o, v_o, h);
-    }
+    h = vae_attn(h, false);
     h = resnet(h, v_mid1, nullptr);
     Ten* hn = groupnorm(h, v_norm_out, true);
     const int C2 = 2 * vcfg.latent_channels;
@@ -1887,6 +1908,151 @@ struct smi_engine {
     float* q = alloc_f32((size_t)y->rows * C2);
     RUN(launch_chan_mix(dtype, (const float*)y->p, v_quant_w, v_quant_b, q, y->rows, C2, stream));
     RUN(launch_nhwc_to_nchw_f32(q, moments_out, n, C2, Ho * Wo, stream));
+    if (cur->overflow && !dry) {
+      set_error("workspace too small for this call (needs %zu bytes, has %zu)", cur->peak, cur->cap);
+      return -3;
+    }
+    return err ? -1 : 0;
+  }
+
+  // ---------------------------------------------------------------------------------------------------------
+  // AutoencoderKL decoder (what the eval scripts do after the sweep: `vae.decode(latents / scaling_factor).sample`,
+  // eval-scripts/generate_images_sd1.py:195-200): post_quant_conv (1x1, fp32 on the latent grid) -> conv_in -> mid block
+  // (resnet, single-head attention, resnet) -> up blocks over the reversed block_out_channels (layers_per_block + 1
+  // resnets, nearest-2x + 3x3 up-sampler on all but the last) -> conv_norm_out + SiLU + conv_out.  The tail runs as one
+  // fused launch (vae_decode.hip) unless SMI_VAE_DEC_TAIL=0 (then: GroupNorm+SiLU, the conv with Cout padded to 4 by a
+  // zero filter row, layout kernels, a separate uint8 pass).  Same engine kind flag as the encoder (`is_vae`), plus
+  // `is_vae_dec`: encode / decode refuse the other kind, the UNet entry points refuse both.
+  // ---------------------------------------------------------------------------------------------------------
+  bool is_vae_dec = false;
+  bool dec_tail_fused = true;
+  std::vector<VLevel> v_up;
+  Conv d_conv_out;                 // Wp: [4][9*C0], rows >= out channels zero
+  const void* d_bias4 = nullptr;   // conv_out bias zero-padded to 4 (unfused path)
+  const void* d_pq_w = nullptr;    // post_quant_conv
+  const void* d_pq_b = nullptr;
+
+  void build_vae_dec() {
+    const int L = vcfg.n_levels;
+    const int* boc = vcfg.block_out_channels;
+    const int lc = vcfg.latent_channels, co = vcfg.in_channels;
+    d_pq_w = Wd("post_quant_conv.weight");
+    d_pq_b = Wd("post_quant_conv.bias");
+    check_shape("post_quant_conv.weight", {lc, lc, 1, 1});
+    check_shape("post_quant_conv.bias", {lc});
+    const int top = boc[L - 1];
+    {  // conv_in on the MFMA conv path: latent channels zero-padded to 64
+      v_conv_in.Cin = 64;
+      v_conv_in.Cout = top;
+      v_conv_in.b = Wd("decoder.conv_in.bias");
+      check_shape("decoder.conv_in.weight", {top, lc, 3, 3});
+      void* wp = pack_alloc((size_t)top * 9 * 64 * esz());
+      pack_conv_into(Wd("decoder.conv_in.weight"), wp, top, lc, 0, 64);
+      v_conv_in.Wp = wp;
+    }
+    v_mid0 = make_resnet("decoder.mid_block.resnets.0", top, top, false, 1e-6f, false);
+    build_vae_attn("decoder.mid_block.attentions.0", top);
+    v_mid1 = make_resnet("decoder.mid_block.resnets.1", top, top, false, 1e-6f, false);
+    v_up.resize(L);
+    int ch = top;
+    for (int i = 0; i < L; ++i) {
+      const int out = boc[L - 1 - i];
+      const std::string b = "decoder.up_blocks." + std::to_string(i);
+      for (int j = 0; j <= vcfg.layers_per_block; ++j)
+        v_up[i].res.push_back(make_resnet(b + ".resnets." + std::to_string(j), j == 0 ? ch : out, out, false, 1e-6f, false));
+      ch = out;
+      v_up[i].has_samp = i != L - 1;
+      if (v_up[i].has_samp) v_up[i].samp = make_conv(b + ".upsamplers.0.conv", ch, ch, 2, false);
+    }
+    v_norm_out = make_norm("decoder.conv_norm_out", ch, 1e-6f);
+    {  // conv_out [co][9*C0] with co padded to 4 by zero rows: the fused tail's B operand and the unfused conv's filter
+      d_conv_out.Cin = ch;
+      d_conv_out.Cout = 4;
+      d_conv_out.b = Wd("decoder.conv_out.bias");
+      check_shape("decoder.conv_out.weight", {co, ch, 3, 3});
+      check_shape("decoder.conv_out.bias", {co});
+      void* wp = pack_alloc((size_t)4 * 9 * ch * esz());
+      void* b4 = pack_alloc(4 * esz());
+      if (!dry && !err) {
+        (void)hipMemsetAsync(wp, 0, (size_t)4 * 9 * ch * esz(), stream);
+        (void)hipMemsetAsync(b4, 0, 4 * esz(), stream);
+        if (d_conv_out.b)
+          (void)hipMemcpyAsync(b4, d_conv_out.b, (size_t)co * esz(), hipMemcpyDeviceToDevice, stream);
+      }
+      pack_conv_into(Wd("decoder.conv_out.weight"), wp, co, ch, 0);
+      d_conv_out.Wp = wp;
+      d_bias4 = b4;
+    }
+    gscale = (float*)pack_alloc(256 * sizeof(float));
+    finish_lora();
+  }
+
+  // latents f32 [n, latent, h/f, w/f] (already / scaling_factor) -> image f32 [n, 3, h, w] (+ uint8 [n, h, w, 3])
+  int forward_vae_dec(int n, const float* latents, float* image_out, uint8_t* rgb8_out) {
+    n_ad = 0;
+    cur = &arena[0];
+    cur->reset();
+    tens = &tens_[0];
+    tens->clear();
+    saving = false;
+    lora_down = lora_up = nullptr;
+    mult = 0.f;
+    const int L = vcfg.n_levels, f = 1 << (L - 1);
+    const int H = lat_h, Wd_ = lat_w;  // image size for this engine kind
+    const int h0 = H / f, w0 = Wd_ / f, lc = vcfg.latent_channels, co = vcfg.in_channels;
+    const int64_t M0 = (int64_t)n * h0 * w0;
+    float* zt = alloc_f32((size_t)M0 * lc);
+    // NCHW -> NHWC: the NHWC -> NCHW kernel with the roles of C and HW swapped
+    RUN(launch_nhwc_to_nchw_f32(latents, zt, n, h0 * w0, lc, stream));
+    float* zq = alloc_f32((size_t)M0 * lc);
+    RUN(launch_chan_mix(dtype, zt, d_pq_w, d_pq_b, zq, M0, lc, stream));
+    Ten* x0 = new_ten(M0, 64, n, h0, w0);
+    RUN(launch_f32_to_padded(dtype, zq, lc, lc, x0->p, 64, M0, 1.f, stream));
+    Ten* h = conv3x3(x0, v_conv_in, nullptr, nullptr);
+    h = resnet(h, v_mid0, nullptr);
+    h = vae_attn(h, true);
+    h = resnet(h, v_mid1, nullptr);
+    for (auto& lv : v_up) {
+      for (auto& r : lv.res) h = resnet(h, r, nullptr);
+      if (lv.has_samp) h = conv3x3(h, lv.samp, nullptr, nullptr);
+    }
+    const int C0 = h->cols, HWi = H * Wd_, G = vcfg.norm_num_groups;
+    if (dec_tail_fused) {
+      float* ab = alloc_f32((size_t)2 * n * C0);
+      float* mr = alloc_f32((size_t)n * G * 2);
+      float* part = alloc_f32(gn_partial_floats(n, HWi, G));
+      RUNP(SMI_PROF_NORM, 0.0, 2.0 * h->rows * C0,
+           launch_groupnorm_stats(dtype, h->p, v_norm_out.gamma, v_norm_out.beta, ab, mr, part, n, HWi, C0, G,
+                                  v_norm_out.eps, stream));
+      RUNP(SMI_PROF_CONV, 2.0 * h->rows * co * 9 * C0, 2.0 * h->rows * C0 + 4.0 * h->rows * co + (rgb8_out ? 1.0 * h->rows * co : 0.0),
+           launch_vae_dec_tail(dtype, h->p, ab, d_conv_out.Wp, d_conv_out.b, image_out, rgb8_out, n, H, Wd_, C0, co,
+                               stream));
+    } else {
+      Ten* hn = groupnorm(h, v_norm_out, true);
+      Ten* y = new_ten((int64_t)n * HWi, 4, n, H, Wd_, sizeof(float));
+      GemmParams p;
+      p.dtype = dtype;
+      p.conv = 1;
+      p.A = hn->p;
+      p.W = d_conv_out.Wp;
+      p.C = y->p;
+      p.ldc = 4;
+      p.out_f32 = 1;
+      p.M = (int)y->rows;
+      p.N = 4;
+      p.K = 9 * C0;
+      p.bias = d_bias4;
+      p.Nb = n;
+      p.Hin = p.Hout = H;
+      p.Win = p.Wout = Wd_;
+      p.Cin = C0;
+      RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * p.K, 0.0, launch_gemm(p, stream));
+      float* t4 = alloc_f32((size_t)n * 4 * HWi);
+      RUN(launch_nhwc_to_nchw_f32((const float*)y->p, t4, n, 4, HWi, stream));
+      RUN(hipMemcpy2DAsync(image_out, (size_t)co * HWi * sizeof(float), t4, (size_t)4 * HWi * sizeof(float),
+                           (size_t)co * HWi * sizeof(float), n, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -1);
+      if (rgb8_out) RUN(launch_rgb8_from_nchw(image_out, rgb8_out, n, co, HWi, stream));
+    }
     if (cur->overflow && !dry) {
       set_error("workspace too small for this call (needs %zu bytes, has %zu)", cur->peak, cur->cap);
       return -3;
@@ -2457,9 +2623,110 @@ int smi_vae_create(const smi_vae_config* cfg, const smi_weight* weights, int n_w
 
 int smi_vae_encode(smi_engine* e, int n, const float* image, float* moments_out) {
   SMI_CHECK(e && e->is_vae && image && moments_out, "smi_vae_encode: NULL argument or not a VAE engine");
+  SMI_CHECK(!e->is_vae_dec, "smi_vae_encode: this engine is a VAE decoder (use smi_vae_decode)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   e->err = false;
   return e->forward_vae(n, image, moments_out);
+}
+
+// ---- AutoencoderKL decoder engine ------------------------------------------------------------------------------------
+// largest 16-bit conv / GEMM operand (input or output) of ONE image: the GEMM addresses each operand with a 32-bit byte
+// offset (gemm.hip: "larger than 4 GiB"), so batch x this must stay below that
+static int64_t vae_dec_image_operand_bytes(const smi_vae_config* c, int h, int w) {
+  const int L = c->n_levels, f = 1 << (L - 1);
+  int64_t hw = (int64_t)(h / f) * (w / f), m = hw * 64;
+  int ch = c->block_out_channels[L - 1];
+  m = std::max(m, hw * ch);
+  for (int i = 0; i < L; ++i) {
+    const int out = c->block_out_channels[L - 1 - i];
+    m = std::max(m, hw * std::max(ch, out));  // first resnet reads ch, the shortcut writes out
+    ch = out;
+    if (i != L - 1) {
+      hw *= 4;
+      m = std::max(m, hw * ch);  // the up-sampler's output
+    }
+  }
+  return m * 2;
+}
+static int check_vae_dec_cfg(const smi_vae_config* c, int batch, int h, int w) {
+  if (check_vae_cfg(c, batch, h, w)) return -1;
+  SMI_CHECK(c->in_channels <= 4, "VAE decoder: %d image channels (the fused conv_out takes at most 4)", c->in_channels);
+  SMI_CHECK(c->block_out_channels[0] <= 512, "VAE decoder: block_out_channels[0] = %d > 512", c->block_out_channels[0]);
+  SMI_CHECK(w % 4 == 0, "VAE decoder: image width %d must be a multiple of 4", w);
+  const int f = 1 << (c->n_levels - 1);
+  const int64_t na = (int64_t)(h / f) * (w / f);
+  SMI_CHECK(na * na * 4 < 0xFFFFFFF0ll, "VAE decoder: %dx%d is too large for the materialised mid-block attention "
+            "(%lld latent pixels)", h, w, (long long)na);
+  const int64_t per = vae_dec_image_operand_bytes(c, h, w);
+  const int64_t maxb = (0xFFFFFFF0ll - 1) / per;
+  SMI_CHECK(batch <= maxb, "VAE decoder: batch %d at %dx%d crosses the GEMM's 4 GiB operand limit (%lld MiB per image); "
+            "the largest batch that fits is %lld", batch, h, w, (long long)(per >> 20), (long long)maxb);
+  return 0;
+}
+static void vae_dec_setup(smi_engine* e, const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch,
+                          int h, int w) {
+  vae_setup(e, cfg, weights, n_weights, batch, h, w);
+  e->is_vae_dec = true;
+  const char* t = getenv("SMI_VAE_DEC_TAIL");
+  e->dec_tail_fused = !(t && t[0] == '0');
+}
+static int vae_dec_plan(const smi_vae_config* cfg, int batch, int h, int w, size_t out[2]) {
+  smi_engine e;
+  e.dry = true;
+  vae_dec_setup(&e, cfg, nullptr, 0, batch, h, w);
+  e.build_vae_dec();
+  if (e.err) return -1;
+  out[0] = align_up(e.wpack.peak, 4096);
+  e.forward_vae_dec(batch, nullptr, nullptr, nullptr);
+  out[1] = align_up(e.arena[0].peak, 4096);
+  return e.err ? -1 : 0;
+}
+
+int smi_vae_decoder_workspace_bytes(const smi_vae_config* cfg, int batch, int h, int w, size_t* bytes) {
+  if (check_vae_dec_cfg(cfg, batch, h, w)) return -1;
+  SMI_CHECK(bytes != nullptr, "bad arguments");
+  size_t r[2];
+  if (vae_dec_plan(cfg, batch, h, w, r)) return -1;
+  *bytes = r[0] + r[1] + 2 * 4096;
+  return 0;
+}
+
+int smi_vae_decoder_create(const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch, int h, int w,
+                           void* workspace, size_t workspace_bytes, void* stream, smi_engine** out) {
+  if (check_vae_dec_cfg(cfg, batch, h, w)) return -1;
+  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
+  size_t r[2];
+  if (vae_dec_plan(cfg, batch, h, w, r)) return -1;
+  SMI_CHECK(r[0] + r[1] + 2 * 4096 <= workspace_bytes, "workspace too small: need %zu bytes, got %zu",
+            r[0] + r[1] + 2 * 4096, workspace_bytes);
+  smi_engine* e = new smi_engine();
+  e->stream = (hipStream_t)stream;
+  vae_dec_setup(e, cfg, weights, n_weights, batch, h, w);
+  char* base = (char*)align_up((size_t)workspace, 4096);
+  e->ws = (char*)workspace;
+  e->ws_bytes = workspace_bytes;
+  e->wpack.base = base;
+  e->wpack.cap = r[0];
+  e->arena[0].base = base + r[0];
+  e->arena[0].cap = r[1];
+  e->build_vae_dec();
+  if (!e->err) (void)hipStreamSynchronize(e->stream);
+  if (e->err || hipGetLastError() != hipSuccess) {
+    if (!e->err) set_error("HIP error while packing the VAE decoder weights");
+    delete e;
+    return -1;
+  }
+  e->wmap.clear();
+  *out = e;
+  return 0;
+}
+
+int smi_vae_decode(smi_engine* e, int n, const float* latents, float* image_out, uint8_t* rgb8_out) {
+  SMI_CHECK(e && latents && image_out, "smi_vae_decode: NULL argument");
+  SMI_CHECK(e->is_vae && e->is_vae_dec, "smi_vae_decode: not a VAE decoder engine (create it with smi_vae_decoder_create)");
+  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  e->err = false;
+  return e->forward_vae_dec(n, latents, image_out, rgb8_out);
 }
 
 // ---- CLIP text encoder engine ------------------------------------------------------------------------------------------
@@ -2613,7 +2880,8 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
                              const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                              const float* lora_up_flat, float multiplier, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && sample && ctx && eps_out, "NULL argument");
-  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE / CLIP encoder (use smi_vae_encode / smi_clip_encode)");
+  SMI_CHECK(!e->is_vae && !e->is_clip,
+            "this engine is a VAE encoder / decoder or a CLIP encoder (use smi_vae_encode / smi_vae_decode / smi_clip_encode)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(n_adapted >= 0 && n_adapted <= n && n_adapted <= e->max_n_ad,
             "adapted batch %d outside [0, min(%d, %d)]", n_adapted, n, e->max_n_ad);
@@ -2630,6 +2898,7 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
                            const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                            const float* lora_up_flat, const float* multipliers, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && multipliers, "NULL argument");
+  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE encoder / decoder or a CLIP encoder: no UNet forward");
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "per-sample multipliers: 1..%d adapted samples", smi_engine::MAXS);
   float mref = 0.f;
   bool same = true;
@@ -2670,7 +2939,7 @@ int smi_unet_forward(smi_engine* e, int n, const float* sample, float timestep, 
 
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE / CLIP encoder: it has no backward");
+  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
   e->err = false;
   GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
   return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat);

@@ -105,6 +105,9 @@ size_t gn_partial_floats(int Nb, int HW, int G);  // floats of `partial` scratch
 int launch_groupnorm_fwd(int dtype, const void* x, const void* gamma, const void* beta, void* y, float* ab,
                          float* mean_rstd, float* partial, int Nb, int HW, int C, int G, float eps, int silu,
                          hipStream_t stream);
+// statistics only: the partial-sum launches (+ fold) and the affine a, b into `ab` ([2][Nb][C]) and mean_rstd; no y
+int launch_groupnorm_stats(int dtype, const void* x, const void* gamma, const void* beta, float* ab, float* mean_rstd,
+                           float* partial, int Nb, int HW, int C, int G, float eps, hipStream_t stream);
 // dx for y = silu?(GN(x)); needs x, gamma, beta, ab and mean_rstd from the forward.
 // `partial`: scratch f32, gn_partial_floats(Nb, HW, G) long
 // `add` (optional, may alias dx): gradient already accumulated for x, added in the same pass
@@ -158,6 +161,13 @@ int launch_f32_to_padded(int dtype, const float* src, int lds, int cols, void* d
 // scale_out[j] = scale, scale_out[inv_off + j] = 1 / scale
 int launch_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, float* scale_out, int inv_off,
                       hipStream_t stream);
+
+// AutoencoderKL decoder tail (vae_decode.hip): sample f32 [Nb, Cout, H, W] = conv_out(silu(x * a + b)) with x T [Nb, H, W, C],
+// a / b = ab / ab + Nb*C (launch_groupnorm_stats), w4 T [4][9*C] (conv pack, rows >= Cout zero), bias T [Cout], Cout <= 4;
+// rgb8 (optional) uint8 [Nb, H, W, Cout] = rint(clamp(sample / 2 + 0.5, 0, 1) * 255)
+int launch_vae_dec_tail(int dtype, const void* x, const float* ab, const void* w4, const void* bias, float* sample,
+                        uint8_t* rgb8, int Nb, int H, int W, int C, int Cout, hipStream_t stream);
+int launch_rgb8_from_nchw(const float* sample, uint8_t* rgb8, int Nb, int C, int HW, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------------------------
 // LoRA skinny kernels (rank r <= 32)

@@ -296,6 +296,46 @@ __device__ __forceinline__ void gn_apply_body(float* st /* LDS [G][2]: MODE 0 (m
     }
   }
 }
+// statistics only (the VAE decoder's fused tail applies the norm itself): the slot partials of sample n -> mean / rstd
+// per group with the apply kernels' head (same order), then the per-(n,c) affine a, b for all C channels
+template <typename T>
+__global__ __launch_bounds__(256) void gn_stats_kernel(const T* __restrict__ gamma, const T* __restrict__ beta,
+                                                       const float* __restrict__ partial, float* __restrict__ aa,
+                                                       float* __restrict__ bb, float* __restrict__ mean_rstd, int HW,
+                                                       int C, int G, int nchunk, float eps) {
+  extern __shared__ float st[];  // [G][2]
+  const int n = blockIdx.x, tid = threadIdx.x;
+  const int cpg = C / G;
+  const float cnt = (float)HW * (float)cpg;
+  for (int g = tid >> 3; g < G; g += 32) {
+    float s = 0.f, sq = 0.f;
+    for (int ch = tid & 7; ch < nchunk; ch += 8) {
+      const float* p = partial + (((int64_t)n * nchunk + ch) * G + g) * 2;
+      s += p[0];
+      sq += p[1];
+    }
+#pragma unroll
+    for (int o = 4; o > 0; o >>= 1) {
+      s += __shfl_xor(s, o);
+      sq += __shfl_xor(sq, o);
+    }
+    if (tid & 7) continue;
+    const float mean = s / cnt;
+    const float var = fmaxf(sq / cnt - mean * mean, 0.f);
+    const float rstd = rsqrtf(var + eps);
+    st[g * 2] = mean;
+    st[g * 2 + 1] = rstd;
+    mean_rstd[((int64_t)n * G + g) * 2] = mean;
+    mean_rstd[((int64_t)n * G + g) * 2 + 1] = rstd;
+  }
+  __syncthreads();
+  for (int c = tid; c < C; c += 256) {
+    const int g = c / cpg;
+    const float a = st[g * 2 + 1] * to_f(gamma[c]);
+    aa[(int64_t)n * C + c] = a;
+    bb[(int64_t)n * C + c] = to_f(beta[c]) - st[g * 2] * a;
+  }
+}
 template <typename T, int MODE, bool SILU>
 __global__ __launch_bounds__(256) void gn_apply_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                        const T* __restrict__ gamma, const T* __restrict__ beta,
@@ -829,6 +869,31 @@ int launch_groupnorm_fwd(int dtype, const void* x, const void* gamma, const void
   SMI_CHECK((size_t)gn_geom(C).rpar * C * 8 <= 65536, "groupnorm: C=%d too large for the LDS reduction", C);
   return dtype == DT_F16 ? gn_fwd_t<f16>(x, gamma, beta, y, ab, mean_rstd, partial, Nb, HW, C, G, eps, silu, stream)
                          : gn_fwd_t<bf16>(x, gamma, beta, y, ab, mean_rstd, partial, Nb, HW, C, G, eps, silu, stream);
+}
+
+int launch_groupnorm_stats(int dtype, const void* x, const void* gamma, const void* beta, float* ab, float* mean_rstd,
+                           float* partial, int Nb, int HW, int C, int G, float eps, hipStream_t stream) {
+  SMI_CHECK(C % 8 == 0 && C % G == 0, "groupnorm stats: C=%d must be a multiple of 8 and of G=%d", C, G);
+  SMI_CHECK((size_t)gn_geom(C).rpar * C * 8 <= 65536, "groupnorm stats: C=%d too large for the LDS reduction", C);
+  const int nchunk = gn_num_chunks(HW);
+  const size_t sm = (size_t)gn_geom(C).rpar * C * 2 * sizeof(float);
+  const size_t sa = (size_t)G * 2 * sizeof(float);
+  const int nslot = nchunk > GN_MAX_SLOTS ? GN_MAX_SLOTS : nchunk;
+  if (dtype == DT_F16) {
+    hipLaunchKernelGGL((gn_partial_kernel<f16, 0, false>), dim3(nchunk, Nb), dim3(256), sm, stream, (const f16*)x, nullptr,
+                       nullptr, nullptr, ab, ab, partial, Nb, HW, C, G, nchunk);
+    const float* red = gn_fold(partial, Nb, nchunk, G, stream);
+    hipLaunchKernelGGL(gn_stats_kernel<f16>, dim3(Nb), dim3(256), sa, stream, (const f16*)gamma, (const f16*)beta, red, ab,
+                       ab + (size_t)Nb * C, mean_rstd, HW, C, G, nslot, eps);
+  } else {
+    hipLaunchKernelGGL((gn_partial_kernel<bf16, 0, false>), dim3(nchunk, Nb), dim3(256), sm, stream, (const bf16*)x,
+                       nullptr, nullptr, nullptr, ab, ab, partial, Nb, HW, C, G, nchunk);
+    const float* red = gn_fold(partial, Nb, nchunk, G, stream);
+    hipLaunchKernelGGL(gn_stats_kernel<bf16>, dim3(Nb), dim3(256), sa, stream, (const bf16*)gamma, (const bf16*)beta, red,
+                       ab, ab + (size_t)Nb * C, mean_rstd, HW, C, G, nslot, eps);
+  }
+  SMI_HIP(hipGetLastError());
+  return 0;
 }
 
 // `partial` must hold Nb*nchunk*G*2 floats.  `a`, `b`: the forward's affine of these Nb samples ([Nb][C] each).
