@@ -14,7 +14,6 @@
 // forward's log-sum-exp; it is split into a dQ kernel (one workgroup per 128 queries, sweeping keys) and a dK/dV
 // kernel (one workgroup per 128 keys, sweeping queries): no atomics, bitwise reproducible.
 #include <stdlib.h>
-#include <type_traits>
 
 #include "kernels.h"
 
@@ -166,21 +165,11 @@ __device__ __forceinline__ int acc_row(int r, int h2) { return (r & 3) + 8 * (r 
 // 64 -> 4) or one of the SD-1.x widths inside a wider tile (40 -> 3 of the 64-wide tile, 80 -> 5 of the 96-wide one) -- with the run-time
 // `s < nsd` test hipcc wraps every (ds_read, MFMA) pair of the QK^T product in its own branch and waits lgkmcnt(0) after
 // each read: eight exposed LDS round trips per key tile and wave instead of eight reads in flight.
-// PRE (with EX): the query fragments are pre-multiplied by scale * log2(e) when they are loaded (once per workgroup; one
-// more 16-bit rounding of Q, of the size of the rounding Q already carries) and the running reference enters the score
-// product as its INITIAL ACCUMULATOR (-m_run in all sixteen registers: the query is on the lane, so it is a lane
-// constant, and it changes only when the lazy rescale fires).  The score tile then leaves its MFMA chain as
-// log2-domain exponents relative to the reference: p = exp2(acc), no multiply, no subtraction -- 32 of the ~150 VALU
-// instructions per key tile of a loop whose busiest resource is the SIMD's vector issue port (rocprofv3: VALU 60 %,
-// MFMA 47 % busy).
-// DEEP (kept as an A/B switch, SMI_ATTN_FWD_DEEP=1; measured: no effect): K / V tiles requested TWO tiles
-// ahead through two alternating register sets (the loop body is instantiated twice, so the sets are named, not indexed).
-template <typename T, int DP, int NSD, bool PRE, bool DEEP = false>
+template <typename T, int DP, int NSD>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
   using S = Stage<T, DP>;
   constexpr int NS = DP / 16, NB = DP / 32;
   constexpr bool EX = NSD > 0;  // the number of 16-wide k-steps is the compile-time NSD (0: run-time, from p.D)
-  static_assert(!PRE || (NSD == NS && NS <= 4), "PRE is the head_dim == tile depth form");
   // two LDS stages: tile t + 1 is written while tile t is being read, so ONE barrier per key tile orders both the
   // "everyone is done with stage s" and the "stage s ^ 1 is complete" edges (it was two barriers on one stage)
   __shared__ __attribute__((aligned(16))) T Ks2[2][TK * S::LDN];
@@ -208,28 +197,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     qf[s] = t.v;
   }
   const float sl = p.scale * LOG2E;
-  if constexpr (PRE) {
-#pragma unroll
-    for (int s = 0; s < NS; ++s)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) qf[s][j] = from_f<T>(to_f(qf[s][j]) * sl);
-  }
 
   f32x16 o[NB];
 #pragma unroll
   for (int i = 0; i < NB; ++i)
 #pragma unroll
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
-  float m_run = PRE ? 0.f : -INFINITY;  // PRE: in the log2 domain of the pre-scaled scores, fixed by the first tile
-  f32x16 minit;                         // PRE: -m_run in every register, the initial accumulator of the score chains
-#pragma unroll
-  for (int r = 0; r < 16; ++r) minit[r] = 0.f;
+  float m_run = -INFINITY;
   f32x4 l4 = {0.f, 0.f, 0.f, 0.f};  // running row sum (all four registers equal), see Sum4
 
   const int ntiles = (p.Nk + TK - 1) / TK;
   // K/V tiles are fetched one tile ahead into registers: the global-load latency hides under the MFMAs / softmax
   u32x4 rk[S::NIT], rv[S::NIT];
-  u32x4 rk2[DEEP ? S::NIT : 1], rv2[DEEP ? S::NIT : 1];  // DEEP: the second register set (tile kt + 2)
   S::load(rk, rK, 0, p.Nk, p.ldk, col0, p.D, tid);
   S::load(rv, rV, 0, p.Nk, p.ldv, col0, p.D, tid);
   S::store_nat(rk, Ks2[0], tid);
@@ -238,25 +217,18 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     S::load(rk, rK, TK, p.Nk, p.ldk, col0, p.D, tid);
     S::load(rv, rV, TK, p.Nk, p.ldv, col0, p.D, tid);
   }
-  if constexpr (DEEP) {
-    if (ntiles > 2) {
-      S::load(rk2, rK, 2 * TK, p.Nk, p.ldk, col0, p.D, tid);
-      S::load(rv2, rV, 2 * TK, p.Nk, p.ldv, col0, p.D, tid);
-    }
-  }
   __syncthreads();
-  constexpr int AHEAD = DEEP ? 3 : 2;  // the set a tile body frees is refilled with tile kt + AHEAD
-  // one key tile; (xk, xv) = the register set that holds tile kt + 1 on entry
+  // one key tile; (xk, xv) = the registers that hold tile kt + 1 on entry
   auto tile_body = [&](int kt, auto& xk, auto& xv) {
     const int k0 = kt * TK;
     const T* Ks = Ks2[kt & 1];
     const T* Vs = Vs2[kt & 1];
-    if (kt + 1 < ntiles) {  // tile kt + 1 (in registers since an earlier iteration) into the other stage, kt + AHEAD on its way
+    if (kt + 1 < ntiles) {  // tile kt + 1 (in registers since the previous tile) into the other stage, kt + 2 on its way
       S::store_nat(xk, Ks2[(kt + 1) & 1], tid);
       S::store_ld(xv, Vs2[(kt + 1) & 1], S::LDV, tid);
-      if (kt + AHEAD < ntiles) {
-        S::load(xk, rK, k0 + AHEAD * TK, p.Nk, p.ldk, col0, p.D, tid);
-        S::load(xv, rV, k0 + AHEAD * TK, p.Nk, p.ldv, col0, p.D, tid);
+      if (kt + 2 < ntiles) {
+        S::load(xk, rK, k0 + 2 * TK, p.Nk, p.ldk, col0, p.D, tid);
+        S::load(xv, rV, k0 + 2 * TK, p.Nk, p.ldv, col0, p.D, tid);
       }
     }
 
@@ -271,16 +243,10 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
         for (int s = 0; s < NSD; ++s) kfr[sub][s] = ld_frag_nat<T>(Ks, S::LDN, sub * 32 + ql, 16 * s + 8 * h2);
 #pragma unroll
       for (int sub = 0; sub < 2; ++sub) {
-        if constexpr (PRE) {
-          st[sub] = TT<T>::mfma32(kfr[sub][0], qf[0], minit);
 #pragma unroll
-          for (int s = 1; s < NSD; ++s) st[sub] = TT<T>::mfma32(kfr[sub][s], qf[s], st[sub]);
-        } else {
+        for (int r = 0; r < 16; ++r) st[sub][r] = 0.f;
 #pragma unroll
-          for (int r = 0; r < 16; ++r) st[sub][r] = 0.f;
-#pragma unroll
-          for (int s = 0; s < NSD; ++s) st[sub] = TT<T>::mfma32(kfr[sub][s], qf[s], st[sub]);
-        }
+        for (int s = 0; s < NSD; ++s) st[sub] = TT<T>::mfma32(kfr[sub][s], qf[s], st[sub]);
       }
     } else {
 #pragma unroll
@@ -316,47 +282,22 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     // exponent domain; until then probabilities are formed against the stale reference (p <= 256: exact in fp32,
     // representable in fp16 / bf16) and O, l stay un-rescaled.  o / l is unchanged mathematically; it saves the
     // 16 NB accumulator multiplies and an exp per tile on all but the first tile or two -- the loop is VALU-bound.
-    if constexpr (PRE) {
-      // mloc is already relative to the reference; the first tile always fixes it (whatever the size of its scores)
-      const bool need = kt == 0 || mloc > 8.f;
-      if (__builtin_amdgcn_ballot_w64(need)) {
-        const float d = need ? mloc : 0.f;
-        const float alpha = __builtin_amdgcn_exp2f(-d);  // 1 for lanes that keep their reference
-        m_run += d;
-        l4 *= alpha;
+    const bool need = (mloc - m_run) * sl > 8.f;  // both halves of a query agree (mloc is already combined)
+    if (__builtin_amdgcn_ballot_w64(need)) {
+      const float m_new = need ? mloc : m_run;
+      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sl);  // 1 for lanes that keep their reference
+      m_run = m_new;
+      l4 *= alpha;
 #pragma unroll
-        for (int i = 0; i < NB; ++i)
+      for (int i = 0; i < NB; ++i)
 #pragma unroll
-          for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) minit[r] -= d;
-#pragma unroll
-        for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) st[sub][r] -= d;  // this tile's exponents were formed against the old reference
-      }
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[sub][r] = __builtin_amdgcn_exp2f(st[sub][r]);
-    } else {
-      const bool need = (mloc - m_run) * sl > 8.f;  // both halves of a query agree (mloc is already combined)
-      if (__builtin_amdgcn_ballot_w64(need)) {
-        const float m_new = need ? mloc : m_run;
-        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sl);  // 1 for lanes that keep their reference
-        m_run = m_new;
-        l4 *= alpha;
-#pragma unroll
-        for (int i = 0; i < NB; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
-      }
-      const float mb = m_run * sl;
-#pragma unroll
-      for (int sub = 0; sub < 2; ++sub)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) st[sub][r] = __builtin_amdgcn_exp2f(st[sub][r] * sl - mb);
+        for (int r = 0; r < 16; ++r) o[i][r] *= alpha;
     }
+    const float mb = m_run * sl;
+#pragma unroll
+    for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[sub][r] = __builtin_amdgcn_exp2f(st[sub][r] * sl - mb);
     // O^T[d, q] += V^T[d, keys] . P^T[keys, q]
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
@@ -373,14 +314,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
       }
     __syncthreads();  // every wave is done with stage kt & 1, and stage (kt + 1) & 1 is complete
   };
-  if constexpr (DEEP) {
-    for (int kt = 0; kt < ntiles; kt += 2) {
-      tile_body(kt, rk, rv);
-      if (kt + 1 < ntiles) tile_body(kt + 1, rk2, rv2);
-    }
-  } else {
-    for (int kt = 0; kt < ntiles; ++kt) tile_body(kt, rk, rv);
-  }
+  for (int kt = 0; kt < ntiles; ++kt) tile_body(kt, rk, rv);
 
   const float l_tot = halves_sum(l4[0]);
   const float inv = 1.f / l_tot;
@@ -400,7 +334,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
       }
     if (p.lse && h2 == 0)
       p.lse[((int64_t)b * p.H + head) * p.Nq + q_idx] =
-          (PRE ? m_run * 0.6931471805599453f : m_run * p.scale) + __logf(l_tot);
+          m_run * p.scale + __logf(l_tot);
   }
 }
 
@@ -1147,10 +1081,8 @@ static int xs_grid_x(const AttnParams& p) {
   const int nqb = cdiv(p.Nq, 128);
   const int64_t heads = (int64_t)p.H * p.B;
   int chain = 1;
-  // measured (tools/bench_attn.py --xs, SMI_XS_CHAIN sweep): chaining pays while >= 5 workgroups per CU remain
+  // measured (tools/bench_attn.py --xs, chain-length sweep): chaining pays while >= 5 workgroups per CU remain
   while (chain < 4 && nqb % (2 * chain) == 0 && heads * (nqb / (2 * chain)) >= 1280) chain *= 2;
-  static const int forced = []() { const char* e = getenv("SMI_XS_CHAIN"); return e ? atoi(e) : 0; }();  // (experiments)
-  if (forced > 0 && nqb % forced == 0) chain = forced;
   return nqb / chain;
 }
 
@@ -1234,33 +1166,16 @@ int fwd_t(const AttnParams& p, hipStream_t st) {
   dim3 grid(cdiv(p.Nq, 128), p.H, p.B);
   constexpr int NS = DP / 16, ALT = alt_steps<DP>();
   const int nsd = (p.D + 15) / 16;
-  // OFF by default (opt in with SMI_ATTN_PRESCALE=1): +4..7 % on the forward, but the re-rounded Q costs accuracy on peaked
-  // rows -- log-sum-exp 2.9e-3 off on the spiked-key test (bar 2e-3 + 1e-4 rel), worst saved-weight element of the
-  // SD-XL trajectory test 2.2e-3 -> 5.1e-3 -- and parity is the first gate
-  static const bool pre = []() { const char* e = getenv("SMI_ATTN_PRESCALE"); return e && e[0] == '1'; }();
-  // PRE re-rounds Q (x scale log2 e) to the storage type: 2^-11 in fp16, 2^-9 in bf16 -- fp16 only
-  constexpr bool is_f16 = sizeof(T) == 2 && std::is_same<T, f16>::value;
   if (p.Nk <= XS_KEYS && xs_enabled()) {  // all keys at once (cross-attention on the text tokens)
     if (nsd == NS) return xs_fwd_launch<T, DP, NS>(p, st);
     if (ALT > 0 && nsd == ALT) return xs_fwd_launch<T, DP, (ALT > 0 ? ALT : NS)>(p, st);
   }
-  if constexpr (DP <= 64 && is_f16) {
-    if (p.D == DP && pre) {
-      hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS, true>), grid, dim3(256), 0, st, p);
-      SMI_HIP(hipGetLastError());
-      return 0;
-    }
-  }
-  static const bool deep = []() { const char* e = getenv("SMI_ATTN_FWD_DEEP"); return e && e[0] == '1'; }();
-  if (nsd == NS && deep && DP == 64) {
-    if constexpr (DP == 64) hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS, false, true>), grid, dim3(256), 0, st, p);
-  } else if (nsd == NS) {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS, false>), grid, dim3(256), 0, st, p);
-  } else if (ALT > 0 && nsd == ALT) {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, (ALT > 0 ? ALT : NS), false>), grid, dim3(256), 0, st, p);
-  } else {
-    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, 0, false>), grid, dim3(256), 0, st, p);
-  }
+  if (nsd == NS)
+    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS>), grid, dim3(256), 0, st, p);
+  else if (ALT > 0 && nsd == ALT)
+    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, (ALT > 0 ? ALT : NS)>), grid, dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((attn_fwd_kernel<T, DP, 0>), grid, dim3(256), 0, st, p);
   SMI_HIP(hipGetLastError());
   return 0;
 }
@@ -1318,10 +1233,7 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     else { if (xs_dq_launch<T, DP, ALTC>(p, st)) return -2; }
   } else if (p.dQ) {
     dim3 grid(cdiv(p.Nq, 128), p.H, p.B);
-    static const bool remat = []() { const char* e = getenv("SMI_ATTN_DQ_REMAT"); return e && e[0] == '1'; }();
-    if (form == 1 && remat)
-      hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, NS, true>), grid, dim3(256), 0, st, p);
-    else if (form == 1)
+    if (form == 1)
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, NS, false>), grid, dim3(256), 0, st, p);
     else if (form == 2)
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, ALTC, false>), grid, dim3(256), 0, st, p);

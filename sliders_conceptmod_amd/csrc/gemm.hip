@@ -415,32 +415,115 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(GemmParams p, const 
 
 bool gemm2_supported(const GemmParams& p);
 bool gemm2_geglu_supported(const GemmParams& p);
-int launch_gemm2(const GemmParams& p, int variant, hipStream_t stream);
 bool gemm3_supported(const GemmParams& p);
 int launch_gemm3(const GemmParams& p, hipStream_t stream);
 bool gemm4_supported(const GemmParams& p);
 int launch_gemm4(const GemmParams& p, hipStream_t stream);
 
-// SMI_GEMM=v1 forces the register-staged kernel, SMI_GEMM=128 / 256 forces a v2 tile height (A/B experiments)
-static int gemm_mode() {
-  static int mode = -1;
-  if (mode < 0) {
+// ---------------------------------------------------------------------------------------------------------------
+// Tile names.  SMI_GEMM forces a tile (A/B experiments; the overrides are bit-identical, tests/test_kernels_gpu.py);
+// the integer codes are the tuner's candidates (persisted in SMI_TUNE_FILE files) and SMI_SPLITK_V's values
+// (tools/bench_splitk.py, tools/check_splitk.py): never renumber them.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+struct TileName {
+  GemmTile tile;
+  const char* env;  // SMI_GEMM value, or null
+  int code;         // tuner candidate / SMI_SPLITK_V code, or -1
+};
+// where a tile cannot take a launch, fit_tile below says what runs instead
+constexpr TileName kTileNames[] = {
+    {GemmTile::Auto, nullptr, 0},           // the heuristic
+    {GemmTile::Auto, "no8ph", -1},          // the heuristic without the 256 x 256 tile
+    {GemmTile::Auto, "no5ph", -1},          // (the same)
+    {GemmTile::T128x128w8, "128", 1},
+    {GemmTile::T128x128w8, nullptr, 5},
+    {GemmTile::T256x128, "256", 2},
+    {GemmTile::T64x128, "64", -1},
+    {GemmTile::T64x128w4, "64w", 7},
+    {GemmTile::T128x160, "160", 4},
+    {GemmTile::T128x160w8, "160w", 10},
+    {GemmTile::T128x160Deep, nullptr, 11},
+    {GemmTile::T64x160, "64x160", 12},
+    {GemmTile::Gemm3, "8ph", 100},
+    {GemmTile::Gemm4, "5ph", 200},
+    {GemmTile::V1, "v1", -1},
+};
+GemmTile tile_of_code(int code) {
+  for (const TileName& t : kTileNames)
+    if (t.code == code) return t.tile;
+  return GemmTile::Auto;
+}
+int code_of_tile(GemmTile tile) {
+  for (const TileName& t : kTileNames)
+    if (t.tile == tile && t.code >= 0) return t.code;
+  return 0;
+}
+// the SMI_GEMM override, or null (unset or unknown: automatic selection).  Every override turns the tuner, the deep rule
+// and gemm3-by-rule off; every one but v1 keeps the split-K rule.
+const TileName* gemm_override() {
+  static const TileName* o = []() -> const TileName* {
     const char* e = getenv("SMI_GEMM");
-    mode = !e ? 0 : (!strcmp(e, "v1") ? 3 : (!strcmp(e, "128") ? 1 : (!strcmp(e, "256") ? 2 : (!strcmp(e, "convv1") ? 4 : (!strcmp(e, "64") ? 5 : (!strcmp(e, "8ph") ? 6 : (!strcmp(e, "no8ph") ? 7 : (!strcmp(e, "160") ? 8 : (!strcmp(e, "8w") ? 9 : (!strcmp(e, "no8w") ? 10 : (!strcmp(e, "64w") ? 11 : (!strcmp(e, "5ph") ? 12 : (!strcmp(e, "no5ph") ? 13 : (!strcmp(e, "160w") ? 14 : (!strcmp(e, "64x160") ? 15 : 0)))))))))))))));
+    for (const TileName& t : kTileNames)
+      if (e && t.env && !strcmp(e, t.env)) return &t;
+    return nullptr;
+  }();
+  return o;
+}
+bool forced_v1() { return gemm_override() && gemm_override()->tile == GemmTile::V1; }
+
+// The heuristic choice (`gemm3`: may it pick the 256 x 256 tile).
+GemmTile heuristic_tile(const GemmParams& p, bool gemm3) {
+  // shapes where the 256x256 tile is the better choice (measured, tools/bench_gemm.py)
+  // (one 256x256 workgroup per CU: it needs >= 2 full rounds of tiles to amortise its longer fill / epilogue; below that
+  // the 128-row v2 tiles with 2-3 resident workgroups per CU win)
+  // convs: only where Cout fills whole 256-column tiles (320 / 640 output channels lose 17-38 % of a tile row)
+  // (N = 1280 convs at 16384 rows: 320 tiles -> gemm2 128x160)
+  if (gemm3 && !(p.conv && p.N % 256 != 0) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 256) >= 512 && gemm3_supported(p))
+    return GemmTile::Gemm3;
+  // measured (tools/bench_gemm.py): the 256-row tile only pays for very wide outputs (N >= 4096: fewer LDS bytes
+  // staged per FLOP); at small N or short K the 128-row tile's extra resident workgroup per CU wins
+  const bool rows256 = (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 512 && (p.conv || p.N >= 4096);
+  // 128 x 160 tiles for the big grids (>= 4 tiles per CU; below that a launch is latency-bound and the smaller
+  // tile wins): cost = tiles per CU x tile area / relative tile efficiency -- reproduces the measured ratios
+  // (conv 262144 x 320: 858 vs 790 TF/s; 65536 x 640: 932 vs 1028; 16384 x 1280: 955 vs 867)
+  if (p.N % 160 == 0 && (!p.geglu_out || p.N % 320 == 0) && (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) >= 1024) {
+    auto cost = [&](int bm, int bn, double eff) {
+      const int64_t tiles = (int64_t)cdiv(p.M, bm) * cdiv(p.N, bn);
+      return (double)((tiles + 255) / 256) * bm * bn / eff;
+    };
+    if (cost(128, 160, 1.04) < cost(rows256 ? 256 : 128, 128, rows256 ? 1.10 : 1.0)) return GemmTile::T128x160;
   }
-  return mode;
+  // the 128 x 128 tile runs with 8 waves (measured better than 4 on every shape of tools/bench_gemm.py, most with
+  // an epilogue: 4096 x 1280 x 1280 + bias + residual 24.7 vs 27.8 us)
+  return rows256 ? GemmTile::T256x128 : GemmTile::T128x128w8;
 }
 
-// shapes where the 256x256 tile is the better choice (measured, tools/bench_gemm.py)
-// (one 256x256 workgroup per CU: it needs >= 2 full rounds of tiles to amortise its longer fill / epilogue; below that
-// the 128-row v2 tiles with 2-3 resident workgroups per CU win)
-// convs: only where Cout fills whole 256-column tiles (320 / 640 output channels lose 17-38 % of a tile row)
-static bool gemm3_wanted(const GemmParams& p) {
-  if (p.conv && p.N % 256 != 0) return false;
-  return (int64_t)cdiv(p.M, 256) * cdiv(p.N, 256) >= 512;  // (N = 1280 convs at 16384 rows: 320 tiles -> gemm2 128x160)
+// `tile` where it can take p (gemm2_supported(p) holds), else what stands in for it
+GemmTile fit_tile(GemmTile tile, const GemmParams& p, bool gemm3) {
+  switch (tile) {
+    case GemmTile::Auto: return heuristic_tile(p, gemm3);
+    case GemmTile::T64x128: return p.conv ? GemmTile::T128x128 : tile;
+    case GemmTile::T128x160:  // (GEGLU: a tile holds matching hidden / gate column groups)
+      return p.N % 8 == 0 && (!p.geglu_out || p.N % 320 == 0) ? tile : GemmTile::T128x128;
+    case GemmTile::T64x160:
+    case GemmTile::T128x160w8:
+    case GemmTile::T128x160Deep: return p.N % 160 == 0 && !p.geglu_out ? tile : heuristic_tile(p, gemm3);
+    case GemmTile::Gemm3: return gemm3_supported(p) ? tile : heuristic_tile(p, gemm3);
+    case GemmTile::Gemm4: return gemm4_supported(p) ? tile : heuristic_tile(p, gemm3);
+    default: return tile;
+  }
 }
+int launch_v1(const GemmParams& p, hipStream_t stream);
+int launch_tile(const GemmParams& p, GemmTile tile, hipStream_t stream) {
+  if (tile == GemmTile::Gemm3) return launch_gemm3(p, stream);
+  if (tile == GemmTile::Gemm4) return launch_gemm4(p, stream);
+  if (tile == GemmTile::V1) return launch_v1(p, stream);
+  return launch_gemm2(p, tile, stream);
+}
+}  // namespace
 
-bool gemm_geglu_supported(const GemmParams& p) { return gemm_mode() != 3 && gemm2_geglu_supported(p); }
+bool gemm_geglu_supported(const GemmParams& p) { return !forced_v1() && gemm2_geglu_supported(p); }
 
 // ---------------------------------------------------------------------------------------------------------------
 // Tile autotuning.  All kernel generations / tile layouts give bit-identical results (same K order, same epilogue
@@ -509,19 +592,11 @@ bool tune_enabled() {
   }
   return on == 1;
 }
-// candidate codes: 0 = heuristic, 1 = v2 128x128 (8 waves), 2 = v2 256x128, 4 = v2 128x160, 7 = v2 64x128, 10 = v2
-// 128x160 with 8 waves, 12 = v2 64x160,
-// 100 = v3 8-phase, 200 = v4 256x320 persistent
-int launch_candidate(const GemmParams& p, int cand, hipStream_t stream) {
-  if (cand == 200 && gemm4_supported(p)) return launch_gemm4(p, stream);
-  if (cand == 100 && gemm3_supported(p)) return launch_gemm3(p, stream);  // (layout re-checked: the key is shape-only)
-  if (cand == 0 || cand == 100 || cand == 200) {
-    if (gemm3_wanted(p) && gemm3_supported(p)) return launch_gemm3(p, stream);
-    return launch_gemm2(p, 0, stream);
-  }
-  return launch_gemm2(p, cand, stream);
+// (fit_tile re-checks the layout: the key is shape-only)
+int launch_candidate(const GemmParams& p, GemmTile cand, hipStream_t stream) {
+  return launch_tile(p, fit_tile(cand, p, true), stream);
 }
-int tuned_choice(const GemmParams& p, hipStream_t stream) {
+GemmTile tuned_choice(const GemmParams& p, hipStream_t stream) {
   TuneKey key;
   const int kv[18] = {(int)p.dtype, (int)p.conv, p.M, p.N, p.K, (int)(p.conv ? p.Cin : p.lda),
                       (int)(p.stride * 4 + p.upsample * 2 + p.transposed), (int)(p.res != nullptr), p.lora_r,
@@ -535,26 +610,30 @@ int tuned_choice(const GemmParams& p, hipStream_t stream) {
   std::lock_guard<std::mutex> lock(mu);
   auto& cache = tune_cache();
   auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int cands[14], nc = 0;
-  cands[nc++] = 0;
+  if (it != cache.end()) return tile_of_code(it->second);
+  // (order matters: ties go to the earlier candidate)
+  GemmTile cands[14];
+  int nc = 0;
+  cands[nc++] = GemmTile::Auto;
   const bool plain_conv = p.conv && p.stride == 1 && !p.upsample && !p.transposed;
   if (!p.conv || plain_conv) {
-    cands[nc++] = 1;
-    if ((int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 128) cands[nc++] = 2;
-    if (p.N % 160 == 0 && (!p.geglu_out || p.N % 320 == 0)) cands[nc++] = 4;
-    if (gemm3_supported(p) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 256) >= 192) cands[nc++] = 100;
-    if ((int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) <= 512) cands[nc++] = 7;  // 64 x 128 tiles for small grids
+    cands[nc++] = GemmTile::T128x128w8;
+    if ((int64_t)cdiv(p.M, 256) * cdiv(p.N, 128) >= 128) cands[nc++] = GemmTile::T256x128;
+    if (p.N % 160 == 0 && (!p.geglu_out || p.N % 320 == 0)) cands[nc++] = GemmTile::T128x160;
+    if (gemm3_supported(p) && (int64_t)cdiv(p.M, 256) * cdiv(p.N, 256) >= 192) cands[nc++] = GemmTile::Gemm3;
+    if ((int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) <= 512) cands[nc++] = GemmTile::T64x128w4;  // small grids
     // 64 x 160 tiles (4 waves of 32 x 80) where 128 x 160 tiles leave CUs idle
-    if (!p.geglu_out && p.N % 160 == 0 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 256) cands[nc++] = 12;
-    if (!p.geglu_out && p.N % 160 == 0 && p.K >= 1280 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 128) cands[nc++] = 11;
-    if (gemm4_supported(p) && (int64_t)(p.M / 256) * (p.N / 320) >= 128) cands[nc++] = 200;
+    if (!p.geglu_out && p.N % 160 == 0 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 256) cands[nc++] = GemmTile::T64x160;
+    if (!p.geglu_out && p.N % 160 == 0 && p.K >= 1280 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 128)
+      cands[nc++] = GemmTile::T128x160Deep;
+    if (gemm4_supported(p) && (int64_t)(p.M / 256) * (p.N / 320) >= 128) cands[nc++] = GemmTile::Gemm4;
     // about one 128 x 160 tile per CU: the eight-wave form of that tile
-    if (!p.geglu_out && p.N % 160 == 0 && p.N % 8 == 0 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 512) cands[nc++] = 10;
+    if (!p.geglu_out && p.N % 160 == 0 && p.N % 8 == 0 && (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 512)
+      cands[nc++] = GemmTile::T128x160w8;
   } else if (p.conv && p.upsample && gemm4_supported(p) && (int64_t)(p.M / 256) * (p.N / 320) >= 128) {
-    cands[nc++] = 200;  // up-sampler convs: gemm2's general gather or gemm4's row-aligned one
+    cands[nc++] = GemmTile::Gemm4;  // up-sampler convs: gemm2's general gather or gemm4's row-aligned one
   }
-  int best = 0;
+  GemmTile best = GemmTile::Auto;
   if (nc > 1) {
     GemmParams q = p;
     void* tmp = nullptr;
@@ -563,7 +642,7 @@ int tuned_choice(const GemmParams& p, hipStream_t stream) {
       if (hipMalloc(&tmp, bytes) != hipSuccess) {
         (void)hipGetLastError();
         cache[key] = 0;
-        return 0;
+        return GemmTile::Auto;
       }
       q.C = tmp;
     }
@@ -572,7 +651,7 @@ int tuned_choice(const GemmParams& p, hipStream_t stream) {
       (void)hipGetLastError();
       if (tmp) (void)hipFree(tmp);
       cache[key] = 0;
-      return 0;
+      return GemmTile::Auto;
     }
     float tbest = 0.f, t0 = 0.f;
     static const bool dump = getenv("SMI_TUNE_DUMP") != nullptr;  // candidate timings of every tuned key on stderr
@@ -586,12 +665,12 @@ int tuned_choice(const GemmParams& p, hipStream_t stream) {
       if (hipEventSynchronize(b) != hipSuccess) break;
       float ms = 0.f;
       (void)hipEventElapsedTime(&ms, a, b);
-      if (dump) fprintf(stderr, " %d:%.1fus", cands[i], ms * 500.f);
+      if (dump) fprintf(stderr, " %d:%.1fus", code_of_tile(cands[i]), ms * 500.f);
       if (i == 0) { t0 = tbest = ms; continue; }
       if (ms < 0.97f * t0 && ms < tbest) { tbest = ms; best = cands[i]; }
     }
     if (dump)
-      fprintf(stderr, "  -> %d   [%s M=%d N=%d K=%d%s%s%s%s]\n", best, p.conv ? "conv" : "gemm", p.M, p.N, p.K,
+      fprintf(stderr, "  -> %d   [%s M=%d N=%d K=%d%s%s%s%s]\n", code_of_tile(best), p.conv ? "conv" : "gemm", p.M, p.N, p.K,
               p.bias ? " bias" : "", p.res ? " res" : "", p.lora_r ? " lora" : "", p.geglu_out ? " geglu" : "");
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
@@ -601,8 +680,8 @@ int tuned_choice(const GemmParams& p, hipStream_t stream) {
     }
     (void)hipGetLastError();
   }
-  cache[key] = best;
-  tune_persist(key, best);
+  cache[key] = code_of_tile(best);
+  tune_persist(key, code_of_tile(best));
   return best;
 }
 }  // namespace
@@ -648,13 +727,6 @@ int splitk_slices(const GemmParams& p) {
   if (nk / 4 < lim) lim = nk / 4;
   const int64_t fit = (int64_t)(t_scratch_bytes / ((size_t)p.M * p.N * sizeof(float)));
   if (fit < lim) lim = fit;
-  static const bool pow2 = []() { const char* e = getenv("SMI_SPLITK_POW2"); return e && e[0] == '1'; }();
-  if (pow2) {  // rounds 3: the largest power of two that keeps the 128 x 128 tiles within the budget
-    if (budget / tiles < lim) lim = budget / tiles;
-    int s = 1;
-    while (2 * s <= lim) s *= 2;
-    return s;
-  }
   // Any slice count, chosen to FILL the budget with the slice kernel launch_splitk will take: 64 x 128 tiles when two or
   // more slices of them fit, else 128 x 128.  2048 x 1280 x 5120 (160 tiles): two slices were 320 workgroups on 256 CUs
   // (50.7 us), three are 480 (43.7); 2048 x 640 x 2560: four slices of 128 x 128 (320 workgroups, 22.9 us) -> three of
@@ -664,11 +736,9 @@ int splitk_slices(const GemmParams& p) {
   if (s < 2) s = budget / tiles < lim ? budget / tiles : lim;
   return s < 1 ? 1 : (int)s;
 }
-int launch_splitk(const GemmParams& p, int S, hipStream_t stream, int variant = -1) {
-  if (p.conv) {
-    SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
-              "conv: inconsistent geometry");
-  }
+// `slice`: the slice kernel (a gemm2 tile), Auto for the rule's
+int launch_splitk(const GemmParams& p, int S, GemmTile slice, hipStream_t stream) {
+  SMI_CHECK(p.lora_seg % 4 == 0, "gemm: lora_seg %% 4 != 0");  // the finish kernel takes one xa row per four columns
   GemmParams q = p;  // the slices: plain accumulation into fp32 slabs [S][M][N]
   q.C = t_scratch;
   q.ldc = p.N;
@@ -677,13 +747,10 @@ int launch_splitk(const GemmParams& p, int S, hipStream_t stream, int variant = 
   q.lora_r = 0;
   q.lora_xa = q.lora_up = nullptr;
   q.ksplit = S;
-  // 64 x 128 tiles (4 waves) while that still leaves CUs idle, else the 128 x 128 eight-wave tile.  (SMI_SPLITK_T160=1: the
-  // 128 x 160 eight-wave tile where N allows -- back to back it wins, 2048 x 1280 x 5120 in two slices 46.5 vs 47.3 us, inside
-  // a pass it loses: 61.4 vs 58.2 us there, SD-1.4 pre-roll 174.0 vs 172.3 ms.)
-  const int64_t wg64 = (int64_t)cdiv(p.M, 64) * cdiv(p.N, 128) * S;
-  static const bool t160 = []() { const char* e = getenv("SMI_SPLITK_T160"); return e && e[0] == '1'; }();
-  const int v = wg64 <= 512 ? 7 : (t160 && p.N % 160 == 0 ? 10 : 5);
-  if (launch_gemm2(q, variant >= 0 ? variant : v, stream) != 0) return -1;
+  // 64 x 128 tiles (4 waves) while that still leaves CUs idle, else the 128 x 128 eight-wave tile
+  if (slice == GemmTile::Auto)
+    slice = (int64_t)cdiv(p.M, 64) * cdiv(p.N, 128) * S <= 512 ? GemmTile::T64x128w4 : GemmTile::T128x128w8;
+  if (launch_gemm2(q, slice, stream) != 0) return -1;
   const int64_t total = (int64_t)p.M * (p.N / 4);
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
 #define FIN(TT_, NS_) hipLaunchKernelGGL((splitk_finish_kernel<TT_, NS_>), dim3(grid), dim3(256), 0, stream, p, (const float*)t_scratch, S)
@@ -714,67 +781,53 @@ void set_gemm_scratch(void* ws, size_t bytes) {
 int launch_gemm(const GemmParams& p, hipStream_t stream) {
   SMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
   SMI_CHECK(!p.geglu_out || gemm_geglu_supported(p), "gemm: fused GEGLU not available for this shape/layout");
-  // SMI_SPLITK_DEBUG (tools/bench_splitk.py): slice count and slice-kernel variant of THIS call from SMI_SPLITK_S / _V
+  if (p.conv) {
+    SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
+              "conv: inconsistent geometry");
+  }
+  // SMI_SPLITK_DEBUG (tools/bench_splitk.py): slice count and slice kernel (a tile code) of THIS call from SMI_SPLITK_S / _V
   static const bool splitk_debug = getenv("SMI_SPLITK_DEBUG") != nullptr;
   if (splitk_debug && gemm2_supported(p) && !p.geglu_out) {
     const char* es = getenv("SMI_SPLITK_S");
     const char* ev = getenv("SMI_SPLITK_V");
-    const int S = es ? atoi(es) : 0, V = ev ? atoi(ev) : 0;
-    if (S > 1 && t_scratch && (size_t)S * p.M * p.N * sizeof(float) <= t_scratch_bytes) return launch_splitk(p, S, stream, V);
-    if (S == 1) return launch_gemm2(p, V, stream);
+    const int S = es ? atoi(es) : 0;
+    const GemmTile t = fit_tile(tile_of_code(ev ? atoi(ev) : 0), p, false);
+    if (S > 1 && t_scratch && (size_t)S * p.M * p.N * sizeof(float) <= t_scratch_bytes) return launch_splitk(p, S, t, stream);
+    if (S == 1) return launch_gemm2(p, t, stream);
   }
-  if (gemm_mode() != 3) {
+  const TileName* forced = gemm_override();
+  if (!forced_v1()) {
     const int S = splitk_slices(p);
-    if (S > 1) return launch_splitk(p, S, stream);
+    if (S > 1) return launch_splitk(p, S, GemmTile::Auto, stream);
   }
+  if (forced_v1() || !gemm2_supported(p)) return launch_v1(p, stream);
+  if (forced) return launch_tile(p, fit_tile(forced->tile, p, false), stream);
   // One 128 x 160 tile per CU with a long K (the 4096-row backward GEMMs and convs): the eight-wave tile with the
   // four-stage deep-prefetch loop, by RULE and not by tuning -- the tuner times candidates back to back with their
   // operands hot in L2 / the Infinity Cache, where prefetch depth buys nothing (121 vs 120 us at 4096 x 1280 x 10240);
   // inside the backward pass the operands come from HBM and the deep form wins (153 -> 129 us, conv K = 11520:
   // 193 -> 160 us; measured in the step, A/B on one device).  Bit-identical to every other form.  SMI_GEMM_DEEP=0 turns
   // the rule off, SMI_GEMM_DEEP_K moves the K threshold.
-  if (gemm_mode() == 0) {
-    // grids of at most `small_grid` 128 x 160 tiles (half the CUs idle: SD-1.x at batch 1-2, the deepest UNet level) are
-    // left to the tuner, which can give them 64-row tiles (twice the workgroups) -- or this same deep form (candidate 11)
-    static int deep = -1, deep_k = 1280, small_grid = 128;
-    if (deep < 0) {
-      const char* e = getenv("SMI_GEMM_DEEP");
-      deep = (e && !strcmp(e, "0")) ? 0 : 1;
-      if (const char* k = getenv("SMI_GEMM_DEEP_K")) deep_k = atoi(k);
-      if (const char* k = getenv("SMI_GEMM_SMALL_GRID")) small_grid = atoi(k);
-    }
-    if (deep && gemm2_supported(p) && !p.geglu_out && p.N % 160 == 0 && p.K >= deep_k &&
-        (int64_t)cdiv(p.M, 128) * (p.N / 160) <= 320 && (int64_t)cdiv(p.M, 128) * (p.N / 160) > small_grid &&
-        (!p.conv || (p.stride == 1 && !p.upsample && !p.transposed))) {
-      if (p.conv) {
-        SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout, "conv: inconsistent geometry");
-      }
-      static const int deep_variant = []() { const char* e = getenv("SMI_GEMM_DEEP_VARIANT"); return e ? atoi(e) : 11; }();
-      return launch_gemm2(p, deep_variant, stream);  // (11 = eight-wave 128 x 160 deep loop; others for A/B experiments)
-    }
+  // Grids of at most `small_grid` 128 x 160 tiles (half the CUs idle: SD-1.x at batch 1-2, the deepest UNet level) are
+  // left to the tuner, which can give them 64-row tiles (twice the workgroups) -- or this same deep form.
+  static int deep = -1, deep_k = 1280, small_grid = 128;
+  if (deep < 0) {
+    const char* e = getenv("SMI_GEMM_DEEP");
+    deep = (e && !strcmp(e, "0")) ? 0 : 1;
+    if (const char* k = getenv("SMI_GEMM_DEEP_K")) deep_k = atoi(k);
+    if (const char* k = getenv("SMI_GEMM_SMALL_GRID")) small_grid = atoi(k);
   }
-  if (gemm_mode() == 0 && tune_enabled() && gemm2_supported(p) && (int64_t)p.M * p.N >= (1 << 17)) {
-    if (p.conv) {
-      SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
-                "conv: inconsistent geometry");
-    }
-    return launch_candidate(p, tuned_choice(p, stream), stream);
-  }
-  // v2 (LDS-DMA staging, full-row epilogue) serves dense GEMMs and convs; SMI_GEMM=convv1 keeps convs on v1, =v1 all
-  // v3 (256x256 tile, 8-phase schedule): SMI_GEMM=8ph forces it wherever its layout rules hold, =no8ph disables it
-  // v4 (256x320 tile, persistent): SMI_GEMM=5ph forces it wherever its layout rules hold
-  if (gemm_mode() == 12 && gemm4_supported(p)) return launch_gemm4(p, stream);
-  if (gemm_mode() == 14 && gemm2_supported(p) && !p.geglu_out && p.N % 160 == 0) return launch_gemm2(p, 10, stream);
-  if (gemm_mode() == 15 && gemm2_supported(p) && !p.geglu_out && p.N % 160 == 0) return launch_gemm2(p, 12, stream);
-  if ((gemm_mode() == 6 || ((gemm_mode() == 0 || gemm_mode() == 10) && gemm3_wanted(p))) && gemm3_supported(p))
-    return launch_gemm3(p, stream);
-  if (gemm_mode() != 3 && gemm2_supported(p) && (!p.conv || gemm_mode() != 4)) {
-    if (p.conv) {
-      SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
-                "conv: inconsistent geometry");
-    }
-    return launch_gemm2(p, gemm_mode() == 11 ? 7 : gemm_mode() == 10 ? 6 : gemm_mode() == 9 ? 5 : gemm_mode() == 8 ? 4 : ((gemm_mode() == 4 || gemm_mode() >= 6) ? 0 : (gemm_mode() == 5 ? 3 : gemm_mode())), stream);
-  }
+  const int64_t tiles160 = (int64_t)cdiv(p.M, 128) * (p.N / 160);
+  if (deep && !p.geglu_out && p.N % 160 == 0 && p.K >= deep_k && tiles160 <= 320 && tiles160 > small_grid &&
+      (!p.conv || (p.stride == 1 && !p.upsample && !p.transposed)))
+    return launch_gemm2(p, GemmTile::T128x160Deep, stream);
+  if (tune_enabled() && (int64_t)p.M * p.N >= (1 << 17)) return launch_candidate(p, tuned_choice(p, stream), stream);
+  return launch_tile(p, heuristic_tile(p, true), stream);
+}
+
+namespace {
+// the register-staged kernel: operands gemm2 cannot take (alignment, layout) and SMI_GEMM=v1
+int launch_v1(const GemmParams& p, hipStream_t stream) {
   SMI_CHECK(p.K % 8 == 0 && p.N % 4 == 0, "gemm: K %% 8 and N %% 4 must be 0 (K=%d N=%d)", p.K, p.N);
   SMI_CHECK(p.ldc % 4 == 0, "gemm: ldc %% 4 != 0");
   SMI_CHECK(p.lora_seg % 4 == 0, "gemm: lora_seg %% 4 != 0");
@@ -804,6 +857,7 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
   SMI_HIP(hipGetLastError());
   return 0;
 }
+}  // namespace
 
 int launch_conv3x3_small(int dtype, const void* in, const void* w, const void* bias, void* out, int out_f32, int Nb,
                          int H, int W, int Cin, int Cout, hipStream_t stream) {

@@ -634,73 +634,34 @@ bool gemm2_supported(const GemmParams& p) {
 }
 
 // fused GEGLU: a tile must hold matching hidden / gate column groups, i.e. N is a multiple of 2 x the tile width of
-// whichever variant launch_gemm2 will pick (N % 256 for the 128-column tiles, N % 320 for the 160-column ones)
+// whichever tile launch_gemm picks (N % 256 for the 128-column tiles, N % 320 for the 160-column ones)
 bool gemm2_geglu_supported(const GemmParams& p) {
   return gemm2_supported(p) && !p.conv && !p.out_f32 && !p.res && !p.rowvec && p.lora_r == 0 && p.N % 256 == 0 &&
          (reinterpret_cast<uintptr_t>(p.geglu_out) & 15) == 0;
 }
 
-int launch_gemm2(const GemmParams& p, int variant, hipStream_t stream) {
-  // variant: 0 = auto, 1 = 128-row tile, 2 = 256-row tile, 3 = 64-row tile, 4 = 128 x 160 tile,
-  //          5 = 128 x 128 tile with 8 waves
-  int wm = 2, nl = 0;
-  const bool ok160 = p.N % 8 == 0 && (!p.geglu_out || p.N % 320 == 0);
-  if (variant == 2) wm = 4;
-  else if (variant == 0 || variant == 6) {
-    // measured (tools/bench_gemm.py): the 256-row tile only pays for very wide outputs (N >= 4096: fewer LDS bytes
-    // staged per FLOP); at small N or short K the 128-row tile's extra resident workgroup per CU wins
-    const int64_t tiles256 = (int64_t)cdiv(p.M, 256) * cdiv(p.N, 128);
-    if (tiles256 >= 512 && p.N >= 4096 && !p.conv) wm = 4;
-    if (p.conv && tiles256 >= 512) wm = 4;
-    // 128 x 160 tiles for the big grids (>= 4 tiles per CU; below that a launch is latency-bound and the smaller
-    // tile wins): cost = tiles per CU x tile area / relative tile efficiency -- reproduces the measured ratios
-    // (conv 262144 x 320: 858 vs 790 TF/s; 65536 x 640: 932 vs 1028; 16384 x 1280: 955 vs 867)
-    if (ok160 && p.N % 160 == 0 && (int64_t)cdiv(p.M, 128) * cdiv(p.N, 128) >= 1024) {
-      auto cost = [&](int bm, int bn, double eff) {
-        const int64_t tiles = (int64_t)cdiv(p.M, bm) * cdiv(p.N, bn);
-        return (double)((tiles + 255) / 256) * bm * bn / eff;
-      };
-      if (cost(128, 160, 1.04) < cost(64 * wm, 128, wm == 4 ? 1.10 : 1.0)) { wm = 2; nl = 1; }
-    }
+template <int WM, int NL, bool DEEP = false>
+int launch_tile(const GemmParams& p, hipStream_t stream) {
+  if (p.dtype == DT_F16)
+    return p.conv ? launch_t<f16, true, WM, NL, DEEP>(p, stream) : launch_t<f16, false, WM, NL, DEEP>(p, stream);
+  return p.conv ? launch_t<bf16, true, WM, NL, DEEP>(p, stream) : launch_t<bf16, false, WM, NL, DEEP>(p, stream);
+}
+
+int launch_gemm2(const GemmParams& p, GemmTile tile, hipStream_t stream) {
+  switch (tile) {
+    case GemmTile::T128x128: return launch_tile<2, 0>(p, stream);
+    case GemmTile::T128x128w8: return launch_tile<2, 2>(p, stream);
+    case GemmTile::T256x128: return launch_tile<4, 0>(p, stream);
+    case GemmTile::T64x128:
+      SMI_CHECK(!p.conv, "gemm: the 64 x 128 two-wave tile takes no convs");
+      return p.dtype == DT_F16 ? launch_t<f16, false, 1, 0>(p, stream) : launch_t<bf16, false, 1, 0>(p, stream);
+    case GemmTile::T64x128w4: return launch_tile<1, 2>(p, stream);
+    case GemmTile::T128x160: return launch_tile<2, 1>(p, stream);
+    case GemmTile::T64x160: return launch_tile<1, 3>(p, stream);
+    case GemmTile::T128x160w8: return launch_tile<2, 3>(p, stream);
+    case GemmTile::T128x160Deep: return launch_tile<2, 3, true>(p, stream);
+    default: SMI_CHECK(false, "gemm: tile %d is not a gemm2 tile", (int)tile);
   }
-  // the 128 x 128 tile runs with 8 waves (measured better than 4 on every shape of tools/bench_gemm.py, most with
-  // an epilogue: 4096 x 1280 x 1280 + bias + residual 24.7 vs 27.8 us); variant 6 = auto with the 4-wave form
-  if ((variant == 0 || variant == 1) && wm == 2 && nl == 0) nl = 2;
-  if (variant == 3) wm = 1;
-  if (variant == 4 && ok160) { wm = 2; nl = 1; }
-  if (variant == 5) { wm = 2; nl = 2; }
-  if (variant == 7) { wm = 1; nl = 2; }  // 64 x 128 tile, 4 waves of 32 x 64: twice the tiles for small grids
-  if (variant == 12 && ok160 && !p.geglu_out) {  // 64 x 160 tile, 4 waves of 32 x 80: small grids with N % 160 == 0
-    if (p.dtype == DT_F16) return p.conv ? launch_t<f16, true, 1, 3>(p, stream) : launch_t<f16, false, 1, 3>(p, stream);
-    return p.conv ? launch_t<bf16, true, 1, 3>(p, stream) : launch_t<bf16, false, 1, 3>(p, stream);
-  }
-  if ((variant == 10 || variant == 11) && ok160 && !p.geglu_out) {  // 128 x 160 tile with eight waves of 32 x 80 (NL = 3)
-    if (variant == 11) {  // ... with the deep-prefetch loop
-      if (p.dtype == DT_F16)
-        return p.conv ? launch_t<f16, true, 2, 3, true>(p, stream) : launch_t<f16, false, 2, 3, true>(p, stream);
-      return p.conv ? launch_t<bf16, true, 2, 3, true>(p, stream) : launch_t<bf16, false, 2, 3, true>(p, stream);
-    }
-    if (p.dtype == DT_F16) return p.conv ? launch_t<f16, true, 2, 3>(p, stream) : launch_t<f16, false, 2, 3>(p, stream);
-    return p.conv ? launch_t<bf16, true, 2, 3>(p, stream) : launch_t<bf16, false, 2, 3>(p, stream);
-  }
-#define GO(TT_, CV, W_, NL_) return launch_t<TT_, CV, W_, NL_>(p, stream)
-#define PICK(TT_, CV)                            \
-  do {                                           \
-    if (nl == 2 && wm == 1) GO(TT_, CV, 1, 2);   \
-    if (nl == 2) GO(TT_, CV, 2, 2);              \
-    if (nl) GO(TT_, CV, 2, 1);                   \
-    if (wm == 4) GO(TT_, CV, 4, 0);              \
-    if (wm == 1 && !CV) GO(TT_, false, 1, 0);    \
-    GO(TT_, CV, 2, 0);                           \
-  } while (0)
-  if (p.dtype == DT_F16) {
-    if (p.conv) PICK(f16, true); else PICK(f16, false);
-  } else {
-    if (p.conv) PICK(bf16, true); else PICK(bf16, false);
-  }
-#undef PICK
-#undef GO
-  return -1;
 }
 
 }  // namespace smi

@@ -635,17 +635,6 @@ bool gemm2_supported(const GemmParams& p);
 // dense GEMMs and plain 3x3 convs on whole 256 x 320 tiles
 bool gemm4_supported(const GemmParams& p) {
   if (!gemm2_supported(p)) return false;
-  {  // SMI_G4_DENY (debugging): bit mask of launch classes kept off this kernel
-    static const int deny = []() { const char* e = getenv("SMI_G4_DENY"); return e ? atoi(e) : 0; }();
-    if ((deny & 1) && p.conv && !p.upsample && p.lora_r > 0) return false;
-    if ((deny & 2) && p.conv && p.Cin == 64) return false;
-    if ((deny & 4) && p.conv && p.upsample && p.lora_r > 0) return false;
-    if ((deny & 8) && !p.conv && p.lora_r > 0 && p.lora_row0 > 0) return false;
-    if ((deny & 16) && p.conv && p.res == p.C && p.res) return false;
-    if ((deny & 32) && p.conv && p.upsample) return false;
-    if ((deny & 64) && p.conv) return false;
-    if ((deny & 128) && !p.conv && p.lora_r > 0) return false;
-  }
   if (p.geglu_out && (p.conv || p.out_f32 || p.res || p.rowvec || p.lora_r > 0 ||
                       (reinterpret_cast<uintptr_t>(p.geglu_out) & 15) != 0))
     return false;

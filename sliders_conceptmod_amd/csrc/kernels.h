@@ -59,6 +59,24 @@ struct GemmParams {
   int ksplit = 0;
 };
 int launch_gemm(const GemmParams& p, hipStream_t stream);
+// The kernels launch_gemm selects among (gemm.hip).  The gemm2 tiles are gemm_glds_kernel<WM, NL, DEEP> (gemm2.hip):
+// BM x BN with 4 or 8 waves.  All of them give the same bits.
+enum class GemmTile {
+  Auto,          // not a kernel: the heuristic's choice
+  T128x128,      // gemm2 (2, 0), 4 waves
+  T128x128w8,    // gemm2 (2, 2), 8 waves
+  T256x128,      // gemm2 (4, 0)
+  T64x128,       // gemm2 (1, 0), 2 waves, dense only
+  T64x128w4,     // gemm2 (1, 2), 4 waves
+  T128x160,      // gemm2 (2, 1), 4 waves
+  T64x160,       // gemm2 (1, 3)
+  T128x160w8,    // gemm2 (2, 3), 8 waves
+  T128x160Deep,  // gemm2 (2, 3, deep): the eight-wave tile with the four-stage prefetch loop
+  Gemm3,         // 256 x 256, 8-phase schedule (gemm3.hip)
+  Gemm4,         // 256 x 320, persistent (gemm4.hip)
+  V1,            // register-staged kernel: the fallback for operands gemm2 cannot take
+};
+int launch_gemm2(const GemmParams& p, GemmTile tile, hipStream_t stream);  // the gemm2 tiles only
 // Scratch for split-K partial sums (fp32 slabs), set by whoever owns memory (the engine, per call; tests through
 // smi_op_gemm_scratch) for the calling host thread; without it launch_gemm never splits.  Launches that use it are ordered
 // on their stream, so one buffer serves every launch of a pass.
@@ -98,7 +116,6 @@ int launch_attn_bwd(const AttnParams& p, hipStream_t stream);
 // GroupNorm over [Nb, HW, C]; writes per-(n,c) affine a,b (f32 [Nb,C] each: y = x*a + b) into `ab` ([2,Nb,C]) and
 // y = (silu?)(x*a+b).  `partial` is scratch f32, gn_partial_floats(Nb, HW, G) long ([Nb, nchunk, G, 2], nchunk from gn_num_chunks(HW), + the fold).
 int gn_num_chunks(int HW);
-int gn_coop_timeouts();  // workgroups of the cooperative one-launch form that gave up waiting (0), norm.hip
 size_t gn_partial_floats(int Nb, int HW, int G);  // floats of `partial` scratch (chunk partials + their fold for maps > 128 x 128)
 // ab: [2][Nb][C] -- a = ab, b = ab + Nb*C.  The backward takes the two halves as separate pointers so that it can run
 // on a sample sub-range of a larger forward batch.

@@ -1,5 +1,6 @@
 """Split-K slices + finish against the un-split kernel, every slice count the rule can pick (2..8, 16) on both slice kernels,
-with and without an epilogue / a rank-r delta: fp32 outputs must agree to summation-order noise.  Runs with
+with and without an epilogue / a rank-r delta: fp32 outputs must agree to summation-order noise; a rank-r delta whose
+column segment is not a multiple of 4 must be refused.  Runs with
 SMI_SPLITK_DEBUG=1 (set here, before the library loads); tests/test_kernels_gpu.py runs it in a subprocess."""
 import ctypes as C
 import os
@@ -55,6 +56,17 @@ def main():
                 got16 = run(S, V, False)
                 # one 16-bit rounding of sums that differ by fp32 summation order: a rare last-bit flip
                 assert (got16.float() - base16.float()).abs().max().item() <= 2.0 ** -10 * base16.float().abs().max().item() * 2
+    # lora_seg % 4 != 0 cannot be split (the finish kernel takes one xa row per four columns): an error, not numbers
+    M, N, K, r, seg = 256, 1272, 1280, 4, 6
+    a = torch.randn(M, K, device="cuda", generator=g).half()
+    w = (torch.randn(N, K, device="cuda", generator=g) * K ** -0.5).half()
+    xa = torch.randn(M, r * (N // seg), device="cuda", generator=g)
+    up = torch.randn(N, r, device="cuda", generator=g) * 0.1
+    c = torch.empty(M, N, device="cuda", dtype=torch.float16)
+    os.environ["SMI_SPLITK_S"], os.environ["SMI_SPLITK_V"] = "2", "5"
+    rc = lib.smi_op_gemm_rows(0, P(a), P(w), P(c), M, N, K, None, None, P(xa), P(up), r, 0.5, 0, seg, None)
+    torch.cuda.synchronize()
+    assert rc != 0, "split-K took lora_seg % 4 != 0"
     print(f"split-K check ok: worst fp32 deviation from the un-split kernel {worst:.2e}")
 
 
