@@ -213,7 +213,38 @@ def arena_bytes(cfg_c: UNetConfigC, sites: Sequence[dict], batch: int, h: int, w
     return out.value
 
 
-class Engine:
+class _EngineBase:
+    """What the four engine wrappers share: the smi_engine `handle`, the `workspace` tensor it lives in, the weight
+    tensors it borrows (kept alive for as long as the wrapper), and their release."""
+
+    handle = None
+
+    def _create(self, prefix: str, cfg_c, shape: tuple, state: dict, dtype: torch.dtype, device):
+        """smi_<prefix>workspace_bytes(cfg, *shape) -> workspace on `device` -> smi_<prefix>create(cfg, weights, *shape)."""
+        size_fn, create_fn = f"smi_{prefix}workspace_bytes", f"smi_{prefix}create"
+        out = C.c_size_t(0)
+        check(getattr(lib(), size_fn)(C.byref(cfg_c), *shape, C.byref(out)), size_fn)
+        self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
+        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.workspace.device):
+            check(getattr(lib(), create_fn)(C.byref(cfg_c), warr, len(state), *shape, ptr(self.workspace), out.value,
+                                            stream_ptr(), C.byref(handle)), create_fn)
+        self.handle = handle
+
+    def close(self):
+        if self.handle:
+            lib().smi_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Engine(_EngineBase):
     """Owns one smi_engine plus the torch tensors backing its workspace.
 
     The packed weights are shape-independent; `plan(batch, batch_adapted, h, w, ctx_len)` switches the engine to
@@ -230,29 +261,8 @@ class Engine:
         self.batch, self.h, self.w, self.ctx_len = batch, h, w, ctx_len
         self.batch_adapted = batch if batch_adapted is None else batch_adapted
         self.sites = list(sites)
-        nbytes = workspace_bytes(self.cfg_c, sites, batch, h, w, ctx_len, self.batch_adapted)
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        self._weights_keepalive = []
-        warr = (WeightC * len(state))()
-        names = []
-        for i, (k, v) in enumerate(state.items()):
-            if v.dtype != dtype or not v.is_contiguous() or v.device != self.workspace.device:
-                raise SmiError(f"weight {k}: expected contiguous {dtype} on {self.workspace.device}")
-            nb = k.encode()
-            names.append(nb)
-            warr[i].name = nb
-            warr[i].data = v.data_ptr()
-            warr[i].ndim = v.ndim
-            for d in range(v.ndim):
-                warr[i].shape[d] = v.shape[d]
-            self._weights_keepalive.append(v)
-        sarr, keep = make_sites(sites)
-        handle = C.c_void_p()
-        with torch.cuda.device(self.workspace.device):
-            check(lib().smi_create(C.byref(self.cfg_c), warr, len(state), sarr, len(sites), batch, self.batch_adapted,
-                                   h, w, ctx_len, ptr(self.workspace), nbytes, stream_ptr(), C.byref(handle)),
-                  "smi_create")
-        self.handle = handle
+        sarr, _keep = make_sites(sites)
+        self._create("", self.cfg_c, (sarr, len(sites), batch, self.batch_adapted, h, w, ctx_len), state, dtype, device)
         self.stream = torch.cuda.current_stream().cuda_stream
         self._home = (batch, self.batch_adapted, h, w, ctx_len)  # the shape the creation workspace was sized for
         self._plans = {}                                         # shape -> arena tensor (LRU, most recent last)
@@ -321,17 +331,6 @@ class Engine:
         return {k: {"ms": ms[i], "flops": fl[i], "bytes": by[i], "launches": la[i]}
                 for i, k in enumerate(self.PROF_CLASSES)}
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().smi_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 def _weight_table(state: dict, dtype, device):
     warr = (WeightC * len(state))()
@@ -349,29 +348,14 @@ def _weight_table(state: dict, dtype, device):
     return warr, keep
 
 
-class VaeEngine:
+class VaeEngine(_EngineBase):
     """AutoencoderKL encoder on the HIP engine for one image size (smi_vae_*): image -> posterior moments."""
 
     def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, h: int, w: int, device):
-        c = VaeConfigC()
-        c.dtype = DTYPE_CODE[dtype]
-        c.in_channels, c.latent_channels = cfg.in_channels, cfg.latent_channels
-        c.n_levels = len(cfg.block_out_channels)
-        for i, v in enumerate(cfg.block_out_channels):
-            c.block_out_channels[i] = v
-        c.layers_per_block, c.norm_num_groups = cfg.layers_per_block, cfg.norm_num_groups
-        self.cfg_c, self.batch, self.h, self.w = c, batch, h, w
+        self.cfg_c, self.batch, self.h, self.w = vae_config_c(cfg, dtype), batch, h, w
         self.latent_channels = cfg.latent_channels
         self.down = 2 ** (len(cfg.block_out_channels) - 1)
-        out = C.c_size_t(0)
-        check(lib().smi_vae_workspace_bytes(C.byref(c), batch, h, w, C.byref(out)), "smi_vae_workspace_bytes")
-        self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
-        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
-        handle = C.c_void_p()
-        with torch.cuda.device(self.workspace.device):
-            check(lib().smi_vae_create(C.byref(c), warr, len(state), batch, h, w, ptr(self.workspace), out.value,
-                                       stream_ptr(), C.byref(handle)), "smi_vae_create")
-        self.handle = handle
+        self._create("vae_", self.cfg_c, (batch, h, w), state, dtype, device)
 
     def moments(self, image: torch.Tensor) -> torch.Tensor:
         n = image.shape[0]
@@ -379,17 +363,6 @@ class VaeEngine:
                           device=image.device)
         check(lib().smi_vae_encode(self.handle, n, ptr(image), ptr(out)), "smi_vae_encode")
         return out
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().smi_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def vae_config_c(cfg, dtype: torch.dtype) -> VaeConfigC:
@@ -403,6 +376,21 @@ def vae_config_c(cfg, dtype: torch.dtype) -> VaeConfigC:
     return c
 
 
+CLIP_ACT = {"quick_gelu": 0, "gelu": 1}
+
+
+def clip_config_c(cfg, dtype: torch.dtype) -> ClipConfigC:
+    if cfg.hidden_act not in CLIP_ACT:
+        raise SmiError(f"CLIP hidden_act '{cfg.hidden_act}' is not built (quick_gelu / gelu)")
+    c = ClipConfigC()
+    c.dtype = DTYPE_CODE[dtype]
+    c.vocab_size, c.hidden_size, c.num_layers = cfg.vocab_size, cfg.hidden_size, cfg.num_hidden_layers
+    c.num_heads, c.intermediate_size = cfg.num_attention_heads, cfg.intermediate_size
+    c.max_positions, c.hidden_act = cfg.max_position_embeddings, CLIP_ACT[cfg.hidden_act]
+    c.projection_dim = cfg.projection_dim or 0
+    return c
+
+
 def vae_decoder_workspace_bytes(cfg, dtype: torch.dtype, batch: int, h: int, w: int) -> int:
     """smi_vae_decoder_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on a refused shape."""
     out = C.c_size_t(0)
@@ -411,22 +399,14 @@ def vae_decoder_workspace_bytes(cfg, dtype: torch.dtype, batch: int, h: int, w: 
     return out.value
 
 
-class VaeDecoderEngine:
+class VaeDecoderEngine(_EngineBase):
     """AutoencoderKL decoder on the HIP engine for one image size (smi_vae_decoder_*): latents -> image (+ uint8)."""
 
     def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, h: int, w: int, device):
-        c = vae_config_c(cfg, dtype)
-        self.cfg_c, self.batch, self.h, self.w = c, batch, h, w
+        self.cfg_c, self.batch, self.h, self.w = vae_config_c(cfg, dtype), batch, h, w
         self.latent_channels, self.out_channels = cfg.latent_channels, cfg.in_channels
         self.down = 2 ** (len(cfg.block_out_channels) - 1)
-        nbytes = vae_decoder_workspace_bytes(cfg, dtype, batch, h, w)
-        self.workspace = torch.empty(nbytes, dtype=torch.uint8, device=device)
-        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
-        handle = C.c_void_p()
-        with torch.cuda.device(self.workspace.device):
-            check(lib().smi_vae_decoder_create(C.byref(c), warr, len(state), batch, h, w, ptr(self.workspace), nbytes,
-                                               stream_ptr(), C.byref(handle)), "smi_vae_decoder_create")
-        self.handle = handle
+        self._create("vae_decoder_", self.cfg_c, (batch, h, w), state, dtype, device)
 
     def decode(self, latents: torch.Tensor, want_rgb8: bool = False):
         """latents f32 [n, latent, h/f, w/f] on the engine's device -> (sample f32 [n, C, h, w], uint8 [n, h, w, C] or None)"""
@@ -440,43 +420,13 @@ class VaeDecoderEngine:
         check(lib().smi_vae_decode(self.handle, n, ptr(latents), ptr(out), ptr(rgb)), "smi_vae_decode")
         return out, rgb
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().smi_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class ClipEngine:
+class ClipEngine(_EngineBase):
     """CLIP text encoder on the HIP engine (smi_clip_*): token ids -> last hidden state, hidden_states[-2], pooled."""
 
-    ACT = {"quick_gelu": 0, "gelu": 1}
-
     def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, device):
-        c = ClipConfigC()
-        c.dtype = DTYPE_CODE[dtype]
-        c.vocab_size, c.hidden_size, c.num_layers = cfg.vocab_size, cfg.hidden_size, cfg.num_hidden_layers
-        c.num_heads, c.intermediate_size = cfg.num_attention_heads, cfg.intermediate_size
-        c.max_positions = cfg.max_position_embeddings
-        if cfg.hidden_act not in self.ACT:
-            raise SmiError(f"CLIP hidden_act '{cfg.hidden_act}' is not built (quick_gelu / gelu)")
-        c.hidden_act = self.ACT[cfg.hidden_act]
-        c.projection_dim = cfg.projection_dim or 0
-        self.cfg_c, self.batch, self.dtype = c, batch, dtype
-        out = C.c_size_t(0)
-        check(lib().smi_clip_workspace_bytes(C.byref(c), batch, C.byref(out)), "smi_clip_workspace_bytes")
-        self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
-        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
-        handle = C.c_void_p()
-        with torch.cuda.device(self.workspace.device):
-            check(lib().smi_clip_create(C.byref(c), warr, len(state), batch, ptr(self.workspace), out.value, stream_ptr(),
-                                        C.byref(handle)), "smi_clip_create")
-        self.handle = handle
+        self.cfg_c, self.batch, self.dtype = clip_config_c(cfg, dtype), batch, dtype
+        self._create("clip_", self.cfg_c, (batch,), state, dtype, device)
 
     def encode(self, ids: torch.Tensor, eos_pos: torch.Tensor):
         n, L = ids.shape
@@ -493,14 +443,3 @@ class ClipEngine:
         check(lib().smi_clip_encode(self.handle, n, ptr(ids), ptr(eos), ptr(last), ptr(pen), ptr(pooled)),
               "smi_clip_encode")
         return last, pen, pooled
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().smi_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _native
+from .engine_cache import EngineCacheMixin
 
 
 @dataclass
@@ -106,8 +107,9 @@ class CLIPTextOutput:
         raise IndexError(i)
 
 
-class CLIPTextModel(nn.Module):
+class CLIPTextModel(EngineCacheMixin, nn.Module):
     with_projection = False
+    _component, _handle = "CLIP text encoder", "text_encoder"
 
     def __init__(self, cfg: CLIPTextConfig):
         super().__init__()
@@ -115,7 +117,7 @@ class CLIPTextModel(nn.Module):
         self.text_model = _TextTransformer(cfg)
         if self.with_projection:
             self.text_projection = nn.Linear(cfg.hidden_size, cfg.projection_dim, bias=False)
-        self._engine = None
+        self._engines = {}
 
     @property
     def dtype(self):
@@ -129,21 +131,11 @@ class CLIPTextModel(nn.Module):
         sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}  # a buffer in older checkpoints
         return super().load_state_dict(sd, strict=strict)
 
-    def _eng(self, n):
-        if self.device.type != "cuda":
-            raise _native.SmiError("the CLIP text encoder runs only on an MI355X through the HIP engine; move it to a "
-                                   "cuda device with text_encoder.to(device, dtype) (there is no CPU fallback)")
-        if self.dtype not in _native.DTYPE_CODE:
-            raise _native.SmiError(f"engine dtypes are float16/bfloat16, got {self.dtype}")
-        if self._engine is None or self._engine.batch < n or self._engine.dtype != self.dtype:
-            if self._engine is not None:
-                self._engine.close()
-            cfg = self.config
-            if not self.with_projection:
-                cfg = CLIPTextConfig(**{**cfg.__dict__, "projection_dim": None})
-            state = {k: v.detach() for k, v in self.state_dict().items()}
-            self._engine = _native.ClipEngine(cfg, self.dtype, state, max(n, 1), self.device)
-        return self._engine
+    def _new_engine(self, state, n):
+        cfg = self.config
+        if not self.with_projection:
+            cfg = CLIPTextConfig(**{**cfg.__dict__, "projection_dim": None})
+        return _native.ClipEngine(cfg, self.dtype, state, max(n, 1), self.device)
 
     @torch.no_grad()
     def forward(self, input_ids, output_hidden_states: bool = False, **_):
@@ -152,7 +144,7 @@ class CLIPTextModel(nn.Module):
         # transformers: the pooled token is the EOS token -- the highest id for the original vocabulary (eos_token_id 2 in
         # old configs), else the first position holding eos_token_id
         eos_pos = ids.argmax(dim=-1) if eos == 2 else (ids == eos).int().argmax(dim=-1)
-        last, pen, pooled = self._eng(ids.shape[0]).encode(ids, eos_pos)
+        last, pen, pooled = self._engine(ids.shape[0]).encode(ids, eos_pos)
         hs = _HiddenStates(pen) if output_hidden_states else None
         if self.with_projection:
             return CLIPTextOutput(pooled, last, None, pooled, hs)

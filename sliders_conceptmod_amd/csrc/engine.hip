@@ -206,6 +206,9 @@ struct Level {
 using namespace smi;
 
 struct smi_engine {
+  // which model the engine holds: set once by its setup; every entry point accepts one kind and refuses the others
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT };
+  Kind kind = UNET;
   smi_unet_config cfg{};
   int dtype = 0;
   hipStream_t stream = nullptr;
@@ -499,7 +502,7 @@ struct smi_engine {
   int scr_i = 0;
   bool in_block = false, persist_next = false;
   void begin_block() {
-    if (saving || is_vae || is_clip) return;
+    if (saving || kind != UNET) return;
     scr_i ^= 1;
     scr[scr_i].reset();
     in_block = true;
@@ -804,6 +807,17 @@ struct smi_engine {
     L.Wt = t;
     attach_lora(L, targets);
     return L;
+  }
+  // the bias that goes with make_fused: the parts' bias vectors copied one after the other into one packed block
+  const void* fused_bias(const std::string& base, const std::vector<std::string>& parts, int out_each) {
+    char* b = (char*)pack_alloc(parts.size() * (size_t)out_each * esz());
+    for (size_t i = 0; i < parts.size(); ++i) {
+      const void* src = Wd(base + "." + parts[i] + ".bias");
+      if (!dry && !err && src)
+        (void)hipMemcpyAsync(b + i * (size_t)out_each * esz(), src, (size_t)out_each * esz(), hipMemcpyDeviceToDevice,
+                             stream);
+    }
+    return b;
   }
   Conv make_conv(const std::string& name, int Cin, int Cout, int mode, bool grad_pack) {
     Conv c;
@@ -1732,7 +1746,6 @@ struct smi_engine {
   // `pad = 0`), 1x1 shortcuts as GEMMs.  The mid block's attention is ONE head of width 512 over all pixels: run as
   // materialised GEMMs (scores in fp32, row softmax, P V), a few GFLOP per image.
   // ---------------------------------------------------------------------------------------------------------
-  bool is_vae = false;
   smi_vae_config vcfg{};
   struct VLevel {
     std::vector<Resnet> res;
@@ -1751,16 +1764,7 @@ struct smi_engine {
   void build_vae_attn(const std::string& pre, int ch) {
     v_attn_norm = make_norm(pre + ".group_norm", ch, 1e-6f);
     v_qkv = make_fused(pre, {"to_q", "to_k", "to_v"}, ch, ch, false);
-    {  // fused q|k|v bias
-      char* bq = (char*)pack_alloc((size_t)3 * ch * esz());
-      const char* parts[3] = {"to_q", "to_k", "to_v"};
-      for (int i = 0; i < 3; ++i) {
-        const void* src = Wd(pre + "." + parts[i] + ".bias");
-        if (!dry && !err && src)
-          (void)hipMemcpyAsync(bq + (size_t)i * ch * esz(), src, (size_t)ch * esz(), hipMemcpyDeviceToDevice, stream);
-      }
-      v_qkv.b = bq;
-    }
+    v_qkv.b = fused_bias(pre, {"to_q", "to_k", "to_v"}, ch);
     v_o = make_lin(pre + ".to_out.0", ch, ch, true, false);
   }
 
@@ -1921,10 +1925,9 @@ struct smi_engine {
   // (resnet, single-head attention, resnet) -> up blocks over the reversed block_out_channels (layers_per_block + 1
   // resnets, nearest-2x + 3x3 up-sampler on all but the last) -> conv_norm_out + SiLU + conv_out.  The tail runs as one
   // fused launch (vae_decode.hip) unless SMI_VAE_DEC_TAIL=0 (then: GroupNorm+SiLU, the conv with Cout padded to 4 by a
-  // zero filter row, layout kernels, a separate uint8 pass).  Same engine kind flag as the encoder (`is_vae`), plus
-  // `is_vae_dec`: encode / decode refuse the other kind, the UNet entry points refuse both.
+  // zero filter row, layout kernels, a separate uint8 pass).  Shares the encoder's config and mid-block
+  // members; `kind` tells the two apart: encode / decode refuse the other kind, the UNet entry points refuse both.
   // ---------------------------------------------------------------------------------------------------------
-  bool is_vae_dec = false;
   bool dec_tail_fused = true;
   std::vector<VLevel> v_up;
   Conv d_conv_out;                 // Wp: [4][9*C0], rows >= out channels zero
@@ -2066,7 +2069,6 @@ struct smi_engine {
   // mask), quick_gelu / gelu MLP, final LayerNorm, pooled EOS row (x text_projection).
   // ---------------------------------------------------------------------------------------------------------
   bool attn_causal = false;
-  bool is_clip = false;
   smi_clip_config ccfg{};
   struct CLayer {
     Norm n1, n2;
@@ -2090,14 +2092,7 @@ struct smi_engine {
       CLayer& L = c_layers[i];
       L.n1 = make_norm(b + ".layer_norm1", d, 1e-5f);
       L.qkv = make_fused(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d, d, false);
-      char* bq = (char*)pack_alloc((size_t)3 * d * esz());
-      const char* parts[3] = {"q_proj", "k_proj", "v_proj"};
-      for (int j = 0; j < 3; ++j) {
-        const void* src = Wd(b + ".self_attn." + parts[j] + ".bias");
-        if (!dry && !err && src)
-          (void)hipMemcpyAsync(bq + (size_t)j * d * esz(), src, (size_t)d * esz(), hipMemcpyDeviceToDevice, stream);
-      }
-      L.qkv.b = bq;
+      L.qkv.b = fused_bias(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d);
       L.out = make_lin(b + ".self_attn.out_proj", d, d, true, false);
       L.n2 = make_norm(b + ".layer_norm2", d, 1e-5f);
       L.fc1 = make_lin(b + ".mlp.fc1", d, ccfg.intermediate_size, true, false);
@@ -2148,6 +2143,25 @@ struct smi_engine {
       return -3;
     }
     return err ? -1 : 0;
+  }
+
+  // the forward-only kinds (everything but the UNet) are created and planned by one path (create_forward_only below);
+  // these two are the one place that maps `kind` to its build and to the dry forward that sizes arena 0
+  void build_forward_only() {
+    switch (kind) {
+      case VAE_ENCODER: build_vae(); break;
+      case VAE_DECODER: build_vae_dec(); break;
+      case CLIP_TEXT: build_clip(); break;
+      case UNET: break;
+    }
+  }
+  void dry_forward_only() {
+    switch (kind) {
+      case VAE_ENCODER: forward_vae(max_n, nullptr, nullptr); break;
+      case VAE_DECODER: forward_vae_dec(max_n, nullptr, nullptr, nullptr); break;
+      case CLIP_TEXT: forward_clip(max_n, nullptr, nullptr, (void*)16, (void*)16, (void*)16); break;  // all outputs
+      case UNET: break;
+    }
   }
 
   // ---------------------------------------------------------------------------------------------------------
@@ -2485,6 +2499,66 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   return e.err ? -1 : 0;
 }
 
+// the end of every create: wait for the packing kernels, turn a failure into a message (`what` names the weights in it),
+// drop the weight table, which is only borrowed during creation
+int finish_create(smi_engine* e, const char* what, smi_engine** out) {
+  if (!e->err) (void)hipStreamSynchronize(e->stream);
+  if (e->err || hipGetLastError() != hipSuccess) {
+    if (!e->err) set_error("HIP error while packing %s", what);
+    delete e;
+    return -1;
+  }
+  e->wmap.clear();
+  *out = e;
+  return 0;
+}
+
+// ---- the forward-only engines (VAE encoder, VAE decoder, CLIP text encoder): one plan, one size, one create ----------
+// `setup` fills a fresh engine with its kind, config and largest shape; the workspace is [packed weights | arena 0]
+using Setup = std::function<void(smi_engine*)>;
+struct ForwardOnlyPlan {
+  size_t wpack = 0, arena = 0;
+  size_t bytes() const { return wpack + arena + 2 * 4096; }
+};
+int plan_forward_only(const Setup& setup, ForwardOnlyPlan* p) {
+  smi_engine e;
+  e.dry = true;
+  setup(&e);
+  e.build_forward_only();
+  if (e.err) return -1;
+  p->wpack = align_up(e.wpack.peak, 4096);
+  e.dry_forward_only();
+  p->arena = align_up(e.arena[0].peak, 4096);
+  return e.err ? -1 : 0;
+}
+int workspace_bytes_forward_only(const Setup& setup, size_t* bytes) {
+  SMI_CHECK(bytes != nullptr, "bad arguments");
+  ForwardOnlyPlan p;
+  if (plan_forward_only(setup, &p)) return -1;
+  *bytes = p.bytes();
+  return 0;
+}
+int create_forward_only(const Setup& setup, const char* what, const smi_weight* weights, int n_weights, void* workspace,
+                        size_t workspace_bytes, void* stream, smi_engine** out) {
+  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
+  ForwardOnlyPlan p;
+  if (plan_forward_only(setup, &p)) return -1;
+  SMI_CHECK(p.bytes() <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", p.bytes(), workspace_bytes);
+  smi_engine* e = new smi_engine();
+  e->stream = (hipStream_t)stream;
+  setup(e);
+  for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
+  char* base = (char*)align_up((size_t)workspace, 4096);
+  e->ws = (char*)workspace;
+  e->ws_bytes = workspace_bytes;
+  e->wpack.base = base;
+  e->wpack.cap = p.wpack;
+  e->arena[0].base = base + p.wpack;
+  e->arena[0].cap = p.arena;
+  e->build_forward_only();
+  return finish_create(e, what, out);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2527,16 +2601,7 @@ int smi_create(const smi_unet_config* cfg, const smi_weight* weights, int n_weig
   e->arena_home = base + r[0];
   e->arena_home_bytes = (size_t)((char*)workspace + workspace_bytes - e->arena_home);
   e->build();
-  if (!e->err) (void)hipStreamSynchronize(e->stream);
-  if (e->err || hipGetLastError() != hipSuccess) {
-    if (!e->err) set_error("HIP error while packing weights");
-    delete e;
-    return -1;
-  }
-  // the weight table is only borrowed during creation
-  e->wmap.clear();
-  *out = e;
-  return 0;
+  return finish_create(e, "weights", out);
 }
 
 void smi_destroy(smi_engine* e) {
@@ -2558,9 +2623,8 @@ static int check_vae_cfg(const smi_vae_config* c, int batch, int h, int w) {
   SMI_CHECK(batch > 0 && h > 0 && w > 0 && h % f == 0 && w % f == 0, "image size must be a multiple of %d", f);
   return 0;
 }
-static void vae_setup(smi_engine* e, const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch, int h,
-                      int w) {
-  e->is_vae = true;
+static void vae_setup(smi_engine* e, smi_engine::Kind kind, const smi_vae_config* cfg, int batch, int h, int w) {
+  e->kind = kind;
   e->vcfg = *cfg;
   e->dtype = cfg->dtype;
   e->cfg.norm_num_groups = cfg->norm_num_groups;
@@ -2568,62 +2632,29 @@ static void vae_setup(smi_engine* e, const smi_vae_config* cfg, const smi_weight
   e->max_n = batch;
   e->lat_h = h;
   e->lat_w = w;
-  for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
-}
-static int vae_plan(const smi_vae_config* cfg, int batch, int h, int w, size_t out[2]) {
-  smi_engine e;
-  e.dry = true;
-  vae_setup(&e, cfg, nullptr, 0, batch, h, w);
-  e.build_vae();
-  if (e.err) return -1;
-  out[0] = align_up(e.wpack.peak, 4096);
-  e.forward_vae(batch, nullptr, nullptr);
-  out[1] = align_up(e.arena[0].peak, 4096);
-  return e.err ? -1 : 0;
+  if (kind == smi_engine::VAE_DECODER) {
+    const char* t = getenv("SMI_VAE_DEC_TAIL");
+    e->dec_tail_fused = !(t && t[0] == '0');
+  }
 }
 
 int smi_vae_workspace_bytes(const smi_vae_config* cfg, int batch, int h, int w, size_t* bytes) {
   if (check_vae_cfg(cfg, batch, h, w)) return -1;
-  SMI_CHECK(bytes != nullptr, "bad arguments");
-  size_t r[2];
-  if (vae_plan(cfg, batch, h, w, r)) return -1;
-  *bytes = r[0] + r[1] + 2 * 4096;
-  return 0;
+  return workspace_bytes_forward_only([&](smi_engine* e) { vae_setup(e, smi_engine::VAE_ENCODER, cfg, batch, h, w); },
+                                      bytes);
 }
 
 int smi_vae_create(const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch, int h, int w,
                    void* workspace, size_t workspace_bytes, void* stream, smi_engine** out) {
   if (check_vae_cfg(cfg, batch, h, w)) return -1;
-  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
-  size_t r[2];
-  if (vae_plan(cfg, batch, h, w, r)) return -1;
-  SMI_CHECK(r[0] + r[1] + 2 * 4096 <= workspace_bytes, "workspace too small: need %zu bytes, got %zu",
-            r[0] + r[1] + 2 * 4096, workspace_bytes);
-  smi_engine* e = new smi_engine();
-  e->stream = (hipStream_t)stream;
-  vae_setup(e, cfg, weights, n_weights, batch, h, w);
-  char* base = (char*)align_up((size_t)workspace, 4096);
-  e->ws = (char*)workspace;
-  e->ws_bytes = workspace_bytes;
-  e->wpack.base = base;
-  e->wpack.cap = r[0];
-  e->arena[0].base = base + r[0];
-  e->arena[0].cap = r[1];
-  e->build_vae();
-  if (!e->err) (void)hipStreamSynchronize(e->stream);
-  if (e->err || hipGetLastError() != hipSuccess) {
-    if (!e->err) set_error("HIP error while packing the VAE weights");
-    delete e;
-    return -1;
-  }
-  e->wmap.clear();
-  *out = e;
-  return 0;
+  return create_forward_only([&](smi_engine* e) { vae_setup(e, smi_engine::VAE_ENCODER, cfg, batch, h, w); },
+                             "the VAE weights", weights, n_weights, workspace, workspace_bytes, stream, out);
 }
 
 int smi_vae_encode(smi_engine* e, int n, const float* image, float* moments_out) {
-  SMI_CHECK(e && e->is_vae && image && moments_out, "smi_vae_encode: NULL argument or not a VAE engine");
-  SMI_CHECK(!e->is_vae_dec, "smi_vae_encode: this engine is a VAE decoder (use smi_vae_decode)");
+  SMI_CHECK(e && image && moments_out && (e->kind == smi_engine::VAE_ENCODER || e->kind == smi_engine::VAE_DECODER),
+            "smi_vae_encode: NULL argument or not a VAE engine");
+  SMI_CHECK(e->kind == smi_engine::VAE_ENCODER, "smi_vae_encode: this engine is a VAE decoder (use smi_vae_decode)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   e->err = false;
   return e->forward_vae(n, image, moments_out);
@@ -2663,67 +2694,23 @@ static int check_vae_dec_cfg(const smi_vae_config* c, int batch, int h, int w) {
             "the largest batch that fits is %lld", batch, h, w, (long long)(per >> 20), (long long)maxb);
   return 0;
 }
-static void vae_dec_setup(smi_engine* e, const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch,
-                          int h, int w) {
-  vae_setup(e, cfg, weights, n_weights, batch, h, w);
-  e->is_vae_dec = true;
-  const char* t = getenv("SMI_VAE_DEC_TAIL");
-  e->dec_tail_fused = !(t && t[0] == '0');
-}
-static int vae_dec_plan(const smi_vae_config* cfg, int batch, int h, int w, size_t out[2]) {
-  smi_engine e;
-  e.dry = true;
-  vae_dec_setup(&e, cfg, nullptr, 0, batch, h, w);
-  e.build_vae_dec();
-  if (e.err) return -1;
-  out[0] = align_up(e.wpack.peak, 4096);
-  e.forward_vae_dec(batch, nullptr, nullptr, nullptr);
-  out[1] = align_up(e.arena[0].peak, 4096);
-  return e.err ? -1 : 0;
-}
 
 int smi_vae_decoder_workspace_bytes(const smi_vae_config* cfg, int batch, int h, int w, size_t* bytes) {
   if (check_vae_dec_cfg(cfg, batch, h, w)) return -1;
-  SMI_CHECK(bytes != nullptr, "bad arguments");
-  size_t r[2];
-  if (vae_dec_plan(cfg, batch, h, w, r)) return -1;
-  *bytes = r[0] + r[1] + 2 * 4096;
-  return 0;
+  return workspace_bytes_forward_only([&](smi_engine* e) { vae_setup(e, smi_engine::VAE_DECODER, cfg, batch, h, w); },
+                                      bytes);
 }
 
 int smi_vae_decoder_create(const smi_vae_config* cfg, const smi_weight* weights, int n_weights, int batch, int h, int w,
                            void* workspace, size_t workspace_bytes, void* stream, smi_engine** out) {
   if (check_vae_dec_cfg(cfg, batch, h, w)) return -1;
-  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
-  size_t r[2];
-  if (vae_dec_plan(cfg, batch, h, w, r)) return -1;
-  SMI_CHECK(r[0] + r[1] + 2 * 4096 <= workspace_bytes, "workspace too small: need %zu bytes, got %zu",
-            r[0] + r[1] + 2 * 4096, workspace_bytes);
-  smi_engine* e = new smi_engine();
-  e->stream = (hipStream_t)stream;
-  vae_dec_setup(e, cfg, weights, n_weights, batch, h, w);
-  char* base = (char*)align_up((size_t)workspace, 4096);
-  e->ws = (char*)workspace;
-  e->ws_bytes = workspace_bytes;
-  e->wpack.base = base;
-  e->wpack.cap = r[0];
-  e->arena[0].base = base + r[0];
-  e->arena[0].cap = r[1];
-  e->build_vae_dec();
-  if (!e->err) (void)hipStreamSynchronize(e->stream);
-  if (e->err || hipGetLastError() != hipSuccess) {
-    if (!e->err) set_error("HIP error while packing the VAE decoder weights");
-    delete e;
-    return -1;
-  }
-  e->wmap.clear();
-  *out = e;
-  return 0;
+  return create_forward_only([&](smi_engine* e) { vae_setup(e, smi_engine::VAE_DECODER, cfg, batch, h, w); },
+                             "the VAE decoder weights", weights, n_weights, workspace, workspace_bytes, stream, out);
 }
 
 int smi_vae_decode(smi_engine* e, int n, const float* latents, float* image_out, uint8_t* rgb8_out) {
   SMI_CHECK(e && latents && image_out, "smi_vae_decode: NULL argument");
-  SMI_CHECK(e->is_vae && e->is_vae_dec, "smi_vae_decode: not a VAE decoder engine (create it with smi_vae_decoder_create)");
+  SMI_CHECK(e->kind == smi_engine::VAE_DECODER, "smi_vae_decode: not a VAE decoder engine (create it with smi_vae_decoder_create)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   e->err = false;
   return e->forward_vae_dec(n, latents, image_out, rgb8_out);
@@ -2740,67 +2727,28 @@ static int check_clip_cfg(const smi_clip_config* c, int batch) {
             "CLIP config out of range (hidden %% 64, hidden <= 2048, head_dim %% 8, intermediate %% 64)");
   return 0;
 }
-static void clip_setup(smi_engine* e, const smi_clip_config* cfg, const smi_weight* weights, int n_weights, int batch) {
-  e->is_clip = true;
+static void clip_setup(smi_engine* e, const smi_clip_config* cfg, int batch) {
+  e->kind = smi_engine::CLIP_TEXT;
   e->ccfg = *cfg;
   e->dtype = cfg->dtype;
   e->max_n = batch;
-  for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
-}
-static int clip_plan(const smi_clip_config* cfg, int batch, size_t out[2]) {
-  smi_engine e;
-  e.dry = true;
-  clip_setup(&e, cfg, nullptr, 0, batch);
-  e.build_clip();
-  if (e.err) return -1;
-  out[0] = align_up(e.wpack.peak, 4096);
-  e.forward_clip(batch, nullptr, nullptr, (void*)16, (void*)16, (void*)16);
-  out[1] = align_up(e.arena[0].peak, 4096);
-  return e.err ? -1 : 0;
 }
 
 int smi_clip_workspace_bytes(const smi_clip_config* cfg, int batch, size_t* bytes) {
   if (check_clip_cfg(cfg, batch)) return -1;
-  SMI_CHECK(bytes != nullptr, "bad arguments");
-  size_t r[2];
-  if (clip_plan(cfg, batch, r)) return -1;
-  *bytes = r[0] + r[1] + 2 * 4096;
-  return 0;
+  return workspace_bytes_forward_only([&](smi_engine* e) { clip_setup(e, cfg, batch); }, bytes);
 }
 
 int smi_clip_create(const smi_clip_config* cfg, const smi_weight* weights, int n_weights, int batch, void* workspace,
                     size_t workspace_bytes, void* stream, smi_engine** out) {
   if (check_clip_cfg(cfg, batch)) return -1;
-  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
-  size_t r[2];
-  if (clip_plan(cfg, batch, r)) return -1;
-  SMI_CHECK(r[0] + r[1] + 2 * 4096 <= workspace_bytes, "workspace too small: need %zu bytes, got %zu",
-            r[0] + r[1] + 2 * 4096, workspace_bytes);
-  smi_engine* e = new smi_engine();
-  e->stream = (hipStream_t)stream;
-  clip_setup(e, cfg, weights, n_weights, batch);
-  char* base = (char*)align_up((size_t)workspace, 4096);
-  e->ws = (char*)workspace;
-  e->ws_bytes = workspace_bytes;
-  e->wpack.base = base;
-  e->wpack.cap = r[0];
-  e->arena[0].base = base + r[0];
-  e->arena[0].cap = r[1];
-  e->build_clip();
-  if (!e->err) (void)hipStreamSynchronize(e->stream);
-  if (e->err || hipGetLastError() != hipSuccess) {
-    if (!e->err) set_error("HIP error while packing the CLIP weights");
-    delete e;
-    return -1;
-  }
-  e->wmap.clear();
-  *out = e;
-  return 0;
+  return create_forward_only([&](smi_engine* e) { clip_setup(e, cfg, batch); }, "the CLIP weights", weights, n_weights,
+                             workspace, workspace_bytes, stream, out);
 }
 
 int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
                     void* penultimate, void* pooled) {
-  SMI_CHECK(e && e->is_clip && ids, "smi_clip_encode: NULL argument or not a CLIP engine");
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && ids, "smi_clip_encode: NULL argument or not a CLIP engine");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
   e->err = false;
@@ -2831,7 +2779,7 @@ int smi_replan(smi_engine* e, int batch, int batch_adapted, int h, int w, int ct
                size_t arena_bytes) {
   SMI_CHECK(e && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
             "bad arguments");
-  SMI_CHECK(!e->is_vae && !e->is_clip, "smi_replan: only UNet engines re-plan");
+  SMI_CHECK(e->kind == smi_engine::UNET, "smi_replan: only UNet engines re-plan");
   size_t r[5];
   if (plan(&e->cfg, e->sites.data(), (int)e->sites.size(), batch, batch_adapted, h, w, ctx_len, r)) return -1;
   char* base = arena ? (char*)align_up((size_t)arena, 4096) : e->arena_home;
@@ -2880,7 +2828,7 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
                              const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                              const float* lora_up_flat, float multiplier, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && sample && ctx && eps_out, "NULL argument");
-  SMI_CHECK(!e->is_vae && !e->is_clip,
+  SMI_CHECK(e->kind == smi_engine::UNET,
             "this engine is a VAE encoder / decoder or a CLIP encoder (use smi_vae_encode / smi_vae_decode / smi_clip_encode)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(n_adapted >= 0 && n_adapted <= n && n_adapted <= e->max_n_ad,
@@ -2898,7 +2846,7 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
                            const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                            const float* lora_up_flat, const float* multipliers, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && multipliers, "NULL argument");
-  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE encoder / decoder or a CLIP encoder: no UNet forward");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: no UNet forward");
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "per-sample multipliers: 1..%d adapted samples", smi_engine::MAXS);
   float mref = 0.f;
   bool same = true;
@@ -2939,7 +2887,7 @@ int smi_unet_forward(smi_engine* e, int n, const float* sample, float timestep, 
 
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(!e->is_vae && !e->is_clip, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
   e->err = false;
   GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
   return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat);

@@ -15,6 +15,7 @@ import torch
 import torch.nn as nn
 
 from . import _native
+from .engine_cache import EngineCacheMixin
 
 
 @dataclass
@@ -121,7 +122,27 @@ class _EncoderOutput:
 _DEPRECATED_ATTN_NAMES = ((".query.", ".to_q."), (".key.", ".to_k."), (".value.", ".to_v."), (".proj_attn.", ".to_out.0."))
 
 
-class AutoencoderKL(nn.Module):
+def half_state_dict(state_dict, prefixes: Tuple[str, ...]) -> dict:
+    """The entries of a full diffusers AutoencoderKL state dict under `prefixes` (one half of the model).  SD-1.x era
+    checkpoints name the mid-block attention query / key / value / proj_attn (diffusers renames them when it loads,
+    `_convert_deprecated_attention_blocks`) and some store them as 1 x 1 conv kernels [C, C, 1, 1]: both are converted."""
+    sd = {}
+    for k, v in state_dict.items():
+        if not k.startswith(prefixes):
+            continue
+        for old, new in _DEPRECATED_ATTN_NAMES:
+            if old in k:
+                k = k.replace(old, new)
+                if v.ndim == 4 and v.shape[-2:] == (1, 1):
+                    v = v.reshape(v.shape[0], v.shape[1])
+                break
+        sd[k] = v
+    return sd
+
+
+class AutoencoderKL(EngineCacheMixin, nn.Module):
+    _component, _handle = "VAE encoder", "vae"
+
     def __init__(self, cfg: VAEConfig):
         super().__init__()
         self.config = cfg
@@ -139,35 +160,10 @@ class AutoencoderKL(nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts a full diffusers AutoencoderKL state dict: the decoder / post_quant_conv entries are not used."""
-        sd = {}
-        for k, v in state_dict.items():
-            if not (k.startswith("encoder.") or k.startswith("quant_conv.")):
-                continue
-            # SD-1.x era checkpoints name the mid-block attention query / key / value / proj_attn (diffusers renames them
-            # when it loads, `_convert_deprecated_attention_blocks`); some store them as 1 x 1 conv kernels [C, C, 1, 1]
-            for old, new in _DEPRECATED_ATTN_NAMES:
-                if old in k:
-                    k = k.replace(old, new)
-                    if v.ndim == 4 and v.shape[-2:] == (1, 1):
-                        v = v.reshape(v.shape[0], v.shape[1])
-                    break
-            sd[k] = v
-        return super().load_state_dict(sd, strict=strict)
+        return super().load_state_dict(half_state_dict(state_dict, ("encoder.", "quant_conv.")), strict=strict)
 
-    def _engine(self, n, h, w):
-        if self.device.type != "cuda":
-            raise _native.SmiError("the VAE encoder runs only on an MI355X through the HIP engine; move it to a cuda "
-                                   "device with vae.to(device, dtype) (there is no CPU fallback)")
-        if self.dtype not in _native.DTYPE_CODE:
-            raise _native.SmiError(f"engine dtypes are float16/bfloat16, got {self.dtype}")
-        key = (self.dtype, str(self.device), h, w)
-        e = self._engines.get(key)
-        if e is None or e.batch < n:
-            if e is not None:
-                e.close()
-            state = {k: v.detach() for k, v in self.state_dict().items()}
-            e = self._engines[key] = _native.VaeEngine(self.config, self.dtype, state, n, h, w, self.device)
-        return e
+    def _new_engine(self, state, n, h, w):
+        return _native.VaeEngine(self.config, self.dtype, state, n, h, w, self.device)
 
     @torch.no_grad()
     def encode(self, x: torch.Tensor):

@@ -16,7 +16,8 @@ import torch
 import torch.nn as nn
 
 from . import _native
-from .vae import VAEConfig, _DEPRECATED_ATTN_NAMES, _Mid, _Resnet
+from .engine_cache import EngineCacheMixin
+from .vae import VAEConfig, _Mid, _Resnet, half_state_dict
 
 _GEMM_OPERAND_LIMIT = 0xFFFFFFF0  # the GEMM addresses an operand with a 32-bit byte offset (csrc/gemm.hip)
 
@@ -76,7 +77,9 @@ class DecoderOutput:
         self.sample = sample
 
 
-class AutoencoderKLDecoder(nn.Module):
+class AutoencoderKLDecoder(EngineCacheMixin, nn.Module):
+    _component, _handle = "VAE decoder", "vae"
+
     def __init__(self, cfg: VAEConfig):
         super().__init__()
         self.config = cfg
@@ -94,45 +97,10 @@ class AutoencoderKLDecoder(nn.Module):
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts a full diffusers AutoencoderKL state dict: the encoder / quant_conv entries are not used."""
-        sd = {}
-        for k, v in state_dict.items():
-            if not (k.startswith("decoder.") or k.startswith("post_quant_conv.")):
-                continue
-            # SD-1.x era names of the mid-block attention (diffusers `_convert_deprecated_attention_blocks`), some stored
-            # as 1 x 1 conv kernels
-            for old, new in _DEPRECATED_ATTN_NAMES:
-                if old in k:
-                    k = k.replace(old, new)
-                    if v.ndim == 4 and v.shape[-2:] == (1, 1):
-                        v = v.reshape(v.shape[0], v.shape[1])
-                    break
-            sd[k] = v
-        self._close_engines()
-        return super().load_state_dict(sd, strict=strict)
+        return super().load_state_dict(half_state_dict(state_dict, ("decoder.", "post_quant_conv.")), strict=strict)
 
-    def _close_engines(self):
-        for e in self._engines.values():
-            e.close()
-        self._engines = {}
-
-    def _apply(self, fn, *a, **kw):
-        self._close_engines()  # the engines borrow the weights' storage
-        return super()._apply(fn, *a, **kw)
-
-    def _engine(self, n, h, w):
-        if self.device.type != "cuda":
-            raise _native.SmiError("the VAE decoder runs only on an MI355X through the HIP engine; move it to a cuda "
-                                   "device with vae.to(device, dtype) (there is no CPU fallback)")
-        if self.dtype not in _native.DTYPE_CODE:
-            raise _native.SmiError(f"engine dtypes are float16/bfloat16, got {self.dtype}")
-        key = (self.dtype, str(self.device), h, w)
-        e = self._engines.get(key)
-        if e is None or e.batch < n:
-            if e is not None:
-                e.close()
-            state = {k: v.detach() for k, v in self.state_dict().items()}
-            e = self._engines[key] = _native.VaeDecoderEngine(self.config, self.dtype, state, n, h, w, self.device)
-        return e
+    def _new_engine(self, state, n, h, w):
+        return _native.VaeDecoderEngine(self.config, self.dtype, state, n, h, w, self.device)
 
     def _run(self, z: torch.Tensor, want_rgb8: bool, max_batch: Optional[int] = None):
         if z.ndim != 4 or z.shape[1] != self.config.latent_channels:

@@ -82,6 +82,27 @@ def test_clip_text_encoder_matches_oracle(which, dtype, bar):
             m(ids[:, :10].cuda())
 
 
+def test_load_state_dict_drops_the_engine():
+    """The engine packs q|k|v at creation and borrows the other weights' storage, so new weights must not meet an old
+    engine: after load_state_dict no engine is left open, and the next forward equals, bit for bit, what a fresh model
+    built from the new state returns."""
+    import sliders_conceptmod_amd.clip as PC
+    cfg = PC.CLIPTextConfig(vocab_size=1000, hidden_size=64, intermediate_size=256, num_hidden_layers=3,
+                            num_attention_heads=4, eos_token_id=999)
+    ids = ids_for(cfg).cuda()
+    m = seeded(PC.CLIPTextModel(cfg), 3).to("cuda", torch.float16)
+    first = m(ids, output_hidden_states=True)
+    old = next(iter(m._engines.values()))
+    m.load_state_dict(seeded(PC.CLIPTextModel(cfg), 4).state_dict())
+    assert m._engines == {} and old.handle is None
+    again = m(ids, output_hidden_states=True)
+    want = seeded(PC.CLIPTextModel(cfg), 4).to("cuda", torch.float16)(ids, output_hidden_states=True)
+    for a, w in ((again.last_hidden_state, want.last_hidden_state), (again.hidden_states[-2], want.hidden_states[-2]),
+                 (again.pooler_output, want.pooler_output)):
+        assert torch.equal(a, w)
+    assert not torch.equal(again.last_hidden_state, first.last_hidden_state)
+
+
 def test_clip_matches_transformers_directly():
     transformers = pytest.importorskip("transformers")
     import sliders_conceptmod_amd.clip as PC

@@ -282,6 +282,64 @@ def test_vae_loads_deprecated_attention_names():
         assert torch.equal(v, new_sd[k]), k
 
 
+def test_forward_only_containers_share_one_engine_cache():
+    """The VAE encoder, VAE decoder and CLIP containers take their engine cache, and the hooks that empty it when the
+    weights are replaced or moved, from one mixin; with no engine open those hooks do nothing (no library needed)."""
+    import sliders_conceptmod_amd.clip as PC
+    import sliders_conceptmod_amd.vae as PV
+    import sliders_conceptmod_amd.vae_decoder as PD
+    from sliders_conceptmod_amd.engine_cache import EngineCacheMixin
+    tiny_vae = PV.VAEConfig(block_out_channels=(64, 64), norm_num_groups=16)
+    tiny_clip = PC.CLIPTextConfig(vocab_size=100, hidden_size=64, intermediate_size=64, num_hidden_layers=1,
+                                  num_attention_heads=1, eos_token_id=99)
+    for m in (PV.AutoencoderKL(tiny_vae), PD.AutoencoderKLDecoder(tiny_vae), PC.CLIPTextModel(tiny_clip),
+              PC.CLIPTextModelWithProjection(dataclasses.replace(tiny_clip, projection_dim=64))):
+        assert type(m)._close_engines is EngineCacheMixin._close_engines
+        assert type(m)._engine is EngineCacheMixin._engine and type(m)._apply is EngineCacheMixin._apply
+        assert m._engines == {}
+        m._close_engines()
+        sd = {k: v.clone() for k, v in m.state_dict().items()}
+        m.load_state_dict(sd)
+        m.half()
+        assert m._engines == {}
+        with pytest.raises(_native.SmiError, match=f"the {type(m)._component} runs only on an MI355X"):
+            m._engine(1)
+
+
+def test_engine_cache_grows_and_empties_with_the_weights():
+    """The mixin's cache with a stand-in engine (no library): one engine per (dtype, device, shape), re-created for a
+    larger batch, all closed when the weights are replaced (load_state_dict) or moved / cast (_apply)."""
+    import sliders_conceptmod_amd.vae as PV
+
+    class FakeEngine:
+        def __init__(self, batch):
+            self.batch, self.handle = batch, object()
+
+        def close(self):
+            self.handle = None
+
+    class OnGpu(PV.AutoencoderKL):
+        device = property(lambda self: torch.device("cuda", 0))
+        dtype = property(lambda self: torch.float16)
+
+        def _new_engine(self, state, n, h, w):
+            assert set(state) == set(self.state_dict())
+            return FakeEngine(n)
+
+    v = OnGpu(PV.VAEConfig(block_out_channels=(64, 64), norm_num_groups=16))
+    e1 = v._engine(1, 64, 64)
+    assert v._engine(1, 64, 64) is e1
+    e2 = v._engine(2, 64, 64)
+    assert e1.handle is None and e2.batch == 2 and v._engine(1, 64, 64) is e2
+    e3 = v._engine(1, 32, 64)
+    assert set(v._engines) == {(torch.float16, "cuda:0", 64, 64), (torch.float16, "cuda:0", 32, 64)}
+    v.load_state_dict({k: t.clone() for k, t in v.state_dict().items()})
+    assert v._engines == {} and e2.handle is None and e3.handle is None
+    e4 = v._engine(1, 64, 64)
+    v.half()
+    assert v._engines == {} and e4.handle is None
+
+
 def test_engine_cache_key_tells_dora_from_lora():
     """ADVICE r2: a DoRANetwork and a LoRANetwork with the same rank / alpha / targets have identical down / up offsets;
     the engine key must still differ (the packed engine holds DoRA sites and delta-weight buffers or it does not)."""

@@ -61,6 +61,28 @@ def test_real_sd_vae_encoder_256px_matches_oracle():
     assert e_mean < 2.4e-3 and e_lv < 2.4e-3, (e_mean, e_lv)  # measured 1.58e-3 / 1.47e-3 (1.5 x)
 
 
+def test_load_state_dict_drops_the_engines():
+    """An engine copies some weights at creation and borrows the storage of the rest, so new weights must not meet an old
+    engine: after load_state_dict no engine is left open, and the next encode equals, bit for bit, what a fresh container
+    built from the new state returns."""
+    import sliders_conceptmod_amd.vae as PV
+    cfg = PV.VAEConfig(**dataclasses.asdict(OV.tiny_vae_config()))
+
+    def seeded(seed):
+        return PV.init_synthetic_(PV.AutoencoderKL(cfg), seed)
+
+    pv = seeded(7).to("cuda", torch.float16)
+    x = (torch.rand(1, 3, 64, 64, generator=torch.Generator().manual_seed(3)) * 2 - 1).cuda()
+    first = pv.encode(x).latent_dist
+    old = next(iter(pv._engines.values()))
+    pv.load_state_dict(seeded(8).state_dict())
+    assert pv._engines == {} and old.handle is None
+    again = pv.encode(x).latent_dist
+    want = seeded(8).to("cuda", torch.float16).encode(x).latent_dist
+    assert torch.equal(again.mean, want.mean) and torch.equal(again.logvar, want.logvar)
+    assert not torch.equal(again.mean, first.mean)
+
+
 def test_get_noisy_image_follows_the_reference_order():
     """I/train_util.py:200-235 on the engine vs the oracle's restatement: same preprocessing, posterior, scaling, noise
     drawn from the CALLER's generator, add_noise at scheduler.timesteps[total_timesteps].  The posterior sample itself uses
