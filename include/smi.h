@@ -223,6 +223,19 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
  * Replaces loss.backward() through the UNet (train_lora.py:298). */
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat);
 
+/* smi_unet_backward over the LAST `n_live` adapted samples of the saved pass only: `d_eps_live` is
+ * [n_live, out_channels, h, w] and THE CALLER PROMISES that the gradient with respect to the output of the other adapted
+ * samples is exactly zero.  A zero output gradient stays zero through every backward op and adds exact zeros to every
+ * weight-gradient sum, so those samples' rows are not run at all: every backward launch works on n_live instead of
+ * n_adapted samples.  The case it is for: the CFG-doubled adapted batch [unconditional x B ; target x B] at guidance
+ * scale 1, where d(u + 1 (t - u)) has no u term (n_live = B).  The forward is untouched.
+ * 1 <= n_live <= n_adapted of the saved pass, anything else is an error; n_live == n_adapted is smi_unet_backward (same
+ * launches, same bits).  With the kernel selection pinned the result equals, bit for bit, smi_unet_backward on
+ * [zeros ; d_eps_live] for LoRA / c3lier sites; at default selection the smaller row count can select other GEMM /
+ * attention kernels (equal to rounding).  DoRA: the common loss scale is the minimum over the live samples only. */
+int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
+                           float* d_lora_up_flat);
+
 /* Per-kernel-class timing, measured with HIP events recorded on the engine's stream around every launch
  * (measurement aid for bench.py's roofline; off by default, adds two event records per launch when on).
  * smi_profile_read synchronises with the host and returns, per class, the summed device time (ms), the algorithmic

@@ -87,6 +87,7 @@ _SIGS = {
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smi_unet_backward_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smi_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "smi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int64)]),
@@ -317,6 +318,12 @@ class Engine(_EngineBase):
 
     def backward(self, d_eps: torch.Tensor, d_down: torch.Tensor, d_up: torch.Tensor):
         check(lib().smi_unet_backward(self.handle, ptr(d_eps), ptr(d_down), ptr(d_up)), "smi_unet_backward")
+
+    def backward_tail(self, d_eps_live: torch.Tensor, d_down: torch.Tensor, d_up: torch.Tensor):
+        """Backward over the LAST d_eps_live.shape[0] adapted samples of the saved pass; the caller promises that the
+        gradient of the other adapted samples' output is exactly zero (smi_unet_backward_tail)."""
+        check(lib().smi_unet_backward_tail(self.handle, int(d_eps_live.shape[0]), ptr(d_eps_live), ptr(d_down),
+                                           ptr(d_up)), "smi_unet_backward_tail")
 
     PROF_CLASSES = ("gemm", "conv", "attention", "norm", "elementwise", "lora")
 

@@ -1206,6 +1206,9 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     static const bool fused_on = []() { const char* e = getenv("SMI_ATTN_BWD_FUSED"); return !(e && e[0] == '0'); }();
     // by measurement (tools/bench_attn.py, SMI_ATTN_BWD_FUSED=0|1): it pays on the small grids -- 4 samples x 20 heads x
     // 1024^2: 116.8 -> 110.6 us -- and loses 3-5 % from 4096 keys on (the two kinds then fill whole rounds by themselves)
+    // (Since the backward runs on the live half of the adapted samples alone, the headline's 4096-key level has 640
+    // workgroups per kind and takes the fused launch as well: measured inside the step against the separate kernels there,
+    // 153.56 vs 153.67 ms per step over three alternations -- no difference, so the rule stays a grid-size rule.)
     if (fused_on && p.dQ && p.dK && p.dV && form != 0 && p.Nk > XS_KEYS &&
         (int64_t)cdiv(p.Nq, 128) * p.H * p.B <= 1024) {
       constexpr size_t sm = dkv_smem<T, DP>() > dq_smem<T, DP>() ? dkv_smem<T, DP>() : dq_smem<T, DP>();

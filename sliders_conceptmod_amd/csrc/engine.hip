@@ -127,6 +127,10 @@ struct Ten {
   // first row of the ADAPTED samples: a batched pass carries frozen samples first and the adapted (LoRA on,
   // differentiated) samples last; gradients `g` cover rows [arow0, rows) only
   int64_t arow0 = 0;
+  // a tail backward (smi_unet_backward_tail) differentiates the last n_live adapted samples only: it moves arow0 up to their
+  // first row in every tensor of the saved pass and notes the distance here, for the few buffers that hold the adapted rows
+  // of the FORWARD only (xa)
+  int64_t bskip = 0;
   bool ng = false;
   float gmul = 1.f;  // the stored gradient g is gmul x the (loss-scaled) gradient; a power of two, 1 but for row vectors
 };
@@ -229,10 +233,12 @@ struct smi_engine {
   bool samp_on = false, bw_samp_on = false;
   int n_conv_sites = 0;
   const float* samp_ptr(bool bwd) const {
-    return (bwd ? bw_samp_on : samp_on) ? samp_mult_dev + (bwd ? MAXS : 0) : nullptr;
+    return (bwd ? bw_samp_on : samp_on) ? samp_mult_dev + (bwd ? MAXS + bw_skip : 0) : nullptr;
   }
   size_t wjobs_cap = 0;
   std::vector<const void*> pinned;
+  // X, P and M describe the rows the backward runs on; in a tail backward the job is still planned over the rows of all
+  // adapted samples, so that its sums are those of the full job (WgradJob::m_begin)
   WgradJob& push_wjob(const void* X, int64_t ldx, const float* P, int64_t ldp, float* dW, int64_t so_r, int64_t so_k,
                       int M, int K, int rr, int seg_cols, int rows_per_sample, float alpha) {
     WgradJob j;
@@ -244,7 +250,8 @@ struct smi_engine {
     j.dW = dW;
     j.so_r = so_r;
     j.so_k = so_k;
-    j.M = M;
+    j.m_begin = bw_skip * rows_per_sample;
+    j.M = j.m_begin + M;
     j.K = K;
     j.r = rr;
     j.seg_cols = seg_cols;
@@ -357,6 +364,7 @@ struct smi_engine {
   Ten* out_ten = nullptr;  // conv_out result (f32 [rows, 4])
   int n_ad = 0;     // adapted samples of the pass in flight (the last n_ad of n)
   int bw_n_ad = 0;  // ... of the saved pass
+  int bw_skip = 0;  // ... of which the backward in flight leaves out the first bw_skip (zero gradient: tail backward)
   int max_n_ad = 0;
 
   size_t esz() const { return 2; }
@@ -1205,7 +1213,7 @@ struct smi_engine {
         WgradJob& j = push_wjob(X, ldx, P, rp, dW, so_r, so_k, M, K, rr, seg_cols, rps, alpha);
         (void)j;
       };
-      push(dy, L->out, xa, d_up ? d_up + L->off_up : nullptr, 1, r, L->out, r, L->nseg > 1 ? cs : 0);
+      push(dy, L->out, xa + x->bskip * rp, d_up ? d_up + L->off_up : nullptr, 1, r, L->out, r, L->nseg > 1 ? cs : 0);
       // all segments of a fused projection in one job only while their rank rows fit the 8-accumulator class; beyond that
       // one job per segment: x is read once per segment, but the reduction kernel keeps R x 8 fp32 accumulators per thread
       // and its speed falls with R -- rank 8 on q|k|v (24 rows -> the 32-row class, 256 accumulators) took 7.5 ms per step
@@ -1563,7 +1571,7 @@ struct smi_engine {
           }
           const int rps = Hout * Wout;
           // d(up)[n][q] += lscale/S * sum_m dy[m][n] xa[m][q];  d(down)[q][ci][tap] += lscale/S * sum_m dxa[m][q] x[pixel(m, tap)][ci]
-          push_wjob(dy, cp->Cout, xa, rp, d_up ? d_up + cp->off_up : nullptr, 1, r, M, cp->Cout, r, 0, rps, lscale);
+          push_wjob(dy, cp->Cout, xa + y->bskip * rp, rp, d_up ? d_up + cp->off_up : nullptr, 1, r, M, cp->Cout, r, 0, rps, lscale);
           for (int t = 0; t < 9; ++t) {
             WgradJob& j = push_wjob(PA(x), cp->Cin, dxa, rp, d_down ? d_down + cp->off_down + t : nullptr,
                                     (int64_t)9 * cp->Cin, 9, M, cp->Cin, r, 0, rps, lscale);
@@ -2339,7 +2347,7 @@ struct smi_engine {
         b.M = (int)MA(hn);
         b.N = C0;
         b.K = 9 * 64;
-        b.Nb = n_adapted;
+        b.Nb = (int)(MA(hn) / HW);
         b.Hin = b.Hout = H;
         b.Win = b.Wout = Wd_;
         b.Cin = 64;
@@ -2364,7 +2372,17 @@ struct smi_engine {
     return err ? -1 : 0;
   }
 
-  int backward(const float* d_eps, float* dd, float* du) {
+  // n_live: d_eps covers the LAST n_live adapted samples of the saved pass; the caller promises that the gradient with
+  // respect to the other adapted samples' output is exactly zero (then so is every gradient row of theirs, and they add
+  // exact zeros to the weight-gradient sums).  n_live == bw_n_ad is the full backward.
+  // a backward consumes the saved pass, also where it fails half way: a tail backward has moved the tensors' arow0
+  void drop_tape() {
+    pinned.clear();
+    tape.clear();
+    tape_valid = false;
+    bw_skip = 0;
+  }
+  int backward(const float* d_eps, float* dd, float* du, int n_live) {
     if (!tape_valid && !dry) {
       set_error("smi_unet_backward: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
       return -4;
@@ -2373,8 +2391,8 @@ struct smi_engine {
     tens = &tens_[1];
     d_down = dd;
     d_up = du;
-    const int n = bw_n_ad, HW = lat_h * lat_w;  // d_eps covers the adapted samples only
-    n_ad = bw_n_ad;
+    const int n = n_live, HW = lat_h * lat_w;  // d_eps covers the live adapted samples only
+    n_ad = n_live;  // rows per sample of a gradient buffer = its rows / n_ad
     Ten* y = out_ten;
     if (!y->ng) {  // adaptor off: nothing depends on the LoRA parameters
       tape.clear();
@@ -2387,6 +2405,14 @@ struct smi_engine {
     }
     wjobs.clear();
     pinned.clear();
+    bw_skip = bw_n_ad - n_live;
+    if (bw_skip > 0) {  // every closure works on rows [arow0, rows): start them at the first live sample (the tape and its
+      for (Ten& t : *tens) {  // tensors do not outlive this call)
+        if (t.n <= 0) continue;
+        t.bskip = (int64_t)bw_skip * (t.rows / t.n);
+        t.arow0 += t.bskip;
+      }
+    }
     // one power-of-two loss scale PER SAMPLE (from max|d_eps[sample]|): a sample's backward arithmetic then does not
     // depend on which other samples share the batch -- W ranks on shards == one rank on the global batch
     RUN(launch_grad_scale(d_eps, n, (int64_t)cfg.out_channels * HW, gscale, MAXS, stream));
@@ -2407,6 +2433,7 @@ struct smi_engine {
       if (!dry) {
         if (wjobs.size() > wjobs_cap) {
           set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", wjobs.size(), wjobs_cap);
+          drop_tape();
           return -1;
         }
         const bool same = wjobs_uploaded.size() == wjobs.size() &&
@@ -2416,20 +2443,19 @@ struct smi_engine {
           if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
                              stream) != hipSuccess) {
             set_error("hipMemcpyAsync (weight-gradient job table) failed");
+            drop_tape();
             return -1;
           }
         }
         double bytes = 0.0, flops = 0.0;
         for (const auto& j : wjobs) {
-          bytes += (double)j.M * j.K * 2.0;
-          flops += 2.0 * j.M * j.K * j.r;
+          bytes += (double)(j.M - j.m_begin) * j.K * 2.0;
+          flops += 2.0 * (j.M - j.m_begin) * j.K * j.r;
         }
         RUNP(SMI_PROF_LORA, flops, bytes, launch_lora_wgrad_grouped(dtype, wjobs, wjobs_dev, stream));
       }
     }
-    pinned.clear();
-    tape.clear();
-    tape_valid = false;
+    drop_tape();
     if (cur->overflow && !dry) {
       set_error("workspace too small for the backward (needs %zu bytes, has %zu)", cur->peak, cur->cap);
       return -3;
@@ -2494,7 +2520,7 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   out[4] = align_up(std::max(e.scr[0].peak, e.scr[1].peak), 4096);
   out[1] = out[3] + 2 * out[4];
   e.forward(batch, batch_adapted, nullptr, 0.f, nullptr, nullptr, nullptr, true, nullptr);
-  e.backward(nullptr, nullptr, nullptr);
+  e.backward(nullptr, nullptr, nullptr, e.bw_n_ad);  // sized for the full backward: a tail backward needs less
   out[2] = align_up(e.arena[1].peak, 4096);
   return e.err ? -1 : 0;
 }
@@ -2890,7 +2916,19 @@ int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat
   SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
   e->err = false;
   GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
-  return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat);
+  return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat, e->bw_n_ad);
+}
+
+int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
+                           float* d_lora_up_flat) {
+  SMI_CHECK(e && d_eps_live && d_lora_down_flat && d_lora_up_flat, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
+  SMI_CHECK(e->tape_valid, "smi_unet_backward_tail: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  SMI_CHECK(n_live >= 1 && n_live <= e->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
+            n_live, e->bw_n_ad);
+  e->err = false;
+  GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
+  return e->backward(d_eps_live, d_lora_down_flat, d_lora_up_flat, n_live);
 }
 
 int smi_profile_enable(smi_engine* e, int enable) {

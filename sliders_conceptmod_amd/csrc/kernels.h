@@ -198,11 +198,15 @@ struct WgradJob {
   const void* X;           // [M, K] 16-bit operand (dY or the layer input), row stride ldx
   const float* P;          // [M, >= nseg * r] fp32 (xa or dxa), row stride ldp
   float* dW;               // output base; element (q, k) at dW[q * so_r + k * so_k]
-  float* partial;          // scratch [nsplit][r][K]
+  float* partial;          // scratch [nsplit - split0][r][K]
   const float* row_scale;  // per-sample factors applied to the rows of P (nullptr: none)
   int64_t ldx, ldp, so_r, so_k;
   int M, K, r, seg_cols, rows_per_sample;
   float alpha;
+  // tail backward: M counts the rows of ALL adapted samples and fixes the geometry below, but only rows [m_begin, M) exist
+  // (and are summed): X, P and row_scale start at row m_begin.  The skipped rows would add exact zeros, so the sums and their
+  // order are those of the full job; split0 = m_begin / rows_per_wg splits are not launched
+  int m_begin, split0;
   // conv_tap >= 0: X is an image [n][Hin][Win][K] and row m = (n, oy, ox) of the OUTPUT grid reads the input pixel of
   // filter tap (ky, kx) = (conv_tap / 3, conv_tap % 3) of a 3x3 / pad-1 conv (zero outside): the k x k LoRA down filter
   int conv_tap, Hin, Win, Hout, Wout, conv_stride, conv_ups;

@@ -137,7 +137,9 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_partial_kernel(const W
   __syncthreads();
   const WgradJob jb = jobs[jsel];
   const int local = blockIdx.x - jb.wg0;
-  const int split = local / jb.ncolblk, colblk = local - split * jb.ncolblk;
+  const int lsplit = local / jb.ncolblk, colblk = local - lsplit * jb.ncolblk;
+  const int split = lsplit + jb.split0;  // rows are counted over all adapted samples; those below m_begin are skipped
+  const int mb = jb.m_begin;
   const int cw = jb.cw;                 // column vectors per workgroup (power of two <= 256)
   const int rpar = 256 / cw;            // row slices
   const int tid = threadIdx.x;
@@ -159,8 +161,8 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_partial_kernel(const W
     for (int i = tid; i < nrow * pw; i += 256) {
       const int rr = i / pw, q = i - rr * pw;
       const int m = row0 + rr;
-      const float rs = jb.row_scale ? jb.row_scale[m / jb.rows_per_sample] : 1.f;
-      ps[i] = jb.P[(int64_t)m * jb.ldp + q] * rs;
+      const float rs = (m >= mb && jb.row_scale) ? jb.row_scale[(m - mb) / jb.rows_per_sample] : 1.f;
+      ps[i] = m >= mb ? jb.P[(int64_t)(m - mb) * jb.ldp + q] * rs : 0.f;
     }
     __syncthreads();
   }
@@ -176,11 +178,11 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_partial_kernel(const W
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
         const int m = m0 + u * rpar;
-        bool ok = m < row1;
-        int64_t xrow = m;
+        bool ok = m < row1 && m >= mb;
+        int64_t xrow = m - mb;
         if (jb.conv_tap >= 0 && ok) {  // output pixel m -> input pixel under this filter tap (3x3, pad 1)
           const int hw = jb.Hout * jb.Wout;
-          const int img = m / hw, rem = m - img * hw;
+          const int img = (m - mb) / hw, rem = (m - mb) - img * hw;
           const int oy = rem / jb.Wout, ox = rem - oy * jb.Wout;
           int iy = oy * jb.conv_stride + jb.conv_tap / 3 - 1, ix = ox * jb.conv_stride + jb.conv_tap % 3 - 1;
           const int hl = jb.conv_ups ? 2 * jb.Hin : jb.Hin, wl = jb.conv_ups ? 2 * jb.Win : jb.Win;
@@ -199,9 +201,9 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_partial_kernel(const W
 #pragma unroll
           for (int q = 0; q < R; ++q) pv[u][q] = (ok && q < r) ? pr[q] : 0.f;
         } else {
-          const float rs = (ok && jb.row_scale) ? jb.row_scale[m / jb.rows_per_sample] : 1.f;
+          const float rs = (ok && jb.row_scale) ? jb.row_scale[(m - mb) / jb.rows_per_sample] : 1.f;
 #pragma unroll
-          for (int q = 0; q < R; ++q) pv[u][q] = (ok && q < r) ? P[(int64_t)m * jb.ldp + q] * rs : 0.f;
+          for (int q = 0; q < R; ++q) pv[u][q] = (ok && q < r) ? P[(int64_t)(m - mb) * jb.ldp + q] * rs : 0.f;
         }
       }
 #pragma unroll
@@ -220,7 +222,7 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_partial_kernel(const W
       for (int e = 0; e < 8; ++e) red[(rsub * cw + cl) * 8 + e] = acc[q][e];
       __syncthreads();
       if (tid < cw && (colblk * cw + tid) * 8 < jb.K) {
-        float* out = jb.partial + ((int64_t)split * r + q) * jb.K + (colblk * cw + tid) * 8;
+        float* out = jb.partial + ((int64_t)lsplit * r + q) * jb.K + (colblk * cw + tid) * 8;
         float sum[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) sum[e] = 0.f;
@@ -254,7 +256,8 @@ __global__ __launch_bounds__(256) void lora_wgrad_grouped_final_kernel(const Wgr
   const int64_t i = (int64_t)(blockIdx.x - jb.fb0) * 32 + e;
   float s = 0.f;
   if (i < total) {
-    for (int sp = g; sp < jb.nsplit; sp += 8) s += jb.partial[(int64_t)sp * total + i];
+    for (int sp = g; sp < jb.nsplit; sp += 8)  // (split sp keeps its group when the first split0 are absent)
+      if (sp >= jb.split0) s += jb.partial[(int64_t)(sp - jb.split0) * total + i];
   }
   red[g][e] = s;
   __syncthreads();
@@ -842,8 +845,9 @@ void wgrad_job_plan(WgradJob& j) {
   // (measured at the headline shape, M = 4096: lora class 6.07 / 5.54 / 5.07 ms with 64 / 128 / 256 rows)
   j.rows_per_wg = rows_env > 0 ? rows_env : (j.M >= 2048 ? 256 : 64);
   j.nsplit = cdiv(j.M, j.rows_per_wg);
+  j.split0 = j.m_begin / j.rows_per_wg;
 }
-size_t wgrad_job_scratch_floats(const WgradJob& j) { return (size_t)j.nsplit * j.r * j.K; }
+size_t wgrad_job_scratch_floats(const WgradJob& j) { return (size_t)(j.nsplit - j.split0) * j.r * j.K; }
 
 // jobs_host: the table as the device will see it (wg0 / fb0 filled here); jobs_dev: its device copy.  Jobs must be
 // sorted by accumulator class (r <= 4, <= 8, <= 16, <= 32): one partial launch per class present, one final launch.
@@ -861,7 +865,7 @@ int wgrad_grouped_finish(std::vector<WgradJob>& jobs) {
       wg = 0;
     }
     j.wg0 = wg;
-    wg += j.nsplit * j.ncolblk;
+    wg += (j.nsplit - j.split0) * j.ncolblk;
     j.fb0 = fb;
     fb += (int)(((int64_t)j.r * j.K + 31) / 32);
   }
@@ -881,7 +885,7 @@ int launch_lora_wgrad_grouped(int dtype, const std::vector<WgradJob>& jobs, cons
     while (k < jobs.size() && cls(jobs[k].r) == c) {
       SMI_CHECK(jobs[k].r >= 1 && jobs[k].r <= 32 && jobs[k].K % 8 == 0 && jobs[k].ldx % 8 == 0,
                 "lora_wgrad: r=%d K=%d", jobs[k].r, jobs[k].K);
-      wgs += jobs[k].nsplit * jobs[k].ncolblk;
+      wgs += (jobs[k].nsplit - jobs[k].split0) * jobs[k].ncolblk;
       final_blocks += (int)(((int64_t)jobs[k].r * jobs[k].K + 31) / 32);
       ++k;
     }

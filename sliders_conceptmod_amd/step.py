@@ -15,6 +15,7 @@ LoRA gradient is all-reduced (RCCL, sum / world) after backward and BEFORE the c
 global-batch gradient exactly as a single-GPU run of the global batch would."""
 from __future__ import annotations
 
+import os
 from typing import Dict, Optional
 
 import torch
@@ -22,11 +23,20 @@ import torch
 from . import _native, parallel
 
 
+def tail_backward_ok(guidance_scale: float, allowed: bool = True) -> bool:
+    """The adapted pass runs the CFG-doubled batch [unconditional x B ; conditional x B] and the prediction is
+    u + g (t - u), so d_eps = [(1 - g) d ; g d].  At g == 1 -- the reference trainers' value for this pass
+    (T/train_lora.py:226-272, `train.cfg` = 1.0 in T/config_util.py:41) -- the first half is exactly zero and the backward
+    runs on the conditional samples alone (smi_unet_backward_tail); the forward is untouched.  SMI_FULL_BACKWARD=1 keeps
+    the full backward on [zeros ; d] (A/B switch)."""
+    return bool(allowed) and 1.0 - float(guidance_scale) == 0.0 and os.environ.get("SMI_FULL_BACKWARD") != "1"
+
+
 class SliderStep:
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, cfg_scale: float = 1.0,
                  skip_dead_cfg_half: bool = False, process_group=None, batch_passes: bool = True,
-                 dedup_uncond: bool = False, preroll_skip_dead_half: bool = True):
+                 dedup_uncond: bool = False, preroll_skip_dead_half: bool = True, tail_backward: bool = True):
         self.unet, self.network, self.scheduler = unet, network, scheduler
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -48,8 +58,9 @@ class SliderStep:
         # T/train_lora_xl.py:66,209-231): predict_noise_xl forms u + 1 * (t - u) from the doubled batch, i.e. t up to one fp32
         # rounding (<= 6e-8 relative) -- the unconditional half only feeds that rounding.  The pre-roll then runs the
         # conditional half alone (UNet batch B instead of 2B).  Off: the doubled batch at every scale.
-        import os
         self.preroll_skip_dead_half = bool(preroll_skip_dead_half) and os.environ.get("SMI_PREROLL_FULL") != "1"  # (A/B switch)
+        # guidance scale exactly 1: the unconditional half of d_eps is zero, the backward skips those samples
+        self.tail_backward = tail_backward_ok(cfg_scale, tail_backward) and not self.skip_dead
         flat = network.flat
         # ONE message per step: [flat fp32 LoRA gradient | loss scalar] -- the loss rides on the
         # gradient's all-reduce
@@ -249,13 +260,15 @@ class SliderStep:
                                                 _native.ptr(negative), sign_eta, target.numel(),
                                                 _native.ptr(self.loss), _native.ptr(dtarget),
                                                 _native.ptr(self.scratch), _native.stream_ptr()), "smi_slider_loss")
-        if self.skip_dead:
-            d_eps = dtarget
-        else:  # d(u + g (t - u)) = (1 - g) du + g dt
-            d_eps = torch.cat([dtarget * (1.0 - self.cfg_scale), dtarget * self.cfg_scale])
         self.grad.zero_()
         n_down = net._n_down
-        engine.backward(d_eps, self.grad[:n_down], self.grad[n_down:])
+        if self.skip_dead:
+            engine.backward(dtarget, self.grad[:n_down], self.grad[n_down:])
+        elif self.tail_backward:  # g == 1: d_eps = [0 ; dtarget], the zero half is not built and not run
+            engine.backward_tail(dtarget, self.grad[:n_down], self.grad[n_down:])
+        else:  # d(u + g (t - u)) = (1 - g) du + g dt
+            d_eps = torch.cat([dtarget * (1.0 - self.cfg_scale), dtarget * self.cfg_scale])
+            engine.backward(d_eps, self.grad[:n_down], self.grad[n_down:])
         parallel.allreduce_mean_(self.msg, self.pg)  # gradient + loss in one collective; no-op on a single rank
         self.step_count += 1
         flat = net.flat
@@ -281,13 +294,15 @@ class ImageSliderStep:
     (c3lier) or DoRA adaptors fall back to one pass per side."""
 
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
-                 weight_decay: float = 1e-2, max_grad_norm: float = 0.0, process_group=None, one_pass: bool = True):
+                 weight_decay: float = 1e-2, max_grad_norm: float = 0.0, process_group=None, one_pass: bool = True,
+                 tail_backward: bool = True):
         self.unet, self.network, self.scheduler = unet, network, scheduler
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
         self.pg = process_group
         self.one_pass = one_pass  # both sides in one UNet pass where the adaptor set allows it (see _one_pass_ok)
         self._one_pass_cached = None
+        self.tail_backward = tail_backward  # at guidance scale 1 the backward skips the unconditional samples
         flat = network.flat
         # one message per step: [flat fp32 LoRA gradient | loss of the high side, loss of the low side]
         self.msg = torch.zeros(flat.numel() + 2, dtype=flat.dtype, device=flat.device)
@@ -332,6 +347,9 @@ class ImageSliderStep:
         diff = pred - noise.float()                       # MSE in fp32 (I/train_lora-scale-xl.py:338)
         self.losses[idx] = (diff * diff).mean()
         dpred = diff * (2.0 / diff.numel())
+        if tail_backward_ok(guidance_scale, self.tail_backward):
+            engine.backward_tail(dpred.contiguous(), self.grad[:n_down], self.grad[n_down:])  # accumulates
+            return
         d_eps = torch.cat([dpred * (1.0 - guidance_scale), dpred * guidance_scale])  # d(u + g (t - u))
         engine.backward(d_eps.contiguous(), self.grad[:n_down], self.grad[n_down:])  # accumulates
 
@@ -348,28 +366,35 @@ class ImageSliderStep:
                     guidance_scale):
         net = self.network
         B = noised_high.shape[0]
-        x = torch.cat([noised_high.float()] * 2 + [noised_low.float()] * 2)       # [high CFG pair | low CFG pair]
+        # [u_hi, u_lo, t_hi, t_lo]: both unconditional halves first, so that the samples with a non-zero output gradient
+        # at guidance 1 are the tail of the batch (per-sample arithmetic does not depend on the batch position)
+        x = torch.cat([noised_high.float(), noised_low.float()] * 2)
         x = self.scheduler.scale_model_input(x, timestep).contiguous()
         n, _, h, w = x.shape
-        c = {k: torch.cat([cond_pos[k], cond_neu[k]]).contiguous() for k in cond_pos}
+        c = {k: torch.cat([cond_pos[k][:B], cond_neu[k][:B], cond_pos[k][B:], cond_neu[k][B:]]).contiguous()
+             for k in cond_pos}
         engine = self.unet._ensure_engine(n, h, w, c["ctx"].shape[1])
         net.set_lora_slider(scale=1)
         net.__enter__()
         flat, n_down, mult = net.engine_params()
         net.__exit__(None, None, None)
-        mults = [mult * scale] * (2 * B) + [-mult * scale] * (2 * B)
+        mults = ([mult * scale] * B + [-mult * scale] * B) * 2
         eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down],
                              flat[n_down:], mults, True)
-        d_parts = []
-        for idx, (e, noise) in enumerate(((eps[:2 * B], noise_high), (eps[2 * B:], noise_low))):
+        dpreds = []
+        for idx, noise in enumerate((noise_high, noise_low)):
+            e = torch.cat([eps[idx * B:(idx + 1) * B], eps[(2 + idx) * B:(3 + idx) * B]])  # this side's CFG pair
             pred = torch.empty((B,) + tuple(e.shape[1:]), dtype=torch.float32, device=e.device)
-            _native.check(self._lib.smi_cfg_combine(_native.ptr(e.contiguous()), _native.ptr(pred), pred.numel(),
+            _native.check(self._lib.smi_cfg_combine(_native.ptr(e), _native.ptr(pred), pred.numel(),
                                                     float(guidance_scale), _native.stream_ptr()), "smi_cfg_combine")
             diff = pred - noise.float()
             self.losses[idx] = (diff * diff).mean()
-            dpred = diff * (2.0 / diff.numel())
-            d_parts += [dpred * (1.0 - guidance_scale), dpred * guidance_scale]
-        engine.backward(torch.cat(d_parts).contiguous(), self.grad[:n_down], self.grad[n_down:])
+            dpreds.append(diff * (2.0 / diff.numel()))
+        if tail_backward_ok(guidance_scale, self.tail_backward):
+            engine.backward_tail(torch.cat(dpreds).contiguous(), self.grad[:n_down], self.grad[n_down:])
+            return
+        d_eps = torch.cat([d * (1.0 - guidance_scale) for d in dpreds] + [d * guidance_scale for d in dpreds])
+        engine.backward(d_eps.contiguous(), self.grad[:n_down], self.grad[n_down:])
 
     def train_step(self, noised_low, noised_high, noise_low, noise_high, timestep, cond_pos: dict, cond_neu: dict,
                    scale: float, guidance_scale: float = 1.0, lr: Optional[float] = None) -> torch.Tensor:
