@@ -315,6 +315,86 @@ int smi_op_lora_skinny(int dtype, const void* x, const void* s, float* out, int 
 int smi_op_lora_wgrad(int dtype, const float* p, const void* x, float* dw, int m, int k, int r, float alpha,
                       float* scratch, void* stream);
 
+/* One entry of the engine's weight-gradient job table (the caller-owned fields of its WgradJob; geometry and scratch
+ * placement are filled by the entry point, as the engine does):
+ *   dW[q * so_r + k * so_k] += alpha * sum_m (P[m][seg * r + q] * row_scale[m / rows_per_sample]) * X[m][k]
+ * with seg = k / seg_cols (seg_cols = 0: one segment) and row_scale NULL for none.  X is 16-bit with row stride ldx, P
+ * fp32 with row stride ldp.  m_begin > 0 is the tail form: M still counts the rows of all samples, but X, P and
+ * row_scale start at row m_begin and only rows [m_begin, M) are summed (rows_per_sample must divide m_begin).
+ * conv_tap >= 0: X is an image [n][Hin][Win][K] and row m = (n, oy, ox) of the [Hout][Wout] output grid reads the input
+ * pixel under tap (conv_tap / 3, conv_tap % 3) of a 3x3 / pad-1 filter with stride conv_stride, on the nearest-2x
+ * upsampled image when conv_ups (zero outside the image); conv_tap = -1: X is a plain [M, K] matrix. */
+typedef struct smi_wgrad_job {
+  const void* X;
+  const float* P;
+  float* dW;
+  const float* row_scale;
+  int64_t ldx, ldp, so_r, so_k;
+  int M, K, r, seg_cols, rows_per_sample;
+  float alpha;
+  int m_begin, conv_tap, Hin, Win, Hout, Wout, conv_stride, conv_ups;
+} smi_wgrad_job;
+/* The engine's grouped reduction on a table of n jobs of any ranks (1..32) in any order: planned, sorted by accumulator
+ * class and launched exactly as a backward pass does it.  scratch (device, fp32): every job's partials, each rounded up
+ * to 64 floats, followed by the device copy of the table; smi_op_lora_wgrad_jobs_floats gives the size.  Fails with a
+ * message when scratch_floats is smaller.  Synchronises the stream before it returns. */
+int smi_op_lora_wgrad_jobs_floats(const smi_wgrad_job* jobs, int n, size_t* out_floats);
+int smi_op_lora_wgrad_jobs(int dtype, const smi_wgrad_job* jobs, int n, float* scratch, size_t scratch_floats,
+                           void* stream);
+
+/* One DoRA Linear (T/dora.py:124-162), possibly a fused projection of nseg segments that share the frozen W
+ * [nseg * cs, K] (16-bit).  down / up are the flat fp32 parameter buffers: segment s has lora_down [r, K] at
+ * down + off_down + s * r * K, lora_up [cs, r] at up + off_up + s * cs * r and dora_scale [K] at up + off_dora + s * K
+ * (off_down a multiple of 4 floats, K % 8 == 0).  Outputs: cnorm [nseg, K] fp32 column norms of V = W + up down,
+ * dW [nseg * cs, K] 16-bit = mult * scale * (V * dora_scale / cnorm - W), dWt [K, nseg * cs] its transpose. */
+typedef struct smi_dora_site {
+  const void* W;
+  int64_t off_down, off_up, off_dora;
+  void* dW;
+  void* dWt;
+  float* cnorm;
+  int r, nseg, K, cs;
+  float scale;
+} smi_dora_site;
+/* cnorm, dW and dWt of n_sites sites in the engine's three launches (norms, deltas, transposes; one rank class for the
+ * whole table).  sites_dev: device memory for the table, n_sites * sizeof(smi_dora_site) bytes.  Synchronises. */
+int smi_op_dora_prep(int dtype, const smi_dora_site* sites, int n_sites, const float* down, const float* up, float mult,
+                     void* sites_dev, void* stream);
+/* Gradients of one site from G = d(loss) / d(dW) (fp32 [nseg * cs, K]) with the column norm detached, accumulated (+=)
+ * into the flat buffers: d_down at off_down, d_up at off_up (lora_up) and off_dora (dora_scale), all times
+ * alpha * (alpha_dev ? alpha_dev[0] : 1).  Reads site->cnorm (smi_op_dora_prep).  scratch: device fp32,
+ * smi_op_dora_grads_floats of them; fails with a message when scratch_floats is smaller. */
+int smi_op_dora_grads_floats(const smi_dora_site* site, size_t* out_floats);
+int smi_op_dora_grads(int dtype, const smi_dora_site* site, const float* G, const float* down, const float* up,
+                      float* d_down, float* d_up, float alpha, const float* alpha_dev, float* scratch,
+                      size_t scratch_floats, void* stream);
+/* dst[c][m] (16-bit, [C, Mp]) = src[m][c] (row stride lds) * (f ? f[m / rows_per_sample] : 1) for m < M, 0 for
+ * M <= m < Mp: the operand transposes of the DoRA weight-gradient GEMM.  16-byte accesses when C % 8 == 0, lds % 8 == 0,
+ * Mp % 64 == 0 and both pointers are 16-byte aligned, element-wise otherwise. */
+int smi_op_transpose_scaled(int dtype, const void* src, int64_t lds, void* dst, int M, int C, int Mp, const float* f,
+                            int rows_per_sample, void* stream);
+/* The 16-bit shadow operands of the adapted GEMMs, rebuilt from the flat fp32 parameters once per forward.  Per site, at
+ * element offsets into `shadow`: downT [rows_pad, K] at dst_down = the nseg * r lora_down rows (at down + off_down), zero
+ * rows up to rows_pad; upT [rows_pad, nseg * cs] at dst_up, block diagonal: upT[s * r + q][s * cs + n] = lora_up_s[n][q]
+ * (lora_up_s [cs, r] at up + off_up + s * cs * r).  conv = 1 / 2: a 3x3 conv site, lora_down is [r][K][3][3]: downT is
+ * [rows_pad, 9 K] in (tap, channel) order, and dst_gw gets the gradient filter [K][9][64], gw[c][tt][q] = down[q][c][t]
+ * with t = 8 - tt (conv = 1: flipped taps) or t = tt (conv = 2: the stride-2 layer), zero for q >= r.
+ * sites_dev: device memory for the table, n_sites * sizeof(smi_lora_prep_site) bytes.  Synchronises. */
+typedef struct smi_lora_prep_site {
+  int64_t off_down, off_up, dst_down, dst_up;
+  int r, nseg, K, cs, rows_pad, conv;
+  int64_t dst_gw;
+} smi_lora_prep_site;
+int smi_op_lora_prep(int dtype, const smi_lora_prep_site* sites, int n_sites, const float* down, const float* up,
+                     void* shadow, void* sites_dev, void* stream);
+/* The per-sample power-of-two loss scales of a backward pass: scale_out[j] = 2^e with max|d_eps[j]| * 2^e in
+ * (target / 2, target] (target 16; 1 for an all-zero sample), scale_out[inv_off + j] = 1 / scale_out[j]; then
+ * min_out[0] = min_j scale, min_out[1] = 1 / min, min_out[2 + j] = min / scale_out[j]. */
+int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, float* scale_out, int inv_off,
+                      float* min_out, void* stream);
+/* x[m][0..n) (fp32, row stride ld) *= row_mul[m / rows_per_mul] */
+int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

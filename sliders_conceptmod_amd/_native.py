@@ -52,6 +52,29 @@ class LoraSiteC(C.Structure):
                 ("scale", C.c_float), ("off_dora", C.c_int64)]
 
 
+class WgradJobC(C.Structure):
+    """include/smi.h smi_wgrad_job: one entry of the grouped weight-gradient job table (test entry point)."""
+    _fields_ = [("X", C.c_void_p), ("P", C.c_void_p), ("dW", C.c_void_p), ("row_scale", C.c_void_p),
+                ("ldx", C.c_int64), ("ldp", C.c_int64), ("so_r", C.c_int64), ("so_k", C.c_int64),
+                ("M", C.c_int), ("K", C.c_int), ("r", C.c_int), ("seg_cols", C.c_int), ("rows_per_sample", C.c_int),
+                ("alpha", C.c_float), ("m_begin", C.c_int), ("conv_tap", C.c_int), ("Hin", C.c_int), ("Win", C.c_int),
+                ("Hout", C.c_int), ("Wout", C.c_int), ("conv_stride", C.c_int), ("conv_ups", C.c_int)]
+
+
+class DoraSiteC(C.Structure):
+    """include/smi.h smi_dora_site: one DoRA Linear of the per-kernel DoRA entry points."""
+    _fields_ = [("W", C.c_void_p), ("off_down", C.c_int64), ("off_up", C.c_int64), ("off_dora", C.c_int64),
+                ("dW", C.c_void_p), ("dWt", C.c_void_p), ("cnorm", C.c_void_p), ("r", C.c_int), ("nseg", C.c_int),
+                ("K", C.c_int), ("cs", C.c_int), ("scale", C.c_float)]
+
+
+class LoraPrepSiteC(C.Structure):
+    """include/smi.h smi_lora_prep_site: one site of the 16-bit shadow-operand preparation."""
+    _fields_ = [("off_down", C.c_int64), ("off_up", C.c_int64), ("dst_down", C.c_int64), ("dst_up", C.c_int64),
+                ("r", C.c_int), ("nseg", C.c_int), ("K", C.c_int), ("cs", C.c_int), ("rows_pad", C.c_int), ("conv", C.c_int),
+                ("dst_gw", C.c_int64)]
+
+
 _lib = None
 
 _SIGS = {
@@ -115,6 +138,19 @@ _SIGS = {
     "smi_op_lora_skinny": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "smi_op_lora_wgrad": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_void_p,
                                                                                    C.c_void_p]),
+    "smi_op_lora_wgrad_jobs_floats": (C.c_int, [C.POINTER(WgradJobC), C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_op_lora_wgrad_jobs": (C.c_int, [C.c_int, C.POINTER(WgradJobC), C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "smi_op_dora_prep": (C.c_int, [C.c_int, C.POINTER(DoraSiteC), C.c_int, C.c_void_p, C.c_void_p, C.c_float,
+                                   C.c_void_p, C.c_void_p]),
+    "smi_op_dora_grads_floats": (C.c_int, [C.POINTER(DoraSiteC), C.POINTER(C.c_size_t)]),
+    "smi_op_dora_grads": (C.c_int, [C.c_int, C.POINTER(DoraSiteC)] + [C.c_void_p] * 5 + [C.c_float, C.c_void_p,
+                                                                                        C.c_void_p, C.c_size_t,
+                                                                                        C.c_void_p]),
+    "smi_op_lora_prep": (C.c_int, [C.c_int, C.POINTER(LoraPrepSiteC), C.c_int] + [C.c_void_p] * 5),
+    "smi_op_transpose_scaled": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                          C.c_void_p, C.c_int, C.c_void_p]),
+    "smi_op_grad_scale": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "smi_op_row_scale_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGS)

@@ -296,9 +296,15 @@ __global__ __launch_bounds__(256) void grad_scale_kernel(const float* __restrict
     amax = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
     float s = 1.f;
     if (amax > 0.f && isfinite(amax)) {
-      int e = (int)floorf(log2f(target / amax));
+      // e = floor(log2(target / amax)) from the exponents, exactly: amax = ma 2^ea, target = mt 2^et with ma, mt in [0.5, 1),
+      // so amax 2^e <= target < amax 2^(e + 1) for e = et - ea - (ma > mt).  (floorf(log2f(target / amax)) was one too large
+      // when the quotient sat within an ulp below a power of two -- log2f rounds up to the integer -- and max * scale then
+      // exceeded the target: DESIGN.md section 5.)
+      int ea, et;
+      const float ma = frexpf(amax, &ea), mt = frexpf(target, &et);
+      int e = et - ea - (ma > mt ? 1 : 0);
       e = e > 40 ? 40 : (e < -40 ? -40 : e);
-      s = exp2f((float)e);
+      s = ldexpf(1.f, e);
     }
     out[blockIdx.x] = s;
     out[inv_off + blockIdx.x] = 1.f / s;

@@ -3182,4 +3182,164 @@ int smi_op_lora_wgrad(int dtype, const float* p, const void* x, float* dw, int m
   return launch_lora_wgrad_grouped(dtype, jobs, dev, (hipStream_t)stream);
 }
 
+// a job table as a backward pass builds it: plan per job, partials laid out in scratch, sort + launch offsets
+static int wgrad_jobs_from_c(const smi_wgrad_job* in, int n, float* scratch, std::vector<WgradJob>& jobs,
+                             size_t* floats) {
+  SMI_CHECK(in && n >= 1, "lora_wgrad_jobs: empty table");
+  jobs.resize(n);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    const smi_wgrad_job& s = in[i];
+    SMI_CHECK(s.M >= 1 && s.K >= 8 && s.r >= 1 && s.r <= 32 && s.rows_per_sample >= 1 && s.m_begin >= 0 &&
+                  s.m_begin < s.M && s.m_begin % s.rows_per_sample == 0 && (s.seg_cols == 0 || s.K % s.seg_cols == 0),
+              "lora_wgrad_jobs: job %d: M=%d K=%d r=%d rows_per_sample=%d m_begin=%d seg_cols=%d", i, s.M, s.K, s.r,
+              s.rows_per_sample, s.m_begin, s.seg_cols);
+    WgradJob& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.X = s.X;
+    j.P = s.P;
+    j.dW = s.dW;
+    j.row_scale = s.row_scale;
+    j.ldx = s.ldx;
+    j.ldp = s.ldp;
+    j.so_r = s.so_r;
+    j.so_k = s.so_k;
+    j.M = s.M;
+    j.K = s.K;
+    j.r = s.r;
+    j.seg_cols = s.seg_cols;
+    j.rows_per_sample = s.rows_per_sample;
+    j.alpha = s.alpha;
+    j.m_begin = s.m_begin;
+    j.conv_tap = s.conv_tap;
+    j.Hin = s.Hin;
+    j.Win = s.Win;
+    j.Hout = s.Hout;
+    j.Wout = s.Wout;
+    j.conv_stride = s.conv_stride;
+    j.conv_ups = s.conv_ups;
+    wgrad_job_plan(j);
+    j.partial = scratch ? scratch + off : nullptr;
+    off += ((wgrad_job_scratch_floats(j) + 63) / 64) * 64;
+  }
+  *floats = off;
+  return 0;
+}
+int smi_op_lora_wgrad_jobs_floats(const smi_wgrad_job* jobs_c, int n, size_t* out_floats) {
+  std::vector<WgradJob> jobs;
+  size_t part = 0;
+  if (int rc = wgrad_jobs_from_c(jobs_c, n, nullptr, jobs, &part)) return rc;
+  *out_floats = part + ((size_t)n * sizeof(WgradJob) + 3) / 4;
+  return 0;
+}
+int smi_op_lora_wgrad_jobs(int dtype, const smi_wgrad_job* jobs_c, int n, float* scratch, size_t scratch_floats,
+                           void* stream) {
+  std::vector<WgradJob> jobs;
+  size_t part = 0;
+  if (int rc = wgrad_jobs_from_c(jobs_c, n, scratch, jobs, &part)) return rc;
+  const size_t need = part + ((size_t)n * sizeof(WgradJob) + 3) / 4;
+  SMI_CHECK(scratch && scratch_floats >= need, "lora_wgrad_jobs: scratch of %zu floats, %zu needed", scratch_floats, need);
+  wgrad_grouped_finish(jobs);
+  WgradJob* dev = reinterpret_cast<WgradJob*>(scratch + part);
+  SMI_HIP(hipMemcpyAsync(dev, jobs.data(), (size_t)n * sizeof(WgradJob), hipMemcpyHostToDevice, (hipStream_t)stream));
+  const int rc = launch_lora_wgrad_grouped(dtype, jobs, dev, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+
+static void dora_site_from_c(const smi_dora_site& s, DoraSite& d) {
+  memset(&d, 0, sizeof(d));
+  d.W = s.W;
+  d.off_down = s.off_down;
+  d.off_up = s.off_up;
+  d.off_dora = s.off_dora;
+  d.dW = s.dW;
+  d.dWt = s.dWt;
+  d.cnorm = s.cnorm;
+  d.r = s.r;
+  d.nseg = s.nseg;
+  d.K = s.K;
+  d.cs = s.cs;
+  d.scale = s.scale;
+}
+int smi_op_dora_prep(int dtype, const smi_dora_site* sites, int n_sites, const float* down, const float* up, float mult,
+                     void* sites_dev, void* stream) {
+  static_assert(sizeof(DoraSite) == sizeof(smi_dora_site), "smi_dora_site sizes the device table");
+  SMI_CHECK(sites && n_sites >= 1 && sites_dev, "dora_prep: empty table");
+  std::vector<DoraSite> host(n_sites);
+  for (int i = 0; i < n_sites; ++i) {
+    SMI_CHECK(sites[i].nseg >= 1 && sites[i].cs >= 1 && sites[i].K >= 8 && sites[i].off_down % 4 == 0,
+              "dora_prep: site %d: nseg=%d cs=%d K=%d off_down=%lld", i, sites[i].nseg, sites[i].cs, sites[i].K,
+              (long long)sites[i].off_down);
+    dora_site_from_c(sites[i], host[i]);
+  }
+  DoraSite* dev = reinterpret_cast<DoraSite*>(sites_dev);
+  SMI_HIP(hipMemcpyAsync(dev, host.data(), (size_t)n_sites * sizeof(DoraSite), hipMemcpyHostToDevice, (hipStream_t)stream));
+  int rc = launch_dora_prep(dtype, dev, host.data(), n_sites, down, up, mult, (hipStream_t)stream);
+  if (!rc) rc = launch_dora_transpose(dtype, dev, host.data(), n_sites, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+int smi_op_dora_grads_floats(const smi_dora_site* site, size_t* out_floats) {
+  SMI_CHECK(site && site->r >= 1 && site->nseg >= 1 && site->K >= 8, "dora_grads: bad site");
+  DoraSite d;
+  dora_site_from_c(*site, d);
+  *out_floats = dora_grad_scratch_floats(d);
+  return 0;
+}
+int smi_op_dora_grads(int dtype, const smi_dora_site* site, const float* G, const float* down, const float* up,
+                      float* d_down, float* d_up, float alpha, const float* alpha_dev, float* scratch,
+                      size_t scratch_floats, void* stream) {
+  SMI_CHECK(site && site->nseg >= 1 && site->cs >= 1 && site->K >= 8 && site->K % 8 == 0 && site->off_down % 4 == 0,
+            "dora_grads: bad site");
+  DoraSite d;
+  dora_site_from_c(*site, d);
+  SMI_CHECK(scratch && scratch_floats >= dora_grad_scratch_floats(d), "dora_grads: scratch of %zu floats, %zu needed",
+            scratch_floats, dora_grad_scratch_floats(d));
+  return launch_dora_grads(dtype, d, G, down, up, d_down, d_up, alpha, alpha_dev, scratch, (hipStream_t)stream);
+}
+int smi_op_lora_prep(int dtype, const smi_lora_prep_site* sites, int n_sites, const float* down, const float* up,
+                     void* shadow, void* sites_dev, void* stream) {
+  static_assert(sizeof(HostLoraPrepSite) == sizeof(smi_lora_prep_site), "smi_lora_prep_site sizes the device table");
+  SMI_CHECK(sites && n_sites >= 1 && sites_dev && shadow, "lora_prep: empty table");
+  std::vector<HostLoraPrepSite> host(n_sites);
+  for (int i = 0; i < n_sites; ++i) {
+    const smi_lora_prep_site& s = sites[i];
+    SMI_CHECK(s.r >= 1 && s.nseg >= 1 && s.K >= 1 && s.cs >= 1 && s.rows_pad >= s.r * s.nseg && s.conv >= 0 && s.conv <= 2 &&
+                  (s.conv == 0 || s.r <= 64),
+              "lora_prep: site %d: r=%d nseg=%d K=%d cs=%d rows_pad=%d conv=%d", i, s.r, s.nseg, s.K, s.cs, s.rows_pad, s.conv);
+    HostLoraPrepSite& h = host[i];
+    memset(&h, 0, sizeof(h));
+    h.off_down = s.off_down;
+    h.off_up = s.off_up;
+    h.dst_down = s.dst_down;
+    h.dst_up = s.dst_up;
+    h.r = s.r;
+    h.nseg = s.nseg;
+    h.K = s.K;
+    h.cs = s.cs;
+    h.rows_pad = s.rows_pad;
+    h.conv = s.conv;
+    h.dst_gw = s.dst_gw;
+  }
+  SMI_HIP(hipMemcpyAsync(sites_dev, host.data(), (size_t)n_sites * sizeof(HostLoraPrepSite), hipMemcpyHostToDevice,
+                         (hipStream_t)stream));
+  const int rc = launch_lora_prep(dtype, sites_dev, n_sites, down, up, shadow, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+int smi_op_transpose_scaled(int dtype, const void* src, int64_t lds, void* dst, int M, int C, int Mp, const float* f,
+                            int rows_per_sample, void* stream) {
+  return launch_transpose_scaled(dtype, src, lds, dst, M, C, Mp, f, rows_per_sample, (hipStream_t)stream);
+}
+int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, float* scale_out, int inv_off,
+                      float* min_out, void* stream) {
+  int rc = launch_grad_scale(d_eps, n_samples, per_sample, scale_out, inv_off, (hipStream_t)stream);
+  if (rc) return rc;
+  return launch_scale_min(scale_out, n_samples, min_out, (hipStream_t)stream);
+}
+int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream) {
+  return launch_row_scale_f32(x, ld, m, n, row_mul, rows_per_mul, (hipStream_t)stream);
+}
+
 }  // extern "C"
