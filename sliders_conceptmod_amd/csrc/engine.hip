@@ -421,6 +421,23 @@ struct smi_engine {
     fprintf(stderr, " %s\n", e == hipSuccess ? "ok" : hipGetErrorString(e));
     fflush(stderr);
   }
+  // RUNP for launch_gemm: `what` names the site in the trace line; `tagged` launches enter the per-shape table of
+  // SMI_PROF_DUMP.  flops / bytes are the site's algorithmic counts (gemm_flops / gemm_bytes of p unless the launched
+  // shape is padded)
+  void run_gemm(int cat, const GemmParams& p, double flops, double bytes, bool tagged, const char* what) {
+    if (dry || err) return;
+    prof_begin(cat, flops, bytes);
+    if (tagged && prof_on && prof_dump) next_tag = gemm_tag(p);
+    if (trace_launches) trace_before(what);
+    if (launch_gemm(p, stream) != 0) err = true;
+    if (trace_launches) trace_after();
+    prof_end();
+    bound_queue_depth();
+  }
+  static double gemm_flops(const GemmParams& p) { return 2.0 * p.M * p.N * p.K; }
+  static double gemm_bytes(const GemmParams& p) {
+    return 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N);
+  }
 
   // ---- per-kernel-class timing with HIP events on the engine's stream (profiling mode only)
   bool prof_on = false;
@@ -476,7 +493,7 @@ struct smi_engine {
   }
   void prof_end() {
     if (!prof_on) return;
-    prof_ev.back().tag.swap(next_tag);  // set while the call's arguments were evaluated
+    prof_ev.back().tag.swap(next_tag);  // set by run_gemm for a tagged launch
     next_tag.clear();
     (void)hipEventRecord(prof_ev.back().b, stream);
   }
@@ -1059,7 +1076,26 @@ struct smi_engine {
   // ---------------------------------------------------------------------------------------------------------
   // ops
   // ---------------------------------------------------------------------------------------------------------
-  bool lora_active(const Lin& L) const { return L.nsite > 0 && (dry || (lora_down && lora_up && mult != 0.f)); }
+  template <class Site>  // Lin or Conv
+  bool lora_active(const Site& L) const { return L.nsite > 0 && (dry || (lora_down && lora_up && mult != 0.f)); }
+  // first adapted sample / adapted samples of t, whose samples are `rows` rows each
+  int ad_first(const Ten* t, int rows) const { return (int)(t->arow0 / rows); }
+  int ad_samples(const Ten* t, int rows) const { return t->n - ad_first(t, rows); }
+  // rows per adapted sample of a buffer that holds M rows of the adapted samples
+  int rows_per_ad(int64_t M) const { return std::max(1, (int)(M / std::max(n_ad, 1))); }
+
+  // out[M, R] (fp32, dense) = X[M, K] * S[R, K]^T against a 16-bit LoRA shadow S: xa = x down^T and dxa = dy up.  The skinny
+  // kernel where it takes the shape, else a GEMM (+ the per-sample multipliers `row_mul` as a launch of their own)
+  void skinny_product(const void* X, int64_t ldx, const void* S, float* out, int M, int R, int K, double flops,
+                      const float* row_mul, bool tagged, const char* what) {
+    if (dry || lora_skinny_supported(X, ldx, S, out, R, M, R, K)) {
+      RUNP(SMI_PROF_LORA, flops, 0.0,
+           launch_lora_skinny(dtype, X, ldx, S, out, R, M, R, K, stream, row_mul, rows_per_ad(M)));
+      return;
+    }
+    run_gemm(SMI_PROF_LORA, gemm_nt(dtype, X, ldx, S, out, R, M, R, K).f32_out(), flops, 0.0, tagged, what);
+    if (row_mul) RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_row_scale_f32(out, R, M, R, row_mul, rows_per_ad(M), stream));
+  }
 
   Ten* linear(Ten* x, const Lin& L, Ten* res = nullptr) {
     Ten* y = new_ten(x->rows, L.out, x->n, x->H, x->W);
@@ -1069,71 +1105,19 @@ struct smi_engine {
     const float lscale = mult * L.scale;
     if (lon && !L.dora) {  // xa[M, rows_pad] = x * down^T as one MFMA GEMM on the 16-bit shadow copy (fp32 result)
       xa = alloc_f32((size_t)MA(x) * L.rows_pad);
-      GemmParams g;
-      g.dtype = dtype;
-      g.A = PA(x);
-      g.lda = x->cols;
-      g.W = shadow_ptr(L.sh_down);
-      g.C = xa;
-      g.ldc = L.rows_pad;
-      g.out_f32 = 1;
-      g.M = (int)MA(x);
-      g.N = L.rows_pad;
-      g.K = L.in;
-      if (dry || lora_skinny_supported(g.A, g.lda, g.W, xa, g.ldc, g.M, g.N, g.K))
-        RUNP(SMI_PROF_LORA, 2.0 * g.M * rtot * g.K, 0.0,
-             launch_lora_skinny(dtype, g.A, g.lda, g.W, xa, g.ldc, g.M, g.N, g.K, stream, samp_ptr(false),
-                                std::max(1, g.M / std::max(n_ad, 1))));
-      else {
-        RUNP(SMI_PROF_LORA, 2.0 * g.M * rtot * g.K, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(g), 0) : 0, launch_gemm(g, stream)));
-        if (samp_on)
-          RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_row_scale_f32(xa, g.ldc, g.M, g.N, samp_ptr(false),
-                                                             std::max(1, g.M / std::max(n_ad, 1)), stream));
-      }
+      skinny_product(PA(x), x->cols, shadow_ptr(L.sh_down), xa, (int)MA(x), L.rows_pad, L.in,
+                     2.0 * (int)MA(x) * rtot * L.in, samp_ptr(false), true, "linear xa");
     }
-    GemmParams p;
-    p.dtype = dtype;
-    p.A = x->p;
-    p.lda = x->cols;
-    p.W = L.W;
-    p.C = y->p;
-    p.ldc = L.out;
-    p.M = (int)x->rows;
-    p.N = L.out;
-    p.K = L.in;
-    p.bias = L.b;
-    if (res) {
-      p.res = res->p;
-      p.ldr = res->cols;
-    }
-    if (lon && !L.dora) {
-      p.lora_xa = xa;
-      p.ld_xa = L.rows_pad;
-      p.lora_up = lora_up + L.off_up;
-      p.up_sn = L.rank;
-      p.up_sq = 1;
-      p.lora_r = L.rank;
-      p.lora_seg = L.nseg > 1 ? L.out / L.nseg : 0;
-      p.lora_scale = lscale;
-      p.lora_row0 = (int)x->arow0;
-    }
-    RUNP(SMI_PROF_GEMM, 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N),
-         (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+    GemmParams p = gemm_nt(dtype, x->p, x->cols, L.W, y->p, L.out, (int)x->rows, L.out, L.in).with_bias(L.b);
+    if (res) p.with_res(res->p, res->cols);
+    if (lon && !L.dora)
+      p.with_lora(xa, L.rows_pad, lora_up + L.off_up, L.rank, L.nseg > 1 ? L.out / L.nseg : 0, lscale, (int)x->arow0);
+    run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), gemm_bytes(p), true, "linear");
     y->arow0 = x->arow0;
     if (lon && L.dora && MA(x) > 0) {  // adapted rows: y += x dW^T (dW holds lscale), accumulated onto the main result
-      GemmParams d;
-      d.dtype = dtype;
-      d.A = PA(x);
-      d.lda = x->cols;
-      d.W = dora_sites[L.dora_idx].dW;
-      d.C = PA(y);
-      d.ldc = L.out;
-      d.res = PA(y);
-      d.ldr = L.out;
-      d.M = (int)MA(x);
-      d.N = L.out;
-      d.K = L.in;
-      RUNP(SMI_PROF_LORA, 2.0 * d.M * d.N * d.K, 0.0, launch_gemm(d, stream));
+      const GemmParams d = gemm_nt(dtype, PA(x), x->cols, dora_sites[L.dora_idx].dW, PA(y), L.out, (int)MA(x), L.out, L.in)
+                               .with_res(PA(y), L.out);
+      run_gemm(SMI_PROF_LORA, d, gemm_flops(d), 0.0, false, "dora forward");
     }
     y->ng = lon || x->ng || (res && res->ng);
     if (saving && y->ng) {
@@ -1154,24 +1138,14 @@ struct smi_engine {
       // power-of-two loss scales, so dY is brought to the smallest one while it is transposed (min / scale_j <= 1)
       const DoraSite& ds = dora_sites[L->dora_idx];
       const int Mp = (M + 63) / 64 * 64;
-      const int rps = (int)(M / std::max(n_ad, 1));
+      const int rps = rows_per_ad(M);
       void* dyT = alloc_t(L->out, Mp);
       void* xT = alloc_t(L->in, Mp);
       float* G = alloc_f32((size_t)L->out * L->in);
       RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_transpose_scaled(dtype, dy, L->out, dyT, M, L->out, Mp, gscale + 2 * MAXS + 2, rps, stream));
       RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_transpose_scaled(dtype, PA(x), x->cols, xT, M, L->in, Mp, nullptr, rps, stream));
-      GemmParams g;
-      g.dtype = dtype;
-      g.A = dyT;
-      g.lda = Mp;
-      g.W = xT;
-      g.C = G;
-      g.ldc = L->in;
-      g.out_f32 = 1;
-      g.M = L->out;
-      g.N = L->in;
-      g.K = Mp;
-      RUNP(SMI_PROF_LORA, 2.0 * g.M * g.N * M, 0.0, launch_gemm(g, stream));
+      run_gemm(SMI_PROF_LORA, gemm_nt(dtype, dyT, Mp, xT, G, L->in, L->out, L->in, Mp).f32_out(),
+               2.0 * L->out * L->in * M, 0.0, false, "dora G");
       // dW was built with lscale folded in: d(dW_unscaled) = lscale * G; the common loss scale (the minimum) divides out
       float* dscr = alloc_f32(dora_grad_scratch_floats(ds));
       RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_dora_grads(dtype, ds, G, bw_down, bw_up, d_down, d_up, lscale / y->gmul, gscale + 2 * MAXS + 1, dscr, stream));
@@ -1181,37 +1155,16 @@ struct smi_engine {
       const int r = L->rank;
       const int rp = L->rows_pad;
       dxa = alloc_f32((size_t)M * rp);
-      {  // dxa[M, rows_pad] = dy * upT^T : one MFMA GEMM against the block-diagonal 16-bit shadow of lora_up
-        GemmParams g;
-        g.dtype = dtype;
-        g.A = dy;
-        g.lda = L->out;
-        g.W = shadow_ptr(L->sh_up);
-        g.C = dxa;
-        g.ldc = rp;
-        g.out_f32 = 1;
-        g.M = M;
-        g.N = rp;
-        g.K = L->out;
-        if (dry || lora_skinny_supported(g.A, g.lda, g.W, dxa, g.ldc, g.M, g.N, g.K))
-          RUNP(SMI_PROF_LORA, 2.0 * M * rtot * cs, 0.0,
-               launch_lora_skinny(dtype, g.A, g.lda, g.W, dxa, g.ldc, g.M, g.N, g.K, stream, samp_ptr(true),
-                                  std::max(1, M / std::max(n_ad, 1))));
-        else {
-          RUNP(SMI_PROF_LORA, 2.0 * M * rtot * cs, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(g), 0) : 0, launch_gemm(g, stream)));
-          if (bw_samp_on)
-            RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_row_scale_f32(dxa, g.ldc, g.M, g.N, samp_ptr(true),
-                                                               std::max(1, M / std::max(n_ad, 1)), stream));
-        }
-      }
+      // dxa[M, rows_pad] = dy * upT^T : one MFMA GEMM against the block-diagonal 16-bit shadow of lora_up
+      skinny_product(dy, L->out, shadow_ptr(L->sh_up), dxa, M, rp, L->out, 2.0 * M * rtot * cs, samp_ptr(true), true,
+                     "linear dxa");
       // deferred (see `wjobs`): d(up)[n][q] += lscale/S * sum_m dy[m][n] * xa[m][seg(n)*r + q]  for all segments,
       //                         d(down)[q'][k] += lscale/S * sum_m dxa[m][q'] * x[m][k]       (q' over the r_tot rows)
-      const int rps = (int)(M / std::max(n_ad, 1));
+      const int rps = rows_per_ad(M);
       const float alpha = lscale / y->gmul;  // y->gmul: power-of-two factor the stored gradient carries (1 but for row vectors)
       auto push = [&](const void* X, int64_t ldx, const float* P, float* dW, int64_t so_r, int64_t so_k, int K, int rr,
                       int seg_cols) {
-        WgradJob& j = push_wjob(X, ldx, P, rp, dW, so_r, so_k, M, K, rr, seg_cols, rps, alpha);
-        (void)j;
+        push_wjob(X, ldx, P, rp, dW, so_r, so_k, M, K, rr, seg_cols, rps, alpha);
       };
       push(dy, L->out, xa + x->bskip * rp, d_up ? d_up + L->off_up : nullptr, 1, r, L->out, r, L->nseg > 1 ? cs : 0);
       // all segments of a fused projection in one job only while their rank rows fit the 8-accumulator class; beyond that
@@ -1236,46 +1189,15 @@ struct smi_engine {
         return;
       }
       const Slot gs = grad_slot(x);
-      GemmParams p;
-      p.dtype = dtype;
-      p.A = dy;
-      p.lda = L->out;
-      p.W = L->Wt;
-      p.C = gs.out;
-      p.ldc = L->in;
-      p.M = M;
-      p.N = L->in;
-      p.K = L->out;
-      if (gs.add) {
-        p.res = gs.add;
-        p.ldr = L->in;
-      }
-      if (lon && !L->dora) {
-        p.lora_xa = dxa;
-        p.ld_xa = L->rows_pad;
-        p.lora_up = bw_down + L->off_down;  // A_cat [rtot, in] read as [in][rtot]
-        p.up_sn = 1;
-        p.up_sq = L->in;
-        p.lora_r = rtot;
-        p.lora_seg = 0;
-        p.lora_scale = lscale;
-      }
-      RUNP(SMI_PROF_GEMM, 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + (double)p.M * p.N),
-           (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+      GemmParams p = gemm_nt(dtype, dy, L->out, L->Wt, gs.out, L->in, M, L->in, L->out);
+      if (gs.add) p.with_res(gs.add, L->in);
+      // (down: A_cat [rtot, in] read as [in][rtot])
+      if (lon && !L->dora) p.with_lora_dx(dxa, L->rows_pad, bw_down + L->off_down, rtot, lscale);
+      run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), gemm_bytes(p), true, "linear dX");
       if (lon && L->dora) {  // dX += dY dW (dW^T [in, out] is the K-contiguous operand), accumulated in place
-        GemmParams d;
-        d.dtype = dtype;
-        d.A = dy;
-        d.lda = L->out;
-        d.W = dora_dWt[L->dora_idx];
-        d.C = gs.out;
-        d.ldc = L->in;
-        d.res = gs.out;
-        d.ldr = L->in;
-        d.M = M;
-        d.N = L->in;
-        d.K = L->out;
-        RUNP(SMI_PROF_LORA, 2.0 * d.M * d.N * d.K, 0.0, launch_gemm(d, stream));
+        const GemmParams d = gemm_nt(dtype, dy, L->out, dora_dWt[L->dora_idx], gs.out, L->in, M, L->in, L->out)
+                                 .with_res(gs.out, L->in);
+        run_gemm(SMI_PROF_LORA, d, gemm_flops(d), 0.0, false, "dora dX");
       }
     }
   }
@@ -1313,7 +1235,7 @@ struct smi_engine {
         if (!y->g) return;
         const Slot gs = grad_slot(x);
         float* scr = alloc_f32(npart);
-        const int n0 = (int)(x->arow0 / HW);  // first adapted sample
+        const int n0 = ad_first(x, HW);
         RUNP(SMI_PROF_NORM, 0.0, 6.0 * MA(x) * x->cols, launch_groupnorm_bwd(dtype, PA(x), y->g, np->gamma, np->beta, ab + (size_t)n0 * C, ab + (size_t)(x->n + n0) * C, mr + (size_t)n0 * G * 2, gs.add, gs.out, scr, x->n - n0, HW,
                                  C, G, silu ? 1 : 0, stream));
       });
@@ -1324,22 +1246,11 @@ struct smi_engine {
   // ff.net.0 (GEGLU): proj = x W^T + b ; out = proj[:, :4C] * gelu(proj[:, 4C:]) as ONE GEMM whose epilogue applies the
   // gate; the projection is written only for the adapted rows (the backward's geglu_bwd needs it).
   Ten* linear_geglu(Ten* x, const Lin& L) {
-    GemmParams p;
-    p.dtype = dtype;
-    p.A = x->p;
-    p.lda = x->cols;
-    p.W = L.W;
-    p.ldc = L.out;
-    p.M = (int)x->rows;
-    p.N = L.out;
-    p.K = L.in;
-    p.bias = L.b;
     const bool need_proj = saving && x->ng;
-    p.geglu_out = reinterpret_cast<void*>(16);  // placeholder for the capability query
-    p.C = reinterpret_cast<void*>(16);
-    if (lora_active(L) || !(dry || gemm_geglu_supported(p))) return geglu(linear(x, L));  // generic path
+    void* const probe = reinterpret_cast<void*>(16);  // placeholder output pointers for the capability query
+    GemmParams p = gemm_nt(dtype, x->p, x->cols, L.W, probe, L.out, (int)x->rows, L.out, L.in).with_bias(L.b);
+    if (lora_active(L) || !(dry || gemm_geglu_supported(p.with_geglu(probe, 0)))) return geglu(linear(x, L));  // generic path
     Ten* out = new_ten(x->rows, L.out / 2, x->n, x->H, x->W);
-    p.geglu_out = out->p;
     // the projection buffer holds the adapted rows only; virtual base so that row m lands at (m - arow0)
     tens->emplace_back();
     Ten* pj = &tens->back();
@@ -1349,9 +1260,9 @@ struct smi_engine {
     char* pbuf = (char*)arena_alloc((size_t)(need_proj ? MA(x) : 1) * L.out * esz());
     pj->p = pbuf - (size_t)x->arow0 * L.out * esz();
     p.C = pj->p;
-    p.geglu_row0 = need_proj ? (int)x->arow0 : p.M;
-    RUNP(SMI_PROF_GEMM, 2.0 * p.M * p.N * p.K, 2.0 * ((double)p.M * p.K + (double)p.N * p.K + 0.5 * (double)p.M * p.N),
-         (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+    p.with_geglu(out->p, need_proj ? (int)x->arow0 : p.M);
+    run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), 2.0 * ((double)p.M * p.K + (double)p.N * p.K + 0.5 * (double)p.M * p.N), true,
+             "linear_geglu");
     out->ng = x->ng;
     pj->ng = x->ng;
     if (saving && out->ng) {
@@ -1426,7 +1337,7 @@ struct smi_engine {
       tape.push_back([=]() {
         if (!o->g) return;
         AttnParams b = p;
-        const int b0 = (int)(o->arow0 / Nq);  // first adapted sample
+        const int b0 = ad_first(o, Nq);
         b.B = nbatch - b0;
         b.Q = (const char*)p.Q + (size_t)b0 * Nq * p.ldq * esz();
         b.K = (const char*)p.K + (size_t)b0 * Nk * p.ldk * esz();
@@ -1464,70 +1375,26 @@ struct smi_engine {
   // 3x3 conv (pad 1): mode 0 stride 1, 1 stride 2, 2 nearest-2x upsample then stride 1
   Ten* conv3x3(Ten* x, const Conv& c, Ten* rowvec, Ten* res, int64_t ld_rowvec = 0) {
     const int Hin = x->H, Win = x->W;
-    const int Hout = c.mode == 1 ? (Hin + 1) / 2 : (c.mode == 2 ? Hin * 2 : Hin);
-    const int Wout = c.mode == 1 ? (Win + 1) / 2 : (c.mode == 2 ? Win * 2 : Win);
+    const int Hout = conv3x3_out(Hin, c.mode), Wout = conv3x3_out(Win, c.mode);
     Ten* y = new_ten((int64_t)x->n * Hout * Wout, c.Cout, x->n, Hout, Wout);
-    GemmParams p;
-    p.dtype = dtype;
-    p.conv = 1;
-    p.A = x->p;
-    p.W = c.Wp;
-    p.C = y->p;
-    p.ldc = c.Cout;
-    p.M = (int)y->rows;
-    p.N = c.Cout;
-    p.K = 9 * c.Cin;
-    p.bias = c.b;
-    p.Nb = x->n;
-    p.Hin = Hin;
-    p.Win = Win;
-    p.Cin = c.Cin;
-    p.Hout = Hout;
-    p.Wout = Wout;
-    p.stride = c.mode == 1 ? 2 : 1;
-    p.pad = c.pad;
-    p.upsample = c.mode == 2 ? 1 : 0;
-    if (rowvec) {
-      p.rowvec = rowvec->p;
-      p.rows_per_vec = Hout * Wout;
-      p.ld_rowvec = ld_rowvec;
-    }
-    if (res) {
-      p.res = res->p;
-      p.ldr = res->cols;
-    }
-    // c3lier adaptor: y += lscale * up(down_conv(x)) on the adapted samples.  xa = down_conv(x) is one more implicit-GEMM
-    // conv with the (16-row padded) shadow filter and fp32 output; the 1x1 up-projection rides in the main epilogue.
-    const bool lon = c.nsite > 0 && (dry || (lora_down && lora_up && mult != 0.f));
+    GemmParams p = conv3x3_fwd(dtype, x->p, c.Wp, y->p, x->n, Hin, Win, c.Cin, c.Cout, c.mode, c.pad).with_bias(c.b);
+    if (rowvec) p.with_rowvec(rowvec->p, Hout * Wout, ld_rowvec);
+    if (res) p.with_res(res->p, res->cols);
+    // c3lier adaptor: y += lscale * up(down_conv(x)) on the adapted samples.  xa = down_conv(x) is the same conv once more on
+    // the adapted samples with the (16-row padded) shadow filter and fp32 output; the 1x1 up-projection rides in the main
+    // epilogue.
+    const bool lon = lora_active(c);
     const float lscale = mult * c.scale;
     float* xa = nullptr;
     if (lon) {
       xa = alloc_f32((size_t)MA(y) * c.rows_pad);
-      GemmParams g = p;
-      g.A = PA(x);
-      g.W = shadow_ptr(c.sh_down);
-      g.C = xa;
-      g.ldc = c.rows_pad;
-      g.out_f32 = 1;
-      g.M = (int)MA(y);
-      g.N = c.rows_pad;
-      g.bias = nullptr;
-      g.rowvec = nullptr;
-      g.res = nullptr;
-      g.Nb = x->n - (int)(x->arow0 / (Hin * Win));
-      RUNP(SMI_PROF_LORA, 2.0 * g.M * c.rank * g.K, 0.0, launch_gemm(g, stream));
-      p.lora_xa = xa;
-      p.ld_xa = c.rows_pad;
-      p.lora_up = lora_up + c.off_up;
-      p.up_sn = c.rank;
-      p.up_sq = 1;
-      p.lora_r = c.rank;
-      p.lora_seg = 0;
-      p.lora_scale = lscale;
-      p.lora_row0 = (int)y->arow0;
+      const GemmParams g = conv3x3_fwd(dtype, PA(x), shadow_ptr(c.sh_down), xa, ad_samples(x, Hin * Win), Hin, Win, c.Cin,
+                                       c.rows_pad, c.mode, c.pad).f32_out();
+      run_gemm(SMI_PROF_LORA, g, 2.0 * g.M * c.rank * g.K, 0.0, false, "conv3x3 xa");
+      p.with_lora(xa, c.rows_pad, lora_up + c.off_up, c.rank, 0, lscale, (int)y->arow0);
     }
-    RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * p.K, 2.0 * ((double)x->rows * c.Cin + (double)p.N * p.K + (double)p.M * p.N),
-         (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+    run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 2.0 * ((double)x->rows * c.Cin + (double)p.N * p.K + (double)p.M * p.N), true,
+             "conv3x3");
     y->ng = lon || x->ng || (res && res->ng) || (rowvec && rowvec->ng);
     if (saving && y->ng) {
       const Conv* cp = &c;
@@ -1535,7 +1402,7 @@ struct smi_engine {
         void* dy = y->g;
         if (!dy) return;
         if (res && res->ng) accumulate(res, dy);
-        const int nb_ad = x->n - (int)(x->arow0 / (Hin * Win));  // adapted samples
+        const int nb_ad = ad_samples(x, Hin * Win);
         if (rowvec && rowvec->ng) {
           // d(rowvec)[n][c] = sum over the pixels of sample n of dy; stored x 2^-k (k ~ log2(HW) / 2) so that a coherent sum
           // cannot leave the fp16 range -- linear_bwd divides it out again (Ten::gmul)
@@ -1551,24 +1418,9 @@ struct smi_engine {
         if (lon) {
           const int M = (int)MA(y), rp = cp->rows_pad, r = cp->rank;
           dxa = alloc_f32((size_t)M * rp);
-          {  // dxa[M, rows_pad] = dy * up
-            GemmParams g;
-            g.dtype = dtype;
-            g.A = dy;
-            g.lda = cp->Cout;
-            g.W = shadow_ptr(cp->sh_up);
-            g.C = dxa;
-            g.ldc = rp;
-            g.out_f32 = 1;
-            g.M = M;
-            g.N = rp;
-            g.K = cp->Cout;
-            if (dry || lora_skinny_supported(g.A, g.lda, g.W, dxa, g.ldc, g.M, g.N, g.K))
-              RUNP(SMI_PROF_LORA, 2.0 * M * r * cp->Cout, 0.0,
-                   launch_lora_skinny(dtype, g.A, g.lda, g.W, dxa, g.ldc, g.M, g.N, g.K, stream));
-            else
-              RUNP(SMI_PROF_LORA, 2.0 * M * r * cp->Cout, 0.0, launch_gemm(g, stream));
-          }
+          // dxa[M, rows_pad] = dy * up
+          skinny_product(dy, cp->Cout, shadow_ptr(cp->sh_up), dxa, M, rp, cp->Cout, 2.0 * M * r * cp->Cout, nullptr, false,
+                         "conv3x3 dxa");
           const int rps = Hout * Wout;
           // d(up)[n][q] += lscale/S * sum_m dy[m][n] xa[m][q];  d(down)[q][ci][tap] += lscale/S * sum_m dxa[m][q] x[pixel(m, tap)][ci]
           push_wjob(dy, cp->Cout, xa + y->bskip * rp, rp, d_up ? d_up + cp->off_up : nullptr, 1, r, M, cp->Cout, r, 0, rps, lscale);
@@ -1594,67 +1446,23 @@ struct smi_engine {
           dxa16 = alloc_t(MA(y), 64);
           RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_f32_to_padded(dtype, dxa, cp->rows_pad, cp->rank, dxa16, 64, MA(y), lscale, stream));
         }
-        auto lora_dx = [&](GemmParams b, void* acc) {  // b: the main gradient conv's parameters
-          if (!lon) return;
-          b.A = dxa16;
-          b.W = shadow_ptr(cp->sh_gw);
-          b.K = 9 * 64;
-          b.Cin = 64;
-          b.C = acc;
-          b.res = acc;
-          b.ldr = cp->Cin;
-          RUNP(SMI_PROF_LORA, 2.0 * b.M * b.N * 9 * cp->rank, 0.0, launch_gemm(b, stream));
-        };
-        GemmParams b;
-        b.dtype = dtype;
-        b.conv = 1;
-        b.A = dy;
-        b.W = cp->Wg;
-        b.N = cp->Cin;
-        b.K = 9 * cp->Cout;
-        b.Cin = cp->Cout;
-        b.Nb = x->n - (int)(x->arow0 / (Hin * Win));
-        b.ldc = cp->Cin;
-        if (cp->mode == 0) {
-          b.Hin = b.Hout = Hin;
-          b.Win = b.Wout = Win;
-          b.M = (int)MA(x);
-          b.C = gs.out;
-          if (gs.add) {
-            b.res = gs.add;
-            b.ldr = cp->Cin;
-          }
-          RUNP(SMI_PROF_CONV, 2.0 * b.M * b.N * b.K, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(b), 0) : 0, launch_gemm(b, stream)));
-          lora_dx(b, gs.out);
-        } else if (cp->mode == 1) {  // gradient of the stride-2 conv: gather dY at (i + 1 - k) / 2
-          b.Hin = Hout;
-          b.Win = Wout;
-          b.Hout = Hin;
-          b.Wout = Win;
-          b.stride = 2;
-          b.transposed = 1;
-          b.M = (int)MA(x);
-          b.C = gs.out;
-          if (gs.add) {
-            b.res = gs.add;
-            b.ldr = cp->Cin;
-          }
-          RUNP(SMI_PROF_CONV, 2.0 * b.M * b.N * b.K, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(b), 0) : 0, launch_gemm(b, stream)));
-          lora_dx(b, gs.out);
-        } else {  // upsample + conv: gradient on the 2x grid, then 2x2 sum-pool
-          void* du = alloc_t(MA(y), cp->Cin);
-          b.Hin = b.Hout = Hout;
-          b.Win = b.Wout = Wout;
-          b.M = (int)MA(y);
-          b.C = du;
-          RUNP(SMI_PROF_CONV, 2.0 * b.M * b.N * b.K, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(b), 0) : 0, launch_gemm(b, stream)));
-          lora_dx(b, du);
+        // mode 2 (upsample + conv): the gradient lands on the 2x grid and is sum-pooled 2x2 afterwards; else straight in dX
+        void* const dst = cp->mode == 2 ? alloc_t(MA(y), cp->Cin) : gs.out;
+        GemmParams b = conv3x3_grad(dtype, dy, cp->Wg, dst, nb_ad, Hin, Win, cp->Cin, cp->Cout, cp->mode);
+        if (cp->mode != 2 && gs.add) b.with_res(gs.add, cp->Cin);
+        run_gemm(SMI_PROF_CONV, b, gemm_flops(b), 0.0, true, "conv3x3 dX");
+        if (lon) {  // the same gradient conv on dxa16, accumulated onto the main result
+          const GemmParams a = conv3x3_grad(dtype, dxa16, shadow_ptr(cp->sh_gw), dst, nb_ad, Hin, Win, cp->Cin, 64, cp->mode)
+                                   .with_res(dst, cp->Cin);
+          run_gemm(SMI_PROF_LORA, a, 2.0 * a.M * a.N * 9 * cp->rank, 0.0, false, "conv3x3 lora dX");
+        }
+        if (cp->mode == 2) {
           if (gs.add) {
             void* tmp = alloc_t(MA(x), cp->Cin);
-            RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_pool2x2_sum(dtype, du, tmp, b.Nb, Hin, Win, cp->Cin, stream));
+            RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_pool2x2_sum(dtype, dst, tmp, nb_ad, Hin, Win, cp->Cin, stream));
             RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_add(dtype, gs.add, tmp, gs.out, MA(x) * x->cols, stream));
           } else {
-            RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_pool2x2_sum(dtype, du, gs.out, b.Nb, Hin, Win, cp->Cin, stream));
+            RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_pool2x2_sum(dtype, dst, gs.out, nb_ad, Hin, Win, cp->Cin, stream));
           }
         }
       });
@@ -1839,36 +1647,17 @@ struct smi_engine {
         P = alloc_t(N, N);
         Vt = alloc_t(C, N);
       }
-      GemmParams g;
-      g.dtype = dtype;
-      g.A = base;
-      g.lda = 3 * C;
       // the GEMM's W operand is dense [N_out, K]: K (and V) are column blocks of the fused tensor, so stage them
       if (!hoist) Kd = alloc_t(N, C);
       RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)C * esz(), 3 * C, Kd, C, 0, N, C, stream));
-      g.W = Kd;
-      g.C = S;
-      g.ldc = N;
-      g.out_f32 = 1;
-      g.M = N;
-      g.N = N;
-      g.K = C;
-      RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(g, stream));
+      run_gemm(SMI_PROF_ATTN, gemm_nt(dtype, base, 3 * C, Kd, S, N, N, N, C).f32_out(), 2.0 * N * N * C, 0.0, false,
+               "vae_attn QK^T");
       RUNP(SMI_PROF_ATTN, 0.0, 0.0, launch_softmax_rows(dtype, S, P, N, N, sc, stream));
       if (!hoist) Vd = alloc_t(N, C);
       RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, base + (size_t)2 * C * esz(), 3 * C, Vd, C, 0, N, C, stream));
       transpose_into(Vd, Vt, N, C, N, 0, false);
-      GemmParams pv;
-      pv.dtype = dtype;
-      pv.A = P;
-      pv.lda = N;
-      pv.W = Vt;
-      pv.C = (char*)o->p + (size_t)i * N * C * esz();
-      pv.ldc = C;
-      pv.M = N;
-      pv.N = C;
-      pv.K = N;
-      RUNP(SMI_PROF_ATTN, 2.0 * N * N * C, 0.0, launch_gemm(pv, stream));
+      run_gemm(SMI_PROF_ATTN, gemm_nt(dtype, P, N, Vt, (char*)o->p + (size_t)i * N * C * esz(), C, N, C, N), 2.0 * N * N * C,
+               0.0, false, "vae_attn PV");
     }
     return linear(o, v_o, h);
   }
@@ -1899,23 +1688,9 @@ struct smi_engine {
     const int Ho = hn->H, Wo = hn->W;
     Ten* y = new_ten((int64_t)n * Ho * Wo, C2, n, Ho, Wo, sizeof(float));
     {
-      GemmParams p;
-      p.dtype = dtype;
-      p.conv = 1;
-      p.A = hn->p;
-      p.W = v_conv_out.Wp;
-      p.C = y->p;
-      p.ldc = C2;
-      p.out_f32 = 1;
-      p.M = (int)y->rows;
-      p.N = C2;
-      p.K = 9 * v_conv_out.Cin;
-      p.bias = v_conv_out.b;
-      p.Nb = n;
-      p.Hin = p.Hout = Ho;
-      p.Win = p.Wout = Wo;
-      p.Cin = v_conv_out.Cin;
-      RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * p.K, 0.0, launch_gemm(p, stream));
+      const GemmParams p =
+          conv3x3_fwd(dtype, hn->p, v_conv_out.Wp, y->p, n, Ho, Wo, v_conv_out.Cin, C2).f32_out().with_bias(v_conv_out.b);
+      run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 0.0, false, "vae conv_out");
     }
     float* q = alloc_f32((size_t)y->rows * C2);
     RUN(launch_chan_mix(dtype, (const float*)y->p, v_quant_w, v_quant_b, q, y->rows, C2, stream));
@@ -2041,23 +1816,8 @@ struct smi_engine {
     } else {
       Ten* hn = groupnorm(h, v_norm_out, true);
       Ten* y = new_ten((int64_t)n * HWi, 4, n, H, Wd_, sizeof(float));
-      GemmParams p;
-      p.dtype = dtype;
-      p.conv = 1;
-      p.A = hn->p;
-      p.W = d_conv_out.Wp;
-      p.C = y->p;
-      p.ldc = 4;
-      p.out_f32 = 1;
-      p.M = (int)y->rows;
-      p.N = 4;
-      p.K = 9 * C0;
-      p.bias = d_bias4;
-      p.Nb = n;
-      p.Hin = p.Hout = H;
-      p.Win = p.Wout = Wd_;
-      p.Cin = C0;
-      RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * p.K, 0.0, launch_gemm(p, stream));
+      const GemmParams p = conv3x3_fwd(dtype, hn->p, d_conv_out.Wp, y->p, n, H, Wd_, C0, 4).f32_out().with_bias(d_bias4);
+      run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 0.0, false, "vae_dec conv_out");
       float* t4 = alloc_f32((size_t)n * 4 * HWi);
       RUN(launch_nhwc_to_nchw_f32((const float*)y->p, t4, n, 4, HWi, stream));
       RUN(hipMemcpy2DAsync(image_out, (size_t)co * HWi * sizeof(float), t4, (size_t)4 * HWi * sizeof(float),
@@ -2242,22 +2002,8 @@ struct smi_engine {
     RUN(launch_nchw_to_nhwc(dtype, sample, 1, x0->p, n, cfg.in_channels, HW, 64, 1.f, stream));
     Ten* h = new_ten((int64_t)n * HW, C0, n, H, Wd_);
     {
-      GemmParams p;
-      p.dtype = dtype;
-      p.conv = 1;
-      p.A = x0->p;
-      p.W = conv_in.Wp;
-      p.C = h->p;
-      p.ldc = C0;
-      p.M = (int)h->rows;
-      p.N = C0;
-      p.K = 9 * 64;
-      p.bias = conv_in.b;
-      p.Nb = n;
-      p.Hin = p.Hout = H;
-      p.Win = p.Wout = Wd_;
-      p.Cin = 64;
-      RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * 9 * cfg.in_channels, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+      const GemmParams p = conv3x3_fwd(dtype, x0->p, conv_in.Wp, h->p, n, H, Wd_, 64, C0).with_bias(conv_in.b);
+      run_gemm(SMI_PROF_CONV, p, 2.0 * p.M * p.N * 9 * cfg.in_channels, 0.0, true, "conv_in");
     }
 
     // (begin_block / end_block: scratch-region liveness of the no-grad passes, see new_ten; no-ops in a saved pass)
@@ -2312,23 +2058,9 @@ struct smi_engine {
     // ---- conv_out (MFMA path, fp32 result) + NHWC->NCHW
     Ten* y = new_ten((int64_t)n * HW, cfg.out_channels, n, H, Wd_, sizeof(float));
     {
-      GemmParams p;
-      p.dtype = dtype;
-      p.conv = 1;
-      p.A = hn->p;
-      p.W = conv_out.Wp;
-      p.C = y->p;
-      p.ldc = cfg.out_channels;
-      p.out_f32 = 1;
-      p.M = (int)y->rows;
-      p.N = cfg.out_channels;
-      p.K = 9 * C0;
-      p.bias = conv_out.b;
-      p.Nb = n;
-      p.Hin = p.Hout = H;
-      p.Win = p.Wout = Wd_;
-      p.Cin = C0;
-      RUNP(SMI_PROF_CONV, 2.0 * p.M * p.N * p.K, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(p), 0) : 0, launch_gemm(p, stream)));
+      const GemmParams p =
+          conv3x3_fwd(dtype, hn->p, conv_out.Wp, y->p, n, H, Wd_, C0, cfg.out_channels).f32_out().with_bias(conv_out.b);
+      run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 0.0, true, "conv_out");
     }
     RUN(launch_nhwc_to_nchw_f32((const float*)y->p, eps_out, n, cfg.out_channels, HW, stream));
     end_block();
@@ -2337,21 +2069,9 @@ struct smi_engine {
       tape.push_back([=]() {
         if (!y->g) return;
         void* dx = grad_slot(hn).out;
-        GemmParams b;
-        b.dtype = dtype;
-        b.conv = 1;
-        b.A = y->g;  // [adapted rows, 64]: d_eps channels zero-padded
-        b.W = conv_out.Wg;
-        b.C = dx;
-        b.ldc = C0;
-        b.M = (int)MA(hn);
-        b.N = C0;
-        b.K = 9 * 64;
-        b.Nb = (int)(MA(hn) / HW);
-        b.Hin = b.Hout = H;
-        b.Win = b.Wout = Wd_;
-        b.Cin = 64;
-        RUNP(SMI_PROF_CONV, 2.0 * b.M * b.N * 9 * cfg.out_channels, 0.0, (prof_on && prof_dump ? (next_tag = gemm_tag(b), 0) : 0, launch_gemm(b, stream)));
+        // y->g [adapted rows, 64]: d_eps channels zero-padded
+        const GemmParams b = conv3x3_grad(dtype, y->g, conv_out.Wg, dx, (int)(MA(hn) / HW), H, Wd_, C0, 64);
+        run_gemm(SMI_PROF_CONV, b, 2.0 * b.M * b.N * 9 * cfg.out_channels, 0.0, true, "conv_out dX");
       });
     }
     if (save) {
@@ -2993,97 +2713,28 @@ int smi_op_gemm_scratch(void* ws, size_t bytes) {
 int smi_op_gemm(int dtype, const void* A, const void* W, void* C, int M, int N, int K, const void* bias,
                 const void* res, const float* lora_xa, const float* lora_up, int lora_r, float lora_scale,
                 int out_f32, void* stream) {
-  GemmParams p;
-  p.dtype = dtype;
-  p.A = A;
-  p.lda = K;
-  p.W = W;
-  p.C = C;
-  p.ldc = N;
-  p.out_f32 = out_f32;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.bias = bias;
-  p.res = res;
-  p.ldr = N;
-  p.lora_xa = lora_xa;
-  p.ld_xa = lora_r;
-  p.lora_up = lora_up;
-  p.up_sn = lora_r;
-  p.up_sq = 1;
-  p.lora_r = lora_xa ? lora_r : 0;
-  p.lora_scale = lora_scale;
-  return launch_gemm(p, (hipStream_t)stream);
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  if (out_f32) p.f32_out();
+  return launch_gemm(p.with_lora(lora_xa, lora_r, lora_up, lora_r, 0, lora_scale, 0), (hipStream_t)stream);
 }
 int smi_op_gemm_rows(int dtype, const void* A, const void* W, void* C, int M, int N, int K, const void* bias,
                      const void* res, const float* lora_xa, const float* lora_up, int lora_r, float lora_scale,
                      int lora_row0, int lora_seg, void* stream) {
-  GemmParams p;
-  p.dtype = dtype;
-  p.A = A;
-  p.lda = K;
-  p.W = W;
-  p.C = C;
-  p.ldc = N;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.bias = bias;
-  p.res = res;
-  p.ldr = N;
-  p.lora_xa = lora_xa;
-  p.ld_xa = (int64_t)lora_r * (lora_seg > 0 ? N / lora_seg : 1);
-  p.lora_up = lora_up;
-  p.up_sn = lora_r;
-  p.up_sq = 1;
-  p.lora_r = lora_xa ? lora_r : 0;
-  p.lora_seg = lora_seg;
-  p.lora_scale = lora_scale;
-  p.lora_row0 = lora_row0;
-  return launch_gemm(p, (hipStream_t)stream);
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  return launch_gemm(p.with_lora(lora_xa, (int64_t)lora_r * (lora_seg > 0 ? N / lora_seg : 1), lora_up, lora_r, lora_seg,
+                                 lora_scale, lora_row0),
+                     (hipStream_t)stream);
 }
 int smi_op_gemm_geglu(int dtype, const void* A, const void* W, const void* bias, void* out, void* proj, int M, int N,
                       int K, int proj_row0, void* stream) {
-  GemmParams p;
-  p.dtype = dtype;
-  p.A = A;
-  p.lda = K;
-  p.W = W;
-  p.C = proj;
-  p.ldc = N;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.bias = bias;
-  p.geglu_out = out;
-  p.geglu_row0 = proj_row0;
-  return launch_gemm(p, (hipStream_t)stream);
+  return launch_gemm(gemm_nt(dtype, A, K, W, proj, N, M, N, K).with_bias(bias).with_geglu(out, proj_row0), (hipStream_t)stream);
 }
 int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin,
                    int win, int cin, int cout, int stride, int upsample, int transposed, int hout, int wout,
                    void* stream) {
-  GemmParams p;
-  p.dtype = dtype;
-  p.conv = 1;
-  p.A = in;
-  p.W = w_packed;
-  p.C = out;
-  p.ldc = cout;
-  p.M = nb * hout * wout;
-  p.N = cout;
-  p.K = 9 * cin;
-  p.bias = bias;
-  p.Nb = nb;
-  p.Hin = hin;
-  p.Win = win;
-  p.Cin = cin;
-  p.Hout = hout;
-  p.Wout = wout;
-  p.stride = stride;
-  p.upsample = upsample;
-  p.transposed = transposed;
-  return launch_gemm(p, (hipStream_t)stream);
+  return launch_gemm(conv3x3_geom(dtype, in, w_packed, out, nb, hin, win, cin, cout, hout, wout, stride, 1, upsample, transposed)
+                         .with_bias(bias),
+                     (hipStream_t)stream);
 }
 int smi_op_attention_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
                          int nq, int nk, int d, float scale, void* stream) {

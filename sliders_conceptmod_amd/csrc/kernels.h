@@ -57,7 +57,93 @@ struct GemmParams {
   // split-K (internal to launch_gemm, gemm2 kernels only): the workgroups of slice s accumulate K-tiles
   // [s nk / ksplit, (s + 1) nk / ksplit) and store fp32 partials to C + s * M * ldc (out_f32 form, no epilogue)
   int ksplit = 0;
+
+  // epilogue setters, chained onto one of the constructors below
+  GemmParams& f32_out() { out_f32 = 1; return *this; }
+  GemmParams& with_bias(const void* b) { bias = b; return *this; }
+  GemmParams& with_res(const void* r, int64_t ld) { res = r; ldr = ld; return *this; }
+  GemmParams& with_rowvec(const void* v, int rows_per, int64_t ld) {
+    rowvec = v;
+    rows_per_vec = rows_per;
+    ld_rowvec = ld;
+    return *this;
+  }
+  // forward delta: xa [M - row0, ld] fp32, up [N, r]; seg > 0: fused projections, column block n / seg reads its own r of xa
+  GemmParams& with_lora(const float* xa, int64_t ld, const float* up, int r, int seg, float scale, int row0) {
+    lora_xa = xa;
+    ld_xa = ld;
+    lora_up = up;
+    up_sn = r;
+    up_sq = 1;
+    lora_r = xa ? r : 0;
+    lora_seg = seg;
+    lora_scale = scale;
+    lora_row0 = row0;
+    return *this;
+  }
+  // dX-form delta: dxa [M, ld] fp32, down [r_tot, N] read transposed
+  GemmParams& with_lora_dx(const float* dxa, int64_t ld, const float* down, int r_tot, float scale) {
+    lora_xa = dxa;
+    ld_xa = ld;
+    lora_up = down;
+    up_sn = 1;
+    up_sq = N;
+    lora_r = r_tot;
+    lora_seg = 0;
+    lora_scale = scale;
+    return *this;
+  }
+  GemmParams& with_geglu(void* out, int row0) { geglu_out = out; geglu_row0 = row0; return *this; }
 };
+// ---- constructors: every launch site (the engine's graph code and the smi_op_* test wrappers alike) states what it is
+// through one of these and the setters above; nobody fills the struct field by field
+inline GemmParams gemm_nt(int dtype, const void* A, int64_t lda, const void* W, void* C, int64_t ldc, int M, int N,
+                          int K) {
+  GemmParams p;
+  p.dtype = dtype;
+  p.A = A;
+  p.lda = lda;
+  p.W = W;
+  p.C = C;
+  p.ldc = ldc;
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  return p;
+}
+// 3x3 implicit-GEMM conv with explicit geometry: in [Nb, Hin, Win, Cin], w [Cout][9 * Cin], out [Nb, Hout, Wout, Cout]
+inline GemmParams conv3x3_geom(int dtype, const void* in, const void* w, void* out, int Nb, int Hin, int Win, int Cin,
+                               int Cout, int Hout, int Wout, int stride, int pad, int upsample, int transposed) {
+  GemmParams p = gemm_nt(dtype, in, 0, w, out, Cout, Nb * Hout * Wout, Cout, 9 * Cin);
+  p.conv = 1;
+  p.Nb = Nb;
+  p.Hin = Hin;
+  p.Win = Win;
+  p.Cin = Cin;
+  p.Hout = Hout;
+  p.Wout = Wout;
+  p.stride = stride;
+  p.pad = pad;
+  p.upsample = upsample;
+  p.transposed = transposed;
+  return p;
+}
+// forward conv of a layer: mode 0 stride 1, 1 stride 2, 2 nearest-2x upsample then stride 1
+inline int conv3x3_out(int in, int mode) { return mode == 1 ? (in + 1) / 2 : (mode == 2 ? in * 2 : in); }
+inline GemmParams conv3x3_fwd(int dtype, const void* in, const void* w, void* out, int Nb, int Hin, int Win, int Cin,
+                              int Cout, int mode = 0, int pad = 1) {
+  return conv3x3_geom(dtype, in, w, out, Nb, Hin, Win, Cin, Cout, conv3x3_out(Hin, mode), conv3x3_out(Win, mode),
+                      mode == 1 ? 2 : 1, pad, mode == 2 ? 1 : 0, 0);
+}
+// gradient conv of that layer (Hin, Win, Cin, Cout are the FORWARD's): dy [Nb, Hout, Wout, Cout] against the gradient
+// pack wg [Cin][9 * Cout].  Mode 0: same size.  Mode 1: transposed stride 2, dx on the input grid.  Mode 2: dx on the 2x
+// (output) grid -- the caller sum-pools it 2x2 onto the input grid afterwards.
+inline GemmParams conv3x3_grad(int dtype, const void* dy, const void* wg, void* dx, int Nb, int Hin, int Win, int Cin,
+                               int Cout, int mode = 0) {
+  const int Hy = conv3x3_out(Hin, mode), Wy = conv3x3_out(Win, mode);
+  const int Hx = mode == 2 ? Hy : Hin, Wx = mode == 2 ? Wy : Win;
+  return conv3x3_geom(dtype, dy, wg, dx, Nb, Hy, Wy, Cout, Cin, Hx, Wx, mode == 1 ? 2 : 1, 1, 0, mode == 1);
+}
 int launch_gemm(const GemmParams& p, hipStream_t stream);
 // The kernels launch_gemm selects among (gemm.hip).  The gemm2 tiles are gemm_glds_kernel<WM, NL, DEEP> (gemm2.hip):
 // BM x BN with 4 or 8 waves.  All of them give the same bits.
