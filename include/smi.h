@@ -101,6 +101,22 @@ typedef struct smi_clip_config {
   int projection_dim;    /* 0: none (CLIPTextModel); > 0: text_projection (CLIPTextModelWithProjection) */
 } smi_clip_config;
 
+/* Architecture of a transformers CLIPVisionModel / CLIPVisionModelWithProjection (the image tower of CLIPModel: what
+ * eval-scripts/clip_score.py scores a slider sweep with). */
+typedef struct smi_clip_vision_config {
+  int dtype;
+  int hidden_size;       /* 768 (ViT-B/32) / 1024 (ViT-L/14) */
+  int num_layers;        /* 12 / 24 */
+  int num_heads;         /* 12 / 16 */
+  int intermediate_size; /* 3072 / 4096 */
+  int image_size;        /* 224 */
+  int patch_size;        /* 32 / 14 */
+  int hidden_act;        /* 0 quick_gelu, 1 gelu */
+  int projection_dim;    /* 0: pooled = post_layernorm(class row); > 0: x visual_projection (512 / 768) */
+  float image_mean[3];   /* CLIPImageProcessor image_mean / image_std: applied to uint8 input only */
+  float image_std[3];
+} smi_clip_vision_config;
+
 typedef struct smi_engine smi_engine;
 
 const char* smi_last_error(void);
@@ -183,6 +199,26 @@ int smi_clip_create(const smi_clip_config* cfg, const smi_weight* weights, int n
                     size_t workspace_bytes, void* stream, smi_engine** out);
 int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
                     void* penultimate, void* pooled);
+
+/* ---- CLIP image tower and similarity head (scoring a slider sweep) -----------------------------------------------------
+ * Replaces `model.get_image_features(pixel_values)` / the image half of `CLIPModel(**inputs).logits_per_image`
+ * (eval-scripts/clip_score.py).  Patch embedding (a GEMM on the patch matrix), class token + position embedding +
+ * pre_layrnorm, the text tower's pre-LayerNorm blocks WITHOUT the causal mask, post_layernorm on the class row.
+ *   weights: the transformers state_dict entries `vision_model.*` (+ `visual_projection.weight` when projection_dim > 0)
+ *   rgb8         uint8 [n, S, S, 3]: resized and centre-cropped, NOT yet rescaled (normalised on the device)  } exactly
+ *   pixel_values f32 [n, 3, S, S]: what CLIPImageProcessor returns                                           } one
+ *   last_hidden  T [n, G*G + 1, hidden]  the encoder's output (no post_layernorm), G = S / patch_size   (may be NULL)
+ *   image_embeds T [n, projection_dim or hidden]  post_layernorm(class row) (x visual_projection)
+ * An image encodes to the same bits alone or in a batch.  The config check refuses image_size % patch_size != 0,
+ * hidden_size % 64 != 0 or > 2048, head_dim % 8 != 0, intermediate_size % 64 != 0 and projection_dim % 8 != 0.
+ * smi_clip_logits needs no engine: logits_per_image f32 [ni, nt] = exp(logit_scale) <i, t> / (|i| |t|), dim % 8 == 0. */
+int smi_clip_vision_workspace_bytes(const smi_clip_vision_config* cfg, int batch, size_t* bytes);
+int smi_clip_vision_create(const smi_clip_vision_config* cfg, const smi_weight* weights, int n_weights, int batch,
+                           void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_clip_vision_encode(smi_engine* e, int n, const uint8_t* rgb8, const float* pixel_values, void* last_hidden,
+                           void* image_embeds);
+int smi_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
+                    float logit_scale, float* logits_per_image, void* stream);
 
 /* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)

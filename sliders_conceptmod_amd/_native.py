@@ -43,6 +43,13 @@ class ClipConfigC(C.Structure):
                 ("hidden_act", C.c_int), ("projection_dim", C.c_int)]
 
 
+class ClipVisionConfigC(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("hidden_size", C.c_int), ("num_layers", C.c_int), ("num_heads", C.c_int),
+                ("intermediate_size", C.c_int), ("image_size", C.c_int), ("patch_size", C.c_int),
+                ("hidden_act", C.c_int), ("projection_dim", C.c_int), ("image_mean", C.c_float * 3),
+                ("image_std", C.c_float * 3)]
+
+
 class WeightC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -107,6 +114,12 @@ _SIGS = {
     "smi_clip_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_clip_encode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "smi_clip_vision_workspace_bytes": (C.c_int, [C.POINTER(ClipVisionConfigC), C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_clip_vision_create": (C.c_int, [C.POINTER(ClipVisionConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p,
+                                         C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_clip_vision_encode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
+    "smi_clip_logits": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
+                                  C.c_void_p]),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -251,7 +264,7 @@ def arena_bytes(cfg_c: UNetConfigC, sites: Sequence[dict], batch: int, h: int, w
 
 
 class _EngineBase:
-    """What the four engine wrappers share: the smi_engine `handle`, the `workspace` tensor it lives in, the weight
+    """What the five engine wrappers share: the smi_engine `handle`, the `workspace` tensor it lives in, the weight
     tensors it borrows (kept alive for as long as the wrapper), and their release."""
 
     handle = None
@@ -486,3 +499,77 @@ class ClipEngine(_EngineBase):
         check(lib().smi_clip_encode(self.handle, n, ptr(ids), ptr(eos), ptr(last), ptr(pen), ptr(pooled)),
               "smi_clip_encode")
         return last, pen, pooled
+
+
+def clip_vision_config_c(cfg, dtype: torch.dtype) -> ClipVisionConfigC:
+    """cfg: sliders_conceptmod_amd.clip.CLIPVisionConfig (the transformers config values + the processor's mean / std)."""
+    if cfg.hidden_act not in CLIP_ACT:
+        raise SmiError(f"CLIP hidden_act '{cfg.hidden_act}' is not built (quick_gelu / gelu)")
+    c = ClipVisionConfigC()
+    c.dtype = DTYPE_CODE[dtype]
+    c.hidden_size, c.num_layers, c.num_heads = cfg.hidden_size, cfg.num_hidden_layers, cfg.num_attention_heads
+    c.intermediate_size, c.image_size, c.patch_size = cfg.intermediate_size, cfg.image_size, cfg.patch_size
+    c.hidden_act, c.projection_dim = CLIP_ACT[cfg.hidden_act], cfg.projection_dim or 0
+    for k in range(3):
+        c.image_mean[k], c.image_std[k] = float(cfg.image_mean[k]), float(cfg.image_std[k])
+    return c
+
+
+def clip_vision_workspace_bytes(cfg, dtype: torch.dtype, batch: int) -> int:
+    """smi_clip_vision_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on a refused config."""
+    out = C.c_size_t(0)
+    check(lib().smi_clip_vision_workspace_bytes(C.byref(clip_vision_config_c(cfg, dtype)), batch, C.byref(out)),
+          "smi_clip_vision_workspace_bytes")
+    return out.value
+
+
+class ClipVisionEngine(_EngineBase):
+    """CLIP image tower on the HIP engine (smi_clip_vision_*): uint8 or normalised float images -> the encoder's output
+    and the (projected) class-token embedding."""
+
+    def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, device):
+        self.cfg_c, self.batch, self.dtype = clip_vision_config_c(cfg, dtype), batch, dtype
+        self._create("clip_vision_", self.cfg_c, (batch,), state, dtype, device)
+
+    def encode(self, rgb8: Optional[torch.Tensor] = None, pixel_values: Optional[torch.Tensor] = None,
+               want_last_hidden: bool = True):
+        """exactly one of rgb8 uint8 [n, S, S, 3] / pixel_values [n, 3, S, S] -> (last_hidden or None, image_embeds)"""
+        if (rgb8 is None) == (pixel_values is None):
+            raise SmiError("CLIP image tower: pass exactly one of rgb8 / pixel_values")
+        c, dev = self.cfg_c, self.workspace.device
+        S, G = c.image_size, c.image_size // c.patch_size
+        if rgb8 is not None:
+            if rgb8.dtype != torch.uint8 or tuple(rgb8.shape[1:]) != (S, S, 3):
+                raise SmiError(f"CLIP image tower: rgb8 must be uint8 [n, {S}, {S}, 3], got {rgb8.dtype} "
+                               f"{tuple(rgb8.shape)}")
+            rgb8 = rgb8.to(dev).contiguous()
+            n = rgb8.shape[0]
+        else:
+            if tuple(pixel_values.shape[1:]) != (3, S, S):
+                raise SmiError(f"CLIP image tower: pixel_values must be [n, 3, {S}, {S}], got "
+                               f"{tuple(pixel_values.shape)}")
+            pixel_values = pixel_values.to(dev, torch.float32).contiguous()
+            n = pixel_values.shape[0]
+        last = torch.empty((n, G * G + 1, c.hidden_size), dtype=self.dtype, device=dev) if want_last_hidden else None
+        emb = torch.empty((n, c.projection_dim or c.hidden_size), dtype=self.dtype, device=dev)
+        with torch.cuda.device(dev):
+            check(lib().smi_clip_vision_encode(self.handle, n, ptr(rgb8), ptr(pixel_values), ptr(last), ptr(emb)),
+                  "smi_clip_vision_encode")
+        return last, emb
+
+
+def clip_logits(image_embeds: torch.Tensor, text_embeds: torch.Tensor, logit_scale: float) -> torch.Tensor:
+    """smi_clip_logits: logits_per_image f32 [ni, nt] = exp(logit_scale) <i, t> / (|i| |t|) of 16-bit embeddings."""
+    if image_embeds.dtype not in DTYPE_CODE or text_embeds.dtype != image_embeds.dtype:
+        raise SmiError(f"clip_logits: embeddings must share float16 / bfloat16, got {image_embeds.dtype} and "
+                       f"{text_embeds.dtype}")
+    if image_embeds.device.type != "cuda" or text_embeds.device != image_embeds.device:
+        raise SmiError("clip_logits: both embeddings must be on the same cuda device (there is no CPU fallback)")
+    if image_embeds.ndim != 2 or text_embeds.ndim != 2 or image_embeds.shape[1] != text_embeds.shape[1]:
+        raise SmiError(f"clip_logits: shapes {tuple(image_embeds.shape)} and {tuple(text_embeds.shape)} do not match")
+    a, b = image_embeds.contiguous(), text_embeds.contiguous()
+    out = torch.empty((a.shape[0], b.shape[0]), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        check(lib().smi_clip_logits(DTYPE_CODE[a.dtype], ptr(a), a.shape[0], ptr(b), b.shape[0], a.shape[1],
+                                    float(logit_scale), ptr(out), stream_ptr()), "smi_clip_logits")
+    return out

@@ -211,7 +211,7 @@ using namespace smi;
 
 struct smi_engine {
   // which model the engine holds: set once by its setup; every entry point accepts one kind and refuses the others
-  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT };
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION };
   Kind kind = UNET;
   smi_unet_config cfg{};
   int dtype = 0;
@@ -1848,24 +1848,39 @@ struct smi_engine {
   const void* c_tok = nullptr;
   const void* c_pos = nullptr;
 
-  void build_clip() {
-    const int d = ccfg.hidden_size;
-    c_tok = Wd("text_model.embeddings.token_embedding.weight");
-    c_pos = Wd("text_model.embeddings.position_embedding.weight");
-    check_shape("text_model.embeddings.token_embedding.weight", {ccfg.vocab_size, d});
-    check_shape("text_model.embeddings.position_embedding.weight", {ccfg.max_positions, d});
-    c_layers.resize(ccfg.num_layers);
-    for (int i = 0; i < ccfg.num_layers; ++i) {
-      const std::string b = "text_model.encoder.layers." + std::to_string(i);
+  // the encoder layers of either tower: `prefix` + layer number names them in the transformers state dict
+  void build_clip_layers(const std::string& prefix, int num_layers, int d, int inter) {
+    c_layers.resize(num_layers);
+    for (int i = 0; i < num_layers; ++i) {
+      const std::string b = prefix + std::to_string(i);
       CLayer& L = c_layers[i];
       L.n1 = make_norm(b + ".layer_norm1", d, 1e-5f);
       L.qkv = make_fused(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d, d, false);
       L.qkv.b = fused_bias(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d);
       L.out = make_lin(b + ".self_attn.out_proj", d, d, true, false);
       L.n2 = make_norm(b + ".layer_norm2", d, 1e-5f);
-      L.fc1 = make_lin(b + ".mlp.fc1", d, ccfg.intermediate_size, true, false);
-      L.fc2 = make_lin(b + ".mlp.fc2", ccfg.intermediate_size, d, true, false);
+      L.fc1 = make_lin(b + ".mlp.fc1", d, inter, true, false);
+      L.fc2 = make_lin(b + ".mlp.fc2", inter, d, true, false);
     }
+  }
+  // one pre-LayerNorm block on h [n L, d]; attn_causal says whether the self-attention is masked
+  Ten* clip_block(Ten* h, const CLayer& ly, int n, int L, int heads, int d, int act) {
+    Ten* qkv = linear(layernorm(h, ly.n1), ly.qkv);
+    Ten* o = attention(qkv, nullptr, nullptr, heads, d, n, L, L);
+    h = linear(o, ly.out, h);
+    Ten* f = linear(layernorm(h, ly.n2), ly.fc1);
+    Ten* a = new_ten(f->rows, f->cols, n, L, 1);
+    RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(dtype, f->p, a->p, f->rows * f->cols, act, stream));
+    return linear(a, ly.fc2, h);
+  }
+
+  void build_clip() {
+    const int d = ccfg.hidden_size;
+    c_tok = Wd("text_model.embeddings.token_embedding.weight");
+    c_pos = Wd("text_model.embeddings.position_embedding.weight");
+    check_shape("text_model.embeddings.token_embedding.weight", {ccfg.vocab_size, d});
+    check_shape("text_model.embeddings.position_embedding.weight", {ccfg.max_positions, d});
+    build_clip_layers("text_model.encoder.layers.", ccfg.num_layers, d, ccfg.intermediate_size);
     c_final = make_norm("text_model.final_layer_norm", d, 1e-5f);
     if (ccfg.projection_dim > 0) c_proj = make_lin("text_projection", d, ccfg.projection_dim, false, false);
     gscale = (float*)pack_alloc(256 * sizeof(float));
@@ -1889,13 +1904,7 @@ struct smi_engine {
       const CLayer& ly = c_layers[i];
       if (i == ccfg.num_layers - 1 && penultimate)  // hidden_states[-2]: what enters the last layer
         RUN(launch_copy_cols(dtype, h->p, d, penultimate, d, 0, (int)h->rows, d, stream));
-      Ten* qkv = linear(layernorm(h, ly.n1), ly.qkv);
-      Ten* o = attention(qkv, nullptr, nullptr, ccfg.num_heads, d, n, L, L);
-      h = linear(o, ly.out, h);
-      Ten* f = linear(layernorm(h, ly.n2), ly.fc1);
-      Ten* a = new_ten(f->rows, f->cols, n, L, 1);
-      RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(dtype, f->p, a->p, f->rows * f->cols, ccfg.hidden_act, stream));
-      h = linear(a, ly.fc2, h);
+      h = clip_block(h, ly, n, L, ccfg.num_heads, d, ccfg.hidden_act);
     }
     attn_causal = false;
     Ten* fin = layernorm(h, c_final);
@@ -1913,6 +1922,84 @@ struct smi_engine {
     return err ? -1 : 0;
   }
 
+  // ---------------------------------------------------------------------------------------------------------
+  // CLIP image tower (transformers CLIPVisionModel[WithProjection]), forward only: patch matrix -> patch GEMM -> class
+  // token + position embedding + pre_layrnorm -> the text tower's blocks without the mask -> post_layernorm of the class
+  // row (x visual_projection).  No split-K scratch is lent to its GEMMs (smi_clip_vision_encode): an image gives the
+  // same bits alone or in a batch.
+  // ---------------------------------------------------------------------------------------------------------
+  smi_clip_vision_config vis{};
+  Lin v_patch;
+  Norm v_pre, v_post;
+  const void* v_cls = nullptr;
+  const void* v_pos = nullptr;
+  int vis_grid() const { return vis.image_size / vis.patch_size; }
+  int vis_kp() const { return (3 * vis.patch_size * vis.patch_size + 63) / 64 * 64; }
+
+  void build_clip_vision() {
+    const int d = vis.hidden_size, P = vis.patch_size, G = vis_grid(), K = 3 * P * P, Kp = vis_kp();
+    const std::string emb = "vision_model.embeddings.";
+    v_cls = Wd(emb + "class_embedding");
+    check_shape(emb + "class_embedding", {d});
+    v_pos = Wd(emb + "position_embedding.weight");
+    check_shape(emb + "position_embedding.weight", {G * G + 1, d});
+    // the patch filter [hidden, 3, P, P] is already [hidden, K] with K in (c, py, px) order: repacked to rows of Kp
+    // with the pad columns zero, so that the patch embedding is gemm_nt on the patch matrix
+    const void* pw = Wd(emb + "patch_embedding.weight");
+    check_shape(emb + "patch_embedding.weight", {d, 3, P, P});
+    void* wp = pack_alloc((size_t)d * Kp * esz());
+    if (!dry && !err && pw) {
+      ++pack_launches;
+      if (Kp != K) (void)hipMemsetAsync(wp, 0, (size_t)d * Kp * esz(), stream);
+      (void)hipMemcpy2DAsync(wp, (size_t)Kp * esz(), pw, (size_t)K * esz(), (size_t)K * esz(), d,
+                             hipMemcpyDeviceToDevice, stream);
+    }
+    v_patch.name = emb + "patch_embedding";
+    v_patch.in = Kp;
+    v_patch.out = d;
+    v_patch.W = wp;
+    v_pre = make_norm("vision_model.pre_layrnorm", d, 1e-5f);  // transformers' spelling
+    build_clip_layers("vision_model.encoder.layers.", vis.num_layers, d, vis.intermediate_size);
+    v_post = make_norm("vision_model.post_layernorm", d, 1e-5f);
+    if (vis.projection_dim > 0) c_proj = make_lin("visual_projection", d, vis.projection_dim, false, false);
+    gscale = (float*)pack_alloc(256 * sizeof(float));
+    finish_lora();
+  }
+
+  int forward_clip_vision(int n, const uint8_t* rgb8, const float* pixel_values, void* last_hidden, void* image_embeds) {
+    n_ad = 0;
+    cur = &arena[0];
+    cur->reset();
+    tens = &tens_[0];
+    tens->clear();
+    saving = false;
+    lora_down = lora_up = nullptr;
+    mult = 0.f;
+    attn_causal = false;
+    const int d = vis.hidden_size, G = vis_grid(), L = G * G + 1, Kp = vis_kp();
+    Ten* pm = new_ten((int64_t)n * G * G, Kp, n, G * G, 1);
+    RUN(launch_clip_patchify(dtype, rgb8, pixel_values, pm->p, n, vis.image_size, vis.patch_size, Kp, vis.image_mean,
+                             vis.image_std, stream));
+    Ten* pe = linear(pm, v_patch);
+    Ten* h = new_ten((int64_t)n * L, d, n, L, 1);
+    RUNP(SMI_PROF_NORM, 0.0, 4.0 * h->rows * d,
+         launch_vit_embed_ln(dtype, pe->p, v_cls, v_pos, v_pre.gamma, v_pre.beta, h->p, n, L, d, v_pre.eps, stream));
+    for (int i = 0; i < vis.num_layers; ++i) h = clip_block(h, c_layers[i], n, L, vis.num_heads, d, vis.hidden_act);
+    if (last_hidden) RUN(launch_copy_cols(dtype, h->p, d, last_hidden, d, 0, (int)h->rows, d, stream));
+    if (image_embeds) {
+      Ten* cls = new_ten(n, d, n, 1, 1);  // the class rows: row i * L of h
+      RUN(launch_copy_cols(dtype, h->p, (int64_t)L * d, cls->p, d, 0, n, d, stream));
+      Ten* pl = layernorm(cls, v_post);
+      if (vis.projection_dim > 0) pl = linear(pl, c_proj);
+      RUN(launch_copy_cols(dtype, pl->p, pl->cols, image_embeds, pl->cols, 0, n, pl->cols, stream));
+    }
+    if (cur->overflow && !dry) {
+      set_error("workspace too small for this call (needs %zu bytes, has %zu)", cur->peak, cur->cap);
+      return -3;
+    }
+    return err ? -1 : 0;
+  }
+
   // the forward-only kinds (everything but the UNet) are created and planned by one path (create_forward_only below);
   // these two are the one place that maps `kind` to its build and to the dry forward that sizes arena 0
   void build_forward_only() {
@@ -1920,6 +2007,7 @@ struct smi_engine {
       case VAE_ENCODER: build_vae(); break;
       case VAE_DECODER: build_vae_dec(); break;
       case CLIP_TEXT: build_clip(); break;
+      case CLIP_VISION: build_clip_vision(); break;
       case UNET: break;
     }
   }
@@ -1928,6 +2016,7 @@ struct smi_engine {
       case VAE_ENCODER: forward_vae(max_n, nullptr, nullptr); break;
       case VAE_DECODER: forward_vae_dec(max_n, nullptr, nullptr, nullptr); break;
       case CLIP_TEXT: forward_clip(max_n, nullptr, nullptr, (void*)16, (void*)16, (void*)16); break;  // all outputs
+      case CLIP_VISION: forward_clip_vision(max_n, nullptr, nullptr, (void*)16, (void*)16); break;
       case UNET: break;
     }
   }
@@ -2259,7 +2348,7 @@ int finish_create(smi_engine* e, const char* what, smi_engine** out) {
   return 0;
 }
 
-// ---- the forward-only engines (VAE encoder, VAE decoder, CLIP text encoder): one plan, one size, one create ----------
+// ---- the forward-only engines (VAE encoder, VAE decoder, CLIP text and image towers): one plan, one size, one create ----------
 // `setup` fills a fresh engine with its kind, config and largest shape; the workspace is [packed weights | arena 0]
 using Setup = std::function<void(smi_engine*)>;
 struct ForwardOnlyPlan {
@@ -2494,11 +2583,70 @@ int smi_clip_create(const smi_clip_config* cfg, const smi_weight* weights, int n
 
 int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
                     void* penultimate, void* pooled) {
-  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && ids, "smi_clip_encode: NULL argument or not a CLIP engine");
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && ids, "smi_clip_encode: NULL argument or not a CLIP text engine");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
   e->err = false;
   return e->forward_clip(n, ids, eos_pos, last_hidden, penultimate, pooled);
+}
+
+// ---- CLIP image tower engine and the similarity head ------------------------------------------------------------------
+static int check_clip_vision_cfg(const smi_clip_vision_config* c, int batch) {
+  SMI_CHECK(c != nullptr, "config is NULL");
+  SMI_CHECK(c->dtype == SMI_DTYPE_F16 || c->dtype == SMI_DTYPE_BF16, "dtype must be f16 (0) or bf16 (1)");
+  SMI_CHECK(c->image_size > 0 && c->patch_size > 0 && c->image_size % c->patch_size == 0,
+            "CLIP vision config: image_size %d is not a multiple of patch_size %d", c->image_size, c->patch_size);
+  SMI_CHECK(c->hidden_size > 0 && c->hidden_size % 64 == 0 && c->hidden_size <= 2048,
+            "CLIP vision config: hidden_size %d must be a multiple of 64 and <= 2048", c->hidden_size);
+  SMI_CHECK(c->num_heads > 0 && c->hidden_size % c->num_heads == 0 && (c->hidden_size / c->num_heads) % 8 == 0,
+            "CLIP vision config: head_dim (hidden_size %d / num_heads %d) must be a multiple of 8", c->hidden_size,
+            c->num_heads);
+  SMI_CHECK(c->intermediate_size > 0 && c->intermediate_size % 64 == 0,
+            "CLIP vision config: intermediate_size %d must be a multiple of 64", c->intermediate_size);
+  SMI_CHECK(c->projection_dim >= 0 && c->projection_dim % 8 == 0,
+            "CLIP vision config: projection_dim %d must be a multiple of 8", c->projection_dim);
+  SMI_CHECK(c->num_layers >= 1 && (c->hidden_act == 0 || c->hidden_act == 1) && batch > 0,
+            "CLIP vision config out of range (num_layers >= 1, hidden_act 0 / 1, batch > 0)");
+  SMI_CHECK(clip_patchify_lds_bytes(c->image_size, c->patch_size) <= 65536,
+            "CLIP vision config: image_size %d x patch_size %d exceeds the patch kernel's LDS strip (image_size x "
+            "patch_size <= 10922)", c->image_size, c->patch_size);
+  for (int k = 0; k < 3; ++k) SMI_CHECK(c->image_std[k] > 0.f, "CLIP vision config: image_std[%d] must be positive", k);
+  return 0;
+}
+static void clip_vision_setup(smi_engine* e, const smi_clip_vision_config* cfg, int batch) {
+  e->kind = smi_engine::CLIP_VISION;
+  e->vis = *cfg;
+  e->dtype = cfg->dtype;
+  e->max_n = batch;
+}
+
+int smi_clip_vision_workspace_bytes(const smi_clip_vision_config* cfg, int batch, size_t* bytes) {
+  if (check_clip_vision_cfg(cfg, batch)) return -1;
+  return workspace_bytes_forward_only([&](smi_engine* e) { clip_vision_setup(e, cfg, batch); }, bytes);
+}
+
+int smi_clip_vision_create(const smi_clip_vision_config* cfg, const smi_weight* weights, int n_weights, int batch,
+                           void* workspace, size_t workspace_bytes, void* stream, smi_engine** out) {
+  if (check_clip_vision_cfg(cfg, batch)) return -1;
+  return create_forward_only([&](smi_engine* e) { clip_vision_setup(e, cfg, batch); }, "the CLIP vision weights",
+                             weights, n_weights, workspace, workspace_bytes, stream, out);
+}
+
+int smi_clip_vision_encode(smi_engine* e, int n, const uint8_t* rgb8, const float* pixel_values, void* last_hidden,
+                           void* image_embeds) {
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_VISION,
+            "smi_clip_vision_encode: NULL or not a CLIP vision engine (create it with smi_clip_vision_create)");
+  SMI_CHECK((rgb8 != nullptr) != (pixel_values != nullptr), "smi_clip_vision_encode: exactly one of rgb8 / pixel_values");
+  SMI_CHECK(last_hidden || image_embeds, "smi_clip_vision_encode: no output requested");
+  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  e->err = false;
+  return e->forward_clip_vision(n, rgb8, pixel_values, last_hidden, image_embeds);
+}
+
+int smi_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
+                    float logit_scale, float* logits_per_image, void* stream) {
+  return launch_clip_logits(dtype, image_embeds, ni, text_embeds, nt, dim, logit_scale, logits_per_image,
+                            (hipStream_t)stream);
 }
 
 int smi_weights_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, size_t* bytes) {
@@ -2575,7 +2723,8 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
                              const float* lora_up_flat, float multiplier, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && sample && ctx && eps_out, "NULL argument");
   SMI_CHECK(e->kind == smi_engine::UNET,
-            "this engine is a VAE encoder / decoder or a CLIP encoder (use smi_vae_encode / smi_vae_decode / smi_clip_encode)");
+            "this engine is a VAE encoder / decoder or a CLIP text / vision encoder (use smi_vae_encode / smi_vae_decode / "
+            "smi_clip_encode / smi_clip_vision_encode)");
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(n_adapted >= 0 && n_adapted <= n && n_adapted <= e->max_n_ad,
             "adapted batch %d outside [0, min(%d, %d)]", n_adapted, n, e->max_n_ad);
@@ -2592,7 +2741,7 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
                            const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                            const float* lora_up_flat, const float* multipliers, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && multipliers, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: no UNet forward");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: no UNet forward");
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "per-sample multipliers: 1..%d adapted samples", smi_engine::MAXS);
   float mref = 0.f;
   bool same = true;
@@ -2633,7 +2782,7 @@ int smi_unet_forward(smi_engine* e, int n, const float* sample, float timestep, 
 
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
   e->err = false;
   GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
   return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat, e->bw_n_ad);
@@ -2642,7 +2791,7 @@ int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat
 int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
                            float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps_live && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP encoder: it has no backward");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
   SMI_CHECK(e->tape_valid, "smi_unet_backward_tail: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
   SMI_CHECK(n_live >= 1 && n_live <= e->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
             n_live, e->bw_n_ad);

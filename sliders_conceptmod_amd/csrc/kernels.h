@@ -272,6 +272,20 @@ int launch_vae_dec_tail(int dtype, const void* x, const float* ab, const void* w
                         uint8_t* rgb8, int Nb, int H, int W, int C, int Cout, hipStream_t stream);
 int launch_rgb8_from_nchw(const float* sample, uint8_t* rgb8, int Nb, int C, int HW, hipStream_t stream);
 
+// CLIP image tower front end and similarity head (clip_vision.hip).
+// patches T [n G^2, Kp] (G = S / P, columns (c, py, px) as the patch filter's, Kp = 3 P^2 rounded up to 64, pad columns 0)
+// from exactly one of rgb8 uint8 [n, S, S, 3] (normalised on the way: (u / 255 - mean[c]) / std[c]) and
+// pixel_values f32 [n, 3, S, S] (already normalised); one workgroup per strip of G patches, clip_patchify_lds_bytes of LDS
+size_t clip_patchify_lds_bytes(int S, int P);
+int launch_clip_patchify(int dtype, const uint8_t* rgb8, const float* pixel_values, void* out, int n, int S, int P,
+                         int Kp, const float mean[3], const float stdv[3], hipStream_t stream);
+// out T [n tokens, d] = LayerNorm((t == 0 ? cls : patch_out[i, t - 1]) + pos[t]), the sum kept in fp32; d <= 2048
+int launch_vit_embed_ln(int dtype, const void* patch_out, const void* cls, const void* pos, const void* gamma,
+                        const void* beta, void* out, int n, int tokens, int d, float eps, hipStream_t stream);
+// logits_per_image f32 [ni, nt] = exp(logit_scale) <i, t> / (|i| |t|) from T [ni, dim], T [nt, dim]; dim % 8 == 0
+int launch_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
+                       float logit_scale, float* logits_per_image, hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------------------------
 // LoRA skinny kernels (rank r <= 32)
 // ---------------------------------------------------------------------------------------------------------------

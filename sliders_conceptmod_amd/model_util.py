@@ -417,3 +417,107 @@ def load_models(pretrained_model_name_or_path: str, scheduler_name: str = "ddim"
         return toks, encs, unet, scheduler
     raise ValueError(f"cannot load '{name}': no network in this environment; pass a local diffusers directory or "
                      f"synthetic://sd1x | synthetic://sdxl")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# CLIP image-text model for scoring a sweep (reference: eval-scripts/clip_score.py loads a hub name)
+# ----------------------------------------------------------------------------------------------------------------
+class SyntheticClipTokenizer:
+    """Deterministic stand-in for `CLIPTokenizer` where no vocabulary files exist (the `synthetic://` CLIP models): BOS,
+    one id per lower-cased word (a hash of the word into [1, bos)), EOS; no padding -- `CLIPModel` pads.  In the spirit
+    of `SyntheticTextEncoder`: equal prompts give equal ids, and that is all a seeded model can use."""
+
+    def __init__(self, vocab_size: int, eos_token_id: int, model_max_length: int = 77):
+        self.vocab_size, self.eos_token_id, self.bos_token_id = vocab_size, eos_token_id, eos_token_id - 1
+        self.model_max_length = model_max_length
+
+    def encode(self, prompt: str):
+        import hashlib
+        words = prompt.lower().split()[: self.model_max_length - 2]
+        ids = [1 + int.from_bytes(hashlib.sha256(w.encode()).digest()[:8], "little") % (self.bos_token_id - 1)
+               for w in words]
+        return [self.bos_token_id] + ids + [self.eos_token_id]
+
+    def __call__(self, prompts, **_):
+        rows = [self.encode(p) for p in ([prompts] if isinstance(prompts, str) else prompts)]
+        width = max(len(r) for r in rows)
+        ids = torch.tensor([r + [self.eos_token_id] * (width - len(r)) for r in rows], dtype=torch.int64)
+
+        class _Encoding:
+            input_ids = ids
+        return _Encoding()
+
+
+def init_synthetic_clip_(model, seed: int):
+    """Seeded weights for a `clip.CLIPModel`: embeddings 0.02 N, matrices 0.8 N / sqrt(fan_in) (the patch filter by its
+    3 P^2 fan-in), norm scales 1 + 0.1 N, biases 0.02 N; logit_scale = ln 100 (what the trained models saturate at)."""
+    g = torch.Generator().manual_seed(seed)
+    with torch.no_grad():
+        for name, p in model.named_parameters():
+            if name == "logit_scale":
+                p.fill_(float(np.log(100.0)))
+            elif p.ndim >= 2 and "embedding" in name and p.ndim == 2:
+                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+            elif p.ndim >= 2:
+                p.copy_(torch.randn(p.shape, generator=g) * (0.8 / (p[0].numel()) ** 0.5))
+            elif name.endswith("class_embedding"):
+                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+            elif name.endswith("weight"):
+                p.copy_(1.0 + 0.1 * torch.randn(p.shape, generator=g))
+            else:
+                p.copy_(0.02 * torch.randn(p.shape, generator=g))
+    return model
+
+
+def load_clip(name: str):
+    """(model, tokenizer, image_size) for `clip_score`: a local transformers directory (config.json, model.safetensors,
+    preprocessor_config.json for mean / std / size; tokenizer through `CLIPTokenizer.from_pretrained(dir)`), or
+    `synthetic://tiny_clip | vit_b32 | vit_l14` with seeded weights and the stand-in tokenizer."""
+    import json
+    from . import clip as PC
+    if name.startswith("synthetic://"):
+        kind = name[len("synthetic://"):]
+        if kind == "tiny_clip":
+            tc = PC.CLIPTextConfig(vocab_size=1000, hidden_size=64, intermediate_size=256, num_hidden_layers=3,
+                                   num_attention_heads=4, projection_dim=32, eos_token_id=999)
+            vc = PC.CLIPVisionConfig(hidden_size=64, intermediate_size=256, num_hidden_layers=3, num_attention_heads=4,
+                                     image_size=32, patch_size=8, projection_dim=32)
+        elif kind == "vit_b32":
+            tc, vc = PC.vit_b32_text_config(), PC.vit_b32_vision_config()
+        elif kind == "vit_l14":
+            tc, vc = PC.vit_l14_text_config(), PC.vit_l14_vision_config()
+        else:
+            raise ValueError(f"unknown synthetic CLIP '{name}': synthetic://tiny_clip | vit_b32 | vit_l14")
+        model = init_synthetic_clip_(PC.CLIPModel(tc, vc), seed=13)
+        return model, SyntheticClipTokenizer(tc.vocab_size, tc.eos_token_id, tc.max_position_embeddings), vc.image_size
+    if os.path.isdir(name):
+        from safetensors.torch import load_file
+        cj = json.load(open(os.path.join(name, "config.json")))
+        pj = json.load(open(os.path.join(name, "preprocessor_config.json")))
+        t, v = cj["text_config"], cj["vision_config"]
+        proj = cj.get("projection_dim", 512)
+        tc = PC.CLIPTextConfig(vocab_size=t.get("vocab_size", 49408), hidden_size=t.get("hidden_size", 512),
+                               intermediate_size=t.get("intermediate_size", 2048),
+                               num_hidden_layers=t.get("num_hidden_layers", 12),
+                               num_attention_heads=t.get("num_attention_heads", 8),
+                               max_position_embeddings=t.get("max_position_embeddings", 77),
+                               hidden_act=t.get("hidden_act", "quick_gelu"), projection_dim=proj,
+                               eos_token_id=t.get("eos_token_id", 2))
+        size = pj.get("crop_size", pj.get("size", 224))
+        if isinstance(size, dict):
+            size = size.get("height", size.get("shortest_edge"))
+        vc = PC.CLIPVisionConfig(hidden_size=v.get("hidden_size", 768), intermediate_size=v.get("intermediate_size", 3072),
+                                 num_hidden_layers=v.get("num_hidden_layers", 12),
+                                 num_attention_heads=v.get("num_attention_heads", 12),
+                                 image_size=v.get("image_size", 224), patch_size=v.get("patch_size", 32),
+                                 hidden_act=v.get("hidden_act", "quick_gelu"), projection_dim=proj,
+                                 image_mean=tuple(pj.get("image_mean", PC.OPENAI_CLIP_MEAN)),
+                                 image_std=tuple(pj.get("image_std", PC.OPENAI_CLIP_STD)))
+        if int(size) != vc.image_size:
+            raise ValueError(f"{name}: the processor crops to {size} but the vision tower takes {vc.image_size}")
+        model = PC.CLIPModel(tc, vc, cj.get("logit_scale_init_value", 2.6592))
+        model.load_state_dict(load_file(os.path.join(name, "model.safetensors")))
+        from transformers import CLIPTokenizer
+        return model, CLIPTokenizer.from_pretrained(name), vc.image_size
+    raise ValueError(f"cannot load '{name}': no network in this environment; pass a local transformers directory or "
+                     f"synthetic://tiny_clip | synthetic://vit_b32 | synthetic://vit_l14")
