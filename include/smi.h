@@ -323,6 +323,17 @@ int smi_op_gemm(int dtype, const void* A, const void* W, void* C, int M, int N, 
 int smi_op_gemm_rows(int dtype, const void* A, const void* W, void* C, int M, int N, int K, const void* bias,
                      const void* res, const float* lora_xa, const float* lora_up, int lora_r, float lora_scale,
                      int lora_row0, int lora_seg, void* stream);
+/* Every epilogue term of a dense GEMM on a NAMED tile (tests/test_gemm_epilogue_gpu.py): C [M, N] (T, or fp32 with
+ * out_f32) = A [M, K] W [N, K]^T + bias [N] + rowvec [M / rows_per_vec, ld_rowvec] + lora_scale * delta + res [M, N]; any
+ * of bias / res / rowvec / lora_xa may be NULL.  Delta, forward form (lora_dx = 0): xa [M - lora_row0, ld_xa] fp32 against
+ * up [N, r], fused column blocks of lora_seg (0: none); dX form (lora_dx != 0): xa [M, ld_xa] against lora_up = down
+ * [lora_r, N] read transposed.  tile_code: a tile's tuner code (csrc/gemm.hip kTileNames; 0 = launch_gemm's own choice);
+ * ksplit > 1 forces split-K in that many slices with the tile as the slice kernel (needs smi_op_gemm_scratch).
+ * *ran_code receives the code of the tile that ran: where the named tile cannot take the launch it is the stand-in's. */
+int smi_op_gemm_epilogue(int dtype, const void* A, const void* W, void* C, int M, int N, int K, int out_f32,
+                         const void* bias, const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec,
+                         const float* lora_xa, int ld_xa, const float* lora_up, int lora_r, int lora_seg, int lora_row0,
+                         float lora_scale, int lora_dx, int tile_code, int ksplit, int* ran_code, void* stream);
 int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin,
                    int win, int cin, int cout, int stride, int upsample, int transposed, int hout, int wout,
                    void* stream);

@@ -30,7 +30,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("smi_common.h", "kernels.h")] + [
+    headers = [os.path.join(CSRC, h) for h in ("smi_common.h", "kernels.h", "gemm_tile.h", "gemm_epilogue.h")] + [
         os.path.join(os.path.dirname(HERE), "include", "smi.h")]
     objs = []
     procs = []

@@ -2874,6 +2874,17 @@ int smi_op_gemm_rows(int dtype, const void* A, const void* W, void* C, int M, in
                                  lora_scale, lora_row0),
                      (hipStream_t)stream);
 }
+int smi_op_gemm_epilogue(int dtype, const void* A, const void* W, void* C, int M, int N, int K, int out_f32,
+                         const void* bias, const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec,
+                         const float* lora_xa, int ld_xa, const float* lora_up, int lora_r, int lora_seg, int lora_row0,
+                         float lora_scale, int lora_dx, int tile_code, int ksplit, int* ran_code, void* stream) {
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  if (out_f32) p.f32_out();
+  if (rowvec) p.with_rowvec(rowvec, rows_per_vec, ld_rowvec);
+  if (lora_xa && lora_dx) p.with_lora_dx(lora_xa, ld_xa, lora_up, lora_r, lora_scale);
+  else if (lora_xa) p.with_lora(lora_xa, ld_xa, lora_up, lora_r, lora_seg, lora_scale, lora_row0);
+  return launch_gemm_on_tile(p, tile_code, ksplit, ran_code, (hipStream_t)stream);
+}
 int smi_op_gemm_geglu(int dtype, const void* A, const void* W, const void* bias, void* out, void* proj, int M, int N,
                       int K, int proj_row0, void* stream) {
   return launch_gemm(gemm_nt(dtype, A, K, W, proj, N, M, N, K).with_bias(bias).with_geglu(out, proj_row0), (hipStream_t)stream);

@@ -18,8 +18,8 @@
 #include <cstring>
 #include <unordered_map>
 
-#include "kernels.h"
-#include <type_traits>
+#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 #include <mutex>
 
@@ -45,16 +45,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmParams p) {
   const int wave = tid >> 6;
   const int wm = wave >> 1, wn = wave & 1;
 
-  // XCD-aware bijective remap of the linear block id: blocks that share an XCD (id % 8) get a contiguous
-  // range of tiles, so neighbouring tiles (same A rows / same W rows) hit the same L2.
   const int nbn = (p.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wg;
-  {
-    const int orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  const int wg = xcd_remap(blockIdx.x, gridDim.x);
   const int bm0 = (wg / nbn) * BM;
   const int bn0 = (wg % nbn) * BN;
 
@@ -198,50 +190,18 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmParams p) {
     const int m = bm0 + wm * 64 + mi * 16 + fr;
     if (m >= p.M) continue;
     const bool lora_on = p.lora_r > 0 && m >= p.lora_row0;
-    const float* xrow0 = p.lora_xa + (int64_t)(m - p.lora_row0) * p.ld_xa;
-    const int64_t vrow = p.rowvec ? (int64_t)(m / p.rows_per_vec) * (p.ld_rowvec ? p.ld_rowvec : (int64_t)p.N) : 0;
+    const int64_t vrow = p.rowvec ? epi_rowvec_offset(p, m) : 0;
 #pragma unroll
     for (int ni = 0; ni < 4; ++ni) {
       const int n = bn0 + wn * 64 + ni * 16 + fq * 4;
       if (n >= p.N) continue;
       float v[4] = {acc[ni][mi][0], acc[ni][mi][1], acc[ni][mi][2], acc[ni][mi][3]};
-      if (p.bias) {
-        Pack4<T> b;
-        b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.bias) + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (p.rowvec) {
-        Pack4<T> b;
-        b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.rowvec) + vrow + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (lora_on) {
-        const float* xrow = xrow0 + (p.lora_seg ? (n / p.lora_seg) * p.lora_r : 0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float* up = p.lora_up + (int64_t)(n + j) * p.up_sn;
-          float d = 0.f;
-          for (int q = 0; q < p.lora_r; ++q) d = __builtin_fmaf(xrow[q], up[q * p.up_sq], d);
-          v[j] = __builtin_fmaf(d, p.lora_scale, v[j]);
-        }
-      }
-      if (p.res) {
-        Pack4<T> b;
-        b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (p.out_f32) {
-        *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n) =
-            f32x4{v[0], v[1], v[2], v[3]};
-      } else {
-        Pack4<T> o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o.e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<u32x2*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) = o.u;
-      }
+      if (p.bias) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.bias) + n);
+      if (p.rowvec) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.rowvec) + vrow + n);
+      if (lora_on) epi_lora<4, false>(v, p, m, n);  // (operands of any alignment: scalar loads)
+      if (p.res) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
+      if (p.out_f32) epi_store_f32<4>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n, v);
+      else epi_store<T, 4>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n, v);
     }
   }
 }
@@ -311,7 +271,7 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(GemmParams p, const 
     const int m = (int)(idx / n4);
     const int n = (int)(idx - (int64_t)m * n4) * 4;
     const float* sp = slab + (int64_t)m * p.N + n;
-    f32x4 v = *reinterpret_cast<const f32x4*>(sp);
+    f32x4 sum = *reinterpret_cast<const f32x4*>(sp);
     if constexpr (NS > 0) {
       f32x4 w[NS > 1 ? NS - 1 : 1];
 #pragma unroll
@@ -319,106 +279,30 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(GemmParams p, const 
 #pragma unroll
       for (int s = 1; s < NS; ++s)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] += w[s - 1][j];
+        for (int j = 0; j < 4; ++j) sum[j] += w[s - 1][j];
     } else {
       for (int s = 1; s < nsplit; ++s) {
         const f32x4 w = *reinterpret_cast<const f32x4*>(sp + s * plane);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] += w[j];
+        for (int j = 0; j < 4; ++j) sum[j] += w[j];
       }
     }
-    if (p.bias) {
-      Pack4<T> b;
-      b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.bias) + n);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-    }
-    if (p.rowvec) {
-      Pack4<T> b;
-      b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.rowvec) + (int64_t)(m / p.rows_per_vec) * (p.ld_rowvec ? p.ld_rowvec : (int64_t)p.N) + n);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-    }
+    float v[4] = {sum[0], sum[1], sum[2], sum[3]};
+    if (p.bias) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.bias) + n);
+    if (p.rowvec) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.rowvec) + epi_rowvec_offset(p, m) + n);
     if (p.lora_r > 0 && m >= p.lora_row0) {
-      // (lora_seg is a multiple of 4: the thread's four columns share one segment, hence one xa row)
-      const float* xr = p.lora_xa + (int64_t)(m - p.lora_row0) * p.ld_xa + (p.lora_seg ? (n / p.lora_seg) * p.lora_r : 0);
-      const float* up0 = p.lora_up + (int64_t)n * p.up_sn;
-      // ranks 4 / 8 unrolled: every operand of the delta is requested before the first fmaf (the rolled loop with its
-      // run-time strides made 2 r dependent round trips per column: +18 us on a 2048 x 1280 launch).  Same canonical chain.
-      auto delta = [&](auto rc) {
-        constexpr int R = decltype(rc)::value;
-        float x[R], u[4][R];
-#pragma unroll
-        for (int r = 0; r < R; ++r) x[r] = xr[r];
-        const bool al = (reinterpret_cast<uintptr_t>(p.lora_up) & 15) == 0;
-        if (al && p.up_sq == 1 && p.up_sn == R) {  // [N, r] rows: 16-byte pieces (a lane's dword loads at a 4 r-byte
-          // stride touch 64 lines per wave-instruction: 16 of them per thread made the delta cost 17 of the finish's 24 us)
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int q = 0; q < R / 4; ++q) {
-              const f32x4 t = *reinterpret_cast<const f32x4*>(up0 + j * R + q * 4);
-#pragma unroll
-              for (int e = 0; e < 4; ++e) u[j][q * 4 + e] = t[e];
-            }
-        } else if (al && p.up_sn == 1 && (p.up_sq & 3) == 0) {  // [r, K] read transposed: four columns of one rank row
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const f32x4 t = *reinterpret_cast<const f32x4*>(up0 + (int64_t)r * p.up_sq);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) u[j][r] = t[j];
-          }
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int r = 0; r < R; ++r) u[j][r] = up0[(int64_t)j * p.up_sn + (int64_t)r * p.up_sq];
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          float d = 0.f;
-#pragma unroll
-          for (int r = 0; r < R; ++r) d = __builtin_fmaf(x[r], u[j][r], d);
-          v[j] = __builtin_fmaf(d, p.lora_scale, v[j]);
-        }
-      };
-      if (p.lora_r == 4) delta(std::integral_constant<int, 4>{});
-      else if (p.lora_r == 8) delta(std::integral_constant<int, 8>{});
-      else {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          const float* up = up0 + (int64_t)j * p.up_sn;
-          float d = 0.f;
-          for (int r = 0; r < p.lora_r; ++r) d = __builtin_fmaf(xr[r], up[r * p.up_sq], d);
-          v[j] = __builtin_fmaf(d, p.lora_scale, v[j]);
-        }
-      }
+      // ranks 4 / 8: every operand of the delta requested before the first fmaf; other ranks: the scalar chain
+      if (p.lora_r == 4) epi_lora4_unrolled<4>(v, p, m, n);
+      else if (p.lora_r == 8) epi_lora4_unrolled<8>(v, p, m, n);
+      else epi_lora<4, false>(v, p, m, n);
     }
-    if (p.res) {
-      Pack4<T> b;
-      b.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-    }
-    if (p.out_f32) {
-      *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n) = v;
-    } else {
-      Pack4<T> o;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o.e[j] = from_f<T>(v[j]);
-      *reinterpret_cast<u32x2*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) = o.u;
-    }
+    if (p.res) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
+    if (p.out_f32) epi_store_f32<4>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n, v);
+    else epi_store<T, 4>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n, v);
   }
 }
 
 }  // namespace
-
-bool gemm2_supported(const GemmParams& p);
-bool gemm2_geglu_supported(const GemmParams& p);
-bool gemm3_supported(const GemmParams& p);
-int launch_gemm3(const GemmParams& p, hipStream_t stream);
-bool gemm4_supported(const GemmParams& p);
-int launch_gemm4(const GemmParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------------------------
 // Tile names.  SMI_GEMM forces a tile (A/B experiments; the overrides are bit-identical, tests/test_kernels_gpu.py);
@@ -436,10 +320,11 @@ constexpr TileName kTileNames[] = {
     {GemmTile::Auto, nullptr, 0},           // the heuristic
     {GemmTile::Auto, "no8ph", -1},          // the heuristic without the 256 x 256 tile
     {GemmTile::Auto, "no5ph", -1},          // (the same)
+    {GemmTile::T128x128, nullptr, 13},      // (what fit_tile puts in place of "160" / "64"; no candidate of the tuner)
     {GemmTile::T128x128w8, "128", 1},
     {GemmTile::T128x128w8, nullptr, 5},
     {GemmTile::T256x128, "256", 2},
-    {GemmTile::T64x128, "64", -1},
+    {GemmTile::T64x128, "64", 14},
     {GemmTile::T64x128w4, "64w", 7},
     {GemmTile::T128x160, "160", 4},
     {GemmTile::T128x160w8, "160w", 10},
@@ -447,7 +332,7 @@ constexpr TileName kTileNames[] = {
     {GemmTile::T64x160, "64x160", 12},
     {GemmTile::Gemm3, "8ph", 100},
     {GemmTile::Gemm4, "5ph", 200},
-    {GemmTile::V1, "v1", -1},
+    {GemmTile::V1, "v1", 300},
 };
 GemmTile tile_of_code(int code) {
   for (const TileName& t : kTileNames)
@@ -514,7 +399,6 @@ GemmTile fit_tile(GemmTile tile, const GemmParams& p, bool gemm3) {
     default: return tile;
   }
 }
-int launch_v1(const GemmParams& p, hipStream_t stream);
 int launch_tile(const GemmParams& p, GemmTile tile, hipStream_t stream) {
   if (tile == GemmTile::Gemm3) return launch_gemm3(p, stream);
   if (tile == GemmTile::Gemm4) return launch_gemm4(p, stream);
@@ -526,8 +410,9 @@ int launch_tile(const GemmParams& p, GemmTile tile, hipStream_t stream) {
 bool gemm_geglu_supported(const GemmParams& p) { return !forced_v1() && gemm2_geglu_supported(p); }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Tile autotuning.  All kernel generations / tile layouts give bit-identical results (same K order, same epilogue
-// arithmetic: tests/test_fullsize_gpu.py), so which one runs is purely a speed question, and the heuristics above were
+// Tile autotuning.  All kernel generations / tile layouts give bit-identical results (same K order, and ONE definition of
+// the epilogue arithmetic that all of them call: gemm_epilogue.h; checked per tile by tests/test_gemm_epilogue_gpu.py and
+// on the whole step by tests/test_fullsize_gpu.py), so which one runs is purely a speed question, and the heuristics above were
 // fitted to a handful of SD-XL shapes.  The first time a (shape, epilogue) key is launched the candidates its layout
 // allows are timed with HIP events on the launch stream (2 launches each after one warm-up; this synchronises with
 // the host, once per key, during the first step) and the winner is cached for the life of the process.  A candidate
@@ -825,7 +710,26 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
   return launch_tile(p, heuristic_tile(p, true), stream);
 }
 
-namespace {
+// Test entry: one named tile (or a forced split-K on it), in-process, and which tile really ran.
+int launch_gemm_on_tile(const GemmParams& p, int tile_code, int ksplit, int* ran_code, hipStream_t stream) {
+  SMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
+  if (ran_code) *ran_code = 0;
+  if (tile_code == 0 && ksplit <= 1) return launch_gemm(p, stream);
+  GemmTile tile = tile_of_code(tile_code);
+  SMI_CHECK(tile_code == 0 || tile != GemmTile::Auto, "gemm: unknown tile code %d", tile_code);
+  SMI_CHECK(!p.geglu_out || gemm2_geglu_supported(p), "gemm: fused GEGLU not available for this shape/layout");
+  tile = (tile == GemmTile::V1 || !gemm2_supported(p)) ? GemmTile::V1 : fit_tile(tile, p, false);
+  if (ran_code) *ran_code = code_of_tile(tile);
+  if (ksplit > 1) {
+    SMI_CHECK(tile != GemmTile::V1 && tile != GemmTile::Gemm3 && tile != GemmTile::Gemm4 && !p.geglu_out && p.N % 4 == 0,
+              "gemm: split-K takes a gemm2 tile as its slice kernel (tile code %d)", tile_code);
+    SMI_CHECK(t_scratch && (size_t)ksplit * p.M * p.N * sizeof(float) <= t_scratch_bytes,
+              "gemm: %d slices need a scratch of %zu bytes", ksplit, (size_t)ksplit * p.M * p.N * sizeof(float));
+    return launch_splitk(p, ksplit, tile, stream);
+  }
+  return launch_tile(p, tile, stream);
+}
+
 // the register-staged kernel: operands gemm2 cannot take (alignment, layout) and SMI_GEMM=v1
 int launch_v1(const GemmParams& p, hipStream_t stream) {
   SMI_CHECK(p.K % 8 == 0 && p.N % 4 == 0, "gemm: K %% 8 and N %% 4 must be 0 (K=%d N=%d)", p.K, p.N);
@@ -857,7 +761,6 @@ int launch_v1(const GemmParams& p, hipStream_t stream) {
   SMI_HIP(hipGetLastError());
   return 0;
 }
-}  // namespace
 
 int launch_conv3x3_small(int dtype, const void* in, const void* w, const void* bias, void* out, int out_f32, int Nb,
                          int H, int W, int Cin, int Cout, hipStream_t stream) {

@@ -14,22 +14,14 @@
 //   * optional 256-row tile (8 waves) for the large-M layers: fewer LDS bytes staged per FLOP;
 //   * epilogue lane remap: the W-fragment rows of each MFMA pair are permuted so that a lane owns 8 CONSECUTIVE
 //     output columns -> 16-byte stores / residual / bias accesses instead of 8-byte ones.
-#include "kernels.h"
+#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace smi {
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page[256];  // zero-initialised
 
 namespace {
 
 constexpr int BK = 64;
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)lds_dst, 16, 0, 0);
-}
 
 // Block tile = (64 WM) x BN with 2 WM waves.  NL = 0: BN = 128, waves as WM (M) x 2 (N), 64 x 64 per wave.
 // NL = 1: BN = 160, waves as 2 WM (M) x 1 (N), 32 x 160 per wave -- every layer width of the UNets (320 / 640 / 1280 and
@@ -69,13 +61,7 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
   constexpr int WROWS = 16 * MI, WCOLS = 16 * NI;  // wave tile
 
   const int nbn = (p.N + BN - 1) / BN;
-  const int nwg = gridDim.x;
-  int wg;
-  {
-    const int orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
+  int wg = xcd_remap(blockIdx.x, gridDim.x);
   // split-K: the grid holds ksplit workgroups per output tile (adjacent after the remap); slice s owns a contiguous range
   // of K-tiles and writes fp32 partials to its own slab
   const int nsplit = p.ksplit > 1 ? p.ksplit : 1;
@@ -84,22 +70,16 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
     kslice = wg % nsplit;
     wg /= nsplit;
   }
-  // grouped rasterisation: consecutive workgroups (= the ones co-resident on one XCD after the remap above) sweep a
-  // band of GW column tiles before moving down a row tile, so the 32-64 tiles sharing an L2 form a ~8x8 patch
-  // (8 + 8 operand panels per K-step instead of 1 + 64 for a wide-N GEMM walked row-major)
-  constexpr int GW = 8;
+  // grouped rasterisation (gemm_tile.h) in bands of 8 column tiles
   const int nbm = (p.M + BM - 1) / BM;
-  const int grp = wg / (GW * nbm);
-  const int gw = min(nbn - grp * GW, GW);
-  const int lw = wg - grp * GW * nbm;
-  const int bm0 = (lw / gw) * BM;
-  const int bn0 = (grp * GW + lw % gw) * BN;
+  int tm, tn;
+  grouped_raster(wg, nbm, nbn, 8, tm, tn);
+  const int bm0 = tm * BM;
+  const int bn0 = tn * BN;
   const bool geglu = p.geglu_out != nullptr;
   const int nhalf = p.N >> 1;
   // tile-local column nl (0..127) -> global output column
-  auto gcol = [&](int nl) {
-    return geglu ? (nl < BN / 2 ? (bn0 >> 1) + nl : nhalf + (bn0 >> 1) + nl - BN / 2) : bn0 + nl;
-  };
+  auto gcol = [&](int nl) { return geglu ? geglu_col<BN>(bn0, nhalf, nl) : bn0 + nl; };
 
   const int nk_all = (p.K + BK - 1) / BK;
   const int kbase = (int)((int64_t)kslice * nk_all / nsplit);                    // first K-tile of this slice
@@ -360,17 +340,14 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
   T* otile = reinterpret_cast<T*>(smem);
 
   // NL = 3 (the tile of the 4096-row backward GEMMs, whose dX carries the rank-r delta on every row): the delta of all
-  // ten (fragment, row-fragment) pairs on the fp32 MFMA, in uniform control flow ahead of the per-lane epilogue --
-  // D[16 cols x 16 rows] = "up"-fragment [16 x 4] * xa-fragment [4 x 16] + D per rank block, the canonical fmaf chain of
-  // smi_common.h in the accumulators' register layout (as in gemm4.hip), for both operand forms (forward: up [N, r];
-  // dX: lora_down [r, K] read along K).  One dword load per operand and lane instead of 3 r 16-byte loads per 8 columns.
+  // ten (fragment, row-fragment) pairs on the fp32 MFMA (gemm_epilogue.h), in uniform control flow ahead of the per-lane
+  // epilogue, for both operand forms.  One dword load per operand and lane instead of 3 r 16-byte loads per 8 columns.
   f32x4 dlt[NL == 3 ? NI : 1][NL == 3 ? MI : 1];
   bool delta_mfma = false;
   if constexpr (NL == 3) {
-    const bool fwd_form = p.up_sq == 1 && p.up_sn == p.lora_r;
-    const bool dx_form = p.up_sn == 1 && !fwd_form;
-    delta_mfma = p.lora_r > 0 && (p.lora_r & 3) == 0 && p.lora_r <= 16 && (fwd_form || dx_form) &&
-                 (p.lora_seg == 0 || p.lora_seg % BN == 0) && bm0 + BM > p.lora_row0 && p.N % BN == 0;
+    const int form = epi_lora_mfma_form(p, BN);
+    const bool fwd_form = form == EPI_MFMA_FWD;
+    delta_mfma = form != EPI_MFMA_NONE && bm0 + BM > p.lora_row0 && p.N % BN == 0;
     if (delta_mfma) {
       const int nblk = p.lora_r >> 2;
       const int xoff = p.lora_seg ? (bn0 / p.lora_seg) * p.lora_r : 0;
@@ -379,26 +356,23 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
       for (int mi = 0; mi < MI; ++mi) {
         const int m = bm0 + wm * WROWS + mi * 16 + fr;
         const bool on = m < p.M && m >= p.lora_row0;
-        const float* xr = p.lora_xa + (int64_t)(on ? m - p.lora_row0 : 0) * p.ld_xa + xoff + fq;
+        const float* xr = epi_mfma_xa(p, m, on, xoff, fq);
 #pragma unroll
         for (int b = 0; b < 4; ++b) bx[mi][b] = (on && b < nblk) ? xr[4 * b] : 0.f;
       }
 #pragma unroll
       for (int ni = 0; ni < NI; ++ni) {
         const int col = bn0 + wn * WCOLS +
-                        (ni < NI - 1 ? (ni >> 1) * 32 + 8 * (fr >> 2) + 4 * (ni & 1) + (fr & 3) : (NI - 1) * 16 + fr);
+                        (ni < NI - 1 ? (ni >> 1) * 32 + epi_pair_col(fr, ni & 1) : (NI - 1) * 16 + fr);
         float au[4];
 #pragma unroll
-        for (int b = 0; b < 4; ++b)
-          au[b] = b < nblk ? (fwd_form ? p.lora_up[(int64_t)col * p.lora_r + 4 * b + fq]
-                                       : p.lora_up[(int64_t)(4 * b + fq) * p.up_sq + col])
-                           : 0.f;
+        for (int b = 0; b < 4; ++b) au[b] = b < nblk ? epi_mfma_up(p, fwd_form, col, b, fq) : 0.f;
 #pragma unroll
         for (int mi = 0; mi < MI; ++mi) {
           f32x4 d = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int b = 0; b < 4; ++b)
-            if (b < nblk) d = __builtin_amdgcn_mfma_f32_16x16x4f32(au[b], bx[mi][b], d, 0, 0, 0);
+            if (b < nblk) d = epi_mfma_block(au[b], bx[mi][b], d);
           dlt[ni][mi] = d;
         }
       }
@@ -410,8 +384,7 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
     const int m = bm0 + ml;
     if (m >= p.M) continue;
     const bool lora_on = p.lora_r > 0 && m >= p.lora_row0;
-    const float* xrow0 = p.lora_xa + (int64_t)(m - p.lora_row0) * p.ld_xa;
-    const int64_t vrow = p.rowvec ? (int64_t)(m / p.rows_per_vec) * (p.ld_rowvec ? p.ld_rowvec : (int64_t)p.N) : 0;
+    const int64_t vrow = p.rowvec ? epi_rowvec_offset(p, m) : 0;
 #pragma unroll
     for (int q = 0; q < (NI + 1) / 2; ++q) {
       constexpr bool ODD = (NI & 1) != 0;
@@ -426,176 +399,34 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
         v[4 + j] = acc[(2 * q + 1 < NI) ? 2 * q + 1 : 0][mi][j];  // (unused for the single fragment)
       }
       const bool full = !single && n + 8 <= p.N;  // N % 8 may be 4 (conv_out): second half masked
-      if (p.bias) {
-        const T* bp = reinterpret_cast<const T*>(p.bias) + n;
-        if (full) {
-          Pack8<T> b;
-          b.u = *reinterpret_cast<const u32x4*>(bp);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-        } else {
-          Pack4<T> b;
-          b.u = *reinterpret_cast<const u32x2*>(bp);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-        }
-      }
-      if (p.rowvec) {
-        const T* bp = reinterpret_cast<const T*>(p.rowvec) + vrow + n;
-        if (full) {
-          Pack8<T> b;
-          b.u = *reinterpret_cast<const u32x4*>(bp);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-        } else {
-          Pack4<T> b;
-          b.u = *reinterpret_cast<const u32x2*>(bp);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-        }
-      }
+      if (p.bias) epi_add<T>(v, reinterpret_cast<const T*>(p.bias) + n, full);
+      if (p.rowvec) epi_add<T>(v, reinterpret_cast<const T*>(p.rowvec) + vrow + n, full);
       if (NL == 3 && delta_mfma) {
         if (lora_on) {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            v[j] = __builtin_fmaf(dlt[NL == 3 ? 2 * q : 0][NL == 3 ? mi : 0][j], p.lora_scale, v[j]);
-            if (!single)
-              v[4 + j] = __builtin_fmaf(dlt[(NL == 3 && 2 * q + 1 < NI) ? 2 * q + 1 : 0][NL == 3 ? mi : 0][j],
-                                        p.lora_scale, v[4 + j]);
-          }
+          epi_add_delta(v, dlt[NL == 3 ? 2 * q : 0][NL == 3 ? mi : 0], p.lora_scale);
+          if (!single) epi_add_delta(v + 4, dlt[(NL == 3 && 2 * q + 1 < NI) ? 2 * q + 1 : 0][NL == 3 ? mi : 0], p.lora_scale);
         }
       } else if (lora_on) {
-        const float* xrow = xrow0 + (p.lora_seg ? (n / p.lora_seg) * p.lora_r : 0);
-        if ((full || single) && p.up_sq == 1 && p.up_sn == p.lora_r && (p.lora_r & 3) == 0) {
-          // forward, rank 4 / 8 / ...: 16-byte loads of xa and of each output column's row of lora_up [N, r]
-          // (the single fragment of the 32 x 80 wave tile: its 4 columns only)
-          float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          for (int r0 = 0; r0 < p.lora_r; r0 += 4) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(xrow + r0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              if (j < 4 || full) {
-                const f32x4 uv = *reinterpret_cast<const f32x4*>(p.lora_up + (int64_t)(n + j) * p.lora_r + r0);
-                d[j] = lora_fma4(d[j], xv, uv);
-              }
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(d[j], p.lora_scale, v[j]);
-        } else if ((full || single) && p.up_sn == 1 && (p.up_sq & 3) == 0) {
-          // backward (dX): "up" is lora_down [r_tot, K] read along K: 8 consecutive columns = two 16-byte loads per q
-          float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          for (int r = 0; r < p.lora_r; ++r) {
-            const float xq = xrow[r];
-            const float* ar = p.lora_up + (int64_t)r * p.up_sq + n;
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(ar);
-            const f32x4 a1 = full ? *reinterpret_cast<const f32x4*>(ar + 4) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              d[j] = __builtin_fmaf(xq, a0[j], d[j]);
-              d[4 + j] = __builtin_fmaf(xq, a1[j], d[4 + j]);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(d[j], p.lora_scale, v[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            if ((full || j < 4) && n + j < p.N) {
-              const float* xr = xrow0 + (p.lora_seg ? ((n + j) / p.lora_seg) * p.lora_r : 0);
-              const float* up = p.lora_up + (int64_t)(n + j) * p.up_sn;
-              float d = 0.f;
-              for (int r = 0; r < p.lora_r; ++r) d = __builtin_fmaf(xr[r], up[r * p.up_sq], d);
-              v[j] = __builtin_fmaf(d, p.lora_scale, v[j]);
-            }
-          }
-        }
+        epi_lora<8>(v, p, m, n, full ? 8 : 4);
       }
-      if (p.res) {
-        const T* rp = reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n;
-        if (full) {
-          Pack8<T> b;
-          b.u = *reinterpret_cast<const u32x4*>(rp);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-        } else {
-          Pack4<T> b;
-          b.u = *reinterpret_cast<const u32x2*>(rp);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) v[j] += to_f(b.e[j]);
-        }
-      }
+      if (p.res) epi_add<T>(v, reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n, full);
       if (p.out_f32) {
         float* op = reinterpret_cast<float*>(p.C) + ((int64_t)kslice * p.M + m) * p.ldc + n;  // (kslice = 0 unsplit)
-        *reinterpret_cast<f32x4*>(op) = f32x4{v[0], v[1], v[2], v[3]};
-        if (full) *reinterpret_cast<f32x4*>(op + 4) = f32x4{v[4], v[5], v[6], v[7]};
+        if (full) epi_store_f32<8>(op, v);
+        else epi_store_f32<4>(op, v);
       } else if (stage_out && full) {
-        Pack8<T> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<u32x4*>(otile + ml * OLD + nl) = o.u;
+        epi_store<T, 8>(otile + ml * OLD + nl, v);
       } else if (stage_out) {
-        Pack4<T> o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o.e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<u32x2*>(otile + ml * OLD + nl) = o.u;
+        epi_store<T, 4>(otile + ml * OLD + nl, v);
       } else {
-        T* op = reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n;
-        Pack4<T> o;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o.e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<u32x2*>(op) = o.u;
+        epi_store<T, 4>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n, v);
       }
     }
   }
-  if (stage_out && geglu) {
+  if (stage_out) {
     __syncthreads();
-    constexpr int NT = NW * 64;
-    {  // hidden * gelu(gate): BN/16 chunks of 8 output columns per row
-      constexpr int CH = BN / 16;
-      T* gout = reinterpret_cast<T*>(p.geglu_out);
-#pragma unroll
-      for (int i = 0; i < (BM * CH) / NT; ++i) {
-        const int idx = tid + i * NT;
-        const int r = idx / CH, c = idx - r * CH;
-        const int m = bm0 + r;
-        if (m < p.M) {
-          Pack8<T> h, g, o;
-          h.u = *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-          g.u = *reinterpret_cast<const u32x4*>(otile + r * OLD + BN / 2 + c * 8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(h.e[e]) * gelu_f(to_f(g.e[e])));
-          *reinterpret_cast<u32x4*>(gout + (int64_t)m * nhalf + (bn0 >> 1) + c * 8) = o.u;
-        }
-      }
-    }
-    if (bm0 + BM > p.geglu_row0) {  // projection kept only for the rows that will be differentiated
-      constexpr int CH = BN / 8;
-#pragma unroll
-      for (int i = 0; i < (BM * CH) / NT; ++i) {
-        const int idx = tid + i * NT;
-        const int r = idx / CH, c = idx - r * CH;
-        const int n = gcol(c * 8);
-        const int m = bm0 + r;
-        if (m < p.M && m >= p.geglu_row0)
-          *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) =
-              *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-      }
-    }
-  } else if (stage_out) {
-    __syncthreads();
-    constexpr int NT = NW * 64;
-    constexpr int CH = BN / 8;  // 16-byte chunks per tile row
-#pragma unroll
-    for (int i = 0; i < (BM * CH) / NT; ++i) {
-      const int idx = tid + i * NT;
-      const int r = idx / CH, c = idx - r * CH;
-      const int n = bn0 + c * 8;
-      const int m = bm0 + r;
-      if (m < p.M && n < p.N)
-        *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) =
-            *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-    }
+    if (geglu) geglu_writeout<T, BM, BN, NW * 64>(p, otile, tid, bm0, bn0);
+    else stage_writeout<T, BM, BN, NW * 64>(p, otile, tid, bm0, bn0);
   }
 }
 

@@ -24,9 +24,8 @@
 // a per-lane pointer that just advances 128 bytes per K-tile.  Requires K % 64 == 0 (all UNet layers); others use v2.
 // CONV = implicit-GEMM 3x3 / stride 1 / pad 1: K runs over (tap, channel); an A row is a pixel, its source for a K-tile
 // is the centre-tap pointer + a wave-uniform tap offset, or a zero page when the tap falls outside the image.
-#include "kernels.h"
-
-#include <type_traits>
+#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace smi {
 namespace {
@@ -36,17 +35,6 @@ constexpr int HALF = 128 * BK * 2;  // one half-tile: 128 rows x 128 B
 constexpr int BUF = 4 * HALF;       // A-h0 | A-h1 | B-h0 | B-h1
 constexpr int OLD = BN + 8;         // staged output row length (elements)
 constexpr int SMEM3 = (BM * OLD * 2 > 2 * BUF) ? BM * OLD * 2 : 2 * BUF;
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)lds_dst, 16, 0, 0);
-}
-
-#define SMI_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page3[256];  // zero-initialised (conv padding source)
 
 template <typename T, bool CONV>
 __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
@@ -60,24 +48,15 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
 
   const int nbn = (p.N + BN - 1) / BN;
   const int nbm = (p.M + BM - 1) / BM;
-  int wg;
-  {
-    const int nwg = gridDim.x, orig = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = orig & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
-  }
-  // grouped rasterisation (see gemm2.hip): the 32 tiles co-resident on an XCD form a ~(32/GW) x GW patch
-  const int ngrp = (nbn + 7) / 8;
-  const int GW = (nbn + ngrp - 1) / ngrp;
-  const int grp = wg / (GW * nbm);
-  const int gw = min(nbn - grp * GW, GW);
-  const int lw = wg - grp * GW * nbm;
-  const int bm0 = (lw / gw) * BM;
-  const int bn0 = (grp * GW + lw % gw) * BN;
+  // grouped rasterisation (gemm_tile.h): the 32 tiles co-resident on an XCD form a ~(32/GW) x GW patch
+  int tm, tn;
+  grouped_raster(xcd_remap(blockIdx.x, gridDim.x), nbm, nbn, raster_band(nbn), tm, tn);
+  const int bm0 = tm * BM;
+  const int bn0 = tn * BN;
 
   const bool geglu = p.geglu_out != nullptr;
   const int nhalf = p.N >> 1;
-  auto gcol = [&](int nl) { return geglu ? (nl < 128 ? (bn0 >> 1) + nl : nhalf + (bn0 >> 1) + nl - 128) : bn0 + nl; };
+  auto gcol = [&](int nl) { return geglu ? geglu_col<BN>(bn0, nhalf, nl) : bn0 + nl; };
 
   // ---- LDS-DMA sources.  Half-tile instruction j of wave w covers LDS rows r = 16 w + 8 j + (lane >> 3); the lane's
   //      16-byte slot (lane & 7) holds source chunk slot ^ (r & 7)  (the read side applies the same XOR).
@@ -129,7 +108,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
       const int tap = kyA[h] * 3 + kxA[h];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
-        const void* src = ((amask[h][j] >> tap) & 1) ? (const void*)(aS[h][j] + toff) : (const void*)g_zero_page3;
+        const void* src = ((amask[h][j] >> tap) & 1) ? (const void*)(aS[h][j] + toff) : (const void*)g_zero_page;
         glds16(src, dst + (wave * 2 + j) * 1024);
       }
       cA[h] += BK;
@@ -292,8 +271,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
     const int m = bm0 + ml;
     if (m >= p.M) continue;
     const bool lora_on = p.lora_r > 0 && m >= p.lora_row0;
-    const float* xrow0 = p.lora_xa + (int64_t)(m - p.lora_row0) * p.ld_xa;
-    const int64_t vrow = p.rowvec ? (int64_t)(m / p.rows_per_vec) * (p.ld_rowvec ? p.ld_rowvec : (int64_t)p.N) : 0;
+    const int64_t vrow = p.rowvec ? epi_rowvec_offset(p, m) : 0;
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int nl = wc * 64 + q * 32 + fq * 8;
@@ -305,118 +283,18 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
         v[j] = acc[2 * q][mi][j];
         v[4 + j] = acc[2 * q + 1][mi][j];
       }
-      if (p.bias) {
-        Pack8<T> b;
-        b.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.bias) + n);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (p.rowvec) {
-        Pack8<T> b;
-        b.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.rowvec) + vrow + n);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (lora_on) {
-        const float* xrow = xrow0 + (p.lora_seg ? (n / p.lora_seg) * p.lora_r : 0);
-        if (p.up_sq == 1 && p.up_sn == p.lora_r && (p.lora_r & 3) == 0) {
-          float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          for (int r0 = 0; r0 < p.lora_r; r0 += 4) {
-            const f32x4 xv = *reinterpret_cast<const f32x4*>(xrow + r0);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-              const f32x4 uv = *reinterpret_cast<const f32x4*>(p.lora_up + (int64_t)(n + j) * p.lora_r + r0);
-              d[j] = lora_fma4(d[j], xv, uv);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(d[j], p.lora_scale, v[j]);
-        } else if (p.up_sn == 1 && (p.up_sq & 3) == 0) {
-          float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          for (int r = 0; r < p.lora_r; ++r) {
-            const float xq = xrow[r];
-            const float* ar = p.lora_up + (int64_t)r * p.up_sq + n;
-            const f32x4 a0 = *reinterpret_cast<const f32x4*>(ar), a1 = *reinterpret_cast<const f32x4*>(ar + 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-              d[j] = __builtin_fmaf(xq, a0[j], d[j]);
-              d[4 + j] = __builtin_fmaf(xq, a1[j], d[4 + j]);
-            }
-          }
-#pragma unroll
-          for (int j = 0; j < 8; ++j) v[j] = __builtin_fmaf(d[j], p.lora_scale, v[j]);
-        } else {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            const float* xr = xrow0 + (p.lora_seg ? ((n + j) / p.lora_seg) * p.lora_r : 0);
-            const float* up = p.lora_up + (int64_t)(n + j) * p.up_sn;
-            float d = 0.f;
-            for (int r = 0; r < p.lora_r; ++r) d = __builtin_fmaf(xr[r], up[r * p.up_sq], d);
-            v[j] = __builtin_fmaf(d, p.lora_scale, v[j]);
-          }
-        }
-      }
-      if (p.res) {
-        Pack8<T> b;
-        b.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] += to_f(b.e[j]);
-      }
-      if (p.out_f32) {
-        float* op = reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n;
-        *reinterpret_cast<f32x4*>(op) = f32x4{v[0], v[1], v[2], v[3]};
-        *reinterpret_cast<f32x4*>(op + 4) = f32x4{v[4], v[5], v[6], v[7]};
-      } else {
-        Pack8<T> o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.e[j] = from_f<T>(v[j]);
-        *reinterpret_cast<u32x4*>(otile + ml * OLD + nl) = o.u;
-      }
+      if (p.bias) epi_add<T, 8>(v, reinterpret_cast<const T*>(p.bias) + n);
+      if (p.rowvec) epi_add<T, 8>(v, reinterpret_cast<const T*>(p.rowvec) + vrow + n);
+      if (lora_on) epi_lora<8>(v, p, m, n);
+      if (p.res) epi_add<T, 8>(v, reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
+      if (p.out_f32) epi_store_f32<8>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n, v);
+      else epi_store<T, 8>(otile + ml * OLD + nl, v);
     }
   }
-  if (stage_out && geglu) {
+  if (stage_out) {
     __syncthreads();
-    {  // hidden * gelu(gate): 16 chunks of 8 output columns per row; a wave writes 4 rows x 256 contiguous bytes
-      const int c = tid & 15;
-      T* gout = reinterpret_cast<T*>(p.geglu_out);
-#pragma unroll
-      for (int i = 0; i < BM / 32; ++i) {
-        const int r = (tid >> 4) + i * 32;
-        const int m = bm0 + r;
-        if (m < p.M) {
-          Pack8<T> h, g, o;
-          h.u = *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-          g.u = *reinterpret_cast<const u32x4*>(otile + r * OLD + 128 + c * 8);
-#pragma unroll
-          for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(h.e[e]) * gelu_f(to_f(g.e[e])));
-          *reinterpret_cast<u32x4*>(gout + (int64_t)m * nhalf + (bn0 >> 1) + c * 8) = o.u;
-        }
-      }
-    }
-    if (bm0 + BM > p.geglu_row0) {  // projection kept only for the rows that will be differentiated
-      const int c = tid & 31;
-      const int n = gcol(c * 8);
-#pragma unroll
-      for (int i = 0; i < BM / 16; ++i) {
-        const int r = (tid >> 5) + i * 16;
-        const int m = bm0 + r;
-        if (m < p.M && m >= p.geglu_row0)
-          *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) =
-              *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-      }
-    }
-  } else if (stage_out) {
-    __syncthreads();
-    const int c = tid & 31;  // 16-byte chunk within the 256-column tile row
-    const int n = bn0 + c * 8;
-#pragma unroll
-    for (int i = 0; i < BM / 16; ++i) {
-      const int r = (tid >> 5) + i * 16;
-      const int m = bm0 + r;
-      if (m < p.M && n < p.N)
-        *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) =
-            *reinterpret_cast<const u32x4*>(otile + r * OLD + c * 8);
-    }
+    if (geglu) geglu_writeout<T, BM, BN, 512>(p, otile, tid, bm0, bn0);
+    else stage_writeout<T, BM, BN, 512>(p, otile, tid, bm0, bn0);
   }
 }
 
@@ -431,8 +309,6 @@ int launch_t(const GemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-
-bool gemm2_supported(const GemmParams& p);
 
 // dense GEMMs whose layout the 8-phase kernel takes: everything gemm2 takes, plus K % 64 == 0 and N % 8 == 0
 bool gemm3_supported(const GemmParams& p) {

@@ -28,13 +28,8 @@
 //
 // Requires M % 256 == 0, N % 320 == 0, K % 64 == 0, K >= 128 (everything else stays on gemm2 / gemm3).  Results are
 // bit-identical to the other generations: same K order per output element, same epilogue arithmetic.
-#include <mutex>
-
-#include <stdlib.h>
-
-#include "kernels.h"
-
-#include <type_traits>
+#include "gemm_epilogue.h"
+#include "gemm_tile.h"
 
 namespace smi {
 namespace {
@@ -44,17 +39,6 @@ constexpr int UNIT = 64 * BK * 2;        // 8 KiB
 constexpr int ABYTES = 4 * UNIT;         // 32 KiB
 constexpr int KBUF = ABYTES + 5 * UNIT;  // 72 KiB per K-tile
 constexpr int SMEM4 = 2 * KBUF;          // 144 KiB
-
-typedef __attribute__((address_space(3))) void lds_void;
-typedef const __attribute__((address_space(1))) void gbl_void;
-
-__device__ __forceinline__ void glds16(const void* gsrc, void* lds_dst) {
-  __builtin_amdgcn_global_load_lds((gbl_void*)gsrc, (lds_void*)lds_dst, 16, 0, 0);
-}
-
-#define SMI_FENCE() __builtin_amdgcn_sched_barrier(0)
-
-__device__ __attribute__((aligned(256))) unsigned char g_zero_page4[256];  // zero-initialised (conv padding source)
 
 // CONV = implicit-GEMM 3x3 / stride 1 / pad 1 (as gemm3.hip): K runs over (tap, channel); an A row is an output pixel,
 // its source for a K-tile is the pixel's own address + a wave-uniform tap offset, or the zero page when the tap falls
@@ -82,16 +66,12 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
 
   // virtual tile id -> tile origin: XCD-contiguous chunks (ids congruent mod 8 share an XCD: G % 8 == 0 or one round),
   // then gemm2's grouped rasterisation inside the chunk
-  const int ngrp = (nbn + 7) / 8;
-  const int GW = (nbn + ngrp - 1) / ngrp;
+  const int GW = raster_band(nbn);
   auto tile_origin = [&](int v, int& bm0, int& bn0) {
-    const int q = ntiles >> 3, r = ntiles & 7, xcd = v & 7;
-    const int wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (v >> 3);
-    const int g = wg / (GW * nbm);
-    const int gw = min(nbn - g * GW, GW);
-    const int lw = wg - g * GW * nbm;
-    bm0 = __builtin_amdgcn_readfirstlane((lw / gw) * BM);
-    bn0 = __builtin_amdgcn_readfirstlane((g * GW + lw % gw) * BN);
+    int tm, tn;
+    grouped_raster(xcd_remap(v, ntiles), nbm, nbn, GW, tm, tn);
+    bm0 = __builtin_amdgcn_readfirstlane(tm * BM);
+    bn0 = __builtin_amdgcn_readfirstlane(tn * BN);
   };
 
   // ---- LDS-DMA lane constants.  One instruction of the workgroup fills a unit: wave w covers its rows 8 w + (lane >> 3),
@@ -199,14 +179,14 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
                          ((int64_t)(ub + (iy2 >> 1) * p.Win + (ox0 >> 1)) * p.Cin + (tt - tap * cpt) * BK) * 2;
       const int vo = kx == 0 ? voffU[0] : (kx == 1 ? voffU[1] : voffU[2]);
       const bool ok = vok && (unsigned)(ox0 + r64 + kx - 1) < (unsigned)(2 * p.Win);
-      glds16(ok ? (const void*)(base + vo) : (const void*)g_zero_page4, buf + u * UNIT + ldsw);
+      glds16(ok ? (const void*)(base + vo) : (const void*)g_zero_page, buf + u * UNIT + ldsw);
     } else if (CONV) {
       const int tap = (tt * cpt_magic) >> 16;
       const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
       const int64_t toff = ((int64_t)((ky - 1) * p.Win + (kx - 1)) * p.Cin + (tt - tap * cpt) * BK) * 2;
       const int mk = nx ? am_nxt[u] : am_cur[u];
       const char* src = (nx ? a_nxt : a_cur) + u * a_unit + toff + voffA;
-      glds16(((mk >> tap) & 1) ? (const void*)src : (const void*)g_zero_page4, buf + u * UNIT + ldsw);
+      glds16(((mk >> tap) & 1) ? (const void*)src : (const void*)g_zero_page, buf + u * UNIT + ldsw);
     } else {
       const char* base = (nx ? a_nxt : a_cur) + (int64_t)tt * (BK * 2);
       glds16(base + u * a_unit + voffA, buf + u * UNIT + ldsw);
@@ -385,36 +365,29 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
     // forward-form delta (up [N, r] row-major, r % 4 == 0, r <= 16, a tile inside one fused segment) on the fp32 MFMA:
     // D[16 cols][16 rows] = up-fragment [16 x 4] * xa-fragment [4 x 16] + D per rank block -- the canonical fmaf chain
     // (smi_common.h lora_fma4) in the accumulators' own register layout, one dword load per operand and lane
-    const bool lora_mfma = p.up_sq == 1 && p.up_sn == p.lora_r && (p.lora_r & 3) == 0 && p.lora_r <= 16 &&
-                           (p.lora_seg == 0 || p.lora_seg % BN == 0);
+    const bool lora_mfma = epi_lora_mfma_form(p, BN) == EPI_MFMA_FWD;
     const int nblk = p.lora_r >> 2;
     const int xoff_t = p.lora_seg ? (bn0 / p.lora_seg) * p.lora_r : 0;  // (lora_mfma: the whole tile is one segment)
     auto epilogue_pair = [&](auto Uc) {
       constexpr int u = decltype(Uc)::value;
       const int n = bn0 + wc * 160 + u * 32 + fq * 8;
-      float bv[8];
+      float bv[8];  // kept across the pair's four rows
 #pragma unroll
       for (int j = 0; j < 8; ++j) bv[j] = 0.f;
-      if (p.bias) {
-        Pack8<T> b;
-        b.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.bias) + n);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) bv[j] = to_f(b.e[j]);
-      }
-      // MFMA A operand: lane (i = lane & 15, k = lane >> 4) holds up[column of fragment row i][4 blk + k]; fragment row i
-      // of the pair's MFMA nip is output column 8 (i >> 2) + 4 nip + (i & 3) of the pair's 32
+      if (p.bias) epi_unpack<T, 8>(bv, reinterpret_cast<const T*>(p.bias) + n);
+      // MFMA A operand of the pair's MFMA nip (operand maps: gemm_epilogue.h)
       float au[2][4];
 #pragma unroll
       for (int nip = 0; nip < 2; ++nip)
 #pragma unroll
         for (int b = 0; b < 4; ++b) au[nip][b] = 0.f;
       if (lora_tile && lora_mfma) {
-        const int ncol = bn0 + wc * 160 + u * 32 + 8 * (fr >> 2) + (fr & 3);
+        const int ncol = bn0 + wc * 160 + u * 32;
 #pragma unroll
         for (int nip = 0; nip < 2; ++nip)
 #pragma unroll
           for (int b = 0; b < 4; ++b)
-            if (b < nblk) au[nip][b] = p.lora_up[(int64_t)(ncol + 4 * nip) * p.lora_r + 4 * b + fq];
+            if (b < nblk) au[nip][b] = epi_mfma_up(p, true, ncol + epi_pair_col(fr, nip), b, fq);
       }
       // the residual rows of all four m-fragments of the pair are requested up front: written inside the mi loop each load
       // sat in its own basic block (the epilogue terms are run-time switches) with its wait right behind it -- 20 dependent
@@ -426,7 +399,7 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
       if (RES_AHEAD && p.res) {
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
-          rbuf[mi].u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.res) + (int64_t)row_of(mi) * p.ldr + n);
+          rbuf[mi] = epi_load<T, 8>(reinterpret_cast<const T*>(p.res) + (int64_t)row_of(mi) * p.ldr + n);
       }
 #pragma unroll
       for (int mi = 0; mi < 4; ++mi) {
@@ -439,85 +412,43 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
           acc[2 * u][mi][j] = 0.f;
           acc[2 * u + 1][mi][j] = 0.f;
         }
-        if (p.bias) {
-#pragma unroll
-          for (int j = 0; j < 8; ++j) vv[j] += bv[j];
-        }
-        if (p.rowvec) {
-          Pack8<T> b;
-          b.u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.rowvec) +
-                                                (int64_t)(m / p.rows_per_vec) * (p.ld_rowvec ? p.ld_rowvec : (int64_t)p.N) + n);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) vv[j] += to_f(b.e[j]);
-        }
+        if (p.bias) epi_add<8>(vv, bv);
+        if (p.rowvec) epi_add<T, 8>(vv, reinterpret_cast<const T*>(p.rowvec) + epi_rowvec_offset(p, m) + n);
         if (lora_tile && (!mix || mi == 3)) {  // (wave-uniform)
           const bool on = m >= p.lora_row0;
           if (lora_mfma) {
             f32x4 d0 = f32x4{0.f, 0.f, 0.f, 0.f}, d1 = d0;
-            const float* xr = p.lora_xa + (int64_t)(on ? m - p.lora_row0 : 0) * p.ld_xa + xoff_t + fq;
+            const float* xr = epi_mfma_xa(p, m, on, xoff_t, fq);
 #pragma unroll
             for (int b = 0; b < 4; ++b)
               if (b < nblk) {
-                const float bx = on ? xr[4 * b] : 0.f;  // B operand: lane (k = lane >> 4, j = lane & 15) holds xa[row j][4 blk + k]
-                d0 = __builtin_amdgcn_mfma_f32_16x16x4f32(au[0][b], bx, d0, 0, 0, 0);
-                d1 = __builtin_amdgcn_mfma_f32_16x16x4f32(au[1][b], bx, d1, 0, 0, 0);
+                const float bx = on ? xr[4 * b] : 0.f;
+                d0 = epi_mfma_block(au[0][b], bx, d0);
+                d1 = epi_mfma_block(au[1][b], bx, d1);
               }
             if (on) {
-#pragma unroll
-              for (int j = 0; j < 4; ++j) {
-                vv[j] = __builtin_fmaf(d0[j], p.lora_scale, vv[j]);
-                vv[4 + j] = __builtin_fmaf(d1[j], p.lora_scale, vv[4 + j]);
-              }
+              epi_add_delta(vv, d0, p.lora_scale);
+              epi_add_delta(vv + 4, d1, p.lora_scale);
             }
           } else if (on) {
-            const float* xrow0 = p.lora_xa + (int64_t)(m - p.lora_row0) * p.ld_xa;
-            if (p.up_sn == 1 && (p.up_sq & 3) == 0) {  // dX form: "up" is lora_down [r, K] read along K
-              const float* xrow = xrow0 + (p.lora_seg ? (n / p.lora_seg) * p.lora_r : 0);
-              float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-              for (int r = 0; r < p.lora_r; ++r) {
-                const float xq = xrow[r];
-                const float* ar = p.lora_up + (int64_t)r * p.up_sq + n;
-                const f32x4 a0 = *reinterpret_cast<const f32x4*>(ar), a1 = *reinterpret_cast<const f32x4*>(ar + 4);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                  d[j] = __builtin_fmaf(xq, a0[j], d[j]);
-                  d[4 + j] = __builtin_fmaf(xq, a1[j], d[4 + j]);
-                }
-              }
-#pragma unroll
-              for (int j = 0; j < 8; ++j) vv[j] = __builtin_fmaf(d[j], p.lora_scale, vv[j]);
-            } else {
-#pragma unroll
-              for (int j = 0; j < 8; ++j) {
-                const float* xr = xrow0 + (p.lora_seg ? ((n + j) / p.lora_seg) * p.lora_r : 0);
-                const float* up = p.lora_up + (int64_t)(n + j) * p.up_sn;
-                float d = 0.f;
-                for (int r = 0; r < p.lora_r; ++r) d = __builtin_fmaf(xr[r], up[r * p.up_sq], d);
-                vv[j] = __builtin_fmaf(d, p.lora_scale, vv[j]);
-              }
-            }
+            // (the column index goes in through an opaque copy: otherwise hipcc keeps the eight columns' 64-bit operand
+            // offsets live across the pair's four rows instead of re-deriving them per row, and the dense and up-sampling
+            // modes, 248-250 registers without that, spill 3-4)
+            int nq = n;
+            asm volatile("" : "+v"(nq));
+            epi_lora<8, true, false>(vv, p, m, nq);
           }
         }
         if (p.res) {
-          if constexpr (!RES_AHEAD)
-            rbuf[mi].u = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
-#pragma unroll
-          for (int j = 0; j < 8; ++j) vv[j] += to_f(rbuf[mi].e[j]);
+          if constexpr (!RES_AHEAD) rbuf[mi] = epi_load<T, 8>(reinterpret_cast<const T*>(p.res) + (int64_t)m * p.ldr + n);
+          epi_add<T, 8>(vv, rbuf[mi]);
         }
-        if (p.out_f32) {
-          float* op = reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n;
-          *reinterpret_cast<f32x4*>(op) = f32x4{vv[0], vv[1], vv[2], vv[3]};
-          *reinterpret_cast<f32x4*>(op + 4) = f32x4{vv[4], vv[5], vv[6], vv[7]};
-        } else {
-          Pack8<T> o;
-#pragma unroll
-          for (int j = 0; j < 8; ++j) o.e[j] = from_f<T>(vv[j]);
-          *reinterpret_cast<u32x4*>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n) = o.u;
-        }
+        if (p.out_f32) epi_store_f32<8>(reinterpret_cast<float*>(p.C) + (int64_t)m * p.ldc + n, vv);
+        else epi_store<T, 8>(reinterpret_cast<T*>(p.C) + (int64_t)m * p.ldc + n, vv);
       }
     };
-    // fused GEGLU (bias only; same arithmetic as gemm2 / gemm3: the projection is rounded to 16 bits first, the gate is
-    // applied to the rounded values): 8-byte stores of 4 consecutive columns
+    // fused GEGLU (bias only; geglu_gate of gemm_epilogue.h, as gemm2 / gemm3), in registers: 8-byte stores of 4
+    // consecutive columns
     auto epilogue_geglu = [&](auto Uc) {
       constexpr int u = decltype(Uc)::value;
       const int hc = (bn0 >> 1) + wc * 80 + u * 16 + fq * 4;  // hidden column; its gate is column nhalf + hc
@@ -548,7 +479,7 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
           }
           h.e[j] = from_f<T>(vh);
           g.e[j] = from_f<T>(vg);
-          o.e[j] = from_f<T>(to_f(h.e[j]) * gelu_f(to_f(g.e[j])));
+          o.e[j] = geglu_gate<T>(h.e[j], g.e[j]);
         }
         *reinterpret_cast<u32x2*>(gout + (int64_t)m * nhalf + hc) = o.u;
         if (m >= p.geglu_row0) {  // projection kept only for the rows that will be differentiated
@@ -594,33 +525,24 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
   }
 }
 
-template <typename T, int MODE>
-int launch_t(const GemmParams& p, hipStream_t stream) {
-  // per device (one bit per ordinal, set once under a mutex): the attribute belongs to the function ON the current
-  // device, and engines on two devices / two host threads may share this process; the persistent grid is the device's
-  // CU count, read from the device instead of assumed
+// CU count of the current device, looked up once per device
+int device_cu_count() {
   static std::mutex mu;
-  static uint64_t attr_done = 0;
   static int cus[64] = {0};
   int dev = 0;
-  SMI_HIP(hipGetDevice(&dev));
-  int ncu = 256;
-  {
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev < 0 || dev >= 64 || !((attr_done >> dev) & 1)) {
-      SMI_HIP(hipFuncSetAttribute((const void*)gemm_5ph_kernel<T, MODE>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  SMEM4));
-      int n = 0;
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      if (dev >= 0 && dev < 64) {
-        cus[dev] = n;
-        attr_done |= 1ull << dev;
-      }
-      ncu = n;
-    } else {
-      ncu = cus[dev];
-    }
-  }
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+  std::lock_guard<std::mutex> lock(mu);
+  if (cus[dev] <= 0 &&
+      (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus[dev] <= 0))
+    cus[dev] = 256;
+  return cus[dev];
+}
+
+template <typename T, int MODE>
+int launch_t(const GemmParams& p, hipStream_t stream) {
+  static DynLdsOnce once;  // (per instantiation, per device)
+  if (int rc = once.set((const void*)gemm_5ph_kernel<T, MODE>, SMEM4)) return rc;
+  const int ncu = device_cu_count();  // the persistent grid is the device's CU count, read from the device
   const int ntiles = (p.M / BM) * (p.N / BN);
   const int grid = ntiles < ncu ? ntiles : ncu;
   hipLaunchKernelGGL((gemm_5ph_kernel<T, MODE>), dim3(grid), dim3(512), SMEM4, stream, p);
@@ -629,8 +551,6 @@ int launch_t(const GemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-
-bool gemm2_supported(const GemmParams& p);
 
 // dense GEMMs and plain 3x3 convs on whole 256 x 320 tiles
 bool gemm4_supported(const GemmParams& p) {

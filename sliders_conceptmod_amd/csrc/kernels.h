@@ -163,6 +163,18 @@ enum class GemmTile {
   V1,            // register-staged kernel: the fallback for operands gemm2 cannot take
 };
 int launch_gemm2(const GemmParams& p, GemmTile tile, hipStream_t stream);  // the gemm2 tiles only
+// what each generation can take, and its launcher (launch_gemm and the tile tuner choose among them; gemm.hip)
+bool gemm2_supported(const GemmParams& p);        // 16-byte alignment / multiple-of-8 layout of the LDS-DMA kernels
+bool gemm2_geglu_supported(const GemmParams& p);  // ... with the fused GEGLU epilogue
+bool gemm3_supported(const GemmParams& p);
+bool gemm4_supported(const GemmParams& p);
+int launch_gemm3(const GemmParams& p, hipStream_t stream);
+int launch_gemm4(const GemmParams& p, hipStream_t stream);
+int launch_v1(const GemmParams& p, hipStream_t stream);  // register-staged kernel: operands gemm2 cannot take, SMI_GEMM=v1
+// Test entry (smi_op_gemm_epilogue): launch p on the tile with tuner code `tile_code` (0: launch_gemm's own choice) where
+// that tile can take it, else on what fit_tile puts in its place; ksplit > 1: split-K in that many slices with the tile as
+// the slice kernel.  *ran_code receives the code of the tile that actually ran (0 for launch_gemm's own choice).
+int launch_gemm_on_tile(const GemmParams& p, int tile_code, int ksplit, int* ran_code, hipStream_t stream);
 // Scratch for split-K partial sums (fp32 slabs), set by whoever owns memory (the engine, per call; tests through
 // smi_op_gemm_scratch) for the calling host thread; without it launch_gemm never splits.  Launches that use it are ordered
 // on their stream, so one buffer serves every launch of a pass.

@@ -463,7 +463,9 @@ def test_euler_a_step_draws_its_noise_on_the_device_when_asked():
 
 def test_gemm_generations_are_bit_identical_per_epilogue_class():
     """The tile autotuner (csrc/gemm.hip) may serve a (shape, epilogue) key with any kernel generation / tile layout;
-    that is only sound while they all produce the SAME BITS.  One op per key class -- full LoRA epilogue (bias + residual
+    that is only sound while they all produce the SAME BITS -- which they do because the epilogue arithmetic has ONE
+    definition, csrc/gemm_epilogue.h, that every generation calls (tests/test_gemm_epilogue_gpu.py checks each term on each
+    tile at kernel level).  One op per key class -- full LoRA epilogue (bias + residual
     + rank-r delta, also in the batched-pass form with the delta on the last quarter of the rows), fp32 output, fused
     GEGLU, 3x3 conv -- hashed in separate processes under every SMI_GEMM override.  "5ph" is the 256 x 320
     persistent kernel (gemm4.hip): its delta comes off the fp32 MFMA and must equal the VALU fmaf chain of the others."""
