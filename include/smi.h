@@ -272,6 +272,34 @@ int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat
 int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
                            float* d_lora_up_flat);
 
+/* ---- gradient with respect to the context (null-text inversion optimises the unconditional embedding) -----------------
+ * Replaces `loss.backward()` reaching `uncond_embeddings` through `unet(latent, t, encoder_hidden_states=uncond_embeddings)`
+ * (demo_image_editing.ipynb, NullInversion.null_optimization).
+ * The backward then needs transposed copies of every cross-attention to_k|to_v weight and a larger saved-pass arena
+ * (gradients exist from the first cross-attention block on, not from the first adapted layer).  Both live in ONE extra
+ * caller-owned buffer, so an engine that never asks keeps the sizes smi_weights_bytes / smi_arena_bytes report today:
+ *   smi_unet_ctx_grad_bytes   bytes of that buffer for a shape (same arguments as smi_arena_bytes)
+ *   smi_unet_ctx_grad_attach  packs the transposed weights into `buffer` and moves the saved-pass arena there, for the
+ *                             engine's CURRENT shape.  It drops a saved forward.  The buffer must outlive its use;
+ *                             smi_replan detaches it (attach again, with a buffer sized for the new shape).
+ *   smi_unet_ctx_grad         on != 0: every following save_for_backward forward also differentiates the context of its
+ *                             adapted samples; 0 (the state of a new engine): forwards are exactly what they were.
+ *                             Turning it on without an attached buffer is an error.
+ *   smi_unet_backward_ctx     smi_unet_backward of such a pass that also WRITES (not +=) d(loss)/d(ctx) of the adapted
+ *                             samples to d_ctx_out, fp32 [n_adapted, ctx_len, cross_attention_dim], with the per-sample
+ *                             loss scale already divided out.  d_lora_down_flat / d_lora_up_flat may both be NULL when
+ *                             the saved pass ran without an adaptor (n_sites == 0, NULL parameters or multiplier 0).
+ * Without LoRA on to_k / to_v every block writes dK|dV into its columns of one gradient of the grouped k|v projection and
+ * d_ctx is one split-K GEMM against the transposed grouped weight; with it, each block's term is a GEMM of its own and the
+ * terms are summed in fp32.  DoRA on to_k / to_v is refused.  smi_unet_backward on such a pass still works (no d_ctx);
+ * smi_unet_backward_tail refuses it: `n_live` does not extend to d_ctx. */
+int smi_unet_ctx_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                            int batch_adapted, int h, int w, int ctx_len, size_t* bytes);
+int smi_unet_ctx_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes);
+int smi_unet_ctx_grad(smi_engine* e, int on);
+int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
+                          float* d_ctx_out);
+
 /* Per-kernel-class timing, measured with HIP events recorded on the engine's stream around every launch
  * (measurement aid for bench.py's roofline; off by default, adds two event records per launch when on).
  * smi_profile_read synchronises with the host and returns, per class, the summed device time (ms), the algorithmic
@@ -295,6 +323,14 @@ int smi_cfg_combine(const float* eps_2n, float* out_n, int64_t n_half, float gui
  * d(loss)/d(target).  scratch: >= 256 floats. */
 int smi_slider_loss(const float* target, const float* positive, const float* neutral, const float* negative,
                     float sign_eta, int64_t n, float* loss_out, float* dtarget, float* scratch, void* stream);
+
+/* One inner step of null-text optimisation after the UNet call (demo_image_editing.ipynb, null_optimization):
+ *   eps = eps_u + g (eps_c - eps_u);  x_prev = c_x x_t + c_eps eps  (DDIM prev_step, coefficients from the host as for
+ *   smi_sched_step);  loss_out[0] = mean((x_prev - target)^2);  d_eps_u = (1 - g) c_eps (2 / n) (x_prev - target).
+ * All tensors fp32 of n elements; d_eps_u may be NULL.  The sum runs in a fixed order (bit-reproducible run to run).
+ * scratch: >= 256 floats. */
+int smi_nulltext_loss(const float* eps_u, const float* eps_c, const float* x_t, const float* target, float guidance_scale,
+                      float c_x, float c_eps, int64_t n, float* loss_out, float* d_eps_u, float* scratch, void* stream);
 
 /* torch.nn.utils.clip_grad_norm_(params, max_norm) (train_lora_xl.py:349; max_norm <= 0: no clipping) followed by
  * one torch.optim.AdamW step (train_lora_xl.py:104,350; train_util.py:1040) over flat fp32 buffers.
@@ -439,6 +475,9 @@ int smi_op_lora_prep(int dtype, const smi_lora_prep_site* sites, int n_sites, co
  * min_out[0] = min_j scale, min_out[1] = 1 / min, min_out[2 + j] = min / scale_out[j]. */
 int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, float* scale_out, int inv_off,
                       float* min_out, void* stream);
+/* dst[i] (T) = src[i] (fp32), n % 8 == 0: the 16-bit operand of an fp32 master tensor (the embedding null-text inversion
+ * optimises is kept in fp32 and handed to smi_unet_forward in T) */
+int smi_op_cast_f32(int dtype, const float* src, void* dst, int64_t n, void* stream);
 /* x[m][0..n) (fp32, row stride ld) *= row_mul[m / rows_per_mul] */
 int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream);
 

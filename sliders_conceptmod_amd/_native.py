@@ -124,6 +124,12 @@ _SIGS = {
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smi_unet_backward_tail": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "smi_unet_ctx_grad_bytes": (C.c_int, [C.POINTER(UNetConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_unet_ctx_grad_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "smi_unet_ctx_grad": (C.c_int, [C.c_void_p, C.c_int]),
+    "smi_unet_backward_ctx": (C.c_int, [C.c_void_p] * 5),
+    "smi_nulltext_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_int64] + [C.c_void_p] * 4),
     "smi_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "smi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
                                    C.POINTER(C.c_int64)]),
@@ -166,6 +172,7 @@ _SIGS = {
     "smi_op_transpose_scaled": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                           C.c_void_p, C.c_int, C.c_void_p]),
     "smi_op_grad_scale": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "smi_op_cast_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "smi_op_row_scale_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
 }
 
@@ -319,6 +326,8 @@ class Engine(_EngineBase):
         self.stream = torch.cuda.current_stream().cuda_stream
         self._home = (batch, self.batch_adapted, h, w, ctx_len)  # the shape the creation workspace was sized for
         self._plans = {}                                         # shape -> arena tensor (LRU, most recent last)
+        self._ctx_buf = None     # smi_unet_ctx_grad_attach buffer of the current shape (None: not attached)
+        self._ctx_on = False
 
     def plan(self, batch: int, batch_adapted: int, h: int, w: int, ctx_len: int):
         """Make (batch, batch_adapted, h, w, ctx_len) the engine's current shape (no-op when it already is)."""
@@ -338,6 +347,31 @@ class Engine(_EngineBase):
         check(lib().smi_replan(self.handle, batch, batch_adapted, h, w, ctx_len, ptr(arena),
                                0 if arena is None else arena.numel()), "smi_replan")
         self.batch, self.batch_adapted, self.h, self.w, self.ctx_len = want
+        self._ctx_buf, self._ctx_on = None, False  # smi_replan detaches the context-gradient buffer
+
+    def set_ctx_grad(self, on: bool):
+        """Saving forwards from here on also differentiate the context of their adapted samples (smi_unet_ctx_grad); the
+        extra buffer (transposed k|v weights + a larger saved-pass arena) is attached on first use for the current shape."""
+        on = bool(on)
+        if on and self._ctx_buf is None:
+            sarr, _keep = make_sites(self.sites)
+            out = C.c_size_t(0)
+            check(lib().smi_unet_ctx_grad_bytes(C.byref(self.cfg_c), sarr, len(self.sites), self.batch, self.batch_adapted,
+                                                self.h, self.w, self.ctx_len, C.byref(out)), "smi_unet_ctx_grad_bytes")
+            buf = torch.empty(out.value, dtype=torch.uint8, device=self.workspace.device)
+            with torch.cuda.device(self.workspace.device):
+                check(lib().smi_unet_ctx_grad_attach(self.handle, ptr(buf), out.value), "smi_unet_ctx_grad_attach")
+            self._ctx_buf = buf
+        if on != self._ctx_on:
+            check(lib().smi_unet_ctx_grad(self.handle, int(on)), "smi_unet_ctx_grad")
+            self._ctx_on = on
+
+    def backward_ctx(self, d_eps: torch.Tensor, d_down: Optional[torch.Tensor], d_up: Optional[torch.Tensor],
+                     d_ctx: torch.Tensor):
+        """smi_unet_backward_ctx: the backward of a pass saved under set_ctx_grad(True); WRITES d(loss)/d(ctx) of the
+        adapted samples into d_ctx (fp32 [n_adapted, ctx_len, D]); d_down / d_up may be None without an adaptor."""
+        check(lib().smi_unet_backward_ctx(self.handle, ptr(d_eps), ptr(d_down), ptr(d_up), ptr(d_ctx)),
+              "smi_unet_backward_ctx")
 
     def stats(self) -> dict:
         out = (C.c_int64 * 4)()
@@ -348,13 +382,14 @@ class Engine(_EngineBase):
         return self.stats()["tape_generation"] if self.handle else 0
 
     def forward(self, sample: torch.Tensor, timestep: float, ctx: torch.Tensor, text_embeds, time_ids, lora_down,
-                lora_up, multiplier, save: bool, n_adapted: Optional[int] = None) -> torch.Tensor:
+                lora_up, multiplier, save: bool, n_adapted: Optional[int] = None,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """n_adapted: the LAST n_adapted samples get the LoRA delta and are differentiated (default: all).
         `multiplier`: one float, or a sequence of n_adapted floats (one adaptor multiplier per adapted sample,
-        smi_unet_forward_multi)."""
+        smi_unet_forward_multi).  `out`: an fp32 tensor of the sample's shape to write eps into (default: a new one)."""
         n = sample.shape[0]
         na = min(n, self.batch_adapted) if n_adapted is None else n_adapted
-        eps = torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
+        eps = out if out is not None else torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
         if isinstance(multiplier, (list, tuple)):
             if len(multiplier) != na:
                 raise SmiError(f"{len(multiplier)} multipliers for {na} adapted samples")
@@ -389,6 +424,27 @@ class Engine(_EngineBase):
         check(lib().smi_profile_read(self.handle, ms, fl, by, la), "smi_profile_read")
         return {k: {"ms": ms[i], "flops": fl[i], "bytes": by[i], "launches": la[i]}
                 for i, k in enumerate(self.PROF_CLASSES)}
+
+
+def nulltext_loss(eps_u, eps_c, x_t, target, guidance_scale: float, c_x: float, c_eps: float, loss_out, d_eps_u, scratch):
+    """smi_nulltext_loss on caller-owned fp32 tensors (loss_out [1], d_eps_u like eps_u or None, scratch >= 256 floats):
+    no allocation, no synchronisation."""
+    check(lib().smi_nulltext_loss(ptr(eps_u), ptr(eps_c), ptr(x_t), ptr(target), float(guidance_scale), float(c_x),
+                                  float(c_eps), eps_u.numel(), ptr(loss_out), ptr(d_eps_u), ptr(scratch), stream_ptr()),
+          "smi_nulltext_loss")
+
+
+def cast_f32(src: torch.Tensor, dst: torch.Tensor):
+    """smi_op_cast_f32: dst (float16 / bfloat16) = src (fp32), same number of elements, a multiple of 8."""
+    check(lib().smi_op_cast_f32(DTYPE_CODE[dst.dtype], ptr(src), ptr(dst), src.numel(), stream_ptr()), "smi_op_cast_f32")
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, beta1=0.9, beta2=0.999, eps=1e-8):
+    """One torch.optim.Adam step on flat fp32 tensors: smi_clip_adamw with weight_decay 0 and no clipping.
+    scratch: >= 1025 floats."""
+    check(lib().smi_clip_adamw(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
+                               float(beta1), float(beta2), float(eps), 0.0, int(step), 0.0, ptr(scratch), stream_ptr()),
+          "smi_clip_adamw")
 
 
 def _weight_table(state: dict, dtype, device):

@@ -346,6 +346,33 @@ __global__ void sum_finalize_kernel(const float* __restrict__ partial, int np, f
   }
 }
 
+// null-text inner step after the UNet call: guided eps, DDIM prev_step, MSE against the target latent and d(loss)/d(eps_u).
+// One workgroup (gridDim.x == 1) writes the loss itself; more write one partial each for sum_finalize_kernel.
+__global__ __launch_bounds__(256) void nulltext_loss_kernel(const float* __restrict__ eu, const float* __restrict__ ec,
+                                                            const float* __restrict__ xt, const float* __restrict__ tg,
+                                                            float g, float cx, float ce, int64_t n,
+                                                            float* __restrict__ d_eu, float* __restrict__ partial,
+                                                            float* __restrict__ loss_out) {
+  __shared__ float sh[4];
+  float acc = 0.f;
+  const float k = (1.f - g) * ce * (2.f / (float)n);
+  GSTRIDE(i, n) {
+    const float u = eu[i];
+    const float eps = u + g * (ec[i] - u);
+    const float d = (cx * xt[i] + ce * eps) - tg[i];
+    acc += d * d;
+    if (d_eu) d_eu[i] = k * d;
+  }
+  acc = wave_sum(acc);
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float s = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    if (gridDim.x == 1) loss_out[0] = s * (1.f / (float)n);
+    else partial[blockIdx.x] = s;
+  }
+}
+
 __global__ void axpby_kernel(float* __restrict__ y, const float* __restrict__ x, float a, float b, int64_t n) {
   GSTRIDE(i, n) y[i] = a * x[i] + b * y[i];
 }
@@ -537,6 +564,18 @@ int launch_slider_loss(const float* target, const float* positive, const float* 
   hipLaunchKernelGGL(slider_loss_partial_kernel, dim3(np), dim3(256), 0, stream, target, positive, neutral, negative,
                      sign_eta, n, dtarget, scratch);
   hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, stream, scratch, np, 1.f / (float)n, loss_out);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+// scratch: >= 256 floats.  Up to 65536 elements (a 4 x 128 x 128 latent) one workgroup does everything in ONE launch -- the
+// inner loop of null-text optimisation runs at 4 x 64 x 64; beyond, block partials and the ordered sum of smi_slider_loss
+int launch_nulltext_loss(const float* eps_u, const float* eps_c, const float* x_t, const float* target, float g, float c_x,
+                         float c_eps, int64_t n, float* loss_out, float* d_eps_u, float* scratch, hipStream_t stream) {
+  SMI_CHECK(eps_u && eps_c && x_t && target && loss_out && scratch && n > 0, "nulltext_loss: bad arguments");
+  const int np = n <= 65536 ? 1 : (ew_grid(n) > 256 ? 256 : ew_grid(n));
+  hipLaunchKernelGGL(nulltext_loss_kernel, dim3(np), dim3(256), 0, stream, eps_u, eps_c, x_t, target, g, c_x, c_eps, n,
+                     d_eps_u, scratch, loss_out);
+  if (np > 1) hipLaunchKernelGGL(sum_finalize_kernel, dim3(1), dim3(64), 0, stream, scratch, np, 1.f / (float)n, loss_out);
   SMI_HIP(hipGetLastError());
   return 0;
 }

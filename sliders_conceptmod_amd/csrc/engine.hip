@@ -132,6 +132,7 @@ struct Ten {
   // of the FORWARD only (xa)
   int64_t bskip = 0;
   bool ng = false;
+  bool f32g = false;  // the context of a pass that differentiates it: its gradient is summed in fp32 in the caller's buffer
   float gmul = 1.f;  // the stored gradient g is gmul x the (loss-scaled) gradient; a power of two, 1 but for row vectors
 };
 
@@ -332,6 +333,29 @@ struct smi_engine {
   Lin kv_all;
   bool kv_grouped = false;
   Ten* kv_all_out = nullptr;
+  // gradient with respect to the context (smi_unet_ctx_grad_*, smi_unet_backward_ctx).  The transposed k|v weights it needs
+  // and the larger saved-pass arena live in a buffer of the caller's (`xpack` + arena 1), so that engines that never ask
+  // keep today's workspace.  ctx_cap: that buffer is attached; ctx_want: saving forwards differentiate the context;
+  // bw_ctx: the saved pass does.  d_ctx: the backward's output (fp32 [adapted rows, D]), d_ctx_written: a term is in it.
+  Arena xpack;
+  bool ctx_cap = false, ctx_want = false, bw_ctx = false;
+  float* d_ctx = nullptr;
+  bool d_ctx_written = false;
+  void build_ctx_grad() {
+    const int D = cfg.cross_attention_dim;
+    xpack.reset();
+    if (kv_grouped) {  // [D, sum N]: the K-contiguous operand of d_ctx = dKV_all W_all
+      void* t = xpack.alloc((size_t)kv_all.out * D * esz());
+      transpose_into(kv_all.W, t, kv_all.out, D, kv_all.out, 0);
+      kv_all.Wt = t;
+    } else {
+      for_each_tblock([&](TBlock& tb) {
+        void* t = xpack.alloc((size_t)tb.kv2.out * D * esz());
+        transpose_into(tb.kv2.W, t, tb.kv2.out, D, tb.kv2.out, 0);
+        tb.kv2.Wt = t;
+      });
+    }
+  }
   Lin temb_all;  // every resnet's time_emb_proj stacked (they all read silu(emb)): one GEMM per pass
   bool temb_grouped = false;
   Ten* temb_all_out = nullptr;
@@ -1188,6 +1212,21 @@ struct smi_engine {
         err = true;
         return;
       }
+      if (x->f32g) {  // the context: one term per cross-attention block, summed in fp32 in the caller's buffer
+        if (!d_ctx) return;
+        if (lon && L->dora && !dry) {
+          set_error("context gradient through a DoRA site ('%s') is not implemented", L->name.c_str());
+          err = true;
+          return;
+        }
+        float* dst = d_ctx_written ? alloc_f32((size_t)M * L->in) : d_ctx;
+        GemmParams p = gemm_nt(dtype, dy, L->out, L->Wt, dst, L->in, M, L->in, L->out).f32_out();
+        if (lon) p.with_lora_dx(dxa, L->rows_pad, bw_down + L->off_down, rtot, lscale);
+        run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), gemm_bytes(p), true, "linear d_ctx");
+        if (d_ctx_written) RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_axpby(d_ctx, dst, 1.f, 1.f, (int64_t)M * L->in, stream));
+        d_ctx_written = true;
+        return;
+      }
       const Slot gs = grad_slot(x);
       GemmParams p = gemm_nt(dtype, dy, L->out, L->Wt, gs.out, L->in, M, L->in, L->out);
       if (gs.add) p.with_res(gs.add, L->in);
@@ -1332,7 +1371,9 @@ struct smi_engine {
     p.ldo = C;
     p.lse = lse;
     RUNP(SMI_PROF_ATTN, 4.0 * nbatch * heads * (double)Nq * Nk * p.D, 0.0, launch_attn_fwd(p, stream));
-    o->ng = qkv ? qkv->ng : (q->ng || (kv && kv->ng));
+    // grouped k|v with the context differentiated: dK|dV go to this block's columns of the grouped projection's gradient
+    Ten* const kvg = (kv_ext && kv_all_out && kv_all_out->ng) ? kv_all_out : nullptr;
+    o->ng = qkv ? qkv->ng : (q->ng || (kv && kv->ng) || kvg);
     if (saving && o->ng) {
       tape.push_back([=]() {
         if (!o->g) return;
@@ -1365,6 +1406,22 @@ struct smi_engine {
             b.dV = g + (size_t)C * esz();
             b.lddk = b.lddv = 2 * C;
           }
+          if (kvg) {
+            if (!kvg->g) {  // every block writes its own columns; zeroed once in case a block's gradient never arrives
+              kvg->g = alloc_t(MA(kvg), kvg->cols);
+              if (!dry && !err) (void)hipMemsetAsync(kvg->g, 0, (size_t)MA(kvg) * kvg->cols * esz(), stream);
+            }
+            char* g = (char*)kvg->g + ((const char*)kv_ext - (const char*)kvg->p);
+            b.dK = g;
+            b.dV = g + (size_t)C * esz();
+            b.lddk = b.lddv = ld_ext;
+          }
+        }
+        // SMI_PROF_DUMP: the cross-attention backward launches that produce dK / dV get a line of their own in the table
+        if (prof_on && prof_dump && !qkv && b.dK) {
+          char tag[96];
+          snprintf(tag, sizeof(tag), "attn_bwd dK|dV%s B=%d H=%d Nq=%d Nk=%d D=%d", b.dQ ? "" : " (no dQ)", b.B, heads, Nq, Nk, b.D);
+          next_tag = tag;
         }
         RUNP(SMI_PROF_ATTN, 10.0 * b.B * heads * (double)Nq * Nk * b.D, 0.0, launch_attn_bwd(b, stream));
       });
@@ -2083,6 +2140,22 @@ struct smi_engine {
     ctx->arow0 = (int64_t)(n - n_ad) * ctx_len;
 
     if (kv_grouped) kv_all_out = linear(ctx, kv_all);
+    const bool ctx_grad = save && ctx_want && n_ad > 0;
+    if (ctx_grad) {
+      ctx->ng = true;
+      ctx->f32g = true;
+      if (kv_grouped) {  // runs after every cross-attention backward: d_ctx = dKV_all [rows, sum N] x W_all as ONE GEMM
+        Ten* kvo = kv_all_out;
+        kvo->ng = true;
+        tape.push_back([=]() {
+          if (!kvo->g || !d_ctx) return;
+          const GemmParams p =
+              gemm_nt(dtype, kvo->g, kv_all.out, kv_all.Wt, d_ctx, ctx->cols, (int)MA(ctx), ctx->cols, kv_all.out).f32_out();
+          run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), gemm_bytes(p), true, "d_ctx");
+          d_ctx_written = true;
+        });
+      }
+    }
     // (only while nothing upstream of emb is trained: the column-block views carry no gradient)
     temb_all_out = (temb_grouped && !temb_act->ng) ? linear(temb_act, temb_all) : nullptr;
 
@@ -2170,6 +2243,7 @@ struct smi_engine {
       bw_up = lora_up;
       bw_mult = mult;
       bw_samp_on = samp_on;
+      bw_ctx = ctx_grad;
       tape_valid = true;
     }
     saving = false;
@@ -2191,7 +2265,9 @@ struct smi_engine {
     tape_valid = false;
     bw_skip = 0;
   }
-  int backward(const float* d_eps, float* dd, float* du, int n_live) {
+  int backward(const float* d_eps, float* dd, float* du, int n_live, float* dctx = nullptr) {
+    d_ctx = dctx;
+    d_ctx_written = false;
     if (!tape_valid && !dry) {
       set_error("smi_unet_backward: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
       return -4;
@@ -2264,6 +2340,12 @@ struct smi_engine {
         RUNP(SMI_PROF_LORA, flops, bytes, launch_lora_wgrad_grouped(dtype, wjobs, wjobs_dev, stream));
       }
     }
+    if (d_ctx && !dry && !err) {  // the loss scale of each sample's rows divides out; no term at all: the gradient is zero
+      const int L = ctx_len, D = cfg.cross_attention_dim;
+      if (d_ctx_written) RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_row_scale_f32(d_ctx, D, n * L, D, gscale + MAXS, L, stream));
+      else (void)hipMemsetAsync(d_ctx, 0, (size_t)n * L * D * sizeof(float), stream);
+    }
+    d_ctx = nullptr;
     drop_tape();
     if (cur->overflow && !dry) {
       set_error("workspace too small for the backward (needs %zu bytes, has %zu)", cur->peak, cur->cap);
@@ -2315,13 +2397,20 @@ int setup(smi_engine* e, const smi_unet_config* cfg, const smi_weight* weights, 
 }
 
 // dry run: sizes of the three regions
+// ctx_bytes != NULL: the plan of an engine that differentiates the context -- *ctx_bytes receives the bytes of its extra
+// transposed weights and out[2] is the saved-pass arena of a forward + backward with the context gradient on
 int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int batch_adapted, int h, int w,
-         int ctx_len, size_t out[5]) {
+         int ctx_len, size_t out[5], size_t* ctx_bytes = nullptr) {
   smi_engine e;
   e.dry = true;
   setup(&e, cfg, nullptr, 0, sites, n_sites, batch, batch_adapted, h, w, ctx_len);
   e.build();
   if (e.err) return -1;
+  if (ctx_bytes) {
+    e.build_ctx_grad();
+    *ctx_bytes = align_up(e.xpack.peak, 4096);
+    e.ctx_want = true;
+  }
   out[0] = align_up(e.wpack.peak, 4096);
   e.forward(batch, batch_adapted, nullptr, 0.f, nullptr, nullptr, nullptr, false, nullptr);
   // arena 0 = [persistent | scratch 0 | scratch 1] (no-grad liveness, smi_engine::begin_block)
@@ -2329,7 +2418,8 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   out[4] = align_up(std::max(e.scr[0].peak, e.scr[1].peak), 4096);
   out[1] = out[3] + 2 * out[4];
   e.forward(batch, batch_adapted, nullptr, 0.f, nullptr, nullptr, nullptr, true, nullptr);
-  e.backward(nullptr, nullptr, nullptr, e.bw_n_ad);  // sized for the full backward: a tail backward needs less
+  // sized for the full backward: a tail backward needs less
+  e.backward(nullptr, nullptr, nullptr, e.bw_n_ad, ctx_bytes ? reinterpret_cast<float*>(16) : nullptr);
   out[2] = align_up(e.arena[1].peak, 4096);
   return e.err ? -1 : 0;
 }
@@ -2694,6 +2784,7 @@ int smi_replan(smi_engine* e, int batch, int batch_adapted, int h, int w, int ct
   e->set_arena0_regions(r[3], r[4]);
   e->tape.clear();  // the saved activations lived in the old arena
   e->tape_valid = false;
+  e->ctx_cap = e->ctx_want = false;  // the context-gradient arena was sized for the old shape: attach one for the new
   e->tens_[0].clear();
   e->tens_[1].clear();
   e->out_ten = nullptr;
@@ -2729,6 +2820,8 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
   SMI_CHECK(n_adapted >= 0 && n_adapted <= n && n_adapted <= e->max_n_ad,
             "adapted batch %d outside [0, min(%d, %d)]", n_adapted, n, e->max_n_ad);
   SMI_CHECK(!e->cfg.addition_embed || (text_embeds && time_ids), "SD-XL engine needs text_embeds and time_ids");
+  SMI_CHECK(!(save_for_backward && e->ctx_want) || e->ctx_cap,
+            "context gradient asked for, but no buffer is attached for this shape (smi_unet_ctx_grad_attach)");
   e->err = false;
   e->lora_down = lora_down_flat;
   e->lora_up = lora_up_flat;
@@ -2788,11 +2881,76 @@ int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat
   return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat, e->bw_n_ad);
 }
 
+int smi_unet_ctx_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                            int batch_adapted, int h, int w, int ctx_len, size_t* bytes) {
+  if (check_cfg(cfg)) return -1;
+  SMI_CHECK(bytes && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
+            "bad arguments");
+  size_t r[5], x = 0;
+  if (plan(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, r, &x)) return -1;
+  *bytes = x + r[2] + 2 * 4096;
+  return 0;
+}
+
+int smi_unet_ctx_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes) {
+  SMI_CHECK(e && buffer, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "smi_unet_ctx_grad_attach: only UNet engines differentiate a context");
+  size_t r[5], x = 0;
+  if (plan(&e->cfg, e->sites.data(), (int)e->sites.size(), e->max_n, e->max_n_ad, e->lat_h, e->lat_w, e->ctx_len, r, &x))
+    return -1;
+  char* base = (char*)align_up((size_t)buffer, 4096);
+  const size_t have = (size_t)((char*)buffer + buffer_bytes - base);
+  SMI_CHECK((char*)buffer + buffer_bytes >= base && x + r[2] <= have,
+            "smi_unet_ctx_grad_attach: buffer too small: need %zu bytes, got %zu", x + r[2] + 2 * 4096, buffer_bytes);
+  e->err = false;
+  e->xpack = Arena();
+  e->xpack.base = base;
+  e->xpack.cap = x;
+  e->build_ctx_grad();
+  SMI_HIP(hipGetLastError());
+  SMI_CHECK(!e->err && !e->xpack.overflow, "smi_unet_ctx_grad_attach: packing the transposed k|v weights failed");
+  e->arena[1] = Arena();
+  e->arena[1].base = base + x;
+  e->arena[1].cap = r[2];
+  e->wjobs_uploaded.clear();
+  e->tape.clear();  // the saved activations lived in the old arena
+  e->tape_valid = false;
+  e->tens_[1].clear();
+  e->out_ten = nullptr;
+  e->ctx_cap = true;
+  return 0;
+}
+
+int smi_unet_ctx_grad(smi_engine* e, int on) {
+  SMI_CHECK(e != nullptr, "NULL argument");
+  SMI_CHECK(!on || e->ctx_cap, "smi_unet_ctx_grad: no context-gradient buffer is attached for the engine's current shape "
+                               "(smi_unet_ctx_grad_attach; smi_replan detaches it)");
+  e->ctx_want = on != 0;
+  return 0;
+}
+
+int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
+                          float* d_ctx_out) {
+  SMI_CHECK(e && d_eps && d_ctx_out, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
+  SMI_CHECK(e->tape_valid, "smi_unet_backward_ctx: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  SMI_CHECK(e->bw_ctx, "smi_unet_backward_ctx: the saved pass does not differentiate the context (smi_unet_ctx_grad(e, 1) "
+                       "before the saving forward)");
+  const bool adapted = e->bw_down && e->bw_up && e->bw_mult != 0.f && !e->sites.empty();
+  SMI_CHECK(!adapted || (d_lora_down_flat && d_lora_up_flat),
+            "smi_unet_backward_ctx: the saved pass ran with the adaptor on: its gradient buffers are required");
+  e->err = false;
+  GemmScratchScope scratch(e->splitk_ws, smi_engine::SPLITK_WS_BYTES);
+  return e->backward(d_eps, d_lora_down_flat, d_lora_up_flat, e->bw_n_ad, d_ctx_out);
+}
+
 int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
                            float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps_live && d_lora_down_flat && d_lora_up_flat, "NULL argument");
   SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
   SMI_CHECK(e->tape_valid, "smi_unet_backward_tail: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  SMI_CHECK(!e->bw_ctx, "smi_unet_backward_tail: the saved pass differentiates the context; a tail backward is not offered "
+                        "there (use smi_unet_backward_ctx)");
   SMI_CHECK(n_live >= 1 && n_live <= e->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
             n_live, e->bw_n_ad);
   e->err = false;
@@ -2842,6 +3000,11 @@ int smi_slider_loss(const float* target, const float* positive, const float* neu
                     float sign_eta, int64_t n, float* loss_out, float* dtarget, float* scratch, void* stream) {
   return launch_slider_loss(target, positive, neutral, negative, sign_eta, n, loss_out, dtarget, scratch,
                             (hipStream_t)stream);
+}
+int smi_nulltext_loss(const float* eps_u, const float* eps_c, const float* x_t, const float* target, float guidance_scale,
+                      float c_x, float c_eps, int64_t n, float* loss_out, float* d_eps_u, float* scratch, void* stream) {
+  return launch_nulltext_loss(eps_u, eps_c, x_t, target, guidance_scale, c_x, c_eps, n, loss_out, d_eps_u, scratch,
+                              (hipStream_t)stream);
 }
 int smi_clip_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
                    float beta1, float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch,
@@ -3148,6 +3311,10 @@ int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, flo
   int rc = launch_grad_scale(d_eps, n_samples, per_sample, scale_out, inv_off, (hipStream_t)stream);
   if (rc) return rc;
   return launch_scale_min(scale_out, n_samples, min_out, (hipStream_t)stream);
+}
+int smi_op_cast_f32(int dtype, const float* src, void* dst, int64_t n, void* stream) {
+  SMI_CHECK(src && dst && n > 0 && n % 8 == 0, "smi_op_cast_f32: bad arguments (n must be a multiple of 8)");
+  return launch_f32_to_padded(dtype, src, 8, 8, dst, 8, n / 8, 1.f, (hipStream_t)stream);
 }
 int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream) {
   return launch_row_scale_f32(x, ld, m, n, row_mul, rows_per_mul, (hipStream_t)stream);

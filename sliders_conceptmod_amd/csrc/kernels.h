@@ -384,6 +384,10 @@ int launch_cfg_combine(const float* eps2 /*[2B,...]*/, float* out /*[B,...]*/, i
 int launch_slider_loss(const float* target, const float* positive, const float* neutral, const float* negative,
                        float sign_eta, int64_t n, float* loss_out, float* dtarget, float* scratch,
                        hipStream_t stream);
+// null-text inner step: loss = mean((c_x x_t + c_eps (eps_u + g (eps_c - eps_u)) - target)^2), d_eps_u (may be NULL) =
+// d(loss)/d(eps_u); fixed-order sum; scratch >= 256 floats
+int launch_nulltext_loss(const float* eps_u, const float* eps_c, const float* x_t, const float* target, float g, float c_x,
+                         float c_eps, int64_t n, float* loss_out, float* d_eps_u, float* scratch, hipStream_t stream);
 int launch_axpby(float* y, const float* x, float a, float b, int64_t n, hipStream_t stream);  // y = a*x + b*y
 // global-norm clip (max_norm<=0: none) + AdamW on flat f32 buffers; state m,v; step>=1
 int launch_clip_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

@@ -78,15 +78,25 @@ def diffusion_xl(unet, scheduler, latents, text_embeddings, add_text_embeddings,
 
 @torch.no_grad()
 def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, scale: float, start_noise: int,
-                         guidance_scale: float = 7.5, num_inference_steps: int = 50, added_cond=None):
+                         guidance_scale: float = 7.5, num_inference_steps: int = 50, added_cond=None,
+                         uncond_per_step=None):
     """The inference-side slider loop of the eval scripts (eval-scripts/generate_images_sd1.py:170-190,
     generate_images_xl.py:327-343): denoise from `latents` (already x init_noise_sigma) with classifier-free guidance, the
     adaptor OFF (set_lora_slider(0)) while t > start_noise and at `scale` afterwards, every UNet call inside `with network`.
     `text_embeddings` = cat([uncond, cond]) as there; `added_cond` = (add_text_embeddings, add_time_ids) for SD-XL.
+    `uncond_per_step` (real-image editing, demo_image_editing.ipynb): one unconditional embedding [1, L, D] per step, as
+    null-text inversion returns them -- step k runs on cat([uncond_per_step[k] expanded to the batch, cond]), `cond` being
+    the second half of `text_embeddings`; None: `text_embeddings` as given at every step.
     Returns the final latents (decoding them is the VAE decoder's job, outside this package)."""
     scheduler.set_timesteps(num_inference_steps)
-    for t in scheduler.timesteps:
+    if uncond_per_step is not None and len(uncond_per_step) != len(scheduler.timesteps):
+        raise ValueError(f"{len(uncond_per_step)} unconditional embeddings for {len(scheduler.timesteps)} steps")
+    cond = text_embeddings.chunk(2)[1]
+    for k, t in enumerate(scheduler.timesteps):
         network.set_lora_slider(scale=0 if t > start_noise else scale)
+        if uncond_per_step is not None:
+            u = uncond_per_step[k].to(cond.device, cond.dtype)
+            text_embeddings = torch.cat([u.expand(*cond.shape), cond])
         with network:
             if added_cond is None:
                 noise_pred = predict_noise(unet, scheduler, t, latents, text_embeddings, guidance_scale=guidance_scale)

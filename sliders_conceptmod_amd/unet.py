@@ -201,22 +201,26 @@ class _UNetFn(torch.autograd.Function):
     """Autograd bookkeeping only: forward and backward are single calls into the HIP engine."""
 
     @staticmethod
-    def forward(ctx, save, engine, sample, timestep, ehs, text_embeds, time_ids, flat, n_down, multiplier):
-        # `save` is decided by the caller: grad mode is always off inside Function.forward
+    def forward(ctx, save, engine, sample, timestep, ehs, text_embeds, time_ids, flat, n_down, multiplier, ctx_grad):
+        # `save` / `ctx_grad` are decided by the caller: grad mode is always off inside Function.forward
         down = up = None
         if flat is not None:
             down, up = flat[:n_down], flat[n_down:]
-        eps = engine.forward(sample, timestep, ehs, text_embeds, time_ids, down, up, multiplier, save)
+        ehs_t = ehs.detach().to(engine.dtype).contiguous()  # the engine's operand; the gradient goes back to `ehs` in fp32
+        engine.set_ctx_grad(bool(save and ctx_grad))
+        eps = engine.forward(sample, timestep, ehs_t, text_embeds, time_ids, down, up, multiplier, save)
         ctx.engine = engine if save else None
         ctx.gen = engine.tape_generation() if save else 0
         ctx.n_down = n_down
-        ctx.keep = (sample, ehs, text_embeds, time_ids, flat)  # borrowed by the engine until backward
+        ctx.ctx_grad = bool(save and ctx_grad)
+        ctx.ehs_meta = (tuple(ehs.shape), ehs.dtype)
+        ctx.keep = (sample, ehs_t, text_embeds, time_ids, flat)  # borrowed by the engine until backward
         return eps
 
     @staticmethod
     def backward(ctx, d_eps):
         if ctx.engine is None:
-            return (None,) * 10
+            return (None,) * 11
         flat = ctx.keep[4]
         # the engine holds ONE tape: a later saved forward, a change of shape (replan) or an earlier backward drops it
         if ctx.engine.tape_generation() != ctx.gen:
@@ -224,9 +228,17 @@ class _UNetFn(torch.autograd.Function):
                 "backward through a UNet output whose saved activations are gone: the engine keeps the tape of the LAST "
                 "grad-enabled forward only (a later grad-enabled forward, a call at another resolution / batch, or a "
                 "previous backward released it). Call backward before the next grad-enabled UNet call.")
-        g = torch.zeros_like(flat)
-        ctx.engine.backward(d_eps.contiguous().float(), g[:ctx.n_down], g[ctx.n_down:])
-        return None, None, None, None, None, None, None, g, None, None
+        g = torch.zeros_like(flat) if flat is not None else None
+        gd, gu = (g[:ctx.n_down], g[ctx.n_down:]) if g is not None else (None, None)
+        g_ehs = None
+        if ctx.ctx_grad:
+            shape, dt = ctx.ehs_meta
+            d_ctx = torch.empty(shape, dtype=torch.float32, device=d_eps.device)
+            ctx.engine.backward_ctx(d_eps.contiguous().float(), gd, gu, d_ctx)
+            g_ehs = d_ctx.to(dt)
+        else:
+            ctx.engine.backward(d_eps.contiguous().float(), gd, gu)
+        return None, None, None, None, g_ehs, None, None, g, None, None, None
 
 
 class UNet2DConditionModel(nn.Module):
@@ -316,7 +328,7 @@ class UNet2DConditionModel(nn.Module):
 
     def forward(self, sample, timestep, encoder_hidden_states, added_cond_kwargs=None, **_):
         n, _c, h, w = sample.shape
-        ehs = encoder_hidden_states.to(self.dtype).contiguous()
+        ehs = encoder_hidden_states
         eng = self._ensure_engine(n, h, w, ehs.shape[1])
         text_embeds = time_ids = None
         if self.cfg.addition_embed_type == "text_time":
@@ -327,9 +339,11 @@ class UNet2DConditionModel(nn.Module):
         flat, n_down, mult = None, 0, 0.0
         if net is not None:
             flat, n_down, mult = net.engine_params()
-        save = bool(torch.is_grad_enabled() and mult != 0 and flat is not None and flat.requires_grad)
-        eps = _UNetFn.apply(save, eng, sample.float().contiguous(), t, ehs, text_embeds, time_ids, flat, n_down,
-                            float(mult))
+        lora_grad = bool(torch.is_grad_enabled() and mult != 0 and flat is not None and flat.requires_grad)
+        # an embedding that requires a gradient (null-text optimisation) is differentiated with or without a LoRA network
+        ctx_grad = bool(torch.is_grad_enabled() and ehs.requires_grad)
+        eps = _UNetFn.apply(lora_grad or ctx_grad, eng, sample.float().contiguous(), t, ehs, text_embeds, time_ids,
+                            flat, n_down, float(mult), ctx_grad)
         return UNetOutput(eps)
 
 
