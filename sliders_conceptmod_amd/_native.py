@@ -439,12 +439,37 @@ def cast_f32(src: torch.Tensor, dst: torch.Tensor):
     check(lib().smi_op_cast_f32(DTYPE_CODE[dst.dtype], ptr(src), ptr(dst), src.numel(), stream_ptr()), "smi_op_cast_f32")
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, beta1=0.9, beta2=0.999, eps=1e-8):
-    """One torch.optim.Adam step on flat fp32 tensors: smi_clip_adamw with weight_decay 0 and no clipping.
-    scratch: >= 1025 floats."""
+def cfg_combine(eps_pair: torch.Tensor, guidance_scale: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """smi_cfg_combine: out = u + g (t - u) for the contiguous fp32 CFG-doubled batch eps_pair = [u ; t].  `out`: an fp32
+    tensor of the half batch to write into (default: a new one).  No synchronisation."""
+    if out is None:
+        out = torch.empty((eps_pair.shape[0] // 2,) + tuple(eps_pair.shape[1:]), dtype=torch.float32,
+                          device=eps_pair.device)
+    check(lib().smi_cfg_combine(ptr(eps_pair), ptr(out), out.numel(), float(guidance_scale), stream_ptr()),
+          "smi_cfg_combine")
+    return out
+
+
+def slider_loss(target, positive, neutral, negative, sign_eta: float, loss_out, d_target, scratch):
+    """smi_slider_loss on caller-owned fp32 tensors (loss_out [1], d_target like target, scratch >= 256 floats):
+    PromptEmbedsPair.loss with sign_eta = +eta (enhance) / -eta (erase) and its gradient.  No allocation, no
+    synchronisation."""
+    check(lib().smi_slider_loss(ptr(target), ptr(positive), ptr(neutral), ptr(negative), float(sign_eta), target.numel(),
+                                ptr(loss_out), ptr(d_target), ptr(scratch), stream_ptr()), "smi_slider_loss")
+
+
+def clip_adamw(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, betas=(0.9, 0.999), eps=1e-8,
+               weight_decay=1e-2, max_grad_norm=0.0):
+    """smi_clip_adamw on flat fp32 tensors: clip_grad_norm_(max_grad_norm) (0: no clipping), then one torch.optim.AdamW
+    step (decoupled weight decay).  scratch: >= 1025 floats.  No allocation, no synchronisation."""
     check(lib().smi_clip_adamw(ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), float(lr),
-                               float(beta1), float(beta2), float(eps), 0.0, int(step), 0.0, ptr(scratch), stream_ptr()),
-          "smi_clip_adamw")
+                               float(betas[0]), float(betas[1]), float(eps), float(weight_decay), int(step),
+                               float(max_grad_norm), ptr(scratch), stream_ptr()), "smi_clip_adamw")
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, beta1=0.9, beta2=0.999, eps=1e-8):
+    """One torch.optim.Adam step on flat fp32 tensors: clip_adamw with weight_decay 0 and no clipping."""
+    clip_adamw(param, grad, exp_avg, exp_avg_sq, lr, step, scratch, (beta1, beta2), eps, 0.0, 0.0)
 
 
 def _weight_table(state: dict, dtype, device):

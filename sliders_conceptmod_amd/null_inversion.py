@@ -12,7 +12,7 @@
 `fused=True` (default) runs an inner step as five native calls and one scalar read, on buffers allocated once: the cast of
 the fp32 embedding to the UNet's dtype, the UNet forward on the one unconditional sample (smi_unet_forward, saving), the fused
 loss and d(loss)/d(eps_u) (smi_nulltext_loss), the backward to the embedding (smi_unet_backward_ctx) and Adam
-(smi_clip_adamw with weight_decay 0 and no clipping).  `fused=False` is the notebook's own code against the product UNet:
+(_native.adam_step: the step's AdamW call with weight_decay 0 and no clipping).  `fused=False` is the notebook's own code against the product UNet:
 torch autograd through `unet(latent, t, encoder_hidden_states=uncond)`, `nnf.mse_loss`, `torch.optim.Adam`.
 
 Differences from the notebook: the UNet computes in fp16 / bf16 storage (the embedding and Adam's state stay fp32 and the

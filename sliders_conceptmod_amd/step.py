@@ -32,19 +32,75 @@ def tail_backward_ok(guidance_scale: float, allowed: bool = True) -> bool:
     return bool(allowed) and 1.0 - float(guidance_scale) == 0.0 and os.environ.get("SMI_FULL_BACKWARD") != "1"
 
 
-class SliderStep:
+def _doubled(first, second, batch_size: int, dev, dt) -> torch.Tensor:
+    """The reference's concat_embeddings (train_util.py:267-272), [first x B ; second x B], on the engine's device."""
+    return torch.cat([first, second]).repeat_interleave(batch_size, dim=0).to(dev, dt).contiguous()
+
+
+def _doubled_cond(unet, batch_size: int, first, second, first_pooled=None, pooled=None, time_ids=None) -> dict:
+    """CFG-doubled conditioning of one prompt: `second` paired with `first` (the unconditional one)."""
+    dt, dev = unet.dtype, unet.device
+    c = {"ctx": _doubled(first, second, batch_size, dev, dt)}
+    if pooled is not None:
+        c["text_embeds"] = _doubled(first_pooled, pooled, batch_size, dev, dt)
+        c["time_ids"] = _doubled(time_ids, time_ids, batch_size, dev, torch.float32)
+    return c
+
+
+class _FusedStep:
+    """What the two steps share: the step's ONE message, [flat fp32 LoRA gradient | n_loss loss
+    scalars] -- the losses ride on the gradient's all-reduce -- the AdamW state, the adaptor snapshot, the backward
+    through the CFG mix and the all-reduce / clip / AdamW tail."""
+
+    def __init__(self, unet, network, scheduler, n_loss: int, lr, betas, eps, weight_decay, max_grad_norm,
+                 process_group):
+        self.unet, self.network, self.scheduler = unet, network, scheduler
+        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
+        self.max_grad_norm = max_grad_norm
+        self.pg = process_group
+        flat = network.flat
+        self.msg = torch.zeros(flat.numel() + n_loss, dtype=flat.dtype, device=flat.device)
+        self.grad = self.msg[:flat.numel()]
+        self.exp_avg = torch.zeros_like(flat)
+        self.exp_avg_sq = torch.zeros_like(flat)
+        self.scratch = torch.empty(4096, dtype=torch.float32, device=flat.device)
+        self.step_count = 0
+
+    def _adaptor_params(self):
+        """(lora_down, lora_up, multiplier) as the engine takes them, read with the adaptor switched on."""
+        net = self.network
+        net.__enter__()
+        flat, n_down, mult = net.engine_params()
+        net.__exit__(None, None, None)
+        return flat[:n_down], flat[n_down:], mult
+
+    def _backward_cfg(self, engine, d_pred: torch.Tensor, guidance_scale: float, tail_ok: bool):
+        """Backward of the saved CFG-doubled pass from d_pred = d(loss)/d(u + g (t - u)); accumulates into self.grad."""
+        n_down = self.network._n_down
+        if tail_ok:  # g == 1: d_eps = [0 ; d_pred], the zero half is not built and not run
+            engine.backward_tail(d_pred, self.grad[:n_down], self.grad[n_down:])
+        else:  # d(u + g (t - u)) = (1 - g) du + g dt
+            d_eps = torch.cat([d_pred * (1.0 - guidance_scale), d_pred * guidance_scale])
+            engine.backward(d_eps, self.grad[:n_down], self.grad[n_down:])
+
+    def _optimizer_tail(self, lr: Optional[float]):
+        parallel.allreduce_mean_(self.msg, self.pg)  # gradient + losses in one collective; no-op on a single rank
+        self.step_count += 1
+        _native.clip_adamw(self.network.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr if lr is None else lr,
+                           self.step_count, self.scratch, self.betas, self.eps, self.weight_decay, self.max_grad_norm)
+
+
+class SliderStep(_FusedStep):
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, cfg_scale: float = 1.0,
                  skip_dead_cfg_half: bool = False, process_group=None, batch_passes: bool = True,
                  dedup_uncond: bool = False, preroll_skip_dead_half: bool = True, tail_backward: bool = True):
-        self.unet, self.network, self.scheduler = unet, network, scheduler
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.max_grad_norm = max_grad_norm
+        super().__init__(unet, network, scheduler, 1, lr, betas, eps, weight_decay, max_grad_norm, process_group)
+        self.loss = self.msg[self.grad.numel():]
         self.cfg_scale = cfg_scale
         # With CFG scale 1 the unconditional half of the doubled batch is algebraically dead (u + 1*(t-u) == t).
         # Off by default: the reference computes it, so the headline number does too.
         self.skip_dead = bool(skip_dead_cfg_half and cfg_scale == 1.0)
-        self.pg = process_group
         # Run the four guidance passes as ONE UNet pass (frozen samples first, adapted target samples last;
         # smi_unet_forward_batched): same per-sample arithmetic, 4x larger GEMM M, ~60 % fewer launches.
         self.batch_passes = batch_passes
@@ -61,17 +117,6 @@ class SliderStep:
         self.preroll_skip_dead_half = bool(preroll_skip_dead_half) and os.environ.get("SMI_PREROLL_FULL") != "1"  # (A/B switch)
         # guidance scale exactly 1: the unconditional half of d_eps is zero, the backward skips those samples
         self.tail_backward = tail_backward_ok(cfg_scale, tail_backward) and not self.skip_dead
-        flat = network.flat
-        # ONE message per step: [flat fp32 LoRA gradient | loss scalar] -- the loss rides on the
-        # gradient's all-reduce
-        self.msg = torch.zeros(flat.numel() + 1, dtype=flat.dtype, device=flat.device)
-        self.grad = self.msg[:flat.numel()]
-        self.loss = self.msg[flat.numel():]
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
-        self.scratch = torch.empty(4096, dtype=torch.float32, device=flat.device)
-        self.step_count = 0
-        self._lib = _native.lib()
 
     # ---- conditioning for one prompt pair, laid out as the reference's concat_embeddings does (train_util.py:267-272)
     def make_conditioning(self, emb: Dict[str, torch.Tensor], batch_size: int, pooled: Optional[dict] = None,
@@ -80,31 +125,27 @@ class SliderStep:
         sub = "negative" if "negative" in emb else "unconditional"
         out = {"B": batch_size, "keys": {"positive": "positive", "neutral": "neutral", "negative": sub,
                                          "target": "target"}}
+
+        def rows(src, key):
+            return src[key].repeat_interleave(batch_size, dim=0)
+
+        def doubled(key):
+            if pooled is None:
+                return _doubled_cond(self.unet, batch_size, emb["unconditional"], emb[key])
+            return _doubled_cond(self.unet, batch_size, emb["unconditional"], emb[key], pooled["unconditional"],
+                                 pooled[key], time_ids)
+
         for role, key in out["keys"].items():
-            if self.skip_dead:
-                te = emb[key].repeat_interleave(batch_size, dim=0)
-            else:
-                te = torch.cat([emb["unconditional"], emb[key]]).repeat_interleave(batch_size, dim=0)
-            c = {"ctx": te.to(dev, dt).contiguous()}
+            if not self.skip_dead:
+                out[role] = doubled(key)
+                continue
+            c = {"ctx": rows(emb, key).to(dev, dt).contiguous()}
             if pooled is not None:
-                if self.skip_dead:
-                    pe = pooled[key].repeat_interleave(batch_size, dim=0)
-                    ti = time_ids.repeat_interleave(batch_size, dim=0)
-                else:
-                    pe = torch.cat([pooled["unconditional"], pooled[key]]).repeat_interleave(batch_size, dim=0)
-                    ti = torch.cat([time_ids, time_ids]).repeat_interleave(batch_size, dim=0)
-                c["text_embeds"] = pe.to(dev, dt).contiguous()
-                c["time_ids"] = ti.to(dev, torch.float32).contiguous()
+                c["text_embeds"] = rows(pooled, key).to(dev, dt).contiguous()
+                c["time_ids"] = time_ids.repeat_interleave(batch_size, dim=0).to(dev, torch.float32).contiguous()
             out[role] = c
         # the pre-roll always runs the doubled [unconditional, target] batch (guidance 3 / train.cfg there)
-        tf = {"ctx": torch.cat([emb["unconditional"], emb["target"]]).repeat_interleave(batch_size, dim=0)
-              .to(dev, dt).contiguous()}
-        if pooled is not None:
-            tf["text_embeds"] = torch.cat([pooled["unconditional"], pooled["target"]]).repeat_interleave(
-                batch_size, dim=0).to(dev, dt).contiguous()
-            tf["time_ids"] = torch.cat([time_ids, time_ids]).repeat_interleave(batch_size, dim=0).to(
-                dev, torch.float32).contiguous()
-        out["target_full"] = tf
+        out["target_full"] = doubled("target")
         order = ("positive", "neutral", "negative", "target")  # adapted (target) samples LAST
         out["all"] = {k: torch.cat([out[r][k] for r in order]).contiguous() for k in out["target"]}
         if self.dedup:
@@ -114,10 +155,6 @@ class SliderStep:
                 if out["keys"][role] not in uniq:
                     uniq.append(out["keys"][role])
             out["uniq"] = uniq
-
-            def rows(src, key):
-                return src[key].repeat_interleave(batch_size, dim=0)
-
             seq = uniq + ["unconditional", "target"]
             d = {"ctx": torch.cat([rows(emb, k) for k in seq]).to(dev, dt).contiguous()}
             if pooled is not None:
@@ -134,12 +171,7 @@ class SliderStep:
             down, up = flat[:n_down], flat[n_down:]
         eps = engine.forward(x, t, c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up,
                              mult if lora else 0.0, save)
-        if self.skip_dead:
-            return eps
-        out = torch.empty((eps.shape[0] // 2,) + tuple(eps.shape[1:]), dtype=torch.float32, device=eps.device)
-        _native.check(self._lib.smi_cfg_combine(_native.ptr(eps), _native.ptr(out), out.numel(), self.cfg_scale,
-                                                _native.stream_ptr()), "smi_cfg_combine")
-        return out
+        return eps if self.skip_dead else _native.cfg_combine(eps, self.cfg_scale)
 
     @torch.no_grad()
     def preroll(self, latents: torch.Tensor, cond: dict, total_timesteps: int, guidance_scale: float,
@@ -148,32 +180,21 @@ class SliderStep:
         `total_timesteps` scheduler timesteps, predict_noise(_xl) with the adaptor ON at `guidance_scale` on the target
         prompt pair, then scheduler.step(...).prev_sample.  Same arithmetic as train_util.diffusion(_xl) on this
         engine, without autograd bookkeeping; returns the denoised latents (fp32)."""
-        net = self.network
         lat = latents.float()
         c = cond["target_full"]
         B = lat.shape[0]
-        net.__enter__()
-        flat, n_down, mult = net.engine_params()
-        net.__exit__(None, None, None)
-        if self.preroll_skip_dead_half and float(guidance_scale) == 1.0:
-            half = {k: v[B:].contiguous() for k, v in c.items()}  # rows [B, 2B) of concat_embeddings: the conditional ones
-            for timestep in self.scheduler.timesteps[start_timesteps:total_timesteps]:
-                x = self.scheduler.scale_model_input(lat, timestep).contiguous()
-                _, _, h, w = x.shape
-                engine = self.unet._ensure_engine(B, h, w, half["ctx"].shape[1])
-                pred = engine.forward(x, float(timestep), half["ctx"], half.get("text_embeds"), half.get("time_ids"),
-                                      flat[:n_down], flat[n_down:], mult, False)
-                lat = self.scheduler.step(pred, timestep, lat).prev_sample
-            return lat
+        down, up, mult = self._adaptor_params()
+        live_only = self.preroll_skip_dead_half and float(guidance_scale) == 1.0  # the conditional half alone
+        if live_only:
+            c = {k: v[B:].contiguous() for k, v in c.items()}  # rows [B, 2B) of concat_embeddings: the conditional ones
         for timestep in self.scheduler.timesteps[start_timesteps:total_timesteps]:
-            x = self.scheduler.scale_model_input(torch.cat([lat] * 2), timestep).contiguous()
-            _, _, h, w = x.shape
-            engine = self.unet._ensure_engine(2 * B, h, w, c["ctx"].shape[1])
-            eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down],
-                                 flat[n_down:], mult, False)
-            pred = torch.empty((B,) + tuple(eps.shape[1:]), dtype=torch.float32, device=eps.device)
-            _native.check(self._lib.smi_cfg_combine(_native.ptr(eps), _native.ptr(pred), pred.numel(),
-                                                    float(guidance_scale), _native.stream_ptr()), "smi_cfg_combine")
+            x = self.scheduler.scale_model_input(lat if live_only else torch.cat([lat] * 2), timestep).contiguous()
+            n, _, h, w = x.shape
+            engine = self.unet._ensure_engine(n, h, w, c["ctx"].shape[1])
+            pred = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up, mult,
+                                  False)
+            if not live_only:
+                pred = _native.cfg_combine(pred, guidance_scale)
             lat = self.scheduler.step(pred, timestep, lat).prev_sample
         return lat
 
@@ -186,11 +207,11 @@ class SliderStep:
         x = lat if self.skip_dead else torch.cat([lat] * 2)
         x = self.scheduler.scale_model_input(x, timestep).contiguous()
         t = float(timestep)
-        n, _, h, w = x.shape
-        engine = None if self.batch_passes else self.unet._ensure_engine(n, h, w, cond["target"]["ctx"].shape[1])
-        net = self.network
         if self.batch_passes:
             return self._train_step_batched(x, t, cond, action, eta, lr)
+        n, _, h, w = x.shape
+        engine = self.unet._ensure_engine(n, h, w, cond["target"]["ctx"].shape[1])
+        net = self.network
         net.__exit__(None, None, None)
         positive = self._pass(engine, x, t, cond["positive"], False, False)
         neutral = self._pass(engine, x, t, cond["neutral"], False, False)
@@ -198,89 +219,54 @@ class SliderStep:
         net.__enter__()
         target = self._pass(engine, x, t, cond["target"], True, True)
         net.__exit__(None, None, None)
-
         return self._finish(engine, target, positive, neutral, negative, action, eta, lr)
 
     def _train_step_dedup(self, lat, timestep, cond, action, eta, lr):
-        net = self.network
         uniq, c = cond["uniq"], cond["dedup"]
         B = lat.shape[0]
         nu = len(uniq)
         x = self.scheduler.scale_model_input(torch.cat([lat] * (nu + 2)), timestep).contiguous()
         _, _, h, w = x.shape
         engine = self.unet._ensure_engine((nu + 2) * B, h, w, c["ctx"].shape[1], n_adapted=2 * B)
-        net.__enter__()
-        flat, n_down, mult = net.engine_params()
-        net.__exit__(None, None, None)
-        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down],
-                             flat[n_down:], mult, True, n_adapted=2 * B)
+        down, up, mult = self._adaptor_params()
+        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up, mult, True,
+                             n_adapted=2 * B)
         e = {k: eps[i * B:(i + 1) * B] for i, k in enumerate(uniq)}
-
-        def cfg(pair):
-            o = torch.empty((B,) + tuple(pair.shape[1:]), dtype=torch.float32, device=pair.device)
-            _native.check(self._lib.smi_cfg_combine(_native.ptr(pair), _native.ptr(o), o.numel(), self.cfg_scale,
-                                                    _native.stream_ptr()), "smi_cfg_combine")
-            return o
-
-        outs = [cfg(torch.cat([e["unconditional"], e[cond["keys"][r]]])) for r in ("positive", "neutral", "negative")]
-        target = cfg(eps[nu * B:].contiguous())
+        outs = [_native.cfg_combine(torch.cat([e["unconditional"], e[cond["keys"][r]]]), self.cfg_scale)
+                for r in ("positive", "neutral", "negative")]
+        target = _native.cfg_combine(eps[nu * B:].contiguous(), self.cfg_scale)
         return self._finish(engine, target, outs[0], outs[1], outs[2], action, eta, lr)
 
     def _train_step_batched(self, x, t, cond, action, eta, lr):
-        net = self.network
         n, _, h, w = x.shape
         engine = self.unet._ensure_engine(4 * n, h, w, cond["target"]["ctx"].shape[1], n_adapted=n)
-        net.__enter__()
-        flat, n_down, mult = net.engine_params()
-        net.__exit__(None, None, None)
+        down, up, mult = self._adaptor_params()
         c = cond["all"]
         x4 = torch.cat([x] * 4)
-        eps = engine.forward(x4, t, c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down], flat[n_down:],
-                             mult, True, n_adapted=n)
-        outs = []
-        for i in range(4):
-            e = eps[i * n:(i + 1) * n]
-            if self.skip_dead:
-                outs.append(e)
-            else:
-                o = torch.empty((n // 2,) + tuple(e.shape[1:]), dtype=torch.float32, device=e.device)
-                _native.check(self._lib.smi_cfg_combine(_native.ptr(e), _native.ptr(o), o.numel(), self.cfg_scale,
-                                                        _native.stream_ptr()), "smi_cfg_combine")
-                outs.append(o)
+        eps = engine.forward(x4, t, c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up, mult, True, n_adapted=n)
+        outs = [eps[i * n:(i + 1) * n] for i in range(4)]
+        if not self.skip_dead:
+            outs = [_native.cfg_combine(e, self.cfg_scale) for e in outs]
         positive, neutral, negative, target = outs
         return self._finish(engine, target, positive, neutral, negative, action, eta, lr)
 
     def _finish(self, engine, target, positive, neutral, negative, action, eta, lr):
-        net = self.network
         sign_eta = eta if action == "enhance" else -eta
         if action not in ("enhance", "erase"):
             raise ValueError("action must be erase or enhance")
         dtarget = torch.empty_like(target)
-        _native.check(self._lib.smi_slider_loss(_native.ptr(target), _native.ptr(positive), _native.ptr(neutral),
-                                                _native.ptr(negative), sign_eta, target.numel(),
-                                                _native.ptr(self.loss), _native.ptr(dtarget),
-                                                _native.ptr(self.scratch), _native.stream_ptr()), "smi_slider_loss")
+        _native.slider_loss(target, positive, neutral, negative, sign_eta, self.loss, dtarget, self.scratch)
         self.grad.zero_()
-        n_down = net._n_down
         if self.skip_dead:
+            n_down = self.network._n_down
             engine.backward(dtarget, self.grad[:n_down], self.grad[n_down:])
-        elif self.tail_backward:  # g == 1: d_eps = [0 ; dtarget], the zero half is not built and not run
-            engine.backward_tail(dtarget, self.grad[:n_down], self.grad[n_down:])
-        else:  # d(u + g (t - u)) = (1 - g) du + g dt
-            d_eps = torch.cat([dtarget * (1.0 - self.cfg_scale), dtarget * self.cfg_scale])
-            engine.backward(d_eps, self.grad[:n_down], self.grad[n_down:])
-        parallel.allreduce_mean_(self.msg, self.pg)  # gradient + loss in one collective; no-op on a single rank
-        self.step_count += 1
-        flat = net.flat
-        _native.check(self._lib.smi_clip_adamw(_native.ptr(flat), _native.ptr(self.grad), _native.ptr(self.exp_avg),
-                                               _native.ptr(self.exp_avg_sq), flat.numel(),
-                                               self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps,
-                                               self.weight_decay, self.step_count, self.max_grad_norm,
-                                               _native.ptr(self.scratch), _native.stream_ptr()), "smi_clip_adamw")
+        else:
+            self._backward_cfg(engine, dtarget, self.cfg_scale, self.tail_backward)
+        self._optimizer_tail(lr)
         return self.loss
 
 
-class ImageSliderStep:
+class ImageSliderStep(_FusedStep):
     """The image-slider step (trainscripts/imagesliders/train_lora-scale-xl.py:317-381; SD-1.x twin train_lora-scale.py:
     283-345) as one device-side sequence, without an autograd graph:
 
@@ -296,23 +282,11 @@ class ImageSliderStep:
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, process_group=None, one_pass: bool = True,
                  tail_backward: bool = True):
-        self.unet, self.network, self.scheduler = unet, network, scheduler
-        self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
-        self.max_grad_norm = max_grad_norm
-        self.pg = process_group
+        super().__init__(unet, network, scheduler, 2, lr, betas, eps, weight_decay, max_grad_norm, process_group)
+        self.losses = self.msg[self.grad.numel():]  # (high side, low side); mean over ranks after the step's all-reduce
         self.one_pass = one_pass  # both sides in one UNet pass where the adaptor set allows it (see _one_pass_ok)
         self._one_pass_cached = None
         self.tail_backward = tail_backward  # at guidance scale 1 the backward skips the unconditional samples
-        flat = network.flat
-        # one message per step: [flat fp32 LoRA gradient | loss of the high side, loss of the low side]
-        self.msg = torch.zeros(flat.numel() + 2, dtype=flat.dtype, device=flat.device)
-        self.grad = self.msg[:flat.numel()]
-        self.losses = self.msg[flat.numel():]  # (high side, low side); mean over ranks after the step's all-reduce
-        self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
-        self.scratch = torch.empty(4096, dtype=torch.float32, device=flat.device)
-        self.step_count = 0
-        self._lib = _native.lib()
 
     def make_conditioning(self, text_embeds: torch.Tensor, batch_size: int, pooled: Optional[torch.Tensor] = None,
                           time_ids: Optional[torch.Tensor] = None, uncond: Optional[torch.Tensor] = None,
@@ -320,38 +294,26 @@ class ImageSliderStep:
         """CFG-doubled conditioning of one side: the prompt paired with the unconditional one (`uncond`,
         `uncond_pooled`), as the reference does (I/train_lora-scale-xl.py:321-337, I/train_lora-scale.py:283-318); without
         them the prompt is paired with itself (the same prediction at guidance 1)."""
-        dt, dev = self.unet.dtype, self.unet.device
-        first = text_embeds if uncond is None else uncond
-        c = {"ctx": torch.cat([first, text_embeds]).repeat_interleave(batch_size, dim=0).to(dev, dt).contiguous()}
-        if pooled is not None:
-            first_p = pooled if uncond_pooled is None else uncond_pooled
-            c["text_embeds"] = torch.cat([first_p, pooled]).repeat_interleave(batch_size, dim=0).to(dev, dt).contiguous()
-            c["time_ids"] = torch.cat([time_ids, time_ids]).repeat_interleave(batch_size, dim=0).to(
-                dev, torch.float32).contiguous()
-        return c
+        return _doubled_cond(self.unet, batch_size, text_embeds if uncond is None else uncond, text_embeds,
+                             pooled if uncond_pooled is None else uncond_pooled, pooled, time_ids)
+
+    def _mse(self, idx, eps_pair, noise, guidance_scale):
+        """Side `idx`: its loss slot = MSE(u + g (t - u), noise) in fp32 (I/train_lora-scale-xl.py:338); returns
+        d(loss)/d(prediction)."""
+        diff = _native.cfg_combine(eps_pair, guidance_scale) - noise.float()
+        self.losses[idx] = (diff * diff).mean()
+        return diff * (2.0 / diff.numel())
 
     def _side(self, idx, sign_scale, noised, noise, timestep, c, guidance_scale):
-        net = self.network
         x = self.scheduler.scale_model_input(torch.cat([noised.float()] * 2), timestep).contiguous()
         n, _, h, w = x.shape
         engine = self.unet._ensure_engine(n, h, w, c["ctx"].shape[1])
-        net.set_lora_slider(scale=sign_scale)
-        net.__enter__()
-        flat, n_down, mult = net.engine_params()
-        net.__exit__(None, None, None)
-        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down],
-                             flat[n_down:], mult, True)
-        pred = torch.empty((n // 2,) + tuple(eps.shape[1:]), dtype=torch.float32, device=eps.device)
-        _native.check(self._lib.smi_cfg_combine(_native.ptr(eps), _native.ptr(pred), pred.numel(),
-                                                float(guidance_scale), _native.stream_ptr()), "smi_cfg_combine")
-        diff = pred - noise.float()                       # MSE in fp32 (I/train_lora-scale-xl.py:338)
-        self.losses[idx] = (diff * diff).mean()
-        dpred = diff * (2.0 / diff.numel())
-        if tail_backward_ok(guidance_scale, self.tail_backward):
-            engine.backward_tail(dpred.contiguous(), self.grad[:n_down], self.grad[n_down:])  # accumulates
-            return
-        d_eps = torch.cat([dpred * (1.0 - guidance_scale), dpred * guidance_scale])  # d(u + g (t - u))
-        engine.backward(d_eps.contiguous(), self.grad[:n_down], self.grad[n_down:])  # accumulates
+        self.network.set_lora_slider(scale=sign_scale)
+        down, up, mult = self._adaptor_params()
+        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up, mult, True)
+        dpred = self._mse(idx, eps, noise, guidance_scale)
+        self._backward_cfg(engine, dpred.contiguous(), guidance_scale,
+                           tail_backward_ok(guidance_scale, self.tail_backward))  # accumulates
 
     def _one_pass_ok(self) -> bool:
         """Both sides can share ONE UNet pass (per-sample adaptor multipliers +s / -s, smi_unet_forward_multi) when every
@@ -364,7 +326,6 @@ class ImageSliderStep:
 
     def _both_sides(self, scale, noised_high, noised_low, noise_high, noise_low, timestep, cond_pos, cond_neu,
                     guidance_scale):
-        net = self.network
         B = noised_high.shape[0]
         # [u_hi, u_lo, t_hi, t_lo]: both unconditional halves first, so that the samples with a non-zero output gradient
         # at guidance 1 are the tail of the batch (per-sample arithmetic does not depend on the batch position)
@@ -374,32 +335,19 @@ class ImageSliderStep:
         c = {k: torch.cat([cond_pos[k][:B], cond_neu[k][:B], cond_pos[k][B:], cond_neu[k][B:]]).contiguous()
              for k in cond_pos}
         engine = self.unet._ensure_engine(n, h, w, c["ctx"].shape[1])
-        net.set_lora_slider(scale=1)
-        net.__enter__()
-        flat, n_down, mult = net.engine_params()
-        net.__exit__(None, None, None)
+        self.network.set_lora_slider(scale=1)
+        down, up, mult = self._adaptor_params()
         mults = ([mult * scale] * B + [-mult * scale] * B) * 2
-        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), flat[:n_down],
-                             flat[n_down:], mults, True)
-        dpreds = []
-        for idx, noise in enumerate((noise_high, noise_low)):
-            e = torch.cat([eps[idx * B:(idx + 1) * B], eps[(2 + idx) * B:(3 + idx) * B]])  # this side's CFG pair
-            pred = torch.empty((B,) + tuple(e.shape[1:]), dtype=torch.float32, device=e.device)
-            _native.check(self._lib.smi_cfg_combine(_native.ptr(e), _native.ptr(pred), pred.numel(),
-                                                    float(guidance_scale), _native.stream_ptr()), "smi_cfg_combine")
-            diff = pred - noise.float()
-            self.losses[idx] = (diff * diff).mean()
-            dpreds.append(diff * (2.0 / diff.numel()))
-        if tail_backward_ok(guidance_scale, self.tail_backward):
-            engine.backward_tail(torch.cat(dpreds).contiguous(), self.grad[:n_down], self.grad[n_down:])
-            return
-        d_eps = torch.cat([d * (1.0 - guidance_scale) for d in dpreds] + [d * guidance_scale for d in dpreds])
-        engine.backward(d_eps.contiguous(), self.grad[:n_down], self.grad[n_down:])
+        eps = engine.forward(x, float(timestep), c["ctx"], c.get("text_embeds"), c.get("time_ids"), down, up, mults, True)
+        dpreds = [self._mse(idx, torch.cat([eps[idx * B:(idx + 1) * B], eps[(2 + idx) * B:(3 + idx) * B]]), noise,
+                            guidance_scale)  # this side's CFG pair
+                  for idx, noise in enumerate((noise_high, noise_low))]
+        self._backward_cfg(engine, torch.cat(dpreds).contiguous(), guidance_scale,
+                           tail_backward_ok(guidance_scale, self.tail_backward))
 
     def train_step(self, noised_low, noised_high, noise_low, noise_high, timestep, cond_pos: dict, cond_neu: dict,
                    scale: float, guidance_scale: float = 1.0, lr: Optional[float] = None) -> torch.Tensor:
         """One optimisation step; returns the two side losses (high, low) as a device tensor (no host sync)."""
-        net = self.network
         self.grad.zero_()
         if self.one_pass and self._one_pass_ok():
             self._both_sides(scale, noised_high, noised_low, noise_high, noise_low, timestep, cond_pos, cond_neu,
@@ -407,13 +355,6 @@ class ImageSliderStep:
         else:
             self._side(0, +scale, noised_high, noise_high, timestep, cond_pos, guidance_scale)
             self._side(1, -scale, noised_low, noise_low, timestep, cond_neu, guidance_scale)
-        net.set_lora_slider(scale=1)
-        parallel.allreduce_mean_(self.msg, self.pg)
-        self.step_count += 1
-        flat = net.flat
-        _native.check(self._lib.smi_clip_adamw(_native.ptr(flat), _native.ptr(self.grad), _native.ptr(self.exp_avg),
-                                               _native.ptr(self.exp_avg_sq), flat.numel(),
-                                               self.lr if lr is None else lr, self.betas[0], self.betas[1], self.eps,
-                                               self.weight_decay, self.step_count, self.max_grad_norm,
-                                               _native.ptr(self.scratch), _native.stream_ptr()), "smi_clip_adamw")
+        self.network.set_lora_slider(scale=1)
+        self._optimizer_tail(lr)
         return self.losses

@@ -13,16 +13,15 @@ names.  Image files (.png / .jpg / .jpeg / .webp) are resized and VAE-encoded ev
 (`train_util.get_noisy_image`, I/train_lora-scale-xl.py:216-247) on the HIP VAE encoder; `<name>.pt` / `.safetensors`
 tensors [4, h, w] are taken as PRE-ENCODED latents (already multiplied by the VAE scaling factor)."""
 import argparse
-import ast
 import os
 import random
-from pathlib import Path
 
 import torch
 from tqdm import tqdm
 
-from . import config_util, model_util, parallel, prompt_util, train_util
+from . import config_util, model_util, parallel, prompt_util, train_common, train_util
 from .lora import DEFAULT_TARGET_REPLACE, UNET_TARGET_REPLACE_MODULE_CONV, LoRANetwork
+from .train_common import launch_device  # noqa: F401  (its home is train_common; importable from here as before)
 from .train_lora_xl import encode_xl
 
 
@@ -81,15 +80,9 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
     weight_dtype = config_util.parse_precision(config.train.precision)
     tokenizers, text_encoders, unet, noise_scheduler = models or model_util.load_models(
         config.pretrained_model.name_or_path, scheduler_name=config.train.noise_scheduler, xl=xl)
-    if isinstance(text_encoders, (list, tuple)):
-        for te in text_encoders:
-            te.to(device, dtype=weight_dtype)
-            te.eval()
     rank_, world = parallel.world_info()
     parallel.sync_control_rng(device=device)  # one control RNG (torch + random) for all ranks, before the adaptor init
-    unet.to(device, dtype=weight_dtype)
-    unet.requires_grad_(False)
-    unet.eval()
+    train_common.place_frozen(text_encoders, unet, device, weight_dtype)
     modules = list(DEFAULT_TARGET_REPLACE)  # I/train_lora-scale-xl.py:57-59: c3lier adds the conv classes
     if config.network.type == "c3lier":
         modules += UNET_TARGET_REPLACE_MODULE_CONV
@@ -97,11 +90,7 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
                           train_method=config.network.training_method, target_replace=modules).to(device,
                                                                                                    dtype=weight_dtype)
     parallel.broadcast_(network.flat.data)
-    optimizer_kwargs = {}  # I/train_lora-scale-xl.py:110-117: "k=v k=v" -> keyword arguments of the optimiser
-    if config.train.optimizer_args is not None and len(config.train.optimizer_args) > 0:
-        for arg in config.train.optimizer_args.split(" "):
-            key, value = arg.split("=")
-            optimizer_kwargs[key] = ast.literal_eval(value)
+    optimizer_kwargs = train_common.parse_optimizer_args(config.train.optimizer_args)  # I/train_lora-scale-xl.py:110-117
     optimizer = train_util.get_optimizer(config.train.optimizer)(network.prepare_optimizer_params(),
                                                                  lr=config.train.lr, **optimizer_kwargs)
     lr_scheduler = train_util.get_lr_scheduler(config.train.lr_scheduler, optimizer,
@@ -142,17 +131,10 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
         vae.requires_grad_(False)
         vae.eval()
     size = image_size or ((512, 512) if xl else (256, 256))
-    save_path = Path(config.save.path)
     save_dtype = config_util.parse_precision(config.train.precision)
     stepper = None
-    oname = config.train.optimizer.lower()
-    wd = optimizer_kwargs.get("weight_decay", 1e-2 if oname == "adamw" else 0.0)
-    unsupported = set(optimizer_kwargs) - {"weight_decay", "betas", "eps", "amsgrad"}
-    fusable = (oname in ("adam", "adamw") and not (oname == "adam" and wd != 0.0) and not optimizer_kwargs.get("amsgrad")
-               and not unsupported)
-    if fused_step and not fusable:
-        raise ValueError("--fused_step implements Adam / AdamW (decoupled weight decay; weight_decay, betas, eps) only")
-    if fused_step or (fused_step is None and fusable):
+    fused, wd = train_common.fused_step_choice(fused_step, config.train.optimizer, optimizer_kwargs)
+    if fused:
         from .step import ImageSliderStep
         stepper = ImageSliderStep(unet, network, noise_scheduler, lr=config.train.lr, weight_decay=wd,
                                   eps=optimizer_kwargs.get("eps", 1e-8), betas=optimizer_kwargs.get("betas", (0.9, 0.999)))
@@ -219,40 +201,16 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
         network.training_losses.append((lh, ll))
         if on_step_complete is not None:
             on_step_complete(i, lh, ll)
-        if rank_ == 0 and i % config.save.per_steps == 0 and i != 0 and i != config.train.iterations - 1:
-            save_path.mkdir(parents=True, exist_ok=True)  # I/train_lora-scale-xl.py:402-412
-            network.save_weights(save_path / f"{config.save.name}_{i}steps.pt", dtype=save_dtype)
+        if rank_ == 0 and train_common.checkpoint_due(i, config):  # I/train_lora-scale-xl.py:402-412
+            train_common.save_checkpoint(network, config, f"{i}steps", ".pt", save_dtype)
     if rank_ == 0:
-        save_path.mkdir(parents=True, exist_ok=True)
-        network.save_weights(save_path / f"{config.save.name}_last.pt", dtype=save_dtype)
+        train_common.save_checkpoint(network, config, "last", ".pt", save_dtype)
     return network
-
-
-def launch_device(args):
-    """One process per GPU under torch.distributed.run (RANK / LOCAL_RANK / WORLD_SIZE in the environment): RCCL process
-    group, device = LOCAL_RANK -- exactly as train_lora_xl.main does.  `SMI_DIST_BACKEND=gloo` is for rehearsals on a
-    box with fewer GPUs than ranks (tests)."""
-    if str(args.device) == "cpu":
-        raise ValueError("--device cpu: the product path has no CPU fallback (the CPU oracle lives under oracle/)")
-    if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        backend = os.environ.get("SMI_DIST_BACKEND", "nccl")
-        local = int(os.environ.get("LOCAL_RANK", "0")) if backend == "nccl" else int(args.device)
-        torch.cuda.set_device(local)
-        if not torch.distributed.is_initialized():
-            torch.distributed.init_process_group(backend)
-        return torch.device("cuda", local)
-    return torch.device(f"cuda:{args.device}")
 
 
 def main(args, xl: bool = True, models=None, vae=None):
     config = config_util.load_config_from_yaml(args.config_file)
-    if args.name is not None:
-        config.save.name = args.name
-    attributes = [a.strip() for a in args.attributes.split(",")] if args.attributes is not None else []
-    config.network.alpha = args.alpha
-    config.network.rank = args.rank
-    config.save.name += f"_alpha{args.alpha}_rank{config.network.rank}_{config.network.training_method}"
-    config.save.path += f"/{config.save.name}"
+    attributes = train_common.apply_cli_overrides(config, args)
     prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
     device = launch_device(args)
     folders = [f.strip() for f in args.folders.split(",")]
@@ -273,8 +231,7 @@ def build_parser():
     p.add_argument("--stylecheck", type=str, default=None)
     p.add_argument("--folders", type=str, default="verylow, low, high, veryhigh")
     p.add_argument("--scales", type=str, default="-2, -1, 1, 2")
-    from .train_lora import add_fused_step_flags
-    add_fused_step_flags(p)  # (--no_dedup_uncond is accepted and has no effect here: the image step has no frozen passes)
+    train_common.add_fused_step_flags(p)  # (--no_dedup_uncond is accepted and has no effect here: the image step has no frozen passes)
     return p
 
 

@@ -8,14 +8,11 @@ By default the step runs through sliders_conceptmod_amd.step.SliderStep (one bat
 loss / clip / AdamW kernels, each distinct frozen sample once) -- the code path bench.py measures; `--no_fused_step` keeps the
 reference-style loop (one UNet call per guidance pass, torch autograd + optimiser), same arithmetic (tested)."""
 import argparse
-import os
-import sys
-from pathlib import Path
 
 import torch
 from tqdm import tqdm
 
-from . import config_util, model_util, parallel, prompt_util, train_util
+from . import config_util, model_util, parallel, prompt_util, train_common, train_util
 from .config_util import RootConfig
 from .lora import LoRANetwork
 from .prompt_util import PromptEmbedsCache, PromptEmbedsPair, PromptEmbedsXL
@@ -38,13 +35,13 @@ def encode_xl(text_encoder, tokenizer, prompt, device, dtype) -> PromptEmbedsXL:
 def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft_type="lora", rank=4, save_file=True,
           models=None, fused_step=None, optimizer_kwargs=None, dedup_uncond=True):
     """`fused_step` (not in the reference signature): None / True = the fused path (the script's optimiser is a hard-coded
-    AdamW, train_lora_xl.py:104), False = the reference-style autograd loop; `dedup_uncond`: inside the fused step, each
+    AdamW, train_lora_xl.py:104; with `optimizer_kwargs` the native AdamW cannot express, train_common.adam_fusable, None
+    takes the autograd loop and True raises), False = the reference-style autograd loop; `dedup_uncond`: inside the fused step, each
     distinct frozen sample runs once (bit-identical results, step.py).  `optimizer_kwargs` (not in the reference signature) overrides keyword arguments of the hard-coded AdamW
     (train_lora_xl.py:104), e.g. {"eps": 1e-3} for the element-wise trajectory parity test; the per-step losses of the
     run are left in `network.training_losses`."""
     if peft_type not in ("lora", "dora"):
         raise ValueError(f"peft_type must be lora or dora, got {peft_type}")
-    save_path = Path(config.save.path)
     weight_dtype = config_util.parse_precision(config.train.precision)
     save_weight_dtype = config_util.parse_precision(config.train.precision)
     guidance_scale = config.train.cfg
@@ -54,14 +51,7 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
     rank_, world = parallel.world_info()
     parallel.sync_control_rng(device=device)
     noise_scheduler.dp_shard = (rank_, world)
-    if isinstance(text_encoders, (list, tuple)):  # train_lora_xl.py:72-75
-        for te in text_encoders:
-            te.to(device, dtype=weight_dtype)
-            te.requires_grad_(False)
-            te.eval()
-    unet.to(device, dtype=weight_dtype)
-    unet.requires_grad_(False)
-    unet.eval()
+    train_common.place_frozen(text_encoders, unet, device, weight_dtype)  # train_lora_xl.py:72-75
     if peft_type == "dora":  # train_lora_xl.py:87-90
         from .dora import DoRANetwork as peft_class
     else:
@@ -91,9 +81,7 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
     del tokenizers, text_encoders
 
     stepper = None
-    if okw.get("amsgrad") and fused_step:
-        raise ValueError("--fused_step implements AdamW without amsgrad")
-    if (fused_step or fused_step is None) and not okw.get("amsgrad"):
+    if train_common.fused_step_choice(fused_step, "adamw", okw)[0]:
         from .step import SliderStep
         stepper = SliderStep(unet, network, noise_scheduler, lr=okw["lr"], weight_decay=okw["weight_decay"],
                              eps=okw.get("eps", 1e-8), betas=okw.get("betas", (0.9, 0.999)), max_grad_norm=0.2,
@@ -105,17 +93,8 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
         with torch.no_grad():
             noise_scheduler.set_timesteps(config.train.max_denoising_steps, device=device)
             optimizer.zero_grad()
-            prompt_pair = prompt_pairs[torch.randint(0, len(prompt_pairs), (1,)).item()]
-            timesteps_to = torch.randint(1, config.train.max_denoising_steps, (1,)).item()
-            height, width = prompt_pair.resolution, prompt_pair.resolution
-            if prompt_pair.dynamic_resolution:
-                height, width = train_util.get_random_resolution_in_bucket(prompt_pair.resolution)
-            bs = prompt_pair.batch_size
-            latents = train_util.get_initial_latents(noise_scheduler, bs, height, width, 1)
-            if world > 1:
-                latents = latents[parallel.shard_slice(bs, rank_, world)]
-                bs = bs // world
-            latents = latents.to(device, dtype=torch.float32)
+            prompt_pair, timesteps_to, height, width, bs, latents = train_common.draw_text_step(
+                prompt_pairs, config, noise_scheduler, rank_, world, device)
             add_time_ids = train_util.get_add_time_ids(height, width, dynamic_crops=prompt_pair.dynamic_crops,
                                                        dtype=torch.float32).to(device)
 
@@ -177,15 +156,13 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
         lv = float(loss.item())  # the one host sync per step, as the reference's loss.item() (train_lora_xl.py:346)
         network.training_losses.append(lv)
         pbar.set_description(f"Loss*1k: {lv * 1000:.4f}")
-        if save_file and rank_ == 0 and i % config.save.per_steps == 0 and i != 0 and i != config.train.iterations - 1:
-            save_path.mkdir(parents=True, exist_ok=True)
-            network.save_weights(save_path / f"{config.save.name}_{i}steps.safetensors", dtype=save_weight_dtype)
+        if save_file and rank_ == 0 and train_common.checkpoint_due(i, config):
+            train_common.save_checkpoint(network, config, f"{i}steps", ".safetensors", save_weight_dtype)
         if on_step_complete is not None:
             on_step_complete(i)
     if save_file:
         if rank_ == 0:
-            save_path.mkdir(parents=True, exist_ok=True)
-            network.save_weights(save_path / f"{config.save.name}_last.safetensors", dtype=save_weight_dtype)
+            train_common.save_checkpoint(network, config, "last", ".safetensors", save_weight_dtype)
         return network
     return network.get_state_dict(save_weight_dtype)
 
@@ -197,12 +174,7 @@ def train_lora(target, positive, negative, unconditional, alpha=1.0, rank=4, dev
     config = config_util.load_config_from_yaml(config_file)
     if steps is not None:
         config.train.iterations = steps
-    if name is not None:
-        config.save.name = name
-    config.network.alpha = alpha
-    config.network.rank = rank
-    config.save.name += f"_alpha{alpha}_rank{rank}_{config.network.training_method}"
-    config.save.path += f"/{config.save.name}"
+    train_common.apply_cli_overrides(config, argparse.Namespace(name=name, alpha=alpha, rank=rank, attributes=None))
     settings = prompt_util.PromptSettings(target=target, positive=positive, negative=negative,
                                           unconditional=unconditional, neutral=neutral if neutral is not None else target,
                                           action=action, guidance_scale=guidance_scale, resolution=resolution,
@@ -213,24 +185,9 @@ def train_lora(target, positive, negative, unconditional, alpha=1.0, rank=4, dev
 
 def main(args):
     config = config_util.load_config_from_yaml(args.config_file)
-    if args.name is not None:
-        config.save.name = args.name
-    attributes = [a.strip() for a in args.attributes.split(",")] if args.attributes is not None else []
-    config.network.alpha = args.alpha
-    config.network.rank = args.rank
-    config.save.name += f"_alpha{args.alpha}"
-    config.save.name += f"_rank{config.network.rank}"
-    config.save.name += f"_{config.network.training_method}"
-    config.save.path += f"/{config.save.name}"
+    attributes = train_common.apply_cli_overrides(config, args)
     prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
-    if str(args.device) == "cpu":
-        raise ValueError("--device cpu: the product path has no CPU fallback (the CPU oracle lives under oracle/)")
-    if "RANK" in os.environ and int(os.environ.get("WORLD_SIZE", "1")) > 1:
-        torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
-        torch.distributed.init_process_group("nccl")
-        device = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")))
-    else:
-        device = torch.device(f"cuda:{args.device}")
+    device = train_common.launch_device(args)
     train(config, prompts, device, None, args.peft_type, args.rank, True, None, args.fused_step,
           dedup_uncond=not args.no_dedup_uncond)
 
@@ -244,8 +201,7 @@ def build_parser():
     parser.add_argument("--name", type=str, required=False, default=None, help="Name of the slider.")
     parser.add_argument("--attributes", type=str, required=False, default=None)
     parser.add_argument("--peft_type", type=str, required=False, default="lora")
-    from .train_lora import add_fused_step_flags
-    add_fused_step_flags(parser)
+    train_common.add_fused_step_flags(parser)
     return parser
 
 

@@ -30,12 +30,7 @@ def concat_embeddings(unconditional, conditional, n_imgs: int):
 
 def _cfg(noise_pred: torch.Tensor, guidance_scale: float) -> torch.Tensor:
     if noise_pred.is_cuda and noise_pred.dtype == torch.float32 and not noise_pred.requires_grad:
-        n_half = noise_pred.numel() // 2
-        out = torch.empty((noise_pred.shape[0] // 2,) + tuple(noise_pred.shape[1:]), dtype=torch.float32,
-                          device=noise_pred.device)
-        _native.check(_native.lib().smi_cfg_combine(_native.ptr(noise_pred.contiguous()), _native.ptr(out), n_half,
-                                                    float(guidance_scale), _native.stream_ptr()), "smi_cfg_combine")
-        return out
+        return _native.cfg_combine(noise_pred.contiguous(), guidance_scale)
     u, t = noise_pred.chunk(2)  # differentiable path (the adapted pass under autograd)
     return u + guidance_scale * (t - u)
 
