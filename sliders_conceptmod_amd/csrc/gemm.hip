@@ -261,7 +261,12 @@ __global__ __launch_bounds__(256) void conv3x3_small_kernel(const T* __restrict_
 // NS > 0: the slice count as a compile-time constant -- with the run-time count hipcc keeps the slab loop rolled, one
 // dependent L2 round trip per slice (6.9 us per launch, 7236 launches in a 22-step SD-1.4 run); unrolled, all slices of an
 // element are in flight at once.  The sum still runs over ascending slices: same bits.
-template <typename T, int NS>
+// LR > 0: the rank of the delta as a compile-time constant, for the ranks of the fused q|k|v projections' dX (three
+// adaptors side by side: 12 at rank 4, 24 at rank 8).  With LR = 0 those ranks ran the rolled scalar chain, 2 r dependent
+// round trips per column: the headline step's `2048 x 1280 x 3840 + rank-12 delta` took 74.8 us in three slices where
+// `2048 x 1280 x 5120` without a delta takes 49.4.  Kernels of their own, because the 4 x r operand registers of the
+// unrolled chain (80 -> 172 VGPRs with rank 24 inside the common kernel) would set the occupancy of every finish launch.
+template <typename T, int NS, int LR = 0>
 __global__ __launch_bounds__(256) void splitk_finish_kernel(GemmParams p, const float* __restrict__ slab, int nsplit_rt) {
   const int nsplit = NS > 0 ? NS : nsplit_rt;
   const int n4 = p.N >> 2;
@@ -291,8 +296,9 @@ __global__ __launch_bounds__(256) void splitk_finish_kernel(GemmParams p, const 
     if (p.bias) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.bias) + n);
     if (p.rowvec) epi_add<T, 4>(v, reinterpret_cast<const T*>(p.rowvec) + epi_rowvec_offset(p, m) + n);
     if (p.lora_r > 0 && m >= p.lora_row0) {
-      // ranks 4 / 8: every operand of the delta requested before the first fmaf; other ranks: the scalar chain
-      if (p.lora_r == 4) epi_lora4_unrolled<4>(v, p, m, n);
+      // ranks 4 / 8 (and LR): every operand of the delta requested before the first fmaf; other ranks: the scalar chain
+      if constexpr (LR > 0) epi_lora4_unrolled<LR>(v, p, m, n);
+      else if (p.lora_r == 4) epi_lora4_unrolled<4>(v, p, m, n);
       else if (p.lora_r == 8) epi_lora4_unrolled<8>(v, p, m, n);
       else epi_lora<4, false>(v, p, m, n);
     }
@@ -582,6 +588,15 @@ GemmTile tuned_choice(const GemmParams& p, hipStream_t stream) {
 //   S = largest power of two <= min(16, 512 / tiles, nk / 4), limited by the scratch the caller provides
 //   (measured 160 / 384 against 256 / 512: SD-1.4 step 24.5 -> 24.2 ms, SD-1.5 B = 4 59.6 -> 59.1, headline 178.9 -> 178.2)
 // SMI_GEMM_SPLITK=0 turns the rule off.
+// The finish pass stays a kernel of its own.  Adding the slabs in each tile's last-arriving workgroup instead (per-tile
+// arrival counters, device-scope release / acquire or write-through slab stores, the epilogue in the slice kernel; same
+// bits) was built and measured in round 6 and is SLOWER: 2048 x 1280 x 5120 in three slices 49.4 -> 63.8 us inside the
+// pre-roll, 2048 x 1280 x 10240 73.2 -> 88.8 us inside the step, the headline step 155.9 -> 157.5 ms.  The tiles of a
+// one-round launch finish together, so the hand-off's chain of dependent latencies (store drain, barrier, atomic, barrier,
+// L1 invalidate, slab reads) ends the launch with the chip idle, about 15 us, where the finish kernel costs 7-9 us at
+// full-chip width; a device-scope release per workgroup writes the whole L2 back and is worse still (+14 us at 320
+// workgroups, +35 at 640).  With it, two slices of 128 x 160 tiles for 2048 x 1280 x 1280 (256 workgroups) ran 32.9-35.4 us
+// against 24.6-25.7 un-split.  Numbers: profiles/r06_splitk_fixup_experiment.txt, DESIGN.md section 5.
 // NOTE (batch dependence): `tiles` counts the launch's rows, so the SAME sample's product is summed over K in S(batch)
 // slices -- its fp32 summation order changes with the batch it travels in (never from run to run).  Everything that is
 // compared bitwise runs both sides at one batch (batched pass vs separate passes at equal per-launch M of the split
@@ -638,7 +653,13 @@ int launch_splitk(const GemmParams& p, int S, GemmTile slice, hipStream_t stream
   if (launch_gemm2(q, slice, stream) != 0) return -1;
   const int64_t total = (int64_t)p.M * (p.N / 4);
   const int grid = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-#define FIN(TT_, NS_) hipLaunchKernelGGL((splitk_finish_kernel<TT_, NS_>), dim3(grid), dim3(256), 0, stream, p, (const float*)t_scratch, S)
+#define FIN_R(TT_, NS_, LR_) hipLaunchKernelGGL((splitk_finish_kernel<TT_, NS_, LR_>), dim3(grid), dim3(256), 0, stream, p, (const float*)t_scratch, S)
+#define FIN(TT_, NS_)                                                                                           \
+  do {                                                                                                          \
+    if (p.lora_r == 12) FIN_R(TT_, NS_, 12);                                                                    \
+    else if (p.lora_r == 24) FIN_R(TT_, NS_, 24);                                                               \
+    else FIN_R(TT_, NS_, 0);                                                                                    \
+  } while (0)
 #define FIN_T(TT_)                                                                                              \
   do {                                                                                                          \
     switch (S) {                                                                                                \
@@ -653,6 +674,7 @@ int launch_splitk(const GemmParams& p, int S, GemmTile slice, hipStream_t stream
   if (p.dtype == DT_F16) FIN_T(f16); else FIN_T(bf16);
 #undef FIN_T
 #undef FIN
+#undef FIN_R
   SMI_HIP(hipGetLastError());
   return 0;
 }
