@@ -1,0 +1,348 @@
+// The C entry points that touch no engine: the last-error text, the fp32 helpers of the training and sampling loops, and
+// the single-kernel `smi_op_*` entries of the parity tests.
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+
+#include "../../include/smi.h"
+#include "kernels.h"
+
+namespace smi {
+
+static thread_local char g_err[2048] = "";
+void set_error(const char* fmt, ...) {
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(g_err, sizeof(g_err), fmt, ap);
+  va_end(ap);
+}
+
+}  // namespace smi
+
+using namespace smi;
+
+extern "C" {
+
+const char* smi_last_error(void) { return g_err; }
+
+int smi_cfg_combine(const float* eps_2n, float* out_n, int64_t n_half, float g, void* stream) {
+  return launch_cfg_combine(eps_2n, out_n, n_half, g, (hipStream_t)stream);
+}
+int smi_slider_loss(const float* target, const float* positive, const float* neutral, const float* negative,
+                    float sign_eta, int64_t n, float* loss_out, float* dtarget, float* scratch, void* stream) {
+  return launch_slider_loss(target, positive, neutral, negative, sign_eta, n, loss_out, dtarget, scratch,
+                            (hipStream_t)stream);
+}
+int smi_nulltext_loss(const float* eps_u, const float* eps_c, const float* x_t, const float* target, float guidance_scale,
+                      float c_x, float c_eps, int64_t n, float* loss_out, float* d_eps_u, float* scratch, void* stream) {
+  return launch_nulltext_loss(eps_u, eps_c, x_t, target, guidance_scale, c_x, c_eps, n, loss_out, d_eps_u, scratch,
+                              (hipStream_t)stream);
+}
+int smi_clip_adamw(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
+                   float beta1, float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch,
+                   void* stream) {
+  return launch_clip_adamw(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, max_norm,
+                           scratch, (hipStream_t)stream);
+}
+int smi_sched_step(float* x, const float* eps, const float* noise, float c_x, float c_eps, float c_noise, int64_t n,
+                   void* stream) {
+  return launch_sched_affine(x, eps, noise, c_x, c_eps, c_noise, n, (hipStream_t)stream);
+}
+
+// ---- single-kernel entry points for the parity tests -----------------------------------------------------------
+int smi_op_gemm_scratch(void* ws, size_t bytes) {
+  smi::set_gemm_scratch(ws, bytes);
+  return 0;
+}
+int smi_op_gemm(int dtype, const void* A, const void* W, void* C, int M, int N, int K, const void* bias,
+                const void* res, const float* lora_xa, const float* lora_up, int lora_r, float lora_scale,
+                int out_f32, void* stream) {
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  if (out_f32) p.f32_out();
+  return launch_gemm(p.with_lora(lora_xa, lora_r, lora_up, lora_r, 0, lora_scale, 0), (hipStream_t)stream);
+}
+int smi_op_gemm_rows(int dtype, const void* A, const void* W, void* C, int M, int N, int K, const void* bias,
+                     const void* res, const float* lora_xa, const float* lora_up, int lora_r, float lora_scale,
+                     int lora_row0, int lora_seg, void* stream) {
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  return launch_gemm(p.with_lora(lora_xa, (int64_t)lora_r * (lora_seg > 0 ? N / lora_seg : 1), lora_up, lora_r, lora_seg,
+                                 lora_scale, lora_row0),
+                     (hipStream_t)stream);
+}
+int smi_op_gemm_epilogue(int dtype, const void* A, const void* W, void* C, int M, int N, int K, int out_f32,
+                         const void* bias, const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec,
+                         const float* lora_xa, int ld_xa, const float* lora_up, int lora_r, int lora_seg, int lora_row0,
+                         float lora_scale, int lora_dx, int tile_code, int ksplit, int* ran_code, void* stream) {
+  GemmParams p = gemm_nt(dtype, A, K, W, C, N, M, N, K).with_bias(bias).with_res(res, N);
+  if (out_f32) p.f32_out();
+  if (rowvec) p.with_rowvec(rowvec, rows_per_vec, ld_rowvec);
+  if (lora_xa && lora_dx) p.with_lora_dx(lora_xa, ld_xa, lora_up, lora_r, lora_scale);
+  else if (lora_xa) p.with_lora(lora_xa, ld_xa, lora_up, lora_r, lora_seg, lora_scale, lora_row0);
+  return launch_gemm_on_tile(p, tile_code, ksplit, ran_code, (hipStream_t)stream);
+}
+int smi_op_gemm_geglu(int dtype, const void* A, const void* W, const void* bias, void* out, void* proj, int M, int N,
+                      int K, int proj_row0, void* stream) {
+  return launch_gemm(gemm_nt(dtype, A, K, W, proj, N, M, N, K).with_bias(bias).with_geglu(out, proj_row0), (hipStream_t)stream);
+}
+int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin,
+                   int win, int cin, int cout, int stride, int upsample, int transposed, int hout, int wout,
+                   void* stream) {
+  return launch_gemm(conv3x3_geom(dtype, in, w_packed, out, nb, hin, win, cin, cout, hout, wout, stride, 1, upsample, transposed)
+                         .with_bias(bias),
+                     (hipStream_t)stream);
+}
+// dense [b, n, h, d] operands: every leading dimension is h * d
+static AttnParams attn_dense(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
+                             int nq, int nk, int d, float scale) {
+  AttnParams p;
+  p.dtype = dtype;
+  p.Q = q;
+  p.K = k;
+  p.V = v;
+  p.O = o;
+  p.lse = lse;
+  p.ldq = p.ldk = p.ldv = p.ldo = p.lddo = p.lddq = p.lddk = p.lddv = (int64_t)h * d;
+  p.B = b;
+  p.H = h;
+  p.Nq = nq;
+  p.Nk = nk;
+  p.D = d;
+  p.scale = scale;
+  return p;
+}
+int smi_op_attention_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
+                         int nq, int nk, int d, float scale, void* stream) {
+  return launch_attn_fwd(attn_dense(dtype, q, k, v, o, lse, b, h, nq, nk, d, scale), (hipStream_t)stream);
+}
+int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
+                         const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
+                         int d, float scale, void* stream) {
+  AttnParams p = attn_dense(dtype, q, k, v, const_cast<void*>(o), const_cast<float*>(lse), b, h, nq, nk, d, scale);
+  p.dO = d_o;
+  p.dQ = dq;
+  p.dK = dk;
+  p.dV = dv;
+  p.delta = delta;
+  return launch_attn_bwd(p, (hipStream_t)stream);
+}
+// scratch layout (floats): ab[2*nb*c] | mean_rstd[nb*g*2] | partial[...]
+int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
+                     float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream) {
+  float* ab = scratch;
+  float* mr = ab + (size_t)2 * nb * c;
+  float* part = mr + (size_t)nb * g * 2;
+  int rc = launch_groupnorm_fwd(dtype, x, gamma, beta, y, ab, mr, part, nb, hw, c, g, eps, silu, (hipStream_t)stream);
+  if (rc || !dy) return rc;
+  return launch_groupnorm_bwd(dtype, x, dy, gamma, beta, ab, ab + (size_t)nb * c, mr, nullptr, dx, part, nb, hw, c, g, silu,
+                              (hipStream_t)stream);
+}
+int smi_op_layernorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
+                     float* mean_rstd, int m, int c, float eps, void* stream) {
+  int rc = launch_layernorm_fwd(dtype, x, gamma, beta, y, mean_rstd, m, c, eps, (hipStream_t)stream);
+  if (rc || !dy) return rc;
+  return launch_layernorm_bwd(dtype, x, dy, gamma, mean_rstd, nullptr, dx, m, c, (hipStream_t)stream);
+}
+int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream) {
+  int rc = launch_geglu_fwd(dtype, proj, out, m, c4, (hipStream_t)stream);
+  if (rc || !dout) return rc;
+  return launch_geglu_bwd(dtype, proj, dout, dproj, m, c4, (hipStream_t)stream);
+}
+int smi_op_lora_down(int dtype, const void* x, const float* a, float* xa, int m, int k, int r, void* stream) {
+  return launch_lora_down(dtype, x, k, a, k, 1, xa, r, m, k, r, (hipStream_t)stream);
+}
+int smi_op_lora_skinny(int dtype, const void* x, const void* s, float* out, int m, int r, int k, void* stream) {
+  return launch_lora_skinny(dtype, x, k, s, out, r, m, r, k, (hipStream_t)stream);
+}
+int smi_op_lora_wgrad(int dtype, const float* p, const void* x, float* dw, int m, int k, int r, float alpha,
+                      float* scratch, void* stream) {
+  // the engine's grouped reduction with a one-job table (scratch: the job's partials followed by the table itself)
+  std::vector<WgradJob> jobs(1);
+  WgradJob& j = jobs[0];
+  memset(&j, 0, sizeof(j));
+  j.conv_tap = -1;
+  j.X = x;
+  j.ldx = k;
+  j.P = p;
+  j.ldp = r;
+  j.dW = dw;
+  j.so_r = k;
+  j.so_k = 1;
+  j.M = m;
+  j.K = k;
+  j.r = r;
+  j.rows_per_sample = m;
+  j.alpha = alpha;
+  wgrad_job_plan(j);
+  j.partial = scratch;
+  wgrad_grouped_finish(jobs);
+  WgradJob* dev = reinterpret_cast<WgradJob*>(scratch + ((wgrad_job_scratch_floats(j) + 63) / 64) * 64);
+  SMI_HIP(hipMemcpyAsync(dev, jobs.data(), sizeof(WgradJob), hipMemcpyHostToDevice, (hipStream_t)stream));
+  return launch_lora_wgrad_grouped(dtype, jobs, dev, (hipStream_t)stream);
+}
+
+// a job table as a backward pass builds it: plan per job, partials laid out in scratch, sort + launch offsets
+static int wgrad_jobs_from_c(const smi_wgrad_job* in, int n, float* scratch, std::vector<WgradJob>& jobs,
+                             size_t* floats) {
+  SMI_CHECK(in && n >= 1, "lora_wgrad_jobs: empty table");
+  jobs.resize(n);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    const smi_wgrad_job& s = in[i];
+    SMI_CHECK(s.M >= 1 && s.K >= 8 && s.r >= 1 && s.r <= 32 && s.rows_per_sample >= 1 && s.m_begin >= 0 &&
+                  s.m_begin < s.M && s.m_begin % s.rows_per_sample == 0 && (s.seg_cols == 0 || s.K % s.seg_cols == 0),
+              "lora_wgrad_jobs: job %d: M=%d K=%d r=%d rows_per_sample=%d m_begin=%d seg_cols=%d", i, s.M, s.K, s.r,
+              s.rows_per_sample, s.m_begin, s.seg_cols);
+    WgradJob& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.X = s.X;
+    j.P = s.P;
+    j.dW = s.dW;
+    j.row_scale = s.row_scale;
+    j.ldx = s.ldx;
+    j.ldp = s.ldp;
+    j.so_r = s.so_r;
+    j.so_k = s.so_k;
+    j.M = s.M;
+    j.K = s.K;
+    j.r = s.r;
+    j.seg_cols = s.seg_cols;
+    j.rows_per_sample = s.rows_per_sample;
+    j.alpha = s.alpha;
+    j.m_begin = s.m_begin;
+    j.conv_tap = s.conv_tap;
+    j.Hin = s.Hin;
+    j.Win = s.Win;
+    j.Hout = s.Hout;
+    j.Wout = s.Wout;
+    j.conv_stride = s.conv_stride;
+    j.conv_ups = s.conv_ups;
+    wgrad_job_plan(j);
+    j.partial = scratch ? scratch + off : nullptr;
+    off += ((wgrad_job_scratch_floats(j) + 63) / 64) * 64;
+  }
+  *floats = off;
+  return 0;
+}
+int smi_op_lora_wgrad_jobs_floats(const smi_wgrad_job* jobs_c, int n, size_t* out_floats) {
+  std::vector<WgradJob> jobs;
+  size_t part = 0;
+  if (int rc = wgrad_jobs_from_c(jobs_c, n, nullptr, jobs, &part)) return rc;
+  *out_floats = part + ((size_t)n * sizeof(WgradJob) + 3) / 4;
+  return 0;
+}
+int smi_op_lora_wgrad_jobs(int dtype, const smi_wgrad_job* jobs_c, int n, float* scratch, size_t scratch_floats,
+                           void* stream) {
+  std::vector<WgradJob> jobs;
+  size_t part = 0;
+  if (int rc = wgrad_jobs_from_c(jobs_c, n, scratch, jobs, &part)) return rc;
+  const size_t need = part + ((size_t)n * sizeof(WgradJob) + 3) / 4;
+  SMI_CHECK(scratch && scratch_floats >= need, "lora_wgrad_jobs: scratch of %zu floats, %zu needed", scratch_floats, need);
+  wgrad_grouped_finish(jobs);
+  WgradJob* dev = reinterpret_cast<WgradJob*>(scratch + part);
+  SMI_HIP(hipMemcpyAsync(dev, jobs.data(), (size_t)n * sizeof(WgradJob), hipMemcpyHostToDevice, (hipStream_t)stream));
+  const int rc = launch_lora_wgrad_grouped(dtype, jobs, dev, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+
+static void dora_site_from_c(const smi_dora_site& s, DoraSite& d) {
+  memset(&d, 0, sizeof(d));
+  d.W = s.W;
+  d.off_down = s.off_down;
+  d.off_up = s.off_up;
+  d.off_dora = s.off_dora;
+  d.dW = s.dW;
+  d.dWt = s.dWt;
+  d.cnorm = s.cnorm;
+  d.r = s.r;
+  d.nseg = s.nseg;
+  d.K = s.K;
+  d.cs = s.cs;
+  d.scale = s.scale;
+}
+int smi_op_dora_prep(int dtype, const smi_dora_site* sites, int n_sites, const float* down, const float* up, float mult,
+                     void* sites_dev, void* stream) {
+  static_assert(sizeof(DoraSite) == sizeof(smi_dora_site), "smi_dora_site sizes the device table");
+  SMI_CHECK(sites && n_sites >= 1 && sites_dev, "dora_prep: empty table");
+  std::vector<DoraSite> host(n_sites);
+  for (int i = 0; i < n_sites; ++i) {
+    SMI_CHECK(sites[i].nseg >= 1 && sites[i].cs >= 1 && sites[i].K >= 8 && sites[i].off_down % 4 == 0,
+              "dora_prep: site %d: nseg=%d cs=%d K=%d off_down=%lld", i, sites[i].nseg, sites[i].cs, sites[i].K,
+              (long long)sites[i].off_down);
+    dora_site_from_c(sites[i], host[i]);
+  }
+  DoraSite* dev = reinterpret_cast<DoraSite*>(sites_dev);
+  SMI_HIP(hipMemcpyAsync(dev, host.data(), (size_t)n_sites * sizeof(DoraSite), hipMemcpyHostToDevice, (hipStream_t)stream));
+  int rc = launch_dora_prep(dtype, dev, host.data(), n_sites, down, up, mult, (hipStream_t)stream);
+  if (!rc) rc = launch_dora_transpose(dtype, dev, host.data(), n_sites, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+int smi_op_dora_grads_floats(const smi_dora_site* site, size_t* out_floats) {
+  SMI_CHECK(site && site->r >= 1 && site->nseg >= 1 && site->K >= 8, "dora_grads: bad site");
+  DoraSite d;
+  dora_site_from_c(*site, d);
+  *out_floats = dora_grad_scratch_floats(d);
+  return 0;
+}
+int smi_op_dora_grads(int dtype, const smi_dora_site* site, const float* G, const float* down, const float* up,
+                      float* d_down, float* d_up, float alpha, const float* alpha_dev, float* scratch,
+                      size_t scratch_floats, void* stream) {
+  SMI_CHECK(site && site->nseg >= 1 && site->cs >= 1 && site->K >= 8 && site->K % 8 == 0 && site->off_down % 4 == 0,
+            "dora_grads: bad site");
+  DoraSite d;
+  dora_site_from_c(*site, d);
+  SMI_CHECK(scratch && scratch_floats >= dora_grad_scratch_floats(d), "dora_grads: scratch of %zu floats, %zu needed",
+            scratch_floats, dora_grad_scratch_floats(d));
+  return launch_dora_grads(dtype, d, G, down, up, d_down, d_up, alpha, alpha_dev, scratch, (hipStream_t)stream);
+}
+int smi_op_lora_prep(int dtype, const smi_lora_prep_site* sites, int n_sites, const float* down, const float* up,
+                     void* shadow, void* sites_dev, void* stream) {
+  static_assert(sizeof(HostLoraPrepSite) == sizeof(smi_lora_prep_site), "smi_lora_prep_site sizes the device table");
+  SMI_CHECK(sites && n_sites >= 1 && sites_dev && shadow, "lora_prep: empty table");
+  std::vector<HostLoraPrepSite> host(n_sites);
+  for (int i = 0; i < n_sites; ++i) {
+    const smi_lora_prep_site& s = sites[i];
+    SMI_CHECK(s.r >= 1 && s.nseg >= 1 && s.K >= 1 && s.cs >= 1 && s.rows_pad >= s.r * s.nseg && s.conv >= 0 && s.conv <= 2 &&
+                  (s.conv == 0 || s.r <= 64),
+              "lora_prep: site %d: r=%d nseg=%d K=%d cs=%d rows_pad=%d conv=%d", i, s.r, s.nseg, s.K, s.cs, s.rows_pad, s.conv);
+    HostLoraPrepSite& h = host[i];
+    memset(&h, 0, sizeof(h));
+    h.off_down = s.off_down;
+    h.off_up = s.off_up;
+    h.dst_down = s.dst_down;
+    h.dst_up = s.dst_up;
+    h.r = s.r;
+    h.nseg = s.nseg;
+    h.K = s.K;
+    h.cs = s.cs;
+    h.rows_pad = s.rows_pad;
+    h.conv = s.conv;
+    h.dst_gw = s.dst_gw;
+  }
+  SMI_HIP(hipMemcpyAsync(sites_dev, host.data(), (size_t)n_sites * sizeof(HostLoraPrepSite), hipMemcpyHostToDevice,
+                         (hipStream_t)stream));
+  const int rc = launch_lora_prep(dtype, sites_dev, n_sites, down, up, shadow, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
+}
+int smi_op_transpose_scaled(int dtype, const void* src, int64_t lds, void* dst, int M, int C, int Mp, const float* f,
+                            int rows_per_sample, void* stream) {
+  return launch_transpose_scaled(dtype, src, lds, dst, M, C, Mp, f, rows_per_sample, (hipStream_t)stream);
+}
+int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, float* scale_out, int inv_off,
+                      float* min_out, void* stream) {
+  int rc = launch_grad_scale(d_eps, n_samples, per_sample, scale_out, inv_off, (hipStream_t)stream);
+  if (rc) return rc;
+  return launch_scale_min(scale_out, n_samples, min_out, (hipStream_t)stream);
+}
+int smi_op_cast_f32(int dtype, const float* src, void* dst, int64_t n, void* stream) {
+  SMI_CHECK(src && dst && n > 0 && n % 8 == 0, "smi_op_cast_f32: bad arguments (n must be a multiple of 8)");
+  return launch_f32_to_padded(dtype, src, 8, 8, dst, 8, n / 8, 1.f, (hipStream_t)stream);
+}
+int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream) {
+  return launch_row_scale_f32(x, ld, m, n, row_mul, rows_per_mul, (hipStream_t)stream);
+}
+
+}  // extern "C"

@@ -487,7 +487,7 @@ def test_per_sample_multipliers_equal_separate_passes(model):
 
 @pytest.mark.parametrize("model", list(CFGS))
 def test_grouped_time_emb_proj_equals_one_gemm_per_resnet(model):
-    """engine.hip build_temb_group: every resnet's time_emb_proj stacked into ONE GEMM per pass, conv1 reading its column
+    """engine_unet.hip build_temb_group: every resnet's time_emb_proj stacked into ONE GEMM per pass, conv1 reading its column
     block as a row vector with a leading dimension -- against `SMI_TEMB_GROUP=0` (one GEMM per resnet), in two processes
     (the switch is read once).  Same products, different split-K partition of the K loop: rounding-level agreement, and
     the adapted pass with gradients must agree as well (no gradient flows into the views)."""
