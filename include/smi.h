@@ -117,6 +117,14 @@ typedef struct smi_clip_vision_config {
   float image_std[3];
 } smi_clip_vision_config;
 
+/* LPIPS v0.1 on AlexNet (`lpips.LPIPS(net='alex')`, what eval-scripts/lpip_score.py scores a sweep with).  The geometry is
+ * AlexNet's and fixed: conv k 11 / stride 4 / pad 2, max-pool 3 / 2, conv k 5 / pad 2, max-pool 3 / 2, three convs k 3 / pad 1,
+ * a tap after every ReLU.  The widths are configurable, for tiny test nets. */
+typedef struct smi_lpips_config {
+  int dtype;
+  int channels[5]; /* (64, 192, 384, 256, 256) */
+} smi_lpips_config;
+
 typedef struct smi_engine smi_engine;
 
 const char* smi_last_error(void);
@@ -219,6 +227,29 @@ int smi_clip_vision_encode(smi_engine* e, int n, const uint8_t* rgb8, const floa
                            void* image_embeds);
 int smi_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
                     float logit_scale, float* logits_per_image, void* stream);
+
+/* ---- LPIPS (AlexNet) distance between image pairs (how much structure a slider preserves) -----------------------------
+ * Replaces `lpips.LPIPS(net='alex')(original, edited)` in eval mode (eval-scripts/lpip_score.py): scaling layer, the five
+ * AlexNet convolutions (GEMMs on patch matrices) with a tap after every ReLU, per tap the channel-unit-normalised squared
+ * difference through the 1x1 `lin` layer, averaged over the map; the five taps added in layer order.  The tower runs on
+ * 2n images at once (a-images, then b-images); the head pairs image i with image n + i.
+ *   weights: `features.{0,3,6,8,10}.weight` T [C_out, C_in, k, k] and `.bias` T [C_out] (torchvision's AlexNet names),
+ *            `lin{0..4}.weight` T [1, C, 1, 1]; the scaling layer's shift / scale are constants of the metric
+ *   rgb8_a, rgb8_b uint8 [n, h, w, 3]: x = u / 127.5 - 1 on the device          } exactly one form, both images of a pair
+ *   img_a, img_b   f32 [n, 3, h, w] in [-1, 1]                                  } in the same one
+ *   dist      f32 [n]
+ *   per_layer f32 [n, 5]: the five terms of dist                                                    (may be NULL)
+ *   feats     5 device pointers, T [2n, Ho, Wo, C] each: the post-ReLU taps, NHWC                   (may be NULL)
+ * h, w are fixed at creation; n <= max_pairs.  Bit for bit: a pair scores the same alone or anywhere in any batch (no
+ * split-K scratch is lent to the GEMMs, every other sum is ordered by the shape alone), d(a, b) == d(b, a), d(a, a) == 0.
+ * Creation refuses h or w below 31 (the second pool would be empty), channel widths that are not multiples of 8 (16-byte
+ * vector access and the GEMM's N % 8), max_pairs above 65535 and a patch matrix of 4 GiB or more (the GEMM's operand
+ * limit: 2 max_pairs x map positions x padded k k C_in x 2 bytes).  smi_destroy frees the engine. */
+int smi_lpips_workspace_bytes(const smi_lpips_config* cfg, int max_pairs, int h, int w, size_t* bytes);
+int smi_lpips_create(const smi_lpips_config* cfg, const smi_weight* weights, int n_weights, int max_pairs, int h, int w,
+                     void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_lpips_distance(smi_engine* e, int n, const uint8_t* rgb8_a, const uint8_t* rgb8_b, const float* img_a,
+                       const float* img_b, float* dist, float* per_layer, void* const* feats);
 
 /* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)

@@ -50,6 +50,10 @@ class ClipVisionConfigC(C.Structure):
                 ("image_std", C.c_float * 3)]
 
 
+class LpipsConfigC(C.Structure):
+    _fields_ = [("dtype", C.c_int), ("channels", C.c_int * 5)]
+
+
 class WeightC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -120,6 +124,10 @@ _SIGS = {
     "smi_clip_vision_encode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4),
     "smi_clip_logits": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p,
                                   C.c_void_p]),
+    "smi_lpips_workspace_bytes": (C.c_int, [C.POINTER(LpipsConfigC), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_lpips_create": (C.c_int, [C.POINTER(LpipsConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_int, C.c_int,
+                                   C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_lpips_distance": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)]),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -274,7 +282,7 @@ def arena_bytes(cfg_c: UNetConfigC, sites: Sequence[dict], batch: int, h: int, w
 
 
 class _EngineBase:
-    """What the five engine wrappers share: the smi_engine `handle`, the `workspace` tensor it lives in, the weight
+    """What the six engine wrappers share: the smi_engine `handle`, the `workspace` tensor it lives in, the weight
     tensors it borrows (kept alive for as long as the wrapper), and their release."""
 
     handle = None
@@ -657,3 +665,73 @@ def clip_logits(image_embeds: torch.Tensor, text_embeds: torch.Tensor, logit_sca
         check(lib().smi_clip_logits(DTYPE_CODE[a.dtype], ptr(a), a.shape[0], ptr(b), b.shape[0], a.shape[1],
                                     float(logit_scale), ptr(out), stream_ptr()), "smi_clip_logits")
     return out
+
+
+def lpips_config_c(channels: Sequence[int], dtype: torch.dtype) -> LpipsConfigC:
+    if len(channels) != 5:
+        raise SmiError(f"LPIPS: five channel widths expected, got {tuple(channels)}")
+    c = LpipsConfigC()
+    c.dtype = DTYPE_CODE[dtype]
+    for i, v in enumerate(channels):
+        c.channels[i] = int(v)
+    return c
+
+
+def lpips_workspace_bytes(channels: Sequence[int], dtype: torch.dtype, max_pairs: int, h: int, w: int) -> int:
+    """smi_lpips_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on a refused config or size."""
+    out = C.c_size_t(0)
+    check(lib().smi_lpips_workspace_bytes(C.byref(lpips_config_c(channels, dtype)), max_pairs, h, w, C.byref(out)),
+          "smi_lpips_workspace_bytes")
+    return out.value
+
+
+def lpips_map_sizes(h: int, w: int):
+    """(Ho, Wo) of the five AlexNet taps for an h x w image: conv 11 / 4 / 2, pool 3 / 2, conv 5 / 1 / 2, pool 3 / 2, then 3 / 1 / 1."""
+    conv = lambda s, k, st, p: (s + 2 * p - k) // st + 1
+    pool = lambda s: (s - 3) // 2 + 1
+    h0, w0 = conv(h, 11, 4, 2), conv(w, 11, 4, 2)
+    h1, w1 = pool(h0), pool(w0)
+    h2, w2 = pool(h1), pool(w1)
+    return [(h0, w0), (h1, w1), (h2, w2), (h2, w2), (h2, w2)]
+
+
+class LpipsEngine(_EngineBase):
+    """LPIPS (AlexNet) on the HIP engine for one image size (smi_lpips_*): image pairs -> distances."""
+
+    def __init__(self, channels: Sequence[int], dtype: torch.dtype, state: dict, batch: int, h: int, w: int, device):
+        self.channels, self.batch, self.h, self.w, self.dtype = tuple(channels), batch, h, w, dtype
+        self.cfg_c = lpips_config_c(channels, dtype)
+        self._create("lpips_", self.cfg_c, (batch, h, w), state, dtype, device)
+
+    def distance(self, rgb8_a=None, rgb8_b=None, img_a=None, img_b=None, want_per_layer: bool = False,
+                 want_feats: bool = False):
+        """exactly one form: uint8 [n, h, w, 3] pairs or f32 [n, 3, h, w] pairs in [-1, 1] -> (dist f32 [n], per_layer
+        f32 [n, 5] or None, five post-ReLU taps [2n, Ho, Wo, C] or None)"""
+        dev = self.workspace.device
+        if (rgb8_a is None) != (rgb8_b is None) or (img_a is None) != (img_b is None) or (rgb8_a is None) == (img_a is None):
+            raise SmiError("LPIPS: pass exactly one form, (rgb8_a, rgb8_b) or (img_a, img_b)")
+        if rgb8_a is not None:
+            want, a, b = (self.h, self.w, 3), rgb8_a, rgb8_b
+            if a.dtype != torch.uint8 or b.dtype != torch.uint8:
+                raise SmiError(f"LPIPS: rgb8 batches must be uint8, got {a.dtype} and {b.dtype}")
+            a, b = a.to(dev).contiguous(), b.to(dev).contiguous()
+        else:
+            want, a, b = (3, self.h, self.w), img_a, img_b
+            a, b = a.to(dev, torch.float32).contiguous(), b.to(dev, torch.float32).contiguous()
+        if a.shape != b.shape or a.ndim != 4 or tuple(a.shape[1:]) != want:
+            raise SmiError(f"LPIPS: both batches must be [n, {want[0]}, {want[1]}, {want[2]}], got {tuple(a.shape)} and "
+                           f"{tuple(b.shape)}")
+        n = a.shape[0]
+        dist = torch.empty(n, dtype=torch.float32, device=dev)
+        per = torch.empty((n, 5), dtype=torch.float32, device=dev) if want_per_layer else None
+        feats, fptr = None, None
+        if want_feats:
+            feats = [torch.empty((2 * n, ho, wo, c), dtype=self.dtype, device=dev)
+                     for (ho, wo), c in zip(lpips_map_sizes(self.h, self.w), self.channels)]
+            fptr = (C.c_void_p * 5)(*[f.data_ptr() for f in feats])
+        u8 = rgb8_a is not None
+        with torch.cuda.device(dev):
+            check(lib().smi_lpips_distance(self.handle, n, ptr(a) if u8 else None, ptr(b) if u8 else None,
+                                           None if u8 else ptr(a), None if u8 else ptr(b), ptr(dist), ptr(per), fptr),
+                  "smi_lpips_distance")
+        return dist, per, feats

@@ -1,6 +1,6 @@
 // The op core of every engine: runs a model's forward -- and the UNet's activation/LoRA-gradient backward -- as a stream
 // of hand-written gfx950 kernels (gemm.hip, attention.hip, norm.hip, elementwise.hip, lora.hip).  It names no model: each
-// (engine_unet.hip, engine_vae.hip, engine_clip.hip) is a `Model` with its config, layers and forward over these ops.
+// (engine_unet.hip, engine_vae.hip, engine_clip.hip, engine_lpips.hip) is a `Model` with its config, layers and forward over these ops.
 //
 // Structure
 //   * Activations are token-major [n*H*W, C] in the model dtype (fp16/bf16); accumulation is fp32 everywhere.
@@ -134,7 +134,7 @@ struct Model {
 
 struct smi_engine {
   // which model the engine holds: set once, by hold(); every entry point accepts one kind and refuses the others
-  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION };
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS };
   Kind kind = UNET;
   std::unique_ptr<Model> model;  // (also keeps a lambda from copying an engine it names through a reference parameter)
   int dtype = 0;

@@ -298,6 +298,35 @@ int launch_vit_embed_ln(int dtype, const void* patch_out, const void* cls, const
 int launch_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
                        float logit_scale, float* logits_per_image, hipStream_t stream);
 
+// LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
+// applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.
+inline int lpips_conv_out(int in, int k, int stride, int pad) { return (in + 2 * pad - k) / stride + 1; }
+inline int lpips_pool_out(int in) { return (in - 3) / 2 + 1; }  // 3 x 3, stride 2, floor mode, no padding
+// dst T [Cout, Kp] from a torch conv filter T [Cout, Cin, k, k]
+int launch_lpips_pack_filter(int dtype, const void* src, void* dst, int Cout, int Cin, int k, int Kp, hipStream_t stream);
+// patch matrix of conv1 (k 11, stride 4, pad 2; 363 columns) over 2n images, a-images first, from exactly one form:
+// uint8 [n, H, W, 3] (x = u / 127.5 - 1) or f32 [n, 3, H, W] in [-1, 1]; the scaling layer (x - shift) / scale is applied
+int launch_lpips_stem(int dtype, const uint8_t* rgb8_a, const uint8_t* rgb8_b, const float* img_a, const float* img_b,
+                      void* out, int n, int H, int W, int Kp, hipStream_t stream);
+int launch_lpips_im2col(int dtype, const void* in, void* out, int Nb, int H, int W, int C, int k, int stride, int pad,
+                        int Kp, hipStream_t stream);
+int launch_lpips_maxpool(int dtype, const void* in, void* out, int Nb, int H, int W, int C, hipStream_t stream);
+int launch_lpips_relu(int dtype, const void* in, void* out, int64_t count, hipStream_t stream);  // out = max(0, in)
+// distance head: per pair i and tap t, mean over the map of sum_c w[c] (a / (|a| + 1e-10) - b / (|b| + 1e-10))^2 with
+// a = max(0, y[i]), b = max(0, y[n + i]) of y T [2n, HW, C], w T [C]; dist f32 [n] = the five taps added in order,
+// per_layer f32 [n, 5] (may be NULL).  A workgroup sums LPIPS_HEAD_POS positions; `partial`: n * blk0[5] floats.
+// The order of every sum follows from (HW, C) alone.
+constexpr int LPIPS_HEAD_POS = 256;
+struct LpipsHeadTaps {
+  const void* y[5];
+  const void* w[5];
+  int HW[5], C[5];
+  int blk0[6];  // first workgroup of each tap, blk0[5] = all of them (lpips_head_plan)
+};
+void lpips_head_plan(LpipsHeadTaps& taps);
+int launch_lpips_head(int dtype, const LpipsHeadTaps& taps, int n, float* partial, float* dist, float* per_layer,
+                      hipStream_t stream);
+
 // ---------------------------------------------------------------------------------------------------------------
 // LoRA skinny kernels (rank r <= 32)
 // ---------------------------------------------------------------------------------------------------------------

@@ -521,3 +521,54 @@ def load_clip(name: str):
         return model, CLIPTokenizer.from_pretrained(name), vc.image_size
     raise ValueError(f"cannot load '{name}': no network in this environment; pass a local transformers directory or "
                      f"synthetic://tiny_clip | synthetic://vit_b32 | synthetic://vit_l14")
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# LPIPS (AlexNet) for scoring a sweep (reference: eval-scripts/lpip_score.py builds lpips.LPIPS(net='alex') from the hub)
+# ----------------------------------------------------------------------------------------------------------------
+TINY_ALEX_CHANNELS = (16, 24, 32, 24, 16)  # multiples of 8 (the kernels' limit), all different from their neighbours
+
+
+def _read_state_file(path: str):
+    """A state dict from `.safetensors`, or from `.pth` with the safe unpickler only (weights_only=True)."""
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+        return load_file(path)
+    if path.endswith(".pth"):
+        return torch.load(path, map_location="cpu", weights_only=True)
+    raise ValueError(f"'{path}': state dicts are read from .safetensors or .pth files")
+
+
+def load_lpips(name: str):
+    """The `lpips.LPIPS(net='alex')` container for `lpips_score`: `synthetic://alex | tiny_alex` with seeded weights, or
+    the released weights from local files -- a directory, or two files joined by a comma -- that together hold an AlexNet
+    state dict (torchvision's `features.*` names or the package's `net.slice*` names) and the `lin` weights
+    (`lin{0..4}.model.1.weight`).  Files are merged in sorted order; every parameter must be found."""
+    from . import lpips as PL
+    if name.startswith("synthetic://"):
+        kind = name[len("synthetic://"):]
+        if kind not in ("alex", "tiny_alex"):
+            raise ValueError(f"unknown synthetic LPIPS '{name}': synthetic://alex | tiny_alex")
+        return PL.init_synthetic_(PL.LPIPS(PL.ALEX_CHANNELS if kind == "alex" else TINY_ALEX_CHANNELS), seed=17)
+    if os.path.isdir(name):
+        files = sorted(os.path.join(name, f) for f in os.listdir(name) if f.endswith((".safetensors", ".pth")))
+    else:
+        files = [f for f in name.split(",") if f]
+    if not files or not all(os.path.isfile(f) for f in files):
+        raise ValueError(f"cannot load LPIPS from '{name}': no network in this environment; pass a local directory, two "
+                         f"files joined by a comma, or synthetic://alex | synthetic://tiny_alex")
+    merged = {}
+    for f in files:
+        merged.update(PL.canonical_state_dict(_read_state_file(f)))
+    want = [f"{c}.weight" for c in PL.conv_names()]
+    missing = [k for k in want if k not in merged]
+    if missing:
+        raise ValueError(f"cannot load LPIPS from '{name}': no AlexNet convolution {missing[0]} (or its torchvision name) "
+                         f"in {files}")
+    model = PL.LPIPS(tuple(int(merged[k].shape[0]) for k in want))
+    model.load_state_dict(merged, strict=False)
+    have = set(merged)
+    lost = [k for k, _ in model.named_parameters() if k not in have]
+    if lost:
+        raise ValueError(f"cannot load LPIPS from '{name}': {lost} not found in {files}")
+    return model
