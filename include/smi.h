@@ -284,6 +284,39 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
                            const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                            const float* lora_up_flat, const float* multipliers, int save_for_backward, float* eps_out);
 
+/* SLIDER COMPOSITION: several sliders in one pass, one scale per (adapted sample, slider).  The engine's adaptor is the
+ * sliders STACKED along the rank axis (smi_lora_stack): every Linear site has rank sum(ranks) and site scale 1, alpha_k / r_k
+ * is folded into lora_up, and slider k owns ranks[k] consecutive rank columns, so that
+ *     y_i = W x_i + sum_k multipliers[i][k] * (alpha_k / r_k) * up_k(down_k(x_i))
+ * is the rank-sum(ranks) delta with the columns of xa = x down^T multiplied per sample.  `ranks`: host int[n_sliders];
+ * `multipliers`: host float[n_adapted][n_sliders].  Inference only: nothing is saved, and a smi_unet_backward after it fails
+ * as after any pass that saved nothing.  Errors: sum(ranks) differs from the rank of a Linear site; n_adapted outside
+ * 1..1024; n_sliders outside 1..16, sum(ranks) > 64 or n_adapted * sum(ranks) > 3072 (the table); any conv (c3lier) or DoRA
+ * site (the engine does not scale a conv xa per sample, the restriction of smi_unet_forward_multi: such a caller folds the
+ * scales into lora_up and runs plain passes).  It also drops a pass saved earlier. */
+int smi_unet_forward_compose(smi_engine* e, int n, int n_adapted, const float* sample, float timestep, const void* ctx,
+                             const void* text_embeds, const float* time_ids, const float* lora_down_flat,
+                             const float* lora_up_flat, int n_sliders, const int* ranks, const float* multipliers,
+                             float* eps_out);
+
+/* One (site, slider) block of the stacked flat buffers: dst_down[c0 + q][0..row_len) = src_down[q][.] (rows of `in` floats
+ * for a Linear site, Cin * kh * kw for a conv site) and dst_up[n][c0 + q] = coef * src_up[n][q] for n < n_out (one fp32
+ * multiply); dst_down / dst_up are the SITE's stacked matrices [R][row_len] / [n_out][R].  src_down == src_up == NULL: the
+ * slider does not adapt the site and its block is written as zeros. */
+typedef struct smi_lora_stack_job {
+  const float* src_down;
+  const float* src_up;
+  float* dst_down;
+  float* dst_up;
+  int64_t row_len;
+  int r, c0, R, n_out;
+  float coef;
+  int reserved;
+} smi_lora_stack_job;
+/* All jobs in one launch.  jobs_dev: device memory for the table, n_jobs * sizeof(smi_lora_stack_job) bytes.
+ * Synchronises. */
+int smi_lora_stack(const smi_lora_stack_job* jobs, int n_jobs, void* jobs_dev, void* stream);
+
 /* Backward of the last save_for_backward forward: accumulates (+=) d(loss)/d(lora_down), d(loss)/d(lora_up) into
  * the flat fp32 gradient buffers (same offsets as the parameters).  Activation gradients are propagated only as far
  * as the first adapted layer; no frozen-weight gradients exist (unet.requires_grad_(False), train_lora.py:69).
@@ -424,6 +457,10 @@ int smi_op_lora_down(int dtype, const void* x, const float* a, float* xa, int m,
 /* out[m, r] (fp32) = x[m, k] * s[r, k]^T on 16-bit operands, r = 16 or 32, k % 128 == 0: the engine's kernel for
  * xa = x * lora_down^T and dxa = dy * lora_up (T/lora.py:134-138 and its backward) on the 16-bit shadow parameters */
 int smi_op_lora_skinny(int dtype, const void* x, const void* s, float* out, int m, int r, int k, void* stream);
+/* smi_op_lora_skinny, then out[i][c] *= col_mul[(i / rows_per_mul) * ld_mul + c % period] (one fp32 multiply after the
+ * fixed-order reduction): the column multipliers of a slider stack */
+int smi_op_lora_skinny_cols(int dtype, const void* x, const void* s, float* out, int m, int r, int k, const float* col_mul,
+                            int ld_mul, int period, int rows_per_mul, void* stream);
 /* dw[r, k] += alpha * p[m, r]^T x[m, k]: the engine's grouped weight-gradient reduction (T/lora.py:134-138 backward)
  * run on a one-job table.  scratch: ceil(m / 64) * r * k + 256 floats (partials + the table). */
 int smi_op_lora_wgrad(int dtype, const float* p, const void* x, float* dw, int m, int k, int r, float alpha,
@@ -511,6 +548,9 @@ int smi_op_grad_scale(const float* d_eps, int n_samples, int64_t per_sample, flo
 int smi_op_cast_f32(int dtype, const float* src, void* dst, int64_t n, void* stream);
 /* x[m][0..n) (fp32, row stride ld) *= row_mul[m / rows_per_mul] */
 int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream);
+/* x[i][j] (fp32, row stride ld) *= col_mul[(i / rows_per_mul) * ld_mul + j % period] for j < n */
+int smi_op_col_scale_f32(float* x, int ld, int m, int n, const float* col_mul, int ld_mul, int period, int rows_per_mul,
+                         void* stream);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,13 @@ class LoraPrepSiteC(C.Structure):
                 ("dst_gw", C.c_int64)]
 
 
+class LoraStackJobC(C.Structure):
+    """include/smi.h smi_lora_stack_job: one (site, slider) block of the rank-stacked flat buffers."""
+    _fields_ = [("src_down", C.c_void_p), ("src_up", C.c_void_p), ("dst_down", C.c_void_p), ("dst_up", C.c_void_p),
+                ("row_len", C.c_int64), ("r", C.c_int), ("c0", C.c_int), ("R", C.c_int), ("n_out", C.c_int),
+                ("coef", C.c_float), ("reserved", C.c_int)]
+
+
 _lib = None
 
 _SIGS = {
@@ -99,6 +106,10 @@ _SIGS = {
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_forward_multi": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
                                          C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_float), C.c_int, C.c_void_p]),
+    "smi_unet_forward_compose": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_int),
+                                           C.POINTER(C.c_float), C.c_void_p]),
+    "smi_lora_stack": (C.c_int, [C.POINTER(LoraStackJobC), C.c_int, C.c_void_p, C.c_void_p]),
     "smi_destroy": (None, [C.c_void_p]),
     "smi_weights_bytes": (C.c_int, [C.POINTER(UNetConfigC), C.POINTER(LoraSiteC), C.c_int, C.POINTER(C.c_size_t)]),
     "smi_arena_bytes": (C.c_int, [C.POINTER(UNetConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int, C.c_int,
@@ -166,6 +177,8 @@ _SIGS = {
     "smi_op_gemm_geglu": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "smi_op_lora_down": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "smi_op_lora_skinny": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "smi_op_lora_skinny_cols": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p] + [C.c_int] * 3 +
+                                [C.c_void_p]),
     "smi_op_lora_wgrad": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_void_p,
                                                                                    C.c_void_p]),
     "smi_op_lora_wgrad_jobs_floats": (C.c_int, [C.POINTER(WgradJobC), C.c_int, C.POINTER(C.c_size_t)]),
@@ -182,6 +195,8 @@ _SIGS = {
     "smi_op_grad_scale": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "smi_op_cast_f32": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]),
     "smi_op_row_scale_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "smi_op_col_scale_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                       C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = sorted(_SIGS)
@@ -409,6 +424,24 @@ class Engine(_EngineBase):
         check(lib().smi_unet_forward_batched(self.handle, n, na, ptr(sample), float(timestep), ptr(ctx),
                                              ptr(text_embeds), ptr(time_ids), ptr(lora_down), ptr(lora_up),
                                              float(multiplier), int(save), ptr(eps)), "smi_unet_forward_batched")
+        return eps
+
+    def forward_compose(self, sample: torch.Tensor, timestep: float, ctx: torch.Tensor, text_embeds, time_ids, lora_down,
+                        lora_up, ranks: Sequence[int], multipliers: Sequence[Sequence[float]],
+                        n_adapted: Optional[int] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """smi_unet_forward_compose: `forward` with a stacked adaptor (compose.SliderStack) and one multiplier per
+        (adapted sample, slider) -- `multipliers`: n_adapted rows of len(ranks) floats.  Inference only (nothing saved)."""
+        n = sample.shape[0]
+        na = min(n, self.batch_adapted) if n_adapted is None else n_adapted
+        k = len(ranks)
+        if len(multipliers) != na or any(len(row) != k for row in multipliers):
+            raise SmiError(f"multipliers must be {na} rows (adapted samples) of {k} floats (sliders)")
+        eps = out if out is not None else torch.empty(sample.shape, dtype=torch.float32, device=sample.device)
+        rk = (C.c_int * max(k, 1))(*[int(r) for r in ranks])
+        arr = (C.c_float * max(na * k, 1))(*[float(m) for row in multipliers for m in row])
+        check(lib().smi_unet_forward_compose(self.handle, n, na, ptr(sample), float(timestep), ptr(ctx), ptr(text_embeds),
+                                             ptr(time_ids), ptr(lora_down), ptr(lora_up), k, rk, arr, ptr(eps)),
+              "smi_unet_forward_compose")
         return eps
 
     def backward(self, d_eps: torch.Tensor, d_down: torch.Tensor, d_up: torch.Tensor):

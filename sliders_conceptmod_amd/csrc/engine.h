@@ -161,6 +161,16 @@ struct smi_engine {
   const float* samp_ptr(bool bwd) const {
     return (bwd ? bw_samp_on : samp_on) ? samp_mult_dev + (bwd ? MAXS + bw_skip : 0) : nullptr;
   }
+  // slider composition (smi_unet_forward_compose): one multiplier per (adapted sample, rank column of the stacked adaptor),
+  // applied to the columns of xa = x down^T -- table [n_adapted][col_ld] on the device, column c of a site's xa reads entry
+  // c % col_period (a fused q|k|v lays xa out segment-major).  Forward only: a compose pass saves nothing and drops any
+  // saved pass, so the table lives in the loss-scale block `gscale`, which only a backward writes and reads (it rewrites
+  // the block before its first read): the workspace layout is what it was without composition.
+  static constexpr int MAX_STACK_RANK = 64, MAX_SLIDERS = 16;  // (COL_TABLE_FLOATS: next to gscale, below)
+  float* col_table() const { return gscale; }
+  bool col_on = false;
+  int col_ld = 0, col_period = 0;
+  std::vector<int> lin_site_ranks;  // rank of every adapted Linear (fused group): a stack's must all be sum r_k
   std::vector<const void*> pinned;
   // X, P and M describe the rows the backward runs on; in a tail backward the job is still planned over the rows of all
   // adapted samples, so that its sums are those of the full job (WgradJob::m_begin)
@@ -203,6 +213,9 @@ struct smi_engine {
   Arena* cur = nullptr;
   // per-sample power-of-two loss scales: [0, MAXS) scale of adapted sample j, [MAXS, 2 MAXS) its inverse, then scratch
   static constexpr int MAXS = 1024;
+  static constexpr int GSCALE_FLOATS = 3 * MAXS + 258;  // + [2 MAXS..): min, 1/min, min / scale_j (DoRA)
+  static constexpr int COL_TABLE_FLOATS = 3 * MAXS;     // the compose table borrows the block
+  static_assert(COL_TABLE_FLOATS <= GSCALE_FLOATS, "the compose table must fit the loss-scale block");
   float* gscale = nullptr;
 
   std::unordered_map<std::string, const smi_weight*> wmap;
@@ -574,6 +587,7 @@ struct smi_engine {
     }
     L.nsite = found;
     L.rank = first->rank;
+    lin_site_ranks.push_back(first->rank);
     L.scale = first->scale;
     L.off_down = first->off_down;
     L.off_up = first->off_up;
@@ -794,7 +808,17 @@ struct smi_engine {
   // out[M, R] (fp32, dense) = X[M, K] * S[R, K]^T against a 16-bit LoRA shadow S: xa = x down^T and dxa = dy up.  The skinny
   // kernel where it takes the shape, else a GEMM (+ the per-sample multipliers `row_mul` as a launch of their own)
   void skinny_product(const void* X, int64_t ldx, const void* S, float* out, int M, int R, int K, double flops,
-                      const float* row_mul, bool tagged, const char* what) {
+                      const float* row_mul, bool tagged, const char* what, bool cols = false) {
+    if (cols && !dry) {  // a slider stack's column table instead of row_mul: same two routes
+      if (lora_skinny_supported(X, ldx, S, out, R, M, R, K)) {
+        RUNP(SMI_PROF_LORA, flops, 0.0,
+             launch_lora_skinny_cols(dtype, X, ldx, S, out, R, M, R, K, col_table(), col_ld, col_period, rows_per_ad(M), stream));
+        return;
+      }
+      run_gemm(SMI_PROF_LORA, gemm_nt(dtype, X, ldx, S, out, R, M, R, K).f32_out(), flops, 0.0, tagged, what);
+      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_col_scale_f32(out, R, M, R, col_table(), col_ld, col_period, rows_per_ad(M), stream));
+      return;
+    }
     if (dry || lora_skinny_supported(X, ldx, S, out, R, M, R, K)) {
       RUNP(SMI_PROF_LORA, flops, 0.0,
            launch_lora_skinny(dtype, X, ldx, S, out, R, M, R, K, stream, row_mul, rows_per_ad(M)));
@@ -813,7 +837,7 @@ struct smi_engine {
     if (lon && !L.dora) {  // xa[M, rows_pad] = x * down^T as one MFMA GEMM on the 16-bit shadow copy (fp32 result)
       xa = alloc_f32((size_t)MA(x) * L.rows_pad);
       skinny_product(PA(x), x->cols, shadow_ptr(L.sh_down), xa, (int)MA(x), L.rows_pad, L.in,
-                     2.0 * (int)MA(x) * rtot * L.in, samp_ptr(false), true, "linear xa");
+                     2.0 * (int)MA(x) * rtot * L.in, samp_ptr(false), true, "linear xa", col_on);
     }
     GemmParams p = gemm_nt(dtype, x->p, x->cols, L.W, y->p, L.out, (int)x->rows, L.out, L.in).with_bias(L.b);
     if (res) p.with_res(res->p, res->cols);

@@ -16,6 +16,19 @@ __global__ void set_floats_kernel(float* dst0, float* dst1, F64Args a, int n) {
     if (dst1) dst1[i] = a.v[i];
   }
 }
+// the column table of a slider stack, rows [row0, row0 + rows) of dst [.][ld]: column c of sample i gets the multiplier of
+// the slider that owns rank column c (sliders in order, ranks.v[k] columns each); a.v = multipliers[rows][n_sliders]
+struct I16Args {
+  int v[16];
+};
+__global__ void col_table_kernel(float* dst, int ld, int row0, int rows, int n_sliders, I16Args ranks, F64Args a) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= rows * ld) return;
+  const int s = i / ld, c = i - s * ld;
+  int k = 0, end = ranks.v[0];
+  while (c >= end && k + 1 < n_sliders) end += ranks.v[++k];
+  dst[(int64_t)(row0 + s) * ld + c] = a.v[s * n_sliders + k];
+}
 __global__ void fill_kernel(float* p, float v, int n) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -55,6 +68,7 @@ struct UNet : Model {
   // grouped cross-attention K|V projection: every block's to_k|to_v stacked into one [sum N, D_ctx] matrix
   Lin kv_all;
   bool kv_grouped = false;
+  bool kv_adapted = false;  // some to_k / to_v carries an adaptor: its weight gradient reads the context itself
   Ten* kv_all_out = nullptr;
   // gradient with respect to the context (smi_unet_ctx_grad_*, smi_unet_backward_ctx).  The transposed k|v weights it needs
   // and the larger saved-pass arena live in a buffer of the caller's (`xpack` + arena 1), so that engines that never ask
@@ -182,7 +196,7 @@ struct UNet : Model {
     build_kv_group(e);
     build_temb_group(e);
     e.finish_lora();
-    e.gscale = (float*)e.pack_alloc((3 * e.MAXS + 258) * sizeof(float));  // + [2 MAXS..): min, 1/min, min / scale_j (DoRA)
+    e.gscale = (float*)e.pack_alloc(e.GSCALE_FLOATS * sizeof(float));
     e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
     splitk_ws = e.pack_alloc(SPLITK_WS_BYTES);  // fp32 slabs of the split-K launches (gemm.hip: S x tiles <= 384 tiles)
     wjobs_cap = 11 * (e.sites.size() + 8);  // a conv site pushes 10 jobs (d_up + one d_down job per filter tap)
@@ -212,6 +226,7 @@ struct UNet : Model {
       total += tb.kv2.out;
       any_lora |= tb.kv2.nsite > 0;
     });
+    kv_adapted = any_lora;
     kv_grouped = !any_lora && total > 0 && total * (int64_t)cfg.cross_attention_dim * 2 < 0xFFFFFFF0ll;
     if (!kv_grouped) return;
     const int D = cfg.cross_attention_dim;
@@ -370,6 +385,14 @@ struct UNet : Model {
     ctx->cols = cfg.cross_attention_dim;
     ctx->n = n;
     ctx->arow0 = (int64_t)(n - e.n_ad) * ctx_len;
+    // The backward of adapted to_k / to_v reads the context again (d(down) = dxa^T ctx), possibly long after this call
+    // returned: the saved pass keeps its own copy, so that it does not matter what the caller does with its buffer in
+    // between (a temporary handed to the forward is free for reuse as soon as the call returns).
+    if (save && kv_adapted && (e.dry || (e.lora_down && e.lora_up && e.mult != 0.f))) {
+      void* own = e.alloc_t(ctx->rows, ctx->cols);
+      RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(e.dtype, ctxp, ctx->cols, own, ctx->cols, 0, (int)ctx->rows, ctx->cols, e.stream));
+      ctx->p = own;
+    }
 
     if (kv_grouped) kv_all_out = e.linear(ctx, kv_all);
     const bool ctx_grad = save && ctx_want && e.n_ad > 0;
@@ -813,6 +836,56 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
   const int rc = smi_unet_forward_batched(e, n, n_adapted, sample, timestep, ctx, text_embeds, time_ids, lora_down_flat,
                                           lora_up_flat, mref, save_for_backward, eps_out);
   e->samp_on = false;
+  return rc;
+}
+
+int smi_unet_forward_compose(smi_engine* e, int n, int n_adapted, const float* sample, float timestep, const void* ctx,
+                             const void* text_embeds, const float* time_ids, const float* lora_down_flat,
+                             const float* lora_up_flat, int n_sliders, const int* ranks, const float* multipliers,
+                             float* eps_out) {
+  SMI_CHECK(e && ranks && multipliers && lora_down_flat && lora_up_flat, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: no UNet forward");
+  SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "slider composition: 1..%d adapted samples, got %d",
+            smi_engine::MAXS, n_adapted);
+  SMI_CHECK(n_sliders >= 1 && n_sliders <= smi_engine::MAX_SLIDERS, "slider composition: 1..%d sliders, got %d",
+            smi_engine::MAX_SLIDERS, n_sliders);
+  int R = 0;
+  I16Args rk;
+  for (int k = 0; k < 16; ++k) rk.v[k] = 0;
+  for (int k = 0; k < n_sliders; ++k) {
+    SMI_CHECK(ranks[k] >= 1, "slider composition: rank %d of slider %d", ranks[k], k);
+    rk.v[k] = ranks[k];
+    R += ranks[k];
+  }
+  SMI_CHECK(R <= smi_engine::MAX_STACK_RANK, "slider composition: stacked rank %d exceeds %d", R, smi_engine::MAX_STACK_RANK);
+  for (int r : e->lin_site_ranks)
+    SMI_CHECK(r == R, "slider composition: the ranks sum to %d but a Linear site of this engine has rank %d (its sites must be "
+                      "the stacked ones, every slider's block present)", R, r);
+  SMI_CHECK(e->n_conv_sites == 0 && e->dora_sites.empty(),
+            "slider composition: the multiplier table is implemented for Linear LoRA sites (attention projections, "
+            "time_emb_proj, conv_shortcut); this network has conv or DoRA sites -- fold the scales into lora_up and run "
+            "samples of different scales in separate plain passes");
+  SMI_CHECK((int64_t)n_adapted * R <= smi_engine::COL_TABLE_FLOATS,
+            "slider composition: %d adapted samples x stacked rank %d exceed the %d entries of the multiplier table", n_adapted,
+            R, smi_engine::COL_TABLE_FLOATS);
+  UNet* u = unet(e);
+  u->drop_tape(*e);  // inference only: no earlier saved pass answers a backward after this one
+  // the table travels in kernel arguments, 64 multipliers per launch, ordered on the engine's stream (as the per-sample
+  // ratios of smi_unet_forward_multi do: no asynchronous copy from pageable memory)
+  const int per = 64 / n_sliders;
+  for (int i0 = 0; i0 < n_adapted; i0 += per) {
+    const int cnt = n_adapted - i0 < per ? n_adapted - i0 : per;
+    F64Args a;
+    for (int i = 0; i < 64; ++i) a.v[i] = i < cnt * n_sliders ? multipliers[i0 * n_sliders + i] : 0.f;
+    hipLaunchKernelGGL(col_table_kernel, dim3((cnt * R + 255) / 256), dim3(256), 0, e->stream, e->col_table(), R, i0, cnt,
+                       n_sliders, rk, a);
+  }
+  SMI_HIP(hipGetLastError());
+  e->col_on = true;
+  e->col_ld = e->col_period = R;
+  const int rc = smi_unet_forward_batched(e, n, n_adapted, sample, timestep, ctx, text_embeds, time_ids, lora_down_flat,
+                                          lora_up_flat, 1.f, 0, eps_out);
+  e->col_on = false;
   return rc;
 }
 

@@ -370,6 +370,26 @@ int launch_row_scale_f32(float* x, int ld, int M, int N, const float* row_mul, i
 bool lora_skinny_supported(const void* X, int64_t ldx, const void* S, const float* out, int ldo, int M, int R, int K);
 int launch_lora_skinny(int dtype, const void* X, int64_t ldx, const void* S, float* out, int ldo, int M, int R, int K,
                        hipStream_t stream, const float* row_mul = nullptr, int rows_per_mul = 1);
+// the same product with one multiplier per (sample, column): out[m][c] *= col_mul[(m / rows_per_mul) * ld_mul + c % period]
+// after the fixed-order reduction (one fp32 multiply); for the shapes launch_lora_skinny takes
+int launch_lora_skinny_cols(int dtype, const void* X, int64_t ldx, const void* S, float* out, int ldo, int M, int R, int K,
+                            const float* col_mul, int ld_mul, int period, int rows_per_mul, hipStream_t stream);
+// x[m][n] *= col_mul[(m / rows_per_mul) * ld_mul + n % period] for n < N: that table on the shapes the kernel above refuses
+int launch_col_scale_f32(float* x, int ld, int M, int N, const float* col_mul, int ld_mul, int period, int rows_per_mul,
+                         hipStream_t stream);
+// slider composition: one (site, slider) block of the rank-stacked flat buffers (lora.hip lora_stack_kernel); the layout of
+// smi_lora_stack_job
+struct LoraStackJob {
+  const float* src_down;  // [r][row_len], NULL: the slider does not adapt the site -- its block is written as zeros
+  const float* src_up;    // [n_out][r], NULL with src_down
+  float* dst_down;        // the site's stacked down [R][row_len]
+  float* dst_up;          // the site's stacked up [n_out][R]
+  int64_t row_len;        // floats per lora_down row: `in` (Linear), Cin * kh * kw (conv)
+  int r, c0, R, n_out;    // the slider's rank at the site, its first rank column, the stacked rank, rows of lora_up
+  float coef;             // folded into up: alpha / r, or scale * alpha / r
+  int pad_;
+};
+int launch_lora_stack(const LoraStackJob* jobs_dev, int n_jobs, hipStream_t stream);
 // ---- DoRA (T/dora.py:124-162): dW = (W + up down) * (g / ||W + up down||_col) - W per adapted Linear (fused segments share W)
 struct DoraSite {
   const void* W;                       // frozen [nseg * cs, K], 16-bit

@@ -317,16 +317,36 @@ int launch_lora_prep(int dtype, const void* sites_dev, int n_sites, const float*
 // four partial tiles meet in LDS: one memory round trip per launch, M/16 workgroups.
 // Operand maps as in the GEMMs: mfma16(S frag, X frag) -> lane (fr = l & 15, fq = l >> 4) holds out[m = fr][n = 4 fq + j].
 // ---------------------------------------------------------------------------------------------------------------
-template <typename T, int NF, int STEPS>  // NF = R / 16 column fragments, STEPS = 32-deep K-steps per wave and chunk
+// COLS (a compile-time switch: the plain and row_mul forms keep the code they had): one multiplier per (sample, column) --
+// `row_mul` is then a table, out[m][c] *= row_mul[(m / rows_per_mul) * ld_mul + c % period] (slider composition: the columns of a
+// stacked adaptor belong to different sliders, and a fused q|k|v lays them out segment-major, so the owner is periodic)
+template <bool COLS>
+struct SkinnyCols {};  // the plain and row_mul forms carry nothing
+template <>
+struct SkinnyCols<true> {
+  int ld_mul, period;
+};
+template <typename T, int NF, int STEPS, bool COLS = false>  // NF = R / 16 column fragments, STEPS = 32-deep K-steps per wave and chunk
 __global__ __launch_bounds__(256) void lora_skinny_kernel(const T* __restrict__ X, int64_t ldx, const T* __restrict__ S,
                                                           float* __restrict__ out, int ldo, int M, int K,
-                                                          const float* __restrict__ row_mul, int rows_per_mul) {
+                                                          const float* __restrict__ row_mul, int rows_per_mul,
+                                                          SkinnyCols<COLS> cols = {}) {
   __shared__ f32x4 red[3][NF][64];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int fr = lane & 15, fq = lane >> 4;
   const int m0 = blockIdx.x * 16;
   const int m = min(m0 + fr, M - 1);           // rows past M are clamped; their results are not stored
+  float cm[NF][4];
+  if constexpr (COLS) {  // requested before the operand loads: the launch stays ONE memory round trip
+    if (wave == 0) {     // wave-uniform: only wave 0 stores
+      const float* mrow = row_mul + (int64_t)(m / rows_per_mul) * cols.ld_mul;
+#pragma unroll
+      for (int f = 0; f < NF; ++f)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) cm[f][j] = mrow[(f * 16 + fq * 4 + j) % cols.period];
+    }
+  }
   const int kw = K >> 2;                       // K range of this wave: [wave * kw, (wave + 1) * kw)
   const T* xp = X + (int64_t)m * ldx + wave * kw + fq * 8;
   const T* sp = S + (int64_t)fr * K + wave * kw + fq * 8;
@@ -370,7 +390,12 @@ __global__ __launch_bounds__(256) void lora_skinny_kernel(const T* __restrict__ 
         v[2] += o[2];
         v[3] += o[3];
       }
-      if (row_mul) {  // per-sample adaptor multipliers (image sliders: +s / -s in one pass): out row *= m[sample] / m_ref
+      if constexpr (COLS) {
+        v[0] *= cm[f][0];
+        v[1] *= cm[f][1];
+        v[2] *= cm[f][2];
+        v[3] *= cm[f][3];
+      } else if (row_mul) {  // per-sample adaptor multipliers (image sliders: +s / -s in one pass): out row *= m[sample] / m_ref
         const float rm = row_mul[(m0 + fr) / rows_per_mul];
         v[0] *= rm;
         v[1] *= rm;
@@ -400,6 +425,29 @@ int launch_row_scale_f32(float* x, int ld, int M, int N, const float* row_mul, i
   return 0;
 }
 
+// out[m, n] *= col_mul[(m / rows_per_mul) * ld_mul + n % period]: the per-(sample, column) multipliers of a slider stack
+// for shapes the skinny kernel does not take (same table as lora_skinny_kernel's COLS form)
+__global__ void col_scale_f32_kernel(float* __restrict__ x, int ld, int M, int N, const float* __restrict__ col_mul,
+                                     int ld_mul, int period, int rows_per_mul) {
+  const int64_t total = (int64_t)M * N;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int m = (int)(i / N), n = (int)(i - (int64_t)m * N);
+    x[(int64_t)m * ld + n] *= col_mul[(int64_t)(m / rows_per_mul) * ld_mul + n % period];
+  }
+}
+int launch_col_scale_f32(float* x, int ld, int M, int N, const float* col_mul, int ld_mul, int period, int rows_per_mul,
+                         hipStream_t stream) {
+  SMI_CHECK(x && col_mul && rows_per_mul > 0 && M > 0 && N > 0 && ld >= N && period > 0 && ld_mul >= period,
+            "col_scale: bad arguments (M=%d N=%d ld=%d period=%d ld_mul=%d rows_per_mul=%d)", M, N, ld, period, ld_mul,
+            rows_per_mul);
+  const int64_t total = (int64_t)M * N;
+  const int grid = (int)((total + 255) / 256 < 1024 ? (total + 255) / 256 : 1024);
+  hipLaunchKernelGGL(col_scale_f32_kernel, dim3(grid), dim3(256), 0, stream, x, ld, M, N, col_mul, ld_mul, period,
+                     rows_per_mul);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
 bool lora_skinny_supported(const void* X, int64_t ldx, const void* S, const float* out, int ldo, int M, int R, int K) {
   auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
   return (R == 16 || R == 32) && K % 128 == 0 && ldx % 8 == 0 && ldo % 4 == 0 && ldo >= R && M > 0 && al16(X) &&
@@ -418,7 +466,7 @@ int launch_lora_skinny(int dtype, const void* X, int64_t ldx, const void* S, flo
   const int ksteps = (K >> 2) / 32;
 #define GO3(TT_, NF_, ST_)                                                                                       \
   hipLaunchKernelGGL((lora_skinny_kernel<TT_, NF_, ST_>), dim3(grid), dim3(256), 0, stream, (const TT_*)X, ldx, \
-                     (const TT_*)S, out, ldo, M, K, row_mul, rows_per_mul)
+                     (const TT_*)S, out, ldo, M, K, row_mul, rows_per_mul, SkinnyCols<false>{})
 #define GO(TT_, NF_)                         \
   do {                                       \
     if (ksteps == 10) GO3(TT_, NF_, 10);     \
@@ -432,6 +480,91 @@ int launch_lora_skinny(int dtype, const void* X, int64_t ldx, const void* S, flo
   }
 #undef GO
 #undef GO3
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_lora_skinny_cols(int dtype, const void* X, int64_t ldx, const void* S, float* out, int ldo, int M, int R, int K,
+                            const float* col_mul, int ld_mul, int period, int rows_per_mul, hipStream_t stream) {
+  SMI_CHECK(col_mul && rows_per_mul > 0 && period > 0 && ld_mul >= period,
+            "lora_skinny_cols: bad table (period=%d ld_mul=%d rows_per_mul=%d)", period, ld_mul, rows_per_mul);
+  SMI_CHECK(lora_skinny_supported(X, ldx, S, out, ldo, M, R, K), "lora_skinny_cols: unsupported layout (R=%d K=%d)", R, K);
+  const int grid = cdiv(M, 16);
+  const int ksteps = (K >> 2) / 32;  // the instantiations of launch_lora_skinny: same MFMA chain, same bits before the multiply
+#define GO3(TT_, NF_, ST_)                                                                                            \
+  hipLaunchKernelGGL((lora_skinny_kernel<TT_, NF_, ST_, true>), dim3(grid), dim3(256), 0, stream, (const TT_*)X, ldx, \
+                     (const TT_*)S, out, ldo, M, K, col_mul, rows_per_mul, SkinnyCols<true>{ld_mul, period})
+#define GO(TT_, NF_)                         \
+  do {                                       \
+    if (ksteps == 10) GO3(TT_, NF_, 10);     \
+    else if (ksteps == 5) GO3(TT_, NF_, 5);  \
+    else GO3(TT_, NF_, 8);                   \
+  } while (0)
+  if (dtype == DT_F16) {
+    if (R == 16) GO(f16, 1); else GO(f16, 2);
+  } else {
+    if (R == 16) GO(bf16, 1); else GO(bf16, 2);
+  }
+#undef GO
+#undef GO3
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Slider composition: K adaptors stacked along the rank axis into one adaptor of rank R = sum r_k per site.
+// One launch over a job table, one job per (site, slider):
+//   dst_down[c0 + q][0..row_len) = src_down[q][0..row_len)                      (rows of `row_len` floats; zeros without a source)
+//   dst_up[n][c0 + q]            = coef * src_up[n][q]    for n < n_out          (ONE fp32 multiply: no add, nothing to contract)
+// grid (LORA_STACK_WGS, n_jobs); every branch below depends on the job alone, so it is uniform over the workgroup.
+// ---------------------------------------------------------------------------------------------------------------
+namespace {
+constexpr int LORA_STACK_WGS = 8;
+__global__ __launch_bounds__(256) void lora_stack_kernel(const LoraStackJob* __restrict__ jobs) {
+  const LoraStackJob jb = jobs[blockIdx.y];
+  const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, nth = (int64_t)gridDim.x * 256;
+  auto al16 = [](const void* q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
+  // ---- down: r * row_len contiguous floats at row c0 of the stacked matrix
+  const int64_t nd = (int64_t)jb.r * jb.row_len;
+  float* dd = jb.dst_down + (int64_t)jb.c0 * jb.row_len;
+  if ((nd & 3) == 0 && al16(dd) && (!jb.src_down || al16(jb.src_down))) {
+    for (int64_t i = tid; i < (nd >> 2); i += nth)
+      reinterpret_cast<f32x4*>(dd)[i] =
+          jb.src_down ? reinterpret_cast<const f32x4*>(jb.src_down)[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+  } else {
+    for (int64_t i = tid; i < nd; i += nth) dd[i] = jb.src_down ? jb.src_down[i] : 0.f;
+  }
+  // ---- up: n_out rows of r floats, each into columns [c0, c0 + r) of a row of R
+  float* du = jb.dst_up + jb.c0;
+  if (((jb.r | jb.c0 | jb.R) & 3) == 0 && al16(jb.dst_up) && (!jb.src_up || al16(jb.src_up))) {
+    const int rq = jb.r >> 2;
+    for (int64_t i = tid; i < (int64_t)jb.n_out * rq; i += nth) {
+      const int64_t n = i / rq;
+      const int q4 = (int)(i - n * rq);
+      f32x4 v{0.f, 0.f, 0.f, 0.f};
+      if (jb.src_up) {
+        v = reinterpret_cast<const f32x4*>(jb.src_up)[i];
+        v[0] = jb.coef * v[0];
+        v[1] = jb.coef * v[1];
+        v[2] = jb.coef * v[2];
+        v[3] = jb.coef * v[3];
+      }
+      *reinterpret_cast<f32x4*>(du + n * jb.R + 4 * q4) = v;
+    }
+  } else {
+    for (int64_t i = tid; i < (int64_t)jb.n_out * jb.r; i += nth) {
+      const int64_t n = i / jb.r;
+      const int q = (int)(i - n * jb.r);
+      du[n * jb.R + q] = jb.src_up ? jb.coef * jb.src_up[i] : 0.f;
+    }
+  }
+}
+}  // namespace
+
+int launch_lora_stack(const LoraStackJob* jobs_dev, int n_jobs, hipStream_t stream) {
+  if (n_jobs <= 0) return 0;
+  SMI_CHECK(jobs_dev != nullptr, "lora_stack: no job table");
+  hipLaunchKernelGGL(lora_stack_kernel, dim3(LORA_STACK_WGS, n_jobs), dim3(256), 0, stream, jobs_dev);
   SMI_HIP(hipGetLastError());
   return 0;
 }

@@ -154,6 +154,10 @@ int smi_op_lora_down(int dtype, const void* x, const float* a, float* xa, int m,
 int smi_op_lora_skinny(int dtype, const void* x, const void* s, float* out, int m, int r, int k, void* stream) {
   return launch_lora_skinny(dtype, x, k, s, out, r, m, r, k, (hipStream_t)stream);
 }
+int smi_op_lora_skinny_cols(int dtype, const void* x, const void* s, float* out, int m, int r, int k, const float* col_mul,
+                            int ld_mul, int period, int rows_per_mul, void* stream) {
+  return launch_lora_skinny_cols(dtype, x, k, s, out, r, m, r, k, col_mul, ld_mul, period, rows_per_mul, (hipStream_t)stream);
+}
 int smi_op_lora_wgrad(int dtype, const float* p, const void* x, float* dw, int m, int k, int r, float alpha,
                       float* scratch, void* stream) {
   // the engine's grouped reduction with a one-job table (scratch: the job's partials followed by the table itself)
@@ -343,6 +347,38 @@ int smi_op_cast_f32(int dtype, const float* src, void* dst, int64_t n, void* str
 }
 int smi_op_row_scale_f32(float* x, int ld, int m, int n, const float* row_mul, int rows_per_mul, void* stream) {
   return launch_row_scale_f32(x, ld, m, n, row_mul, rows_per_mul, (hipStream_t)stream);
+}
+
+int smi_op_col_scale_f32(float* x, int ld, int m, int n, const float* col_mul, int ld_mul, int period, int rows_per_mul,
+                         void* stream) {
+  return launch_col_scale_f32(x, ld, m, n, col_mul, ld_mul, period, rows_per_mul, (hipStream_t)stream);
+}
+int smi_lora_stack(const smi_lora_stack_job* jobs, int n_jobs, void* jobs_dev, void* stream) {
+  static_assert(sizeof(LoraStackJob) == sizeof(smi_lora_stack_job), "smi_lora_stack_job sizes the device table");
+  SMI_CHECK(jobs && n_jobs >= 1 && jobs_dev, "lora_stack: empty table");
+  std::vector<LoraStackJob> host(n_jobs);
+  for (int i = 0; i < n_jobs; ++i) {
+    const smi_lora_stack_job& s = jobs[i];
+    SMI_CHECK(s.dst_down && s.dst_up && (s.src_down != nullptr) == (s.src_up != nullptr) && s.row_len >= 1 && s.r >= 1 &&
+                  s.c0 >= 0 && s.c0 + s.r <= s.R && s.n_out >= 1,
+              "lora_stack: job %d: row_len=%lld r=%d c0=%d R=%d n_out=%d", i, (long long)s.row_len, s.r, s.c0, s.R, s.n_out);
+    LoraStackJob& h = host[i];
+    memset(&h, 0, sizeof(h));
+    h.src_down = s.src_down;
+    h.src_up = s.src_up;
+    h.dst_down = s.dst_down;
+    h.dst_up = s.dst_up;
+    h.row_len = s.row_len;
+    h.r = s.r;
+    h.c0 = s.c0;
+    h.R = s.R;
+    h.n_out = s.n_out;
+    h.coef = s.coef;
+  }
+  SMI_HIP(hipMemcpyAsync(jobs_dev, host.data(), (size_t)n_jobs * sizeof(LoraStackJob), hipMemcpyHostToDevice, (hipStream_t)stream));
+  const int rc = launch_lora_stack(reinterpret_cast<const LoraStackJob*>(jobs_dev), n_jobs, (hipStream_t)stream);
+  SMI_HIP(hipStreamSynchronize((hipStream_t)stream));  // the host table leaves scope
+  return rc;
 }
 
 }  // extern "C"

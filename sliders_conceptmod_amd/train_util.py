@@ -104,6 +104,74 @@ def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, sca
 
 
 @torch.no_grad()
+def slider_grid_latents(unet, stack, scheduler, latents, text_embeddings, scale_rows, start_noise: int,
+                        guidance_scale: float = 7.5, num_inference_steps: int = 50, added_cond=None,
+                        max_batch: Optional[int] = None):
+    """`slider_sweep_latents` for a list of scale rows (one row of K scales per cell of a grid) on a compose.SliderStack.
+
+    While t > start_noise the adaptor is off and every cell is the same computation: it runs ONCE, on the `num_samples`
+    CFG pairs of `latents`, and is broadcast at the switch.  From there every cell runs in one UNet pass per step: a batch of
+    cells x num_samples x 2 with both CFG halves adapted (as in the reference) and one multiplier row per sample.
+    `max_batch` bounds that UNet batch: the grid is processed in chunks of max(1, max_batch // (2 num_samples)) cells, each
+    chunk on its own copy of the scheduler (a multistep scheduler's history is expanded to the chunk).  Schedulers that draw
+    noise per step (ddpm, euler_a) draw it for the whole chunk at once, so only the deterministic ones (ddim, lms) give a
+    cell the latents it would get on its own.  The scales or grid set on the stack before the call are put back.
+    Returns the final latents [cells, num_samples, C, h, w]."""
+    import copy
+    from .compose import grid_multiplier_rows
+    scheduler.set_timesteps(num_inference_steps)
+    scale_rows = [list(r) for r in scale_rows]
+    if not scale_rows:
+        raise ValueError("slider_grid_latents: no scale rows")
+    ns = latents.shape[0]
+    timesteps = list(scheduler.timesteps)
+    added = added_cond
+
+    def predict(sched, t, lat, te, add):
+        if add is None:
+            return predict_noise(unet, sched, t, lat, te, guidance_scale=guidance_scale)
+        return predict_noise_xl(unet, sched, t, lat, te, add[0], add[1], guidance_scale=guidance_scale)
+
+    k0 = 0
+    while k0 < len(timesteps) and timesteps[k0] > start_noise:  # adaptor off: shared by every cell
+        noise_pred = predict(scheduler, timesteps[k0], latents, text_embeddings, added)
+        latents = scheduler.step(noise_pred, timesteps[k0], latents).prev_sample
+        k0 += 1
+    per = len(scale_rows) if max_batch is None else max(1, int(max_batch) // (2 * ns))
+    if getattr(stack, "fold", False):  # conv sites: the scales live in lora_up, one cell per pass
+        per = 1
+    else:  # the engine's multiplier table bounds the samples of a pass
+        if 2 * ns > stack.max_samples:
+            raise ValueError(f"one cell is {2 * ns} samples, but a pass of this stack takes at most {stack.max_samples} "
+                             f"(the multiplier table: {stack.max_samples} x rank {sum(stack.ranks)}); lower num_samples")
+        per = min(per, stack.max_samples // (2 * ns))
+    saved = stack.scale_state()
+    unc, cond = text_embeddings.chunk(2)
+    out = []
+    for c0 in range(0, len(scale_rows), per):
+        rows = scale_rows[c0:c0 + per]
+        c = len(rows)
+        sched = copy.deepcopy(scheduler)
+        if getattr(sched, "derivatives", None):
+            sched.derivatives = [d.repeat(c, 1, 1, 1) for d in sched.derivatives]
+        lat = latents.repeat(c, 1, 1, 1)
+        te = torch.cat([unc.repeat(c, 1, 1), cond.repeat(c, 1, 1)])
+        add = None
+        if added is not None:
+            pu, pc = added[0].chunk(2)
+            tu, tc = added[1].chunk(2)
+            add = (torch.cat([pu.repeat(c, 1), pc.repeat(c, 1)]), torch.cat([tu.repeat(c, 1), tc.repeat(c, 1)]))
+        stack.set_scale_grid(grid_multiplier_rows(rows, ns))
+        for t in timesteps[k0:]:
+            with stack:
+                noise_pred = predict(sched, t, lat, te, add)
+            lat = sched.step(noise_pred, t, lat).prev_sample
+        out.append(lat.view(c, ns, *lat.shape[1:]))
+    stack.restore_scale_state(saved)
+    return torch.cat(out)
+
+
+@torch.no_grad()
 def get_noisy_image(img, vae, generator, unet, scheduler, total_timesteps: int = 1000, start_timesteps=0, **kwargs):
     """Image-slider front end (trainscripts/imagesliders/train_util.py:200-235), same signature and order of operations:
     preprocess -> vae.encode(image).latent_dist.sample(None) -> x vae.config.scaling_factor -> noise = randn(shape,

@@ -339,6 +339,14 @@ class UNet2DConditionModel(nn.Module):
         flat, n_down, mult = None, 0, 0.0
         if net is not None:
             flat, n_down, mult = net.engine_params()
+        if getattr(net, "engine_compose", None) is not None:  # a compose.SliderStack: inference only
+            net.check_inference(sample, ehs)
+            grid = net.engine_compose(n)
+            if grid is not None:  # one multiplier per (sample, slider): smi_unet_forward_compose, nothing saved
+                ranks, rows = grid
+                eps = eng.forward_compose(sample.float().contiguous(), t, ehs.detach().to(eng.dtype).contiguous(),
+                                          text_embeds, time_ids, flat[:n_down], flat[n_down:], ranks, rows, n_adapted=n)
+                return UNetOutput(eps)
         lora_grad = bool(torch.is_grad_enabled() and mult != 0 and flat is not None and flat.requires_grad)
         # an embedding that requires a gradient (null-text optimisation) is differentiated with or without a LoRA network
         ctx_grad = bool(torch.is_grad_enabled() and ehs.requires_grad)
