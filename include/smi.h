@@ -208,6 +208,33 @@ int smi_clip_create(const smi_clip_config* cfg, const smi_weight* weights, int n
 int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
                     void* penultimate, void* pooled);
 
+/* smi_clip_encode with one more optional output: last_layer_out T [n, L, hidden] = hidden_states[-1], the last layer's output
+ * WITHOUT the final norm (what conceptmod/notrigger/train_notrigger.py:241 reads). */
+int smi_clip_encode_layers(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
+                           void* penultimate, void* pooled, void* last_layer_out);
+
+/* ---- CLIP text tower with LoRA sites (the no-trigger text-encoder trainer) --------------------------------------------
+ * The same tower, created with Linear LoRA sites (rank <= 16) on self_attn.{q,k,v}_proj -- all three of a layer or none,
+ * adjacent in the flat buffers in that order, as the UNet's fused attn1 -- and self_attn.out_proj.  DoRA sites, other
+ * targets, head_dim != 64 and more than 128 positions are refused.  workspace = [packed weights | no-grad arena | arena of
+ * the saved pass and its backward], sized by a dry forward + backward.
+ * smi_clip_forward_lora: every sample is adapted, sample i at multipliers[i] (f32, HOST memory, [n]); the effective weight
+ * of a site is W + m_i (alpha / r) up down.  All multipliers 0 gives the bits of smi_clip_encode, which also runs on such
+ * an engine.  Outputs, T [n, L, hidden] (pooled: [n, projection_dim or hidden]), any may be NULL: last_layer_out =
+ * hidden_states[-1], the last layer's output WITHOUT the final norm; the other three as in smi_clip_encode.
+ * save_for_backward: keeps the pass for ONE smi_clip_backward; a no-grad call in between leaves it intact.
+ * smi_clip_backward: d_hidden f32 [n, L, hidden] is the gradient of last_layer_out (which 0) or of penultimate (which 1:
+ * the last layer's sites then get none); accumulates (+=) into the flat gradient buffers.  No gradient flows into the
+ * embeddings.  -4 without a saved pass. */
+int smi_clip_lora_workspace_bytes(const smi_clip_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                                  size_t* bytes);
+int smi_clip_lora_create(const smi_clip_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                         int n_sites, int batch, void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_clip_forward_lora(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, const float* lora_down_flat,
+                          const float* lora_up_flat, const float* multipliers, int save_for_backward, void* last_layer_out,
+                          void* penultimate, void* last_hidden, void* pooled);
+int smi_clip_backward(smi_engine* e, int which, const float* d_hidden, float* d_lora_down_flat, float* d_lora_up_flat);
+
 /* ---- CLIP image tower and similarity head (scoring a slider sweep) -----------------------------------------------------
  * Replaces `model.get_image_features(pixel_values)` / the image half of `CLIPModel(**inputs).logits_per_image`
  * (eval-scripts/clip_score.py).  Patch embedding (a GEMM on the patch matrix), class token + position embedding +
@@ -442,6 +469,19 @@ int smi_op_attention_fwd(int dtype, const void* q, const void* k, const void* v,
 int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
                          const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
                          int d, float scale, void* stream);
+/* Causal self-attention (key j visible to query i iff j <= i; CLIP text towers) with explicit leading dimensions, so that
+ * q | k | v may be column blocks of one fused [b n, 3 h d] tensor.  The backward is one workgroup per (sample, head):
+ * nq == nk <= 128, head_dim 64, all of dq / dk / dv; anything else returns an error that names the limit.  `delta` is
+ * unused and may be NULL.  Operands 16-byte aligned, leading dimensions multiples of 8. */
+int smi_op_attention_causal_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
+                                int n, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, void* stream);
+int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
+                                const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
+                                int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
+                                int64_t lddk, int64_t lddv, float scale, void* stream);
+/* The CLIP MLP activation, kind 0 quick_gelu / 1 erf-gelu: y = act(x) when y is given (n % 8 == 0), dx = dy * act'(x) when
+ * dy is given (any n >= 1). */
+int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream);
 int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
                      float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream);
 int smi_op_layernorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,

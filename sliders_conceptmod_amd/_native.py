@@ -129,6 +129,14 @@ _SIGS = {
     "smi_clip_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
                                   C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_clip_encode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
+    "smi_clip_encode_layers": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "smi_clip_lora_workspace_bytes": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int,
+                                                C.POINTER(C.c_size_t)]),
+    "smi_clip_lora_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                       C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_clip_forward_lora": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_int] +
+                              [C.c_void_p] * 4),
+    "smi_clip_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smi_clip_vision_workspace_bytes": (C.c_int, [C.POINTER(ClipVisionConfigC), C.c_int, C.POINTER(C.c_size_t)]),
     "smi_clip_vision_create": (C.c_int, [C.POINTER(ClipVisionConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p,
                                          C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -171,6 +179,11 @@ _SIGS = {
                        [C.c_void_p]),
     "smi_op_attention_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "smi_op_attention_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "smi_op_attention_causal_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64] * 4 +
+                                    [C.c_float, C.c_void_p]),
+    "smi_op_attention_causal_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_int64] * 8 +
+                                    [C.c_float, C.c_void_p]),
+    "smi_op_act": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_groupnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
     "smi_op_layernorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
     "smi_op_geglu": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p]),
@@ -624,6 +637,72 @@ class ClipEngine(_EngineBase):
         check(lib().smi_clip_encode(self.handle, n, ptr(ids), ptr(eos), ptr(last), ptr(pen), ptr(pooled)),
               "smi_clip_encode")
         return last, pen, pooled
+
+    def last_layer_out(self, ids: torch.Tensor) -> torch.Tensor:
+        """hidden_states[-1]: the last layer's output without the final norm (smi_clip_encode_layers), [n, L, hidden]."""
+        n, L = ids.shape
+        dev = self.workspace.device
+        out = torch.empty((n, L, self.cfg_c.hidden_size), dtype=self.dtype, device=dev)
+        ids = ids.to(dev, torch.int32).contiguous()
+        check(lib().smi_clip_encode_layers(self.handle, n, ptr(ids), None, None, None, None, ptr(out)), "smi_clip_encode_layers")
+        return out
+
+
+def clip_lora_workspace_bytes(cfg, dtype: torch.dtype, sites: Sequence[dict], batch: int) -> int:
+    """smi_clip_lora_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on refused sites or shapes."""
+    arr, _keep = make_sites(sites)
+    out = C.c_size_t(0)
+    check(lib().smi_clip_lora_workspace_bytes(C.byref(clip_config_c(cfg, dtype)), arr, len(sites), batch, C.byref(out)),
+          "smi_clip_lora_workspace_bytes")
+    return out.value
+
+
+class ClipLoraEngine(ClipEngine):
+    """CLIP text encoder with LoRA sites on its attention projections (smi_clip_lora_*): `encode` as ClipEngine, plus a
+    forward with one adaptor multiplier per sample that can be saved, and its backward to the flat LoRA gradients."""
+
+    def __init__(self, cfg, dtype: torch.dtype, state: dict, sites: Sequence[dict], batch: int, device):
+        self.cfg_c, self.batch, self.dtype = clip_config_c(cfg, dtype), batch, dtype
+        arr, self._site_keep = make_sites(sites)
+        out = C.c_size_t(0)
+        check(lib().smi_clip_lora_workspace_bytes(C.byref(self.cfg_c), arr, len(sites), batch, C.byref(out)),
+              "smi_clip_lora_workspace_bytes")
+        self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
+        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.workspace.device):
+            check(lib().smi_clip_lora_create(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch,
+                                             ptr(self.workspace), out.value, stream_ptr(), C.byref(handle)),
+                  "smi_clip_lora_create")
+        self.handle = handle
+
+    def forward_lora(self, ids: torch.Tensor, eos_pos: Optional[torch.Tensor], lora_down: torch.Tensor,
+                     lora_up: torch.Tensor, multipliers: Sequence[float], save: bool = False,
+                     want=("last_layer_out", "penultimate", "last_hidden", "pooled")) -> dict:
+        """smi_clip_forward_lora: sample i under the adaptor at multipliers[i].  Returns the outputs named in `want`
+        (model dtype); save=True keeps the pass for one `backward`."""
+        n, L = ids.shape
+        if L != self.cfg_c.max_positions:
+            raise SmiError(f"CLIP text encoder: token ids must be padded to {self.cfg_c.max_positions} positions, got {L}")
+        if len(multipliers) != n:
+            raise SmiError(f"forward_lora: {len(multipliers)} multipliers for {n} samples")
+        dev, d = self.workspace.device, self.cfg_c.hidden_size
+        out = {k: torch.empty((n, self.cfg_c.projection_dim or d) if k == "pooled" else (n, L, d), dtype=self.dtype,
+                              device=dev) for k in want}
+        ids = ids.to(dev, torch.int32).contiguous()
+        eos = None if eos_pos is None else eos_pos.to(dev, torch.int32).contiguous()
+        marr = (C.c_float * n)(*[float(m) for m in multipliers])
+        check(lib().smi_clip_forward_lora(self.handle, n, ptr(ids), ptr(eos), ptr(lora_down), ptr(lora_up), marr, int(save),
+                                          ptr(out.get("last_layer_out")), ptr(out.get("penultimate")),
+                                          ptr(out.get("last_hidden")), ptr(out.get("pooled"))), "smi_clip_forward_lora")
+        return out
+
+    def backward(self, d_hidden: torch.Tensor, d_down: torch.Tensor, d_up: torch.Tensor, which: int = 0):
+        """smi_clip_backward: d_hidden fp32 [n, L, hidden], the gradient of last_layer_out (which 0) or penultimate (1);
+        accumulates (+=) into the flat fp32 gradient buffers."""
+        if d_hidden.dtype != torch.float32 or not d_hidden.is_contiguous():
+            raise SmiError("backward: d_hidden must be contiguous fp32")
+        check(lib().smi_clip_backward(self.handle, int(which), ptr(d_hidden), ptr(d_down), ptr(d_up)), "smi_clip_backward")
 
 
 def clip_vision_config_c(cfg, dtype: torch.dtype) -> ClipVisionConfigC:

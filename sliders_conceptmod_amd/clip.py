@@ -5,7 +5,9 @@ and `CLIPTextModelWithProjection` (SD-XL encoder 2) as the reference calls them:
 They are parameter containers with the transformers parameter names (a transformers state dict loads by key); the
 arithmetic runs in the HIP engine (csrc/engine.hip `forward_clip`: fused causal attention, LayerNorm, GEMM kernels).  No
 PyTorch forward: without the HIP library, or on a CPU device, a call raises.  Tokenisation stays host text processing
-(`transformers.CLIPTokenizer`).
+(`transformers.CLIPTokenizer`).  A `lora.LoRANetwork` built on a text encoder (the no-trigger trainer,
+conceptmod/notrigger/train_notrigger.py:204-213) attaches itself: the forward then runs under the adaptor at the network's
+multiplier, and `notrigger.TextEncoderStep` differentiates it (csrc/engine_clip.hip `smi_clip_forward_lora` / `smi_clip_backward`).
 
 The image tower and the joint model -- `CLIPVisionModelWithProjection` and `CLIPModel`, what eval-scripts/clip_score.py
 scores a slider sweep with -- are containers of the same kind (csrc/engine.hip `forward_clip_vision`, csrc/clip_vision.hip).
@@ -46,7 +48,11 @@ def open_clip_bigg_config() -> CLIPTextConfig:    # laion CLIP-ViT-bigG-14 text 
                           hidden_act="gelu", projection_dim=1280)
 
 
-class _Attn(nn.Module):
+class CLIPAttention(nn.Module):
+    """Named as transformers names it: the reference's no-trigger trainer selects the text encoders' LoRA targets by this
+    class name (notrigger/train_notrigger.py:186); the children in transformers' order k, v, q, out (the order of the walk
+    and so of the RNG draws)."""
+
     def __init__(self, d):
         super().__init__()
         self.k_proj, self.v_proj, self.q_proj, self.out_proj = (nn.Linear(d, d) for _ in range(4))
@@ -61,7 +67,7 @@ class _MLP(nn.Module):
 class _Layer(nn.Module):
     def __init__(self, d, inter):
         super().__init__()
-        self.self_attn = _Attn(d)
+        self.self_attn = CLIPAttention(d)
         self.layer_norm1 = nn.LayerNorm(d)
         self.mlp = _MLP(d, inter)
         self.layer_norm2 = nn.LayerNorm(d)
@@ -89,16 +95,23 @@ class _TextTransformer(nn.Module):
 
 
 class _HiddenStates:
-    """What the reference reads of `hidden_states`: [-1] (last layer, before the final norm is NOT kept by the engine)
-    is not needed; [-2] is the penultimate layer's output (train_util.py:142)."""
+    """What the reference reads of `hidden_states`: [-2], the penultimate layer's output (train_util.py:142), and [-1],
+    the last layer's output before the final norm (notrigger/train_notrigger.py:241 `chosenlayer = -1`).  A pass under an
+    attached LoRA network returns both; the plain encoder returns [-2] and computes [-1] when it is first asked for
+    (`compute_last`: one more pass, smi_clip_encode_layers), so that the prompt front end pays nothing for it."""
 
-    def __init__(self, penultimate):
-        self._pen = penultimate
+    def __init__(self, penultimate, last_layer_out=None, compute_last=None):
+        self._pen, self._last, self._compute_last = penultimate, last_layer_out, compute_last
 
     def __getitem__(self, i):
-        if i != -2:
-            raise IndexError("the engine returns hidden_states[-2] only (what text_encode_xl reads)")
-        return self._pen
+        if i == -2:
+            return self._pen
+        if i == -1:
+            if self._last is None and self._compute_last is not None:
+                self._last = self._compute_last()
+            if self._last is not None:
+                return self._last
+        raise IndexError("the engine returns hidden_states[-2] and hidden_states[-1] only")
 
 
 class CLIPTextOutput:
@@ -137,21 +150,50 @@ class CLIPTextModel(EngineCacheMixin, nn.Module):
         sd = {k: v for k, v in state_dict.items() if not k.endswith("position_ids")}  # a buffer in older checkpoints
         return super().load_state_dict(sd, strict=strict)
 
-    def _new_engine(self, state, n):
+    def engine_config(self):
         cfg = self.config
-        if not self.with_projection:
-            cfg = CLIPTextConfig(**{**cfg.__dict__, "projection_dim": None})
-        return _native.ClipEngine(cfg, self.dtype, state, max(n, 1), self.device)
+        return cfg if self.with_projection else CLIPTextConfig(**{**cfg.__dict__, "projection_dim": None})
+
+    def _new_engine(self, state, n, *shape):
+        if shape == ("lora",):  # a LoRANetwork is attached (lora.py: `text_encoder._lora_network`)
+            return _native.ClipLoraEngine(self.engine_config(), self.dtype, state, self._lora_network.engine_sites(),
+                                          max(n, 1), self.device)
+        return _native.ClipEngine(self.engine_config(), self.dtype, state, max(n, 1), self.device)
+
+    def lora_engine(self, n: int):
+        """The engine of this tower with the attached network's sites, for a batch of n.  The sites are fixed at creation: an
+        engine built for another network is closed first."""
+        net = self._lora_network
+        for key, e in list(self._engines.items()):
+            if key[-1] == "lora" and getattr(e, "network", None) is not net:
+                e.close()
+                del self._engines[key]
+        e = self._engine(n, "lora")
+        e.network = net
+        return e
+
+    def eos_positions(self, ids):
+        # transformers: the pooled token is the EOS token -- the highest id for the original vocabulary (eos_token_id 2 in
+        # old configs), else the first position holding eos_token_id
+        eos = self.config.eos_token_id
+        return ids.argmax(dim=-1) if eos == 2 else (ids == eos).int().argmax(dim=-1)
 
     @torch.no_grad()
     def forward(self, input_ids, output_hidden_states: bool = False, **_):
         ids = input_ids.to(torch.int64)
-        eos = self.config.eos_token_id
-        # transformers: the pooled token is the EOS token -- the highest id for the original vocabulary (eos_token_id 2 in
-        # old configs), else the first position holding eos_token_id
-        eos_pos = ids.argmax(dim=-1) if eos == 2 else (ids == eos).int().argmax(dim=-1)
-        last, pen, pooled = self._engine(ids.shape[0]).encode(ids, eos_pos)
-        hs = _HiddenStates(pen) if output_hidden_states else None
+        eos_pos = self.eos_positions(ids)
+        net = self.__dict__.get("_lora_network")
+        if net is not None and net.unet_loras:
+            # an attached network: a no-grad forward under the adaptor at the network's multiplier (0 outside `with network:`)
+            flat, n_down, mult = net.engine_params()
+            flat = flat.detach()
+            out = self.lora_engine(ids.shape[0]).forward_lora(ids, eos_pos, flat[:n_down], flat[n_down:],
+                                                              [mult] * ids.shape[0])
+            last, pen, pooled = out["last_hidden"], out["penultimate"], out["pooled"]
+            hs = _HiddenStates(pen, out["last_layer_out"]) if output_hidden_states else None
+        else:
+            last, pen, pooled = self._engine(ids.shape[0]).encode(ids, eos_pos)
+            hs = _HiddenStates(pen, compute_last=lambda: self._engine(ids.shape[0]).last_layer_out(ids)) if output_hidden_states else None
         if self.with_projection:
             return CLIPTextOutput(pooled, last, None, pooled, hs)
         return CLIPTextOutput(last, last, pooled, None, hs)

@@ -1278,6 +1278,7 @@ int launch_attn_fwd(const AttnParams& p, hipStream_t stream) {
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, false) : dispatch<bf16>(p, stream, false);
 }
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream) {
+  if (p.causal) return launch_attn_causal_bwd(p, stream);  // the kernels below know no mask
   if (check_attn(p)) return -1;
   SMI_CHECK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, true) : dispatch<bf16>(p, stream, true);

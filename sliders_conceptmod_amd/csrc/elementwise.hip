@@ -67,6 +67,29 @@ __global__ void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* _
   }
 }
 
+// dx = dy * act'(x): KIND 0 quick_gelu (x sigmoid(1.702 x))' = s (1 + 1.702 x (1 - s)), KIND 1 erf-gelu (dgelu_f).  Whole
+// 8-packs vectorised; the n % 8 tail elements one thread each
+template <typename T, int KIND>
+__device__ __forceinline__ float dact_f(float v) {
+  if (KIND == 1) return dgelu_f(v);
+  const float s = 1.f / (1.f + __expf(-1.702f * v));
+  return s * (1.f + 1.702f * v * (1.f - s));
+}
+template <typename T, int KIND>
+__global__ void act_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy, T* __restrict__ dx, int64_t n) {
+  const int64_t n8 = n / 8;
+  GSTRIDE(i, n8) {
+    Pack8<T> a, g, o;
+    a.u = *reinterpret_cast<const u32x4*>(x + i * 8);
+    g.u = *reinterpret_cast<const u32x4*>(dy + i * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(g.e[e]) * dact_f<T, KIND>(to_f(a.e[e])));
+    *reinterpret_cast<u32x4*>(dx + i * 8) = o.u;
+  }
+  const int64_t t = n8 * 8 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t < n) dx[t] = from_f<T>(to_f(dy[t]) * dact_f<T, KIND>(to_f(x[t])));
+}
+
 template <typename T>
 __global__ void copy_cols_kernel(const T* __restrict__ src, int64_t lds, T* __restrict__ dst, int64_t ldd, int col0,
                                  int64_t M, int C) {
@@ -449,6 +472,20 @@ int launch_act(int dtype, const void* x, void* y, int64_t n, int kind, hipStream
     if (kind == 0) L(f16, 2); else L(f16, 3);
   } else {
     if (kind == 0) L(bf16, 2); else L(bf16, 3);
+  }
+#undef L
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int launch_act_bwd(int dtype, const void* x, const void* dy, void* dx, int64_t n, int kind, hipStream_t stream) {
+  SMI_CHECK(n >= 1 && (kind == 0 || kind == 1), "act bwd: n >= 1, kind 0 (quick_gelu) or 1 (gelu)");
+  SMI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "act bwd: x, dy and dx must be 16-byte aligned");
+  const int grid = ew_grid(n / 8 > 0 ? n / 8 : 1);
+#define L(TT_, K_) hipLaunchKernelGGL((act_bwd_kernel<TT_, K_>), dim3(grid), dim3(256), 0, stream, (const TT_*)x, (const TT_*)dy, (TT_*)dx, n)
+  if (dtype == DT_F16) {
+    if (kind == 0) L(f16, 0); else L(f16, 1);
+  } else {
+    if (kind == 0) L(bf16, 0); else L(bf16, 1);
   }
 #undef L
   SMI_HIP(hipGetLastError());

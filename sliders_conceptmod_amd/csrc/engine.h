@@ -1,4 +1,5 @@
-// The op core of every engine: runs a model's forward -- and the UNet's activation/LoRA-gradient backward -- as a stream
+// The op core of every engine: runs a model's forward -- and the activation/LoRA-gradient backward of the two models that
+// are differentiated, the UNet and the CLIP text tower with LoRA sites -- as a stream
 // of hand-written gfx950 kernels (gemm.hip, attention.hip, norm.hip, elementwise.hip, lora.hip).  It names no model: each
 // (engine_unet.hip, engine_vae.hip, engine_clip.hip, engine_lpips.hip) is a `Model` with its config, layers and forward over these ops.
 //
@@ -1252,6 +1253,22 @@ struct smi_engine {
   Ten* silu(Ten* x) {  // only used on the (gradient-free) time embedding path
     Ten* y = new_ten(x->rows, x->cols, x->n, x->H, x->W);
     RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_silu(dtype, x->p, y->p, x->rows * x->cols, stream));
+    return y;
+  }
+
+  // the CLIP MLP activation: kind 0 quick_gelu, 1 erf-gelu
+  Ten* act(Ten* x, int kind) {
+    Ten* y = new_ten(x->rows, x->cols, x->n, x->H, x->W);
+    RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(dtype, x->p, y->p, x->rows * x->cols, kind, stream));
+    y->ng = x->ng;
+    if (saving && y->ng) {
+      tape.push_back([=]() {
+        if (!y->g) return;
+        into_slot(grad_slot(x), MA(x), x->cols, [&](void* dx) {
+          RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act_bwd(dtype, PA(x), y->g, dx, MA(x) * x->cols, kind, stream));
+        });
+      });
+    }
     return y;
   }
 

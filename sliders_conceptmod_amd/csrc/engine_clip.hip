@@ -1,28 +1,42 @@
-// The CLIP engines, forward only: the text tower (transformers CLIPTextModel[WithProjection]; T/train_util.py:108-155)
-// and the image tower (CLIPVisionModel[WithProjection]).  Both are pre-LayerNorm blocks on the op core (engine.h); the
-// blocks are written once and differ in the causal mask only.
+// The CLIP engines: the text tower (transformers CLIPTextModel[WithProjection]; T/train_util.py:108-155) and the image
+// tower (CLIPVisionModel[WithProjection]).  Both are pre-LayerNorm blocks on the op core (engine.h); the blocks are
+// written once and differ in the causal mask only.  Forward only -- except a text tower created with LoRA sites on its
+// attention projections (smi_clip_lora_*: the no-trigger trainer), which also saves a pass and differentiates it.
 #include "engine.h"
 
 namespace {
+
+// per-sample multiplier ratios travel in kernel arguments, 64 per launch, ordered on the engine's stream (as the UNet's)
+struct MultArgs {
+  float v[64];
+};
+__global__ void clip_set_mults_kernel(float* dst0, float* dst1, MultArgs a, int n) {
+  const int i = threadIdx.x;
+  if (i < n) {
+    dst0[i] = a.v[i];
+    if (dst1) dst1[i] = a.v[i];
+  }
+}
 
 struct CLayer {
   Norm n1, n2;
   Lin qkv, out, fc1, fc2;
 };
 // the encoder layers of either tower: `prefix` + layer number names them in the transformers state dict
+// grad: the tower is differentiated -- every Linear gets its transposed copy (dX) and may carry LoRA sites
 void build_clip_layers(smi_engine& e, std::vector<CLayer>& layers, const std::string& prefix, int num_layers, int d,
-                       int inter) {
+                       int inter, bool grad = false) {
   layers.resize(num_layers);
   for (int i = 0; i < num_layers; ++i) {
     const std::string b = prefix + std::to_string(i);
     CLayer& L = layers[i];
     L.n1 = e.make_norm(b + ".layer_norm1", d, 1e-5f, 0);
-    L.qkv = e.make_fused(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d, d, false);
+    L.qkv = e.make_fused(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d, d, grad);
     L.qkv.b = e.fused_bias(b + ".self_attn", {"q_proj", "k_proj", "v_proj"}, d);
-    L.out = e.make_lin(b + ".self_attn.out_proj", d, d, true, false);
+    L.out = e.make_lin(b + ".self_attn.out_proj", d, d, true, grad);
     L.n2 = e.make_norm(b + ".layer_norm2", d, 1e-5f, 0);
-    L.fc1 = e.make_lin(b + ".mlp.fc1", d, inter, true, false);
-    L.fc2 = e.make_lin(b + ".mlp.fc2", inter, d, true, false);
+    L.fc1 = e.make_lin(b + ".mlp.fc1", d, inter, true, grad);
+    L.fc2 = e.make_lin(b + ".mlp.fc2", inter, d, true, grad);
   }
 }
 // one pre-LayerNorm block on h [n L, d]; `causal` says whether the self-attention is masked
@@ -31,9 +45,7 @@ Ten* clip_block(smi_engine& e, Ten* h, const CLayer& ly, int n, int L, int heads
   Ten* o = e.attention(qkv, nullptr, nullptr, heads, d, n, L, L, causal);
   h = e.linear(o, ly.out, h);
   Ten* f = e.linear(e.layernorm(h, ly.n2), ly.fc1);
-  Ten* a = e.new_ten(f->rows, f->cols, n, L, 1);
-  RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(e.dtype, f->p, a->p, f->rows * f->cols, act, e.stream));
-  return e.linear(a, ly.fc2, h);
+  return e.linear(e.act(f, act), ly.fc2, h);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -47,7 +59,15 @@ struct ClipText : Model {
   Lin proj;
   const void* tok = nullptr;
   const void* pos = nullptr;
-  explicit ClipText(const smi_clip_config& c) : cfg(c) {}
+  // a tower created with LoRA sites (smi_clip_lora_create): arena 1 holds the saved pass and its backward
+  bool trainable = false;
+  bool tape_valid = false;
+  int bw_n = 0;                                      // samples of the saved pass (all adapted)
+  Ten *out_last = nullptr, *out_pen = nullptr;       // hidden_states[-1] (no final norm) and [-2] of the saved pass
+  std::vector<WgradJob> wjobs_uploaded;              // the device table of the deferred weight-gradient jobs, as in the UNet
+  WgradJob* wjobs_dev = nullptr;
+  size_t wjobs_cap = 0;
+  explicit ClipText(const smi_clip_config& c, bool train = false) : cfg(c), trainable(train) {}
 
   void build(smi_engine& e) override {
     const int d = cfg.hidden_size;
@@ -55,34 +75,144 @@ struct ClipText : Model {
     pos = e.Wd("text_model.embeddings.position_embedding.weight");
     e.check_shape("text_model.embeddings.token_embedding.weight", {cfg.vocab_size, d});
     e.check_shape("text_model.embeddings.position_embedding.weight", {cfg.max_positions, d});
-    build_clip_layers(e, layers, "text_model.encoder.layers.", cfg.num_layers, d, cfg.intermediate_size);
+    build_clip_layers(e, layers, "text_model.encoder.layers.", cfg.num_layers, d, cfg.intermediate_size, trainable);
     final_norm = e.make_norm("text_model.final_layer_norm", d, 1e-5f, 0);
     if (cfg.projection_dim > 0) proj = e.make_lin("text_projection", d, cfg.projection_dim, false, false);
   }
+  // what a trainable tower packs after its layers (the forward-only create path packs its own: engine.hip build_model)
+  void build_trainable(smi_engine& e) {
+    build(e);
+    e.finish_lora();
+    e.gscale = (float*)e.pack_alloc(e.GSCALE_FLOATS * sizeof(float));
+    e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
+    wjobs_cap = 2 * e.sites.size() + 8;  // a fused q|k|v pushes at most 4 jobs for its 3 sites, out_proj 2
+    wjobs_dev = (WgradJob*)e.pack_alloc(wjobs_cap * sizeof(WgradJob));
+    for (size_t i = 0; i < e.sites.size(); ++i)
+      if (!e.site_used[i] && !e.err) {
+        set_error("LoRA target '%s' is not a layer of this text tower", e.site_names[i].c_str());
+        e.err = true;
+      }
+  }
   void dry_forward(smi_engine& e) override {  // all outputs
+    e.begin_forward_only_pass();
     forward(e, e.max_n, nullptr, nullptr, (void*)16, (void*)16, (void*)16);
   }
 
+  // the pass itself; whoever calls has begun it (begin_forward_only_pass / begin_adapted_pass)
   int forward(smi_engine& e, int n, const int* ids, const int* eos_pos, void* last_hidden, void* penultimate,
-              void* pooled) {
-    e.begin_forward_only_pass();
+              void* pooled, void* last_layer_out = nullptr) {
     const int L = cfg.max_positions, d = cfg.hidden_size;
-    Ten* h = e.new_ten((int64_t)n * L, d, n, L, 1);
+    if (!e.prep_sites.empty() && (e.dry || (e.lora_down && e.lora_up && e.mult != 0.f)))
+      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.lora_down, e.lora_up, e.lora_shadow, e.stream));
+    Ten* h = e.new_ten((int64_t)n * L, d, n, L, 1);  // the embeddings: no gradient flows into them (ng stays false)
     RUN(launch_embed(e.dtype, ids, tok, pos, h->p, (int64_t)n * L, L, d, cfg.vocab_size, e.stream));
+    Ten* pen = h;
     for (int i = 0; i < cfg.num_layers; ++i) {
-      if (i == cfg.num_layers - 1 && penultimate)  // hidden_states[-2]: what enters the last layer
-        RUN(launch_copy_cols(e.dtype, h->p, d, penultimate, d, 0, (int)h->rows, d, e.stream));
+      if (i == cfg.num_layers - 1) {  // hidden_states[-2]: what enters the last layer
+        pen = h;
+        if (penultimate) RUN(launch_copy_cols(e.dtype, h->p, d, penultimate, d, 0, (int)h->rows, d, e.stream));
+      }
       h = clip_block(e, h, layers[i], n, L, cfg.num_heads, d, cfg.hidden_act, true);
     }
-    Ten* fin = e.layernorm(h, final_norm);
-    if (last_hidden) RUN(launch_copy_cols(e.dtype, fin->p, d, last_hidden, d, 0, (int)fin->rows, d, e.stream));
-    if (pooled) {
-      Ten* pl = e.new_ten(n, d, n, 1, 1);
-      RUN(launch_gather_rows(e.dtype, fin->p, eos_pos, pl->p, n, L, d, e.stream));
-      if (cfg.projection_dim > 0) pl = e.linear(pl, proj);
-      RUN(launch_copy_cols(e.dtype, pl->p, pl->cols, pooled, pl->cols, 0, n, pl->cols, e.stream));
+    if (last_layer_out) RUN(launch_copy_cols(e.dtype, h->p, d, last_layer_out, d, 0, (int)h->rows, d, e.stream));
+    if (e.saving) {
+      out_last = h;
+      out_pen = pen;
+      bw_n = n;
+      e.bw_down = e.lora_down;
+      e.bw_up = e.lora_up;
+      e.bw_mult = e.mult;
+      e.bw_samp_on = e.samp_on;
+      tape_valid = true;
+    }
+    {
+      e.saving = false;  // neither output below is differentiated: the final norm and the projection stay off the tape
+      Ten* fin = e.layernorm(h, final_norm);
+      if (last_hidden) RUN(launch_copy_cols(e.dtype, fin->p, d, last_hidden, d, 0, (int)fin->rows, d, e.stream));
+      if (pooled) {
+        Ten* pl = e.new_ten(n, d, n, 1, 1);
+        RUN(launch_gather_rows(e.dtype, fin->p, eos_pos, pl->p, n, L, d, e.stream));
+        if (cfg.projection_dim > 0) pl = e.linear(pl, proj);
+        RUN(launch_copy_cols(e.dtype, pl->p, pl->cols, pooled, pl->cols, 0, n, pl->cols, e.stream));
+      }
     }
     return e.end_pass("this call (");
+  }
+
+  // an adapted pass of n samples, every one under the adaptor: arena 1 and a fresh tape when it is saved, else arena 0
+  void begin_adapted_pass(smi_engine& e, int n, bool save) {
+    e.n_ad = n;
+    e.cur = &e.arena[save ? 1 : 0];
+    e.cur->reset();
+    e.in_block = e.persist_next = false;
+    e.tens = &e.tens_[save ? 1 : 0];
+    e.tens->clear();
+    if (save) drop_tape(e);
+    e.saving = save;
+  }
+  void drop_tape(smi_engine& e) {
+    e.pinned.clear();
+    e.tape.clear();
+    tape_valid = false;
+    e.bw_skip = 0;
+  }
+
+  // UNet::backward without the UNet parts: one power-of-two loss scale per sample, the 16-bit LoRA operands rebuilt from
+  // the SAVED parameters, the tape in reverse, one grouped weight-gradient launch.  which 0: d_hidden is the gradient of
+  // hidden_states[-1] (the last layer's output, no final norm); 1: of hidden_states[-2], and the last layer's closures
+  // see no gradient -- its sites get none.  A backward consumes the saved pass.
+  int backward(smi_engine& e, int which, const float* d_hidden, float* dd, float* du) {
+    if (!tape_valid && !e.dry) {
+      set_error("smi_clip_backward: no saved forward pass (call smi_clip_forward_lora with save_for_backward=1 first)");
+      return -4;
+    }
+    e.cur = &e.arena[1];
+    e.tens = &e.tens_[1];
+    e.d_down = dd;
+    e.d_up = du;
+    e.d_ctx = nullptr;
+    e.n_ad = bw_n;
+    Ten* y = which == 0 ? out_last : out_pen;
+    if (!y->ng) {  // adaptor off, or nothing adapted upstream of hidden_states[-2]: the gradient is zero
+      drop_tape(e);
+      return 0;
+    }
+    const int n = bw_n, L = cfg.max_positions, d = cfg.hidden_size;
+    e.wjobs.clear();
+    e.pinned.clear();
+    e.bw_skip = 0;
+    RUN(launch_grad_scale(d_hidden, n, (int64_t)L * d, e.gscale, e.MAXS, e.stream));
+    if (!e.prep_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f)
+      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.bw_down, e.bw_up, e.lora_shadow, e.stream));
+    e.mult = e.bw_mult;
+    y->g = e.alloc_t(e.MA(y), d);
+    // f32 [n, L d] -> 16-bit rows, sample j x its loss scale: the cast of the UNet's d_eps with one "channel"
+    RUN(launch_nchw_to_nhwc_scaled(e.dtype, d_hidden, y->g, n, 1, L * d, 1, e.gscale, e.stream));
+    for (auto it = e.tape.rbegin(); it != e.tape.rend(); ++it) (*it)();
+    if (!e.wjobs.empty() && !e.err) {
+      wgrad_grouped_finish(e.wjobs);
+      if (!e.dry) {
+        if (e.wjobs.size() > wjobs_cap) {
+          set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", e.wjobs.size(), wjobs_cap);
+          drop_tape(e);
+          return -1;
+        }
+        const bool same = wjobs_uploaded.size() == e.wjobs.size() &&
+                          memcmp(wjobs_uploaded.data(), e.wjobs.data(), e.wjobs.size() * sizeof(WgradJob)) == 0;
+        if (!same) {  // bump allocation gives the same addresses every step: uploaded once, then reused
+          wjobs_uploaded = e.wjobs;
+          if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), e.wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
+                             e.stream) != hipSuccess) {
+            set_error("hipMemcpyAsync (weight-gradient job table) failed");
+            drop_tape(e);
+            return -1;
+          }
+        }
+        RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_wgrad_grouped(e.dtype, e.wjobs, wjobs_dev, e.stream));
+      }
+    }
+    drop_tape(e);
+    return e.end_pass("the backward (");
   }
 };
 
@@ -170,6 +300,58 @@ Setup clip_setup(const smi_clip_config* cfg, int batch) {
   return [=](smi_engine* e) { e->hold(smi_engine::CLIP_TEXT, new ClipText(*cfg), cfg->dtype, batch); };
 }
 
+// a text tower with LoRA sites: what the causal attention backward takes, and Linear LoRA on the attention projections only
+int check_clip_lora(const smi_clip_config* c, const smi_lora_site* sites, int n_sites, int batch) {
+  if (check_clip_cfg(c, batch)) return -1;
+  SMI_CHECK(sites && n_sites > 0, "smi_clip_lora: no LoRA sites (a tower without them is smi_clip_create's)");
+  SMI_CHECK(c->hidden_size / c->num_heads == 64 && c->max_positions <= 128,
+            "smi_clip_lora: head_dim %d / %d positions -- the causal attention backward takes head_dim 64 and at most 128 "
+            "positions", c->hidden_size / c->num_heads, c->max_positions);
+  SMI_CHECK(batch <= smi_engine::MAXS, "smi_clip_lora: batch %d exceeds the %d per-sample multipliers", batch, smi_engine::MAXS);
+  for (int i = 0; i < n_sites; ++i) {
+    const std::string t = sites[i].target ? sites[i].target : "";
+    SMI_CHECK(sites[i].off_dora < 0, "smi_clip_lora: DoRA site '%s' -- the text tower takes plain LoRA sites only", t.c_str());
+    SMI_CHECK(sites[i].rank >= 1 && sites[i].rank <= 16, "smi_clip_lora: rank %d of '%s' outside [1, 16]", sites[i].rank, t.c_str());
+    bool ok = false;
+    for (const char* suf : {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj", ".self_attn.out_proj"}) {
+      const size_t m = strlen(suf);
+      ok = ok || (t.size() > m && t.compare(t.size() - m, m, suf) == 0);
+    }
+    SMI_CHECK(ok, "smi_clip_lora: target '%s' -- sites sit on self_attn.{q,k,v}_proj and self_attn.out_proj", t.c_str());
+  }
+  return 0;
+}
+ClipText* clip_lora_setup(smi_engine* e, const smi_clip_config* cfg, const smi_lora_site* sites, int n_sites, int batch) {
+  ClipText* t = new ClipText(*cfg, true);
+  e->hold(smi_engine::CLIP_TEXT, t, cfg->dtype, batch);
+  e->sites.assign(sites, sites + n_sites);
+  e->site_names.resize(n_sites);
+  e->site_used.assign(n_sites, 0);
+  for (int i = 0; i < n_sites; ++i) {
+    e->site_names[i] = sites[i].target;
+    e->sites[i].target = e->site_names[i].c_str();
+  }
+  for (int i = 0; i < n_sites; ++i) e->smap[e->site_names[i]] = &e->sites[i];
+  return t;
+}
+// dry run: out = {packed weights, arena 0 (the largest no-grad pass), arena 1 (a saved pass and its backward)}
+int clip_lora_plan(const smi_clip_config* cfg, const smi_lora_site* sites, int n_sites, int batch, size_t out[3]) {
+  smi_engine e;
+  e.dry = true;
+  ClipText& t = *clip_lora_setup(&e, cfg, sites, n_sites, batch);
+  t.build_trainable(e);
+  if (e.err) return -1;
+  out[0] = align_up(e.wpack.peak, 4096);
+  t.begin_adapted_pass(e, batch, false);  // the adapted no-grad pass allocates what the plain one does, and xa
+  t.forward(e, batch, nullptr, nullptr, (void*)16, (void*)16, (void*)16, (void*)16);
+  out[1] = align_up(e.arena[0].peak, 4096);
+  t.begin_adapted_pass(e, batch, true);
+  t.forward(e, batch, nullptr, nullptr, (void*)16, (void*)16, (void*)16, (void*)16);
+  t.backward(e, 0, nullptr, nullptr, nullptr);
+  out[2] = align_up(e.arena[1].peak, 4096);
+  return e.err ? -1 : 0;
+}
+
 int check_clip_vision_cfg(const smi_clip_vision_config* c, int batch) {
   SMI_CHECK(c != nullptr, "config is NULL");
   SMI_CHECK(c->dtype == SMI_DTYPE_F16 || c->dtype == SMI_DTYPE_BF16, "dtype must be f16 (0) or bf16 (1)");
@@ -219,7 +401,96 @@ int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
   e->err = false;
+  e->begin_forward_only_pass();
   return static_cast<ClipText*>(e->model.get())->forward(*e, n, ids, eos_pos, last_hidden, penultimate, pooled);
+}
+
+// smi_clip_encode plus hidden_states[-1], the last layer's output without the final norm (any output may be NULL)
+int smi_clip_encode_layers(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
+                           void* penultimate, void* pooled, void* last_layer_out) {
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && ids, "smi_clip_encode_layers: NULL argument or not a CLIP text engine");
+  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
+  e->err = false;
+  e->begin_forward_only_pass();
+  return static_cast<ClipText*>(e->model.get())->forward(*e, n, ids, eos_pos, last_hidden, penultimate, pooled, last_layer_out);
+}
+
+// ---- CLIP text tower with LoRA sites: saved forward with one multiplier per sample, backward to the LoRA parameters ---
+int smi_clip_lora_workspace_bytes(const smi_clip_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                                  size_t* bytes) {
+  if (check_clip_lora(cfg, sites, n_sites, batch)) return -1;
+  SMI_CHECK(bytes != nullptr, "bad arguments");
+  size_t r[3];
+  if (clip_lora_plan(cfg, sites, n_sites, batch, r)) return -1;
+  *bytes = r[0] + r[1] + r[2] + 3 * 4096;
+  return 0;
+}
+
+int smi_clip_lora_create(const smi_clip_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                         int n_sites, int batch, void* workspace, size_t workspace_bytes, void* stream, smi_engine** out) {
+  if (check_clip_lora(cfg, sites, n_sites, batch)) return -1;
+  SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
+  size_t r[3];
+  if (clip_lora_plan(cfg, sites, n_sites, batch, r)) return -1;
+  SMI_CHECK(r[0] + r[1] + r[2] + 3 * 4096 <= workspace_bytes, "workspace too small: need %zu bytes, got %zu",
+            r[0] + r[1] + r[2] + 3 * 4096, workspace_bytes);
+  smi_engine* e = new smi_engine();
+  e->stream = (hipStream_t)stream;
+  ClipText* t = clip_lora_setup(e, cfg, sites, n_sites, batch);
+  for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
+  char* base = (char*)align_up((size_t)workspace, 4096);
+  e->wpack.base = base;
+  e->wpack.cap = r[0];
+  e->arena[0].base = base + r[0];
+  e->arena[0].cap = r[1];
+  e->arena[1].base = base + r[0] + r[1];
+  e->arena[1].cap = r[2];
+  t->build_trainable(*e);
+  return finish_create(e, "the CLIP weights", out);
+}
+
+int smi_clip_forward_lora(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, const float* lora_down_flat,
+                          const float* lora_up_flat, const float* multipliers, int save_for_backward, void* last_layer_out,
+                          void* penultimate, void* last_hidden, void* pooled) {
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && ids, "smi_clip_forward_lora: NULL argument or not a CLIP text engine");
+  ClipText* t = static_cast<ClipText*>(e->model.get());
+  SMI_CHECK(t->trainable, "smi_clip_forward_lora: this engine has no LoRA sites (create it with smi_clip_lora_create)");
+  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  SMI_CHECK(lora_down_flat && lora_up_flat && multipliers, "smi_clip_forward_lora: lora_down_flat, lora_up_flat and multipliers are required");
+  SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
+  e->err = false;
+  float mref = 0.f;
+  for (int i = 0; i < n; ++i) mref = fmaxf(mref, fabsf(multipliers[i]));
+  // every adapted pass takes the per-sample route (sigma_i = m_i / max |m|), so that a sample gives the same bits alone and
+  // in a batch; all multipliers 0 is the frozen tower
+  if (mref != 0.f) {
+    for (int i0 = 0; i0 < n; i0 += 64) {
+      MultArgs a;
+      const int cnt = n - i0 < 64 ? n - i0 : 64;
+      for (int i = 0; i < 64; ++i) a.v[i] = i < cnt ? multipliers[i0 + i] / mref : 0.f;
+      hipLaunchKernelGGL(clip_set_mults_kernel, dim3(1), dim3(64), 0, e->stream, e->samp_mult_dev + i0,
+                         save_for_backward ? e->samp_mult_dev + smi_engine::MAXS + i0 : (float*)nullptr, a, cnt);
+    }
+    SMI_HIP(hipGetLastError());
+  }
+  t->begin_adapted_pass(*e, n, save_for_backward != 0);
+  e->lora_down = lora_down_flat;
+  e->lora_up = lora_up_flat;
+  e->mult = mref;
+  e->samp_on = mref != 0.f;
+  const int rc = t->forward(*e, n, ids, eos_pos, last_hidden, penultimate, pooled, last_layer_out);
+  e->samp_on = false;
+  return rc;
+}
+
+int smi_clip_backward(smi_engine* e, int which, const float* d_hidden, float* d_lora_down_flat, float* d_lora_up_flat) {
+  SMI_CHECK(e && e->kind == smi_engine::CLIP_TEXT && d_hidden, "smi_clip_backward: NULL argument or not a CLIP text engine");
+  ClipText* t = static_cast<ClipText*>(e->model.get());
+  SMI_CHECK(t->trainable, "smi_clip_backward: this engine has no LoRA sites (create it with smi_clip_lora_create)");
+  SMI_CHECK(which == 0 || which == 1, "smi_clip_backward: which must be 0 (last_layer_out) or 1 (penultimate), got %d", which);
+  e->err = false;
+  return t->backward(*e, which, d_hidden, d_lora_down_flat, d_lora_up_flat);
 }
 
 // ---- CLIP image tower engine and the similarity head ------------------------------------------------------------------

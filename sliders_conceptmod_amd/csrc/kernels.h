@@ -197,7 +197,9 @@ struct AttnParams {
   int64_t ldq = 0, ldk = 0, ldv = 0, ldo = 0;
   int B = 0, H = 0, Nq = 0, Nk = 0, D = 0;
   float scale = 1.f;
-  int causal = 0;  // forward only: key j is visible to query i iff j <= i (CLIP text encoder)
+  // key j is visible to query i iff j <= i (CLIP text encoder).  The forward kernels of attention.hip know the mask; the
+  // backward of a causal pass is launch_attn_causal_bwd (attention_causal.hip), to which launch_attn_bwd routes
+  int causal = 0;
   // backward
   const void* dO = nullptr;
   int64_t lddo = 0;
@@ -207,6 +209,9 @@ struct AttnParams {
 };
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream);
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream);
+// causal self-attention backward, one workgroup per (sample, head): Nq == Nk <= 128, head_dim 64, dQ, dK and dV all wanted;
+// every other shape is refused with an error that names the limit.  p.delta is not used (delta stays in LDS)
+int launch_attn_causal_bwd(const AttnParams& p, hipStream_t stream);
 
 // ---------------------------------------------------------------------------------------------------------------
 // normalisation
@@ -243,6 +248,8 @@ int launch_silu(int dtype, const void* x, void* y, int64_t n, hipStream_t stream
 int launch_add(int dtype, const void* a, const void* b, void* y, int64_t n, hipStream_t stream);  // y = a + b
 // CLIP text encoder pieces: y = quick_gelu(x) (kind 0) / gelu(x) (kind 1); token + position embedding lookup; row gather
 int launch_act(int dtype, const void* x, void* y, int64_t n, int kind, hipStream_t stream);
+// dx = dy * act'(x) in fp32, one 16-bit rounding at the store; any n (x, dy, dx 16-byte aligned)
+int launch_act_bwd(int dtype, const void* x, const void* dy, void* dx, int64_t n, int kind, hipStream_t stream);
 int launch_embed(int dtype, const int* ids, const void* tok, const void* pos, void* out, int64_t rows, int L, int d,
                  int vocab, hipStream_t stream);
 int launch_gather_rows(int dtype, const void* src, const int* idx, void* out, int n, int L, int d, hipStream_t stream);

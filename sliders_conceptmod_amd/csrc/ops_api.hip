@@ -126,6 +126,44 @@ int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v,
   p.delta = delta;
   return launch_attn_bwd(p, (hipStream_t)stream);
 }
+// causal self-attention (nq == nk == n) with explicit leading dimensions: the engine's fused [M, 3C] q|k|v layout
+static AttnParams attn_causal(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h, int n,
+                              int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale) {
+  AttnParams p = attn_dense(dtype, q, k, v, o, lse, b, h, n, n, d, scale);
+  p.ldq = ldq;
+  p.ldk = ldk;
+  p.ldv = ldv;
+  p.ldo = ldo;
+  p.causal = 1;
+  return p;
+}
+int smi_op_attention_causal_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
+                                int n, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale, void* stream) {
+  return launch_attn_fwd(attn_causal(dtype, q, k, v, o, lse, b, h, n, d, ldq, ldk, ldv, ldo, scale), (hipStream_t)stream);
+}
+int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
+                                const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
+                                int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
+                                int64_t lddk, int64_t lddv, float scale, void* stream) {
+  AttnParams p = attn_causal(dtype, q, k, v, const_cast<void*>(o), const_cast<float*>(lse), b, h, nq, d, ldq, ldk, ldv, ldo, scale);
+  p.Nk = nk;
+  p.dO = d_o;
+  p.lddo = lddo;
+  p.dQ = dq;
+  p.dK = dk;
+  p.dV = dv;
+  p.lddq = lddq;
+  p.lddk = lddk;
+  p.lddv = lddv;
+  p.delta = delta;
+  return launch_attn_bwd(p, (hipStream_t)stream);
+}
+int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream) {
+  if (y)
+    if (int rc = launch_act(dtype, x, y, n, kind, (hipStream_t)stream)) return rc;
+  if (!dy) return 0;
+  return launch_act_bwd(dtype, x, dy, dx, n, kind, (hipStream_t)stream);
+}
 // scratch layout (floats): ab[2*nb*c] | mean_rstd[nb*g*2] | partial[...]
 int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
                      float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream) {

@@ -14,7 +14,16 @@ lora_down shapes, its `.alpha` entries, its key set matched against LoRANetwork 
 guessed from folder names; `--image_size` is honoured (the SD-1.x script overrides it with 512); SD-XL samples with DDIM
 by default (the pipeline's EulerDiscrete is not a native scheduler); the VAE decodes in `--vae_dtype` (bf16 for SD-XL:
 its decoder overflows fp16 and this engine has no fp32 path); the `all/` strip is a plain PIL image, not a matplotlib
-figure."""
+figure.
+
+Text-encoder LoRA files (`train_notrigger`, conceptmod/notrigger): `--te_model_name` takes them, repeated or as a comma list;
+the tower a file belongs to is told by its key prefix (`lora_te1_` / `lora_te2_`).  A file written by `combine_loras` given as
+`--model_name` is split by prefix into its UNet slider and its text-encoder parts.  Per scale the text-encoder adaptor runs
+at multiplier = scale on every prompt the sweep encodes, conditional and unconditional; the steps with t > start_noise use
+the un-adapted embeddings and the later steps the adapted ones -- the flip the UNet slider makes.  `--model_name` may be
+left out: a text-encoder-only sweep.  On a `synthetic://` model the text front end is then a pair of seeded CLIP towers
+(`train_notrigger.synthetic_towers`) instead of the hashed-embedding stand-in; `--synthetic_towers` asks for them without a
+file (the images a text-encoder file at scale 0 must reproduce)."""
 from __future__ import annotations
 
 import argparse
@@ -96,7 +105,41 @@ def lora_file_params(state: Dict[str, torch.Tensor], unet) -> Tuple[int, float, 
 
 
 def load_lora_network(unet, path: str, device):
-    state = load_lora_state(path)
+    return lora_network_from_state(unet, load_lora_state(path), device)
+
+
+TE_PREFIXES = ("lora_te1_", "lora_te2_")
+
+
+def parse_te_names(values) -> List[str]:
+    """--te_model_name, repeated and / or comma lists -> file names."""
+    return [p.strip() for v in (values or []) for p in v.split(",") if p.strip()]
+
+
+def te_tower_of(state: Dict[str, torch.Tensor], what: str) -> int:
+    """The tower (0 / 1) a text-encoder LoRA state belongs to: every key carries the one prefix."""
+    towers = {i for k in state for i, p in enumerate(TE_PREFIXES) if k.startswith(p)}
+    if len(towers) != 1 or not all(k.startswith(TE_PREFIXES) for k in state):
+        raise ValueError(f"{what}: a text-encoder LoRA file holds keys of exactly one of {TE_PREFIXES}")
+    return towers.pop()
+
+
+def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: int, device):
+    """The LoRANetwork of a text-encoder file on its tower (rank and alpha read from the file), adaptor off."""
+    downs = [v for k, v in state.items() if k.endswith(".lora_down.weight")]
+    ranks = {int(v.shape[0]) for v in downs}
+    alphas = {float(v) for k, v in state.items() if k.endswith(".alpha")}
+    if len(ranks) != 1 or len(alphas) > 1:
+        raise ValueError(f"text-encoder LoRA file mixes ranks {sorted(ranks)} or alphas {sorted(alphas)}")
+    rank = ranks.pop()
+    net = LM.LoRANetwork(text_encoder, rank=rank, multiplier=1.0, alpha=alphas.pop() if alphas else float(rank),
+                         target_replace=LM.CLIP_TARGET_REPLACE, prefix=TE_PREFIXES[tower][:-1], train_method="full").to(device)
+    net.load_state_dict(state)  # strict: the file's layers must be this tower's
+    net.__exit__(None, None, None)  # multiplier 0 outside `with net:`
+    return net
+
+
+def lora_network_from_state(unet, state: Dict[str, torch.Tensor], device):
     rank, alpha, method, target_replace = lora_file_params(state, unet)
     net = LM.LoRANetwork(unet, rank=rank, multiplier=1.0, alpha=alpha, train_method=method,
                          target_replace=target_replace).to(device)
@@ -156,13 +199,58 @@ def generate(args) -> List[str]:
     if isinstance(text_encoders, (list, tuple)):
         for te in text_encoders:
             te.to(device, unet_dtype)
-    network = load_lora_network(unet, args.model_name, device)
-    if args.rank is not None and args.rank != network.lora_dim:
+    # ---- the adaptor files: a UNet slider, text-encoder files, or a combined file split by prefix
+    te_states: Dict[int, Dict[str, torch.Tensor]] = {}
+    unet_state = None
+    if args.model_name:
+        unet_state = load_lora_state(args.model_name)
+        if any(k.startswith(TE_PREFIXES) for k in unet_state):
+            from .combine_loras import PREFIXES, split_by_prefix
+            parts = split_by_prefix(unet_state)
+            unet_state = parts[PREFIXES[0]] or None
+            for i, p in enumerate(TE_PREFIXES):
+                if parts[p]:
+                    te_states[i] = parts[p]
+    for path in parse_te_names(args.te_model_name):
+        state = load_lora_state(path)
+        tower = te_tower_of(state, path)
+        if tower in te_states:
+            raise ValueError(f"{path}: text encoder {tower + 1} already has a LoRA ({TE_PREFIXES[tower]}*)")
+        te_states[tower] = state
+    if unet_state is None and not te_states:
+        raise ValueError("nothing to sweep: give --model_name, --te_model_name or both")
+    if (te_states or args.synthetic_towers) and isinstance(text_encoders, model_util.SyntheticTextEncoder):
+        from .train_notrigger import synthetic_towers
+        tokenizers, text_encoders = synthetic_towers(args.pretrained_model[len("synthetic://"):])
+        width = sum(te.config.hidden_size for te in text_encoders)
+        if width != unet.cfg.cross_attention_dim:
+            raise ValueError(f"{args.pretrained_model}: the synthetic text towers are {width} wide, the UNet's context "
+                             f"{unet.cfg.cross_attention_dim}: no text-encoder sweep on this model")
+        for te in text_encoders:
+            te.to(device, unet_dtype)
+    te_networks = []
+    for tower, state in sorted(te_states.items()):
+        if not isinstance(text_encoders, (list, tuple)) or tower >= len(text_encoders):
+            raise ValueError(f"{TE_PREFIXES[tower]}* keys, but the model has no text encoder {tower + 1}")
+        te_networks.append(te_network_from_state(text_encoders[tower], state, tower, device))
+    network = lora_network_from_state(unet, unet_state, device) if unet_state is not None else None
+    if network is not None and args.rank is not None and args.rank != network.lora_dim:
         raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
     vae = model_util.load_vae_decoder(args.pretrained_model, xl=xl).to(device, vae_dtype)
     factor = 2 ** (len(vae.config.block_out_channels) - 1)
     scales = parse_scales(args.scales)
-    name = os.path.splitext(os.path.basename(args.model_name))[0]
+    name = os.path.splitext(os.path.basename(args.model_name or parse_te_names(args.te_model_name)[0]))[0]
+
+    def conditioning(prompt, scale):
+        """The prompt pair's embeddings; scale None: the un-adapted towers, else every text-encoder adaptor at `scale`."""
+        import contextlib
+        with contextlib.ExitStack() as stack:
+            for net in (te_networks if scale is not None else []):
+                net.set_lora_slider(scale)
+                stack.enter_context(net)
+            return prompt_conditioning(text_encoders, tokenizers, prompt, args.negative_prompts, args.num_samples, xl, h, w,
+                                       device, unet_dtype)
+
     folder = os.path.join(args.save_path, name)
     for d in [scale_str(s) for s in scales] + ["all"]:
         os.makedirs(os.path.join(folder, d), exist_ok=True)
@@ -172,15 +260,16 @@ def generate(args) -> List[str]:
         case = row["case_number"]
         if not (args.from_case <= case <= args.till_case):
             continue
-        te, added = prompt_conditioning(text_encoders, tokenizers, row["prompt"], args.negative_prompts,
-                                        args.num_samples, xl, h, w, device, unet_dtype)
+        te, added = conditioning(row["prompt"], None)
         images = []  # [scale][num] -> PIL
         for scale in scales:
             scheduler.set_timesteps(args.ddim_steps)
             lat = initial_latents(row["evaluation_seed"], args.num_samples, h, w, scheduler,
                                   vae.config.latent_channels, factor).to(device)
+            te_on, added_on = conditioning(row["prompt"], scale) if te_networks else (None, None)
             lat = train_util.slider_sweep_latents(unet, network, scheduler, lat, te, scale, start_noise,
-                                                  args.guidance_scale, args.ddim_steps, added_cond=added)
+                                                  args.guidance_scale, args.ddim_steps, added_cond=added,
+                                                  adapted_embeddings=te_on, adapted_added_cond=added_on)
             rgb = vae.decode_to_uint8(lat.float() / vae.config.scaling_factor).cpu().numpy()
             images.append([Image.fromarray(rgb[i]) for i in range(rgb.shape[0])])
         for num in range(args.num_samples):
@@ -196,7 +285,13 @@ def generate(args) -> List[str]:
 def build_parser():
     p = argparse.ArgumentParser(prog="python -m sliders_conceptmod_amd.generate_images",
                                 description="Generate slider sweeps (eval-scripts/generate_images_*.py) on the MI355X.")
-    p.add_argument("--model_name", required=True, help="LoRA file (.pt / .safetensors) written by the trainers")
+    p.add_argument("--model_name", default=None, help="LoRA file (.pt / .safetensors) written by the trainers, or a file "
+                   "written by combine_loras (split by key prefix); may be left out with --te_model_name")
+    p.add_argument("--te_model_name", action="append", default=None,
+                   help="text-encoder LoRA file(s) written by train_notrigger: repeat the flag or join with commas; the "
+                        "tower is told by the key prefix (lora_te1_ / lora_te2_)")
+    p.add_argument("--synthetic_towers", action="store_true",
+                   help="synthetic:// models: seeded CLIP towers as the text front end (implied by a text-encoder file)")
     p.add_argument("--prompts_path", required=True, help="CSV with prompt, evaluation_seed, case_number")
     p.add_argument("--save_path", required=True, help="output folder")
     p.add_argument("--pretrained_model", default="synthetic://sd1x",

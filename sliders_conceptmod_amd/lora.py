@@ -140,6 +140,27 @@ def select_targets(root_module: nn.Module, train_method: str, target_replace_mod
     return out
 
 
+CLIP_TARGET_REPLACE = ["CLIPAttention", "CLIPSdpaAttention"]  # notrigger/train_notrigger.py:186
+_CLIP_QKV = {"q_proj": 0, "k_proj": 1, "v_proj": 2}
+
+
+def flat_order(targets):
+    """The order in which the targets' matrices are laid out in the flat buffers: the order of the walk, except that the
+    q_proj / k_proj / v_proj of one CLIP `self_attn` lie in that order wherever the walk met them (transformers declares
+    k, v, q): the engine fuses the three into one q|k|v GEMM and wants their sites adjacent and in its order.  File keys,
+    `unet_loras` and the RNG draws keep the order of the walk; UNet targets (to_q, to_k, to_v, ...) are not touched."""
+    first = {}
+    for i, (_name, path, _child) in enumerate(targets):
+        parent, _, leaf = path.rpartition(".")
+        if leaf in _CLIP_QKV and parent.endswith("self_attn"):
+            first.setdefault(parent, i)
+
+    def key(i):
+        parent, _, leaf = targets[i][1].rpartition(".")
+        return (first[parent], _CLIP_QKV[leaf]) if parent in first and leaf in _CLIP_QKV else (i, 0)
+    return sorted(range(len(targets)), key=key)
+
+
 class LoRANetwork(nn.Module):
     def __init__(self, unet, rank: int = 4, multiplier: float = 1.0, delimiter: str = "_", alpha: float = 1.0,
                  target_replace=DEFAULT_TARGET_REPLACE, prefix=LORA_PREFIX_UNET,
@@ -157,13 +178,17 @@ class LoRANetwork(nn.Module):
         self.flat = nn.Parameter(torch.zeros(max(n_down + n_up, 1), dtype=torch.float32))
         self.unet_loras: List[LoRAModule] = []
         od = ou = 0
+        offsets = {}
+        for i in flat_order(targets):
+            offsets[i] = (od, ou)
+            _r, dshape, ushape = lora_shapes(targets[i][2], rank)
+            od += math.prod(dshape)
+            ou += math.prod(ushape)
         by_name = {}
-        for lora_name, path, child in targets:
-            m = LoRAModule(self, lora_name, path, child, multiplier, rank, alpha, od, ou)
+        for i, (lora_name, path, child) in enumerate(targets):
+            m = LoRAModule(self, lora_name, path, child, multiplier, rank, alpha, *offsets[i])
             self.unet_loras.append(m)
             by_name[lora_name] = m
-            od += m.lora_down._numel
-            ou += m.lora_up._numel
         lora_names = set()
         for lora in self.unet_loras:
             assert lora.lora_name not in lora_names, f"duplicated lora name: {lora.lora_name}. {lora_names}"

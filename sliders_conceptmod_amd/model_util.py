@@ -438,9 +438,12 @@ class SyntheticClipTokenizer:
                for w in words]
         return [self.bos_token_id] + ids + [self.eos_token_id]
 
-    def __call__(self, prompts, **_):
+    def __call__(self, prompts, padding=None, max_length=None, **_):
         rows = [self.encode(p) for p in ([prompts] if isinstance(prompts, str) else prompts)]
         width = max(len(r) for r in rows)
+        if padding == "max_length":  # as CLIPTokenizer: every row to max_length (EOS fills: the stand-in's pad token)
+            width = max_length or self.model_max_length
+            rows = [r[:width - 1] + [self.eos_token_id] if len(r) > width else r for r in rows]
         ids = torch.tensor([r + [self.eos_token_id] * (width - len(r)) for r in rows], dtype=torch.int64)
 
         class _Encoding:

@@ -74,7 +74,7 @@ def diffusion_xl(unet, scheduler, latents, text_embeddings, add_text_embeddings,
 @torch.no_grad()
 def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, scale: float, start_noise: int,
                          guidance_scale: float = 7.5, num_inference_steps: int = 50, added_cond=None,
-                         uncond_per_step=None):
+                         uncond_per_step=None, adapted_embeddings=None, adapted_added_cond=None):
     """The inference-side slider loop of the eval scripts (eval-scripts/generate_images_sd1.py:170-190,
     generate_images_xl.py:327-343): denoise from `latents` (already x init_noise_sigma) with classifier-free guidance, the
     adaptor OFF (set_lora_slider(0)) while t > start_noise and at `scale` afterwards, every UNet call inside `with network`.
@@ -82,24 +82,35 @@ def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, sca
     `uncond_per_step` (real-image editing, demo_image_editing.ipynb): one unconditional embedding [1, L, D] per step, as
     null-text inversion returns them -- step k runs on cat([uncond_per_step[k] expanded to the batch, cond]), `cond` being
     the second half of `text_embeddings`; None: `text_embeddings` as given at every step.
+    `adapted_embeddings` / `adapted_added_cond` (a text-encoder LoRA, conceptmod/notrigger): the same two things encoded under
+    the text-encoder adaptor at `scale`; they replace `text_embeddings` / `added_cond` at the steps where the UNet slider is
+    on (t <= start_noise) -- the same flip.  `network` may then be None: a text-encoder-only sweep.
     Returns the final latents (decoding them is the VAE decoder's job, outside this package)."""
+    import contextlib
     scheduler.set_timesteps(num_inference_steps)
+    plain_embeddings, plain_added = text_embeddings, added_cond
     if uncond_per_step is not None and len(uncond_per_step) != len(scheduler.timesteps):
         raise ValueError(f"{len(uncond_per_step)} unconditional embeddings for {len(scheduler.timesteps)} steps")
     cond = text_embeddings.chunk(2)[1]
     for k, t in enumerate(scheduler.timesteps):
-        network.set_lora_slider(scale=0 if t > start_noise else scale)
+        on = not (t > start_noise)
+        if network is not None:
+            network.set_lora_slider(scale=scale if on else 0)
+        text_embeddings = adapted_embeddings if on and adapted_embeddings is not None else plain_embeddings
+        added_cond = adapted_added_cond if on and adapted_added_cond is not None else plain_added
         if uncond_per_step is not None:
+            cond = text_embeddings.chunk(2)[1]
             u = uncond_per_step[k].to(cond.device, cond.dtype)
             text_embeddings = torch.cat([u.expand(*cond.shape), cond])
-        with network:
+        with (network if network is not None else contextlib.nullcontext()):
             if added_cond is None:
                 noise_pred = predict_noise(unet, scheduler, t, latents, text_embeddings, guidance_scale=guidance_scale)
             else:
                 noise_pred = predict_noise_xl(unet, scheduler, t, latents, text_embeddings, added_cond[0], added_cond[1],
                                               guidance_scale=guidance_scale)
         latents = scheduler.step(noise_pred, t, latents).prev_sample
-    network.set_lora_slider(scale=1)
+    if network is not None:
+        network.set_lora_slider(scale=1)
     return latents
 
 
