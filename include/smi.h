@@ -469,6 +469,45 @@ int smi_op_attention_fwd(int dtype, const void* q, const void* k, const void* v,
 int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,
                          const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
                          int d, float scale, void* stream);
+/* Attention with every operand at its own leading dimension (elements; the engine's layouts: q|k|v as column blocks of one
+ * [b n, 3 h d] tensor, k|v inside a [b nk, 2 h d] tensor or inside a wider tensor of the caller's, gradients likewise),
+ * the kernel selection pinned for the call, and a report of what ran.  Test entry of tests/test_attention_kernels_gpu.py.
+ *   forward:  q, k, v, o, lse (lse may be NULL)
+ *   backward: q, k, v, o, lse, d_o, delta (f32 [b, h, nq] workspace) and dq and / or dk + dv; dq NULL: dK / dV only (delta
+ *             from its own kernel); dk and dv NULL: dQ only
+ *   sel_xs / sel_fused: -1 = as SMI_ATTN_XS / SMI_ATTN_BWD_FUSED say (the default), 0 = off, 1 = on, for this call only:
+ *             the single-pass kernels for nk <= 96, and the one-launch backward.  The shape rules still apply.
+ * Operands 16-byte aligned, leading dimensions multiples of 8. */
+typedef struct smi_attn_args {
+  const void *q, *k, *v;
+  void* o;
+  float* lse;
+  const void* d_o;
+  void *dq, *dk, *dv;
+  float* delta;
+  void* stream;
+  int64_t ldq, ldk, ldv, ldo, lddo, lddq, lddk, lddv;
+  int dtype, b, h, nq, nk, d;
+  float scale;
+  int causal, sel_xs, sel_fused;
+} smi_attn_args;
+#define SMI_ATTN_FWD 1       /* tiled forward (online softmax over 64-key tiles) */
+#define SMI_ATTN_XS_FWD 2    /* single-pass forward, nk <= 96 */
+#define SMI_ATTN_BWD_FUSED 3 /* dQ and dK / dV workgroups in one launch */
+#define SMI_ATTN_DQ 4        /* tiled dQ (publishes delta) */
+#define SMI_ATTN_XS_DQ 5     /* single-pass dQ, nk <= 96 (publishes delta) */
+#define SMI_ATTN_DKV 6       /* dK and dV in one kernel (tile depth <= 96) */
+#define SMI_ATTN_DK_DV 7     /* dK and dV as two launches (tile depth 160) */
+#define SMI_ATTN_DELTA 8     /* delta kernel of the dK / dV-only form */
+typedef struct smi_attn_ran {
+  int dp;         /* tile depth: 32, 64, 96 or 160 */
+  int form;       /* k-steps over d: 1 = full depth at compile time, 2 = the alternative (40 in 64, 80 in 96), 0 = run-time */
+  int n_launches; /* kernel families launched, in order, in family[0 .. n_launches) */
+  int family[4];  /* SMI_ATTN_* */
+  int chain;      /* single-pass kernels: 128-query blocks per workgroup; otherwise 0 */
+} smi_attn_ran;
+int smi_op_attention_ex_fwd(const smi_attn_args* args, smi_attn_ran* ran);
+int smi_op_attention_ex_bwd(const smi_attn_args* args, smi_attn_ran* ran);
 /* Causal self-attention (key j visible to query i iff j <= i; CLIP text towers) with explicit leading dimensions, so that
  * q | k | v may be column blocks of one fused [b n, 3 h d] tensor.  The backward is one workgroup per (sample, head):
  * nq == nk <= 128, head_dim 64, all of dq / dk / dv; anything else returns an error that names the limit.  `delta` is

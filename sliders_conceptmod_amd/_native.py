@@ -72,6 +72,22 @@ class WgradJobC(C.Structure):
                 ("Hout", C.c_int), ("Wout", C.c_int), ("conv_stride", C.c_int), ("conv_ups", C.c_int)]
 
 
+class AttnArgsC(C.Structure):
+    """include/smi.h smi_attn_args: one attention launch with explicit leading dimensions (test entry point)."""
+    _fields_ = [("q", C.c_void_p), ("k", C.c_void_p), ("v", C.c_void_p), ("o", C.c_void_p), ("lse", C.c_void_p),
+                ("d_o", C.c_void_p), ("dq", C.c_void_p), ("dk", C.c_void_p), ("dv", C.c_void_p), ("delta", C.c_void_p),
+                ("stream", C.c_void_p),
+                ("ldq", C.c_int64), ("ldk", C.c_int64), ("ldv", C.c_int64), ("ldo", C.c_int64), ("lddo", C.c_int64),
+                ("lddq", C.c_int64), ("lddk", C.c_int64), ("lddv", C.c_int64),
+                ("dtype", C.c_int), ("b", C.c_int), ("h", C.c_int), ("nq", C.c_int), ("nk", C.c_int), ("d", C.c_int),
+                ("scale", C.c_float), ("causal", C.c_int), ("sel_xs", C.c_int), ("sel_fused", C.c_int)]
+
+
+class AttnRanC(C.Structure):
+    """include/smi.h smi_attn_ran: what an smi_op_attention_ex_* call launched."""
+    _fields_ = [("dp", C.c_int), ("form", C.c_int), ("n_launches", C.c_int), ("family", C.c_int * 4), ("chain", C.c_int)]
+
+
 class DoraSiteC(C.Structure):
     """include/smi.h smi_dora_site: one DoRA Linear of the per-kernel DoRA entry points."""
     _fields_ = [("W", C.c_void_p), ("off_down", C.c_int64), ("off_up", C.c_int64), ("off_dora", C.c_int64),
@@ -179,6 +195,8 @@ _SIGS = {
                        [C.c_void_p]),
     "smi_op_attention_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
     "smi_op_attention_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),
+    "smi_op_attention_ex_fwd": (C.c_int, [C.POINTER(AttnArgsC), C.POINTER(AttnRanC)]),
+    "smi_op_attention_ex_bwd": (C.c_int, [C.POINTER(AttnArgsC), C.POINTER(AttnRanC)]),
     "smi_op_attention_causal_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_int64] * 4 +
                                     [C.c_float, C.c_void_p]),
     "smi_op_attention_causal_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_int64] * 8 +

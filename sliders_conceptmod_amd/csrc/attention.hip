@@ -15,6 +15,8 @@
 // kernel (one workgroup per 128 keys, sweeping queries): no atomics, bitwise reproducible.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "kernels.h"
 
 namespace smi {
@@ -205,6 +207,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     for (int r = 0; r < 16; ++r) o[i][r] = 0.f;
   float m_run = -INFINITY;
   f32x4 l4 = {0.f, 0.f, 0.f, 0.f};  // running row sum (all four registers equal), see Sum4
+  // bf16: lse from an fp32 sum of the UNROUNDED probabilities.  l4 adds the 16-bit values (the normaliser of exactly what
+  // P.V consumes, so O is unchanged), and against the lazily rescaled reference the probability of a row's dominant key is
+  // not 1 but a rounded number in [1, 256]: log(l4) is off by up to 2^-8 = 3.9e-3 when one key carries the row, above the
+  // 2e-3 the backward's lse is held to.  fp16 (2^-11) stays on l4 alone: 32 VALU adds per tile in a VALU-bound loop.
+  constexpr bool LSE_F32 = std::is_same<T, bf16>::value;
+  float lx = 0.f;
 
   const int ntiles = (p.Nk + TK - 1) / TK;
   // K/V tiles are fetched one tile ahead into registers: the global-load latency hides under the MFMAs / softmax
@@ -288,6 +296,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
       const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * sl);  // 1 for lanes that keep their reference
       m_run = m_new;
       l4 *= alpha;
+      if constexpr (LSE_F32) lx *= alpha;
 #pragma unroll
       for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -298,6 +307,12 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     for (int sub = 0; sub < 2; ++sub)
 #pragma unroll
       for (int r = 0; r < 16; ++r) st[sub][r] = __builtin_amdgcn_exp2f(st[sub][r] * sl - mb);
+    if constexpr (LSE_F32) {
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lx += st[sub][r];
+    }
     // O^T[d, q] += V^T[d, keys] . P^T[keys, q]
 #pragma unroll
     for (int sub = 0; sub < 2; ++sub)
@@ -318,6 +333,8 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
 
   const float l_tot = halves_sum(l4[0]);
   const float inv = 1.f / l_tot;
+  float l_lse = l_tot;
+  if constexpr (LSE_F32) l_lse = halves_sum(lx);
   if (q_idx < p.Nq) {
     T* orow = (T*)p.O + ((int64_t)b * p.Nq + q_idx) * p.ldo + col0;
 #pragma unroll
@@ -334,7 +351,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
       }
     if (p.lse && h2 == 0)
       p.lse[((int64_t)b * p.H + head) * p.Nq + q_idx] =
-          m_run * p.scale + __logf(l_tot);
+          m_run * p.scale + __logf(l_lse);
   }
 }
 
@@ -892,6 +909,22 @@ __global__ __launch_bounds__(256, DP <= 64 ? 3 : 1) void attn_xs_fwd_kernel(Attn
 #pragma unroll
       for (int r = 8; r < 16; ++r) st[2][r] = __builtin_amdgcn_exp2f(st[2][r] * sl - mb);
     }
+    // bf16: lse from the fp32 sum of the unrounded probabilities, as in attn_fwd_kernel (here the dominant probability is
+    // exactly 1, but the roundings of the others still reach 2e-3 in log(l)); O keeps the sum of the rounded ones
+    constexpr bool LSE_F32 = std::is_same<T, bf16>::value;
+    float lx = 0.f;
+    if constexpr (LSE_F32) {
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) lx += st[sub][r];
+#pragma unroll
+      for (int r = 0; r < 8; ++r) lx += st[2][r];
+      if (tail16) {
+#pragma unroll
+        for (int r = 8; r < 16; ++r) lx += st[2][r];
+      }
+    }
 
     // O^T[d, q] = V^T[d, keys] P^T[keys, q]
     f32x16 o[NB];
@@ -934,7 +967,9 @@ __global__ __launch_bounds__(256, DP <= 64 ? 3 : 1) void attn_xs_fwd_kernel(Attn
       }
     wave_lds_sync();
     X::store_rows(tile, rO, q0, p.Nq, p.ldo, col0, p.D, lane);
-    if (p.lse && h2 == 0 && q_idx < p.Nq) p.lse[((int64_t)b * p.H + head) * p.Nq + q_idx] = m * p.scale + __logf(l_tot);
+    float l_lse = l_tot;
+    if constexpr (LSE_F32) l_lse = halves_sum(lx);
+    if (p.lse && h2 == 0 && q_idx < p.Nq) p.lse[((int64_t)b * p.H + head) * p.Nq + q_idx] = m * p.scale + __logf(l_lse);
     wave_lds_sync();  // the stores' tile reads precede the next block's Q rows
   }
 }
@@ -1110,10 +1145,26 @@ int xs_dq_launch(const AttnParams& p, hipStream_t st) {
   SMI_HIP(hipGetLastError());
   return 0;
 }
+// Selection override of the parity tests (set_attn_select): -1 = the environment variable, 0 = off, 1 = on
+static int g_sel_xs = -1, g_sel_fused = -1;
+// what the last launch_attn_fwd / launch_attn_bwd of this thread launched (attn_last_ran); host side only
+static thread_local AttnRan g_ran;
+static void ran_begin(int dp, int form) {
+  g_ran = AttnRan();
+  g_ran.dp = dp;
+  g_ran.form = form;
+}
+static void ran_add(int family, int chain = 0) {
+  if (g_ran.n < 4) g_ran.family[g_ran.n] = family;
+  ++g_ran.n;
+  if (chain) g_ran.chain = chain;
+}
+static int xs_chain(const AttnParams& p) { return cdiv(p.Nq, 128) / xs_grid_x(p); }
+
 // SMI_ATTN_XS=0: short key sequences through the generic tiled kernels (A/B)
 static bool xs_enabled() {
   static const bool on = []() { const char* e = getenv("SMI_ATTN_XS"); return !(e && e[0] == '0'); }();
-  return on;
+  return g_sel_xs < 0 ? on : g_sel_xs != 0;
 }
 
 template <typename T, int DP>
@@ -1151,7 +1202,11 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(AttnParams p) {
 
 int check_attn(const AttnParams& p) {
   SMI_CHECK(p.D % 8 == 0 && p.D >= 8 && p.D <= 160, "attention: head_dim %d unsupported (need D %% 8 == 0, <= 160)", p.D);
-  SMI_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 4 == 0, "attention: row strides must be 16-byte multiples");
+  // O leaves the tiled forward in 8-byte quads, but the single-pass forward stores it, and every backward kernel reads it,
+  // in whole 16-byte chunks (buf_store16 / buf_load16, the u32x4 loads of attn_delta_kernel): 16 bytes like the others
+  SMI_CHECK(p.ldq % 8 == 0 && p.ldk % 8 == 0 && p.ldv % 8 == 0 && p.ldo % 8 == 0,
+            "attention: row strides ldq %lld ldk %lld ldv %lld ldo %lld must be multiples of 8 elements (16 bytes)",
+            (long long)p.ldq, (long long)p.ldk, (long long)p.ldv, (long long)p.ldo);
   SMI_CHECK(p.B > 0 && p.H > 0 && p.Nq > 0 && p.Nk > 0, "attention: empty shape");
   SMI_CHECK((int64_t)p.Nq * p.ldq * 2 < 0xFFFFFFF0ll && (int64_t)p.Nk * p.ldk * 2 < 0xFFFFFFF0ll, "attention: per-batch tensor larger than 4 GiB");
   return 0;
@@ -1166,10 +1221,13 @@ int fwd_t(const AttnParams& p, hipStream_t st) {
   dim3 grid(cdiv(p.Nq, 128), p.H, p.B);
   constexpr int NS = DP / 16, ALT = alt_steps<DP>();
   const int nsd = (p.D + 15) / 16;
-  if (p.Nk <= XS_KEYS && xs_enabled()) {  // all keys at once (cross-attention on the text tokens)
+  ran_begin(DP, nsd == NS ? 1 : (ALT > 0 && nsd == ALT ? 2 : 0));
+  if (p.Nk <= XS_KEYS && xs_enabled() && g_ran.form != 0) {  // all keys at once (cross-attention on the text tokens)
+    ran_add(ATTN_RAN_XS_FWD, xs_chain(p));
     if (nsd == NS) return xs_fwd_launch<T, DP, NS>(p, st);
-    if (ALT > 0 && nsd == ALT) return xs_fwd_launch<T, DP, (ALT > 0 ? ALT : NS)>(p, st);
+    return xs_fwd_launch<T, DP, (ALT > 0 ? ALT : NS)>(p, st);
   }
+  ran_add(ATTN_RAN_FWD);
   if (nsd == NS)
     hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS>), grid, dim3(256), 0, st, p);
   else if (ALT > 0 && nsd == ALT)
@@ -1196,7 +1254,9 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
   constexpr int ALTC = ALT > 0 ? ALT : NS;
   const int nsd = (p.D + 15) / 16;
   const int form = nsd == NS ? 1 : (ALT > 0 && nsd == ALT ? 2 : 0);  // 1: full depth, 2: the alternative, 0: run-time
+  ran_begin(DP, form);
   if (!p.dQ) {  // dK / dV only: nobody else forms delta
+    ran_add(ATTN_RAN_DELTA);
     const int64_t total = (int64_t)p.B * p.H * p.Nq;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(attn_delta_kernel<T>, dim3(grid), dim3(256), 0, st, p);
@@ -1209,8 +1269,9 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     // (Since the backward runs on the live half of the adapted samples alone, the headline's 4096-key level has 640
     // workgroups per kind and takes the fused launch as well: measured inside the step against the separate kernels there,
     // 153.56 vs 153.67 ms per step over three alternations -- no difference, so the rule stays a grid-size rule.)
-    if (fused_on && p.dQ && p.dK && p.dV && form != 0 && p.Nk > XS_KEYS &&
+    if ((g_sel_fused < 0 ? fused_on : g_sel_fused != 0) && p.dQ && p.dK && p.dV && form != 0 && p.Nk > XS_KEYS &&
         (int64_t)cdiv(p.Nq, 128) * p.H * p.B <= 1024) {
+      ran_add(ATTN_RAN_BWD_FUSED);
       constexpr size_t sm = dkv_smem<T, DP>() > dq_smem<T, DP>() ? dkv_smem<T, DP>() : dq_smem<T, DP>();
       const int64_t total = (int64_t)(cdiv(p.Nk, 128) + cdiv(p.Nq, 128)) * p.H * p.B;
       SMI_CHECK(total < (1ll << 31), "attention bwd: grid too large");
@@ -1232,9 +1293,11 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     }
   }
   if (p.dQ && p.Nk <= XS_KEYS && xs_enabled() && form != 0) {
+    ran_add(ATTN_RAN_XS_DQ, xs_chain(p));
     if (form == 1) { if (xs_dq_launch<T, DP, NS>(p, st)) return -2; }
     else { if (xs_dq_launch<T, DP, ALTC>(p, st)) return -2; }
   } else if (p.dQ) {
+    ran_add(ATTN_RAN_DQ);
     dim3 grid(cdiv(p.Nq, 128), p.H, p.B);
     if (form == 1)
       hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, NS, false>), grid, dim3(256), 0, st, p);
@@ -1247,6 +1310,7 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     SMI_CHECK(p.dK && p.dV, "attention bwd: dK and dV must both be given");
     dim3 grid(cdiv(p.Nk, 128), p.H, p.B);
     const size_t sm = dkv_smem<T, DP>();
+    ran_add(DP <= 96 ? ATTN_RAN_DKV : ATTN_RAN_DK_DV);
     if (DP <= 96) {
       if (form == 1) { if (dkv_launch<T, DP, 3, NS>(p, grid, sm, st)) return -2; }
       else if (form == 2) { if (dkv_launch<T, DP, 3, ALTC>(p, grid, sm, st)) return -2; }
@@ -1273,14 +1337,26 @@ int dispatch(const AttnParams& p, hipStream_t st, bool bwd) {
 
 }  // namespace
 
+void set_attn_select(int xs, int fused) {
+  g_sel_xs = xs;
+  g_sel_fused = fused;
+}
+AttnRan attn_last_ran() { return g_ran; }
+
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream) {
+  g_ran = AttnRan();
   if (check_attn(p)) return -1;
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, false) : dispatch<bf16>(p, stream, false);
 }
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream) {
+  g_ran = AttnRan();
   if (p.causal) return launch_attn_causal_bwd(p, stream);  // the kernels below know no mask
   if (check_attn(p)) return -1;
   SMI_CHECK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");
+  // dO rows are read, and dQ rows written by the single-pass kernel, in whole 16-byte chunks
+  SMI_CHECK(p.lddo % 8 == 0 && (!p.dQ || p.lddq % 8 == 0) && (!p.dK || p.lddk % 8 == 0) && (!p.dV || p.lddv % 8 == 0),
+            "attention bwd: row strides lddo %lld lddq %lld lddk %lld lddv %lld must be multiples of 8 elements (16 bytes)",
+            (long long)p.lddo, (long long)p.lddq, (long long)p.lddk, (long long)p.lddv);
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, true) : dispatch<bf16>(p, stream, true);
 }
 

@@ -209,6 +209,30 @@ struct AttnParams {
 };
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream);
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream);
+// Kernel selection of the two launchers for the parity tests: xs = the single-pass kernels for Nk <= 96, fused = the
+// one-launch backward; -1 = as the environment says (SMI_ATTN_XS / SMI_ATTN_BWD_FUSED, the default), 0 = off, 1 = on.
+// Process-wide, host side; the shape rules of the dispatcher still apply (1 does not force a kernel a shape cannot take).
+void set_attn_select(int xs, int fused);
+// What the last launch_attn_fwd / launch_attn_bwd of the calling thread launched (recorded on the host, like the
+// ran_code of launch_gemm_on_tile): n == 0 after a refused call or the causal backward.
+enum {
+  ATTN_RAN_FWD = 1,        // attn_fwd_kernel
+  ATTN_RAN_XS_FWD = 2,     // attn_xs_fwd_kernel
+  ATTN_RAN_BWD_FUSED = 3,  // attn_bwd_fused_kernel
+  ATTN_RAN_DQ = 4,         // attn_bwd_dq_kernel
+  ATTN_RAN_XS_DQ = 5,      // attn_xs_bwd_dq_kernel
+  ATTN_RAN_DKV = 6,        // attn_bwd_dkv_kernel<WHICH = 3>
+  ATTN_RAN_DK_DV = 7,      // attn_bwd_dkv_kernel<1> then <2>
+  ATTN_RAN_DELTA = 8,      // attn_delta_kernel
+};
+struct AttnRan {
+  int dp = 0;     // tile depth DP
+  int form = 0;   // 1 = full-depth compile-time k-steps, 2 = the alternative (40 in 64, 80 in 96), 0 = run-time
+  int n = 0;      // launches, in order
+  int family[4] = {0, 0, 0, 0};
+  int chain = 0;  // single-pass kernels: query blocks per workgroup (nqb / gridDim.x), else 0
+};
+AttnRan attn_last_ran();
 // causal self-attention backward, one workgroup per (sample, head): Nq == Nk <= 128, head_dim 64, dQ, dK and dV all wanted;
 // every other shape is refused with an error that names the limit.  p.delta is not used (delta stays in LDS)
 int launch_attn_causal_bwd(const AttnParams& p, hipStream_t stream);

@@ -126,6 +126,58 @@ int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v,
   p.delta = delta;
   return launch_attn_bwd(p, (hipStream_t)stream);
 }
+// every operand at its own leading dimension, the kernel selection pinned for this call, what ran reported back
+static AttnParams attn_ex(const smi_attn_args* a) {
+  AttnParams p;
+  p.dtype = a->dtype;
+  p.Q = a->q;
+  p.K = a->k;
+  p.V = a->v;
+  p.O = a->o;
+  p.lse = a->lse;
+  p.ldq = a->ldq;
+  p.ldk = a->ldk;
+  p.ldv = a->ldv;
+  p.ldo = a->ldo;
+  p.B = a->b;
+  p.H = a->h;
+  p.Nq = a->nq;
+  p.Nk = a->nk;
+  p.D = a->d;
+  p.scale = a->scale;
+  p.causal = a->causal;
+  p.dO = a->d_o;
+  p.lddo = a->lddo;
+  p.delta = a->delta;
+  p.dQ = a->dq;
+  p.dK = a->dk;
+  p.dV = a->dv;
+  p.lddq = a->lddq;
+  p.lddk = a->lddk;
+  p.lddv = a->lddv;
+  return p;
+}
+static int attn_ex_run(const smi_attn_args* a, smi_attn_ran* ran, bool bwd) {
+  if (!a) {
+    set_error("smi_op_attention_ex: NULL arguments");
+    return -1;
+  }
+  set_attn_select(a->sel_xs, a->sel_fused);
+  const AttnParams p = attn_ex(a);
+  const int rc = bwd ? launch_attn_bwd(p, (hipStream_t)a->stream) : launch_attn_fwd(p, (hipStream_t)a->stream);
+  set_attn_select(-1, -1);
+  if (ran) {
+    const AttnRan r = attn_last_ran();
+    ran->dp = r.dp;
+    ran->form = r.form;
+    ran->n_launches = r.n;
+    for (int i = 0; i < 4; ++i) ran->family[i] = r.family[i];
+    ran->chain = r.chain;
+  }
+  return rc;
+}
+int smi_op_attention_ex_fwd(const smi_attn_args* a, smi_attn_ran* ran) { return attn_ex_run(a, ran, false); }
+int smi_op_attention_ex_bwd(const smi_attn_args* a, smi_attn_ran* ran) { return attn_ex_run(a, ran, true); }
 // causal self-attention (nq == nk == n) with explicit leading dimensions: the engine's fused [M, 3C] q|k|v layout
 static AttnParams attn_causal(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h, int n,
                               int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, float scale) {
