@@ -525,6 +525,58 @@ int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* be
                      float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream);
 int smi_op_layernorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
                      float* mean_rstd, int m, int c, float eps, void* stream);
+/* GroupNorm / LayerNorm as the engine launches them.  Test entries of tests/test_norm_kernels_gpu.py.
+ *   smi_op_groupnorm_ex: forward on nb samples of x [nb, hw, c] (y NULL: the statistics-only launch of the VAE decoder's
+ *     tail: a, b and mean_rstd, no y); when dy is given, the backward on samples [bwd_n0, nb) with the forward's a, b and
+ *     mean_rstd at their offsets: dy, add and dx are [nb - bwd_n0, hw, c]; add is optional and may equal dx.
+ *     scratch (f32) as smi_op_groupnorm: a [nb, c] | b [nb, c] | mean_rstd [nb, g, 2] | partials.
+ *     sel_fused: -1 = as SMI_GN_FUSED_HW / SMI_GN_FUSED_MAX say (the default), 0 = never the one-launch forward, 1 = the
+ *     one-launch forward wherever its shape rules hold (group width even and <= 256, slice within LDS), for this call.
+ *   smi_op_layernorm_ex: nb = rows m, x [m, c], scratch = mean_rstd f32 [m, 2]; backward on rows [bwd_n0, m): dy, add and
+ *     dx are [m - bwd_n0, c].  hw, g, silu and sel_fused are not read.
+ * ran_fwd / ran_bwd (either may be NULL) receive what the forward / backward launched. */
+typedef struct smi_norm_args {
+  const void *x, *gamma, *beta;
+  void* y;
+  const void *dy, *add;
+  void* dx;
+  float* scratch;
+  void* stream;
+  int dtype, nb, hw, c, g;
+  float eps;
+  int silu, bwd_n0, sel_fused;
+} smi_norm_args;
+#define SMI_NORM_GN_ONE 1  /* GroupNorm forward in one launch (slice in LDS) */
+#define SMI_NORM_GN_TWO 2  /* chunk partials + apply (or + statistics) */
+#define SMI_NORM_GN_FOLD 3 /* chunk partials + fold to 64 slots + apply */
+#define SMI_NORM_LN 4      /* LayerNorm kernel <nv, r> */
+typedef struct smi_norm_ran {
+  int form;          /* SMI_NORM_*; 0 after a refused call */
+  int chunks, slots; /* GroupNorm two-launch forms: chunks per sample, partial slots the apply head merges */
+  int nv, r;         /* LayerNorm: 8-element vectors per lane, rows per wave */
+} smi_norm_ran;
+int smi_op_groupnorm_ex(const smi_norm_args* args, smi_norm_ran* ran_fwd, smi_norm_ran* ran_bwd);
+int smi_op_layernorm_ex(const smi_norm_args* args, smi_norm_ran* ran_fwd, smi_norm_ran* ran_bwd);
+/* The small elementwise kernels, one launch each (tests/test_elementwise_kernels_gpu.py):
+ *   pool2x2_sum  dx [nb, h, w, c] = sum of the 2 x 2 block of du [nb, 2h, 2w, c], c % 8 == 0
+ *   colsum       out [nb, c] (T) = mul * sum over hw of x [nb, hw, c]; scratch f32, smi_op_colsum_floats of them
+ *   timestep_embed  out [n, dim] = cos(t f_i) | sin(t f_i), f_i = 10000^(-i / (dim / 2))
+ *   softmax_rows P [rows, cols] (T) = softmax(scale * S) of fp32 rows
+ *   chan_mix     y [m, c] (f32) = b + x W^T on fp32 rows, c <= 16
+ *   conv3x3_small  stride 1, pad 1: in [nb, h, w, cin], w [cout][9 cin] (tap-major), out [nb, h, w, cout] T or f32
+ *   nchw_to_nhwc(_scaled)  NCHW (T or f32) -> [nb, hw, cpad] T, columns >= c zero, times scale (times scale_dev[n]) */
+int smi_op_pool2x2_sum(int dtype, const void* du, void* dx, int nb, int h, int w, int c, void* stream);
+int smi_op_colsum_floats(int nb, int c, size_t* out_floats);
+int smi_op_colsum(int dtype, const void* x, void* out, float* scratch, int nb, int hw, int c, float mul, void* stream);
+int smi_op_timestep_embed(int dtype, const float* vals, void* out, int n, int dim, void* stream);
+int smi_op_softmax_rows(int dtype, const float* s, void* p, int rows, int cols, float scale, void* stream);
+int smi_op_chan_mix(int dtype, const float* x, const void* w, const void* b, float* y, int64_t m, int c, void* stream);
+int smi_op_conv3x3_small(int dtype, const void* in, const void* w, const void* bias, void* out, int out_f32, int nb, int h,
+                         int wd, int cin, int cout, void* stream);
+int smi_op_nchw_to_nhwc(int dtype, const void* src, int src_f32, void* dst, int nb, int c, int hw, int cpad, float scale,
+                        void* stream);
+int smi_op_nchw_to_nhwc_scaled(int dtype, const float* src, void* dst, int nb, int c, int hw, int cpad, const float* scale_dev,
+                               void* stream);
 int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream);
 /* ff.net.0 with the GEGLU gate fused into the GEMM epilogue (the engine's forward path for
  * diffusers GEGLU: proj = x W^T + b [M, N]; out[M, N/2] = proj[:, :N/2] * gelu(proj[:, N/2:])).  Rows >= proj_row0 of

@@ -88,6 +88,19 @@ class AttnRanC(C.Structure):
     _fields_ = [("dp", C.c_int), ("form", C.c_int), ("n_launches", C.c_int), ("family", C.c_int * 4), ("chain", C.c_int)]
 
 
+class NormArgsC(C.Structure):
+    """include/smi.h smi_norm_args: one GroupNorm / LayerNorm forward (+ backward on a sub-range) (test entry point)."""
+    _fields_ = [("x", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("y", C.c_void_p), ("dy", C.c_void_p),
+                ("add", C.c_void_p), ("dx", C.c_void_p), ("scratch", C.c_void_p), ("stream", C.c_void_p),
+                ("dtype", C.c_int), ("nb", C.c_int), ("hw", C.c_int), ("c", C.c_int), ("g", C.c_int), ("eps", C.c_float),
+                ("silu", C.c_int), ("bwd_n0", C.c_int), ("sel_fused", C.c_int)]
+
+
+class NormRanC(C.Structure):
+    """include/smi.h smi_norm_ran: what an smi_op_groupnorm_ex / smi_op_layernorm_ex call launched."""
+    _fields_ = [("form", C.c_int), ("chunks", C.c_int), ("slots", C.c_int), ("nv", C.c_int), ("r", C.c_int)]
+
+
 class DoraSiteC(C.Structure):
     """include/smi.h smi_dora_site: one DoRA Linear of the per-kernel DoRA entry points."""
     _fields_ = [("W", C.c_void_p), ("off_down", C.c_int64), ("off_up", C.c_int64), ("off_dora", C.c_int64),
@@ -204,6 +217,17 @@ _SIGS = {
     "smi_op_act": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_groupnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
     "smi_op_layernorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
+    "smi_op_groupnorm_ex": (C.c_int, [C.POINTER(NormArgsC), C.POINTER(NormRanC), C.POINTER(NormRanC)]),
+    "smi_op_layernorm_ex": (C.c_int, [C.POINTER(NormArgsC), C.POINTER(NormRanC), C.POINTER(NormRanC)]),
+    "smi_op_pool2x2_sum": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p]),
+    "smi_op_colsum_floats": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_op_colsum": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
+    "smi_op_timestep_embed": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "smi_op_softmax_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "smi_op_chan_mix": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
+    "smi_op_conv3x3_small": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
+    "smi_op_nchw_to_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
+    "smi_op_nchw_to_nhwc_scaled": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 4 + [C.c_void_p, C.c_void_p]),
     "smi_op_geglu": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 2 + [C.c_void_p]),
     "smi_op_gemm_geglu": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_void_p]),
     "smi_op_lora_down": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),

@@ -253,11 +253,13 @@ __global__ __launch_bounds__(256) void softmax_rows_kernel(const float* __restri
   const float* s = S + (int64_t)blockIdx.x * cols;
   T* p = P + (int64_t)blockIdx.x * cols;
   float m = -3.0e38f;
-  for (int i = threadIdx.x; i < cols; i += 256) m = fmaxf(m, s[i]);
+  // the maximum of the SCALED scores (max(s) * scale is the minimum of them for a negative scale; the same bits for a
+  // positive one, where rounding keeps the order)
+  for (int i = threadIdx.x; i < cols; i += 256) m = fmaxf(m, s[i] * scale);
   m = wave_max(m);
   if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = m;
   __syncthreads();
-  m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3])) * scale;
+  m = fmaxf(fmaxf(sh[0], sh[1]), fmaxf(sh[2], sh[3]));
   __syncthreads();
   float sum = 0.f;
   for (int i = threadIdx.x; i < cols; i += 256) sum += __expf(s[i] * scale - m);

@@ -258,6 +258,24 @@ int launch_groupnorm_stats(int dtype, const void* x, const void* gamma, const vo
 int launch_groupnorm_bwd(int dtype, const void* x, const void* dy, const void* gamma, const void* beta,
                          const float* a, const float* b, const float* mean_rstd, const void* add, void* dx,
                          float* partial, int Nb, int HW, int C, int G, int silu, hipStream_t stream);
+// Selection override of the parity tests, process-wide like set_attn_select: -1 follows SMI_GN_FUSED_HW / SMI_GN_FUSED_MAX
+// (the default), 0 never takes the one-launch forward, 1 takes it wherever its shape rules hold (even group width of at
+// most 256 channels, slice within LDS).
+void set_gn_select(int fused);
+// What the last launch_groupnorm_* / launch_layernorm_* of the calling thread launched (recorded on the host): form 0
+// after a refused call.
+enum {
+  NORM_RAN_GN_ONE = 1,   // gn_fused_fwd_kernel
+  NORM_RAN_GN_TWO = 2,   // partial + apply (or + stats), chunks == slots
+  NORM_RAN_GN_FOLD = 3,  // partial + fold + apply: chunks > slots == 64
+  NORM_RAN_LN = 4,       // ln_kernel<NV, R>
+};
+struct NormRan {
+  int form = 0;
+  int chunks = 0, slots = 0;  // GroupNorm two-launch forms: grid chunks per sample, partial slots the head re-reduces
+  int nv = 0, r = 0;          // LayerNorm: 8-element vectors per lane, rows per wave
+};
+NormRan gn_last_ran();
 int launch_layernorm_fwd(int dtype, const void* x, const void* gamma, const void* beta, void* y, float* mean_rstd,
                          int M, int C, float eps, hipStream_t stream);
 int launch_layernorm_bwd(int dtype, const void* x, const void* dy, const void* gamma, const float* mean_rstd,

@@ -233,6 +233,94 @@ int smi_op_layernorm(int dtype, const void* x, const void* gamma, const void* be
   if (rc || !dy) return rc;
   return launch_layernorm_bwd(dtype, x, dy, gamma, mean_rstd, nullptr, dx, m, c, (hipStream_t)stream);
 }
+static void norm_ran_out(smi_norm_ran* out) {
+  if (!out) return;
+  const NormRan r = gn_last_ran();
+  out->form = r.form;
+  out->chunks = r.chunks;
+  out->slots = r.slots;
+  out->nv = r.nv;
+  out->r = r.r;
+}
+// forward (or statistics only) on nb samples, backward on samples [bwd_n0, nb) with the engine's offset pointers
+int smi_op_groupnorm_ex(const smi_norm_args* a, smi_norm_ran* ran_fwd, smi_norm_ran* ran_bwd) {
+  if (!a) {
+    set_error("smi_op_groupnorm_ex: NULL arguments");
+    return -1;
+  }
+  if (a->bwd_n0 < 0 || a->bwd_n0 >= a->nb) {
+    set_error("smi_op_groupnorm_ex: bwd_n0=%d outside [0, nb=%d)", a->bwd_n0, a->nb);
+    return -1;
+  }
+  const int nb = a->nb, hw = a->hw, c = a->c, g = a->g, n0 = a->bwd_n0;
+  float* ab = a->scratch;
+  float* mr = ab + (size_t)2 * nb * c;
+  float* part = mr + (size_t)nb * g * 2;
+  hipStream_t st = (hipStream_t)a->stream;
+  set_gn_select(a->sel_fused);
+  int rc = a->y ? launch_groupnorm_fwd(a->dtype, a->x, a->gamma, a->beta, a->y, ab, mr, part, nb, hw, c, g, a->eps, a->silu, st)
+                : launch_groupnorm_stats(a->dtype, a->x, a->gamma, a->beta, ab, mr, part, nb, hw, c, g, a->eps, st);
+  set_gn_select(-1);
+  norm_ran_out(ran_fwd);
+  if (rc || !a->dy) return rc;
+  const char* xs = (const char*)a->x + (size_t)n0 * hw * c * 2;  // both types are 2 bytes wide
+  rc = launch_groupnorm_bwd(a->dtype, xs, a->dy, a->gamma, a->beta, ab + (size_t)n0 * c, ab + (size_t)(nb + n0) * c,
+                            mr + (size_t)n0 * g * 2, a->add, a->dx, part, nb - n0, hw, c, g, a->silu, st);
+  norm_ran_out(ran_bwd);
+  return rc;
+}
+// forward on m rows (nb = m; hw, g, silu, sel_fused unused; scratch = mean_rstd f32 [m, 2]), backward on rows [bwd_n0, m)
+int smi_op_layernorm_ex(const smi_norm_args* a, smi_norm_ran* ran_fwd, smi_norm_ran* ran_bwd) {
+  if (!a) {
+    set_error("smi_op_layernorm_ex: NULL arguments");
+    return -1;
+  }
+  if (a->bwd_n0 < 0 || a->bwd_n0 >= a->nb) {
+    set_error("smi_op_layernorm_ex: bwd_row0=%d outside [0, m=%d)", a->bwd_n0, a->nb);
+    return -1;
+  }
+  const int m = a->nb, c = a->c, r0 = a->bwd_n0;
+  hipStream_t st = (hipStream_t)a->stream;
+  int rc = launch_layernorm_fwd(a->dtype, a->x, a->gamma, a->beta, a->y, a->scratch, m, c, a->eps, st);
+  norm_ran_out(ran_fwd);
+  if (rc || !a->dy) return rc;
+  rc = launch_layernorm_bwd(a->dtype, (const char*)a->x + (size_t)r0 * c * 2, a->dy, a->gamma, a->scratch + (size_t)r0 * 2, a->add,
+                            a->dx, m - r0, c, st);
+  norm_ran_out(ran_bwd);
+  return rc;
+}
+// ---- the small elementwise kernels, one thin entry each
+int smi_op_pool2x2_sum(int dtype, const void* du, void* dx, int nb, int h, int w, int c, void* stream) {
+  return launch_pool2x2_sum(dtype, du, dx, nb, h, w, c, (hipStream_t)stream);
+}
+int smi_op_colsum_floats(int nb, int c, size_t* out_floats) {
+  *out_floats = colsum_scratch_floats(nb, c);
+  return 0;
+}
+int smi_op_colsum(int dtype, const void* x, void* out, float* scratch, int nb, int hw, int c, float mul, void* stream) {
+  return launch_colsum(dtype, x, out, scratch, nb, hw, c, mul, (hipStream_t)stream);
+}
+int smi_op_timestep_embed(int dtype, const float* vals, void* out, int n, int dim, void* stream) {
+  return launch_timestep_embed(dtype, vals, out, n, dim, (hipStream_t)stream);
+}
+int smi_op_softmax_rows(int dtype, const float* s, void* p, int rows, int cols, float scale, void* stream) {
+  return launch_softmax_rows(dtype, s, p, rows, cols, scale, (hipStream_t)stream);
+}
+int smi_op_chan_mix(int dtype, const float* x, const void* w, const void* b, float* y, int64_t m, int c, void* stream) {
+  return launch_chan_mix(dtype, x, w, b, y, m, c, (hipStream_t)stream);
+}
+int smi_op_conv3x3_small(int dtype, const void* in, const void* w, const void* bias, void* out, int out_f32, int nb, int h,
+                         int wd, int cin, int cout, void* stream) {
+  return launch_conv3x3_small(dtype, in, w, bias, out, out_f32, nb, h, wd, cin, cout, (hipStream_t)stream);
+}
+int smi_op_nchw_to_nhwc(int dtype, const void* src, int src_f32, void* dst, int nb, int c, int hw, int cpad, float scale,
+                        void* stream) {
+  return launch_nchw_to_nhwc(dtype, src, src_f32, dst, nb, c, hw, cpad, scale, (hipStream_t)stream);
+}
+int smi_op_nchw_to_nhwc_scaled(int dtype, const float* src, void* dst, int nb, int c, int hw, int cpad, const float* scale_dev,
+                               void* stream) {
+  return launch_nchw_to_nhwc_scaled(dtype, src, dst, nb, c, hw, cpad, scale_dev, (hipStream_t)stream);
+}
 int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream) {
   int rc = launch_geglu_fwd(dtype, proj, out, m, c4, (hipStream_t)stream);
   if (rc || !dout) return rc;
