@@ -391,6 +391,38 @@ int smi_unet_ctx_grad(smi_engine* e, int on);
 int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
                           float* d_ctx_out);
 
+/* ---- gradient with respect to the pooled embedding (SD-XL null-text inversion optimises both unconditional parts) ------
+ * SD-XL's conditioning has a second part, added_cond_kwargs["text_embeds"] [n, P], P = projection_class_embeddings_input_dim
+ * - 6 addition_time_embed_dim, which reaches every resnet through the time embedding:
+ *   text_embeds -> cat[:, :P] -> add_embedding.linear_1 -> SiLU -> linear_2 -> (+ time embedding) -> SiLU -> every resnet's
+ *   time_emb_proj -> added to every pixel of conv1's output.
+ * Its gradient rides on a pass that differentiates the context (above) and needs a transposed copy of the grouped
+ * time_emb_proj weight plus a saved-pass arena that is larger again (gradients now exist from the first resnet on).  Both
+ * live in ONE MORE caller-owned buffer; smi_weights_bytes / smi_arena_bytes / smi_workspace_bytes / smi_unet_ctx_grad_bytes
+ * report what they reported without it:
+ *   smi_unet_pooled_grad_bytes   bytes of that buffer for a shape (same arguments as smi_arena_bytes); a dry run
+ *   smi_unet_pooled_grad_attach  packs the transposed weight into `buffer` and moves the saved-pass arena there, for the
+ *                                engine's CURRENT shape (the copy folds the per-level gradient scale, which depends on the
+ *                                map sizes).  Needs the context-gradient buffer attached; drops a saved forward;
+ *                                smi_replan and smi_unet_ctx_grad_attach detach it.
+ *   smi_unet_pooled_grad         on != 0: every following save_for_backward forward that differentiates the context also
+ *                                differentiates text_embeds of its adapted samples.  Requires smi_unet_ctx_grad(e, 1) and an
+ *                                attached buffer; an error on an engine without addition_embed and with an adaptor on a
+ *                                time_emb_proj (c3lier; the error names the site).  smi_unet_ctx_grad(e, 0) turns it off too.
+ *                                The forward's eps has the bits it has without the switch.
+ *   smi_unet_backward_cond       smi_unet_backward_ctx of such a pass that also WRITES (not +=) d(loss)/d(text_embeds) of
+ *                                the adapted samples to d_text_embeds_out, fp32 [n_adapted, P], each sample's loss scale
+ *                                divided out, zero when no term arrived; nothing is written for frozen samples in front.
+ *                                time_ids gets no gradient.
+ * smi_unet_backward / smi_unet_backward_ctx on such a pass still work (without the new output); smi_unet_backward_tail
+ * refuses it. */
+int smi_unet_pooled_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                               int batch_adapted, int h, int w, int ctx_len, size_t* bytes);
+int smi_unet_pooled_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes);
+int smi_unet_pooled_grad(smi_engine* e, int on);
+int smi_unet_backward_cond(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
+                           float* d_ctx_out, float* d_text_embeds_out);
+
 /* Per-kernel-class timing, measured with HIP events recorded on the engine's stream around every launch
  * (measurement aid for bench.py's roofline; off by default, adds two event records per launch when on).
  * smi_profile_read synchronises with the host and returns, per class, the summed device time (ms), the algorithmic

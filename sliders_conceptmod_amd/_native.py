@@ -185,6 +185,11 @@ _SIGS = {
     "smi_unet_ctx_grad_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "smi_unet_ctx_grad": (C.c_int, [C.c_void_p, C.c_int]),
     "smi_unet_backward_ctx": (C.c_int, [C.c_void_p] * 5),
+    "smi_unet_pooled_grad_bytes": (C.c_int, [C.POINTER(UNetConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int,
+                                             C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_unet_pooled_grad_attach": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "smi_unet_pooled_grad": (C.c_int, [C.c_void_p, C.c_int]),
+    "smi_unet_backward_cond": (C.c_int, [C.c_void_p] * 6),
     "smi_nulltext_loss": (C.c_int, [C.c_void_p] * 4 + [C.c_float] * 3 + [C.c_int64] + [C.c_void_p] * 4),
     "smi_profile_enable": (C.c_int, [C.c_void_p, C.c_int]),
     "smi_profile_read": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
@@ -406,6 +411,8 @@ class Engine(_EngineBase):
         self._plans = {}                                         # shape -> arena tensor (LRU, most recent last)
         self._ctx_buf = None     # smi_unet_ctx_grad_attach buffer of the current shape (None: not attached)
         self._ctx_on = False
+        self._pool_buf = None    # smi_unet_pooled_grad_attach buffer of the current shape
+        self._pool_on = False
 
     def plan(self, batch: int, batch_adapted: int, h: int, w: int, ctx_len: int):
         """Make (batch, batch_adapted, h, w, ctx_len) the engine's current shape (no-op when it already is)."""
@@ -426,6 +433,7 @@ class Engine(_EngineBase):
                                0 if arena is None else arena.numel()), "smi_replan")
         self.batch, self.batch_adapted, self.h, self.w, self.ctx_len = want
         self._ctx_buf, self._ctx_on = None, False  # smi_replan detaches the context-gradient buffer
+        self._pool_buf, self._pool_on = None, False  # ... and the pooled-gradient buffer
 
     def set_ctx_grad(self, on: bool):
         """Saving forwards from here on also differentiate the context of their adapted samples (smi_unet_ctx_grad); the
@@ -443,6 +451,37 @@ class Engine(_EngineBase):
         if on != self._ctx_on:
             check(lib().smi_unet_ctx_grad(self.handle, int(on)), "smi_unet_ctx_grad")
             self._ctx_on = on
+            if not on:
+                self._pool_on = False  # the engine turns the pooled gradient off with the context gradient
+
+    def set_pooled_grad(self, on: bool):
+        """Saving forwards that differentiate the context also differentiate the pooled embedding text_embeds of their
+        adapted samples (smi_unet_pooled_grad; SD-XL only).  Call after set_ctx_grad(True); the extra buffer (the transposed
+        grouped time_emb_proj weight + a saved-pass arena that is larger again) is attached on first use for the shape."""
+        on = bool(on)
+        if on and self._pool_buf is None:
+            if self._ctx_buf is None:
+                raise SmiError("set_pooled_grad(True) needs set_ctx_grad(True) first: the pooled-embedding gradient rides "
+                               "on the context gradient's pass")
+            sarr, _keep = make_sites(self.sites)
+            out = C.c_size_t(0)
+            check(lib().smi_unet_pooled_grad_bytes(C.byref(self.cfg_c), sarr, len(self.sites), self.batch,
+                                                   self.batch_adapted, self.h, self.w, self.ctx_len, C.byref(out)),
+                  "smi_unet_pooled_grad_bytes")
+            buf = torch.empty(out.value, dtype=torch.uint8, device=self.workspace.device)
+            with torch.cuda.device(self.workspace.device):
+                check(lib().smi_unet_pooled_grad_attach(self.handle, ptr(buf), out.value), "smi_unet_pooled_grad_attach")
+            self._pool_buf = buf
+        if on != self._pool_on:
+            check(lib().smi_unet_pooled_grad(self.handle, int(on)), "smi_unet_pooled_grad")
+            self._pool_on = on
+
+    def backward_cond(self, d_eps: torch.Tensor, d_down: Optional[torch.Tensor], d_up: Optional[torch.Tensor],
+                      d_ctx: torch.Tensor, d_text_embeds: torch.Tensor):
+        """smi_unet_backward_cond: backward_ctx of a pass saved under set_pooled_grad(True) that also WRITES
+        d(loss)/d(text_embeds) of the adapted samples into d_text_embeds (fp32 [n_adapted, P])."""
+        check(lib().smi_unet_backward_cond(self.handle, ptr(d_eps), ptr(d_down), ptr(d_up), ptr(d_ctx), ptr(d_text_embeds)),
+              "smi_unet_backward_cond")
 
     def backward_ctx(self, d_eps: torch.Tensor, d_down: Optional[torch.Tensor], d_up: Optional[torch.Tensor],
                      d_ctx: torch.Tensor):

@@ -208,13 +208,41 @@ __global__ __launch_bounds__(256) void colsum_partial_kernel(const T* __restrict
   }
 }
 template <typename T>
-__global__ void colsum_final_kernel(const float* __restrict__ part, T* __restrict__ out, int Nb, int C, float mul) {
+__global__ void colsum_final_kernel(const float* __restrict__ part, T* __restrict__ out, int Nb, int C, int64_t ldo,
+                                    float mul) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= Nb * C) return;
   const int n = i / C, c = i - n * C;
   float t = 0.f;
   for (int rs = 0; rs < COLSUM_RS; ++rs) t += part[((int64_t)n * COLSUM_RS + rs) * C + c];
-  out[i] = from_f<T>(t * mul);
+  out[(int64_t)n * ldo + c] = from_f<T>(t * mul);
+}
+// g[i] *= silu'(x[i]): an fp32 gradient against the 16-bit pre-activation (the embedding MLPs of the pooled-embedding
+// gradient, which stays in fp32 from the grouped time_emb_proj product down to d(text_embeds))
+template <typename T>
+__global__ void silu_bwd_f32_kernel(const T* __restrict__ x, float* __restrict__ g, int64_t n) {
+  GSTRIDE(i, n) g[i] *= dsilu_f(to_f(x[i]));
+}
+// dx[m][j] = sum_i dy[m][i] W[i][j], j < J: the input gradient of a Linear from its own [I, ldw] weight (no transposed
+// copy), for a handful of fp32 rows.  A workgroup owns 64 columns; its 16 waves take every 16th i (128-byte row pieces)
+// and meet in LDS in a fixed order -- deterministic
+template <typename T>
+__global__ __launch_bounds__(1024) void vecmat_f32_kernel(const float* __restrict__ dy, const T* __restrict__ W,
+                                                          float* __restrict__ dx, int I, int64_t ldw, int J, int64_t lddx) {
+  __shared__ float red[16][64];
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int j = blockIdx.x * 64 + tx, m = blockIdx.y;
+  float acc = 0.f;
+  if (j < J)
+    for (int i = ty; i < I; i += 16) acc += dy[(int64_t)m * I + i] * to_f(W[(int64_t)i * ldw + j]);
+  red[ty][tx] = acc;
+  __syncthreads();
+  if (ty == 0 && j < J) {
+    float t = 0.f;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) t += red[k][tx];
+    dx[(int64_t)m * lddx + j] = t;
+  }
 }
 // CLIP text embeddings: out[n*L + l][:] = tok[ids[n*L + l]][:] + pos[l][:]
 template <typename T>
@@ -666,17 +694,37 @@ int launch_chan_mix(int dtype, const float* x, const void* W, const void* b, flo
 }
 size_t colsum_scratch_floats(int Nb, int C) { return (size_t)Nb * COLSUM_RS * C; }
 int launch_colsum(int dtype, const void* x, void* out, float* scratch, int Nb, int HW, int C, float mul,
-                  hipStream_t stream) {
+                  hipStream_t stream, int64_t ldo) {
   SMI_CHECK(C % 8 == 0 && scratch, "colsum: C %% 8 != 0 or no scratch");
+  SMI_CHECK(ldo == 0 || ldo >= C, "colsum: output row stride %lld below C = %d", (long long)ldo, C);
+  if (ldo == 0) ldo = C;
   dim3 grid(cdiv(C, 256), COLSUM_RS, Nb);
   const int fb = cdiv((int64_t)Nb * C, 256);
   if (dtype == DT_F16) {
     hipLaunchKernelGGL(colsum_partial_kernel<f16>, grid, dim3(256), 0, stream, (const f16*)x, scratch, HW, C);
-    hipLaunchKernelGGL(colsum_final_kernel<f16>, dim3(fb), dim3(256), 0, stream, scratch, (f16*)out, Nb, C, mul);
+    hipLaunchKernelGGL(colsum_final_kernel<f16>, dim3(fb), dim3(256), 0, stream, scratch, (f16*)out, Nb, C, ldo, mul);
   } else {
     hipLaunchKernelGGL(colsum_partial_kernel<bf16>, grid, dim3(256), 0, stream, (const bf16*)x, scratch, HW, C);
-    hipLaunchKernelGGL(colsum_final_kernel<bf16>, dim3(fb), dim3(256), 0, stream, scratch, (bf16*)out, Nb, C, mul);
+    hipLaunchKernelGGL(colsum_final_kernel<bf16>, dim3(fb), dim3(256), 0, stream, scratch, (bf16*)out, Nb, C, ldo, mul);
   }
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int launch_silu_bwd_f32(int dtype, const void* x, float* g, int64_t n, hipStream_t stream) {
+  const int grid = ew_grid(n);
+  if (dtype == DT_F16) hipLaunchKernelGGL(silu_bwd_f32_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)x, g, n);
+  else hipLaunchKernelGGL(silu_bwd_f32_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)x, g, n);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int launch_vecmat_f32(int dtype, const float* dy, const void* W, float* dx, int M, int I, int64_t ldw, int J, int64_t lddx,
+                      hipStream_t stream) {
+  SMI_CHECK(dy && W && dx && M > 0 && M <= 65535 && I > 0 && J > 0 && ldw >= J && lddx >= J, "vecmat: bad arguments");
+  dim3 grid(cdiv(J, 64), M);
+  if (dtype == DT_F16)
+    hipLaunchKernelGGL(vecmat_f32_kernel<f16>, grid, dim3(1024), 0, stream, dy, (const f16*)W, dx, I, ldw, J, lddx);
+  else
+    hipLaunchKernelGGL(vecmat_f32_kernel<bf16>, grid, dim3(1024), 0, stream, dy, (const bf16*)W, dx, I, ldw, J, lddx);
   SMI_HIP(hipGetLastError());
   return 0;
 }

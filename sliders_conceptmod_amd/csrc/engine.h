@@ -271,6 +271,10 @@ struct smi_engine {
   std::deque<Ten>* tens = &tens_[0];
   std::vector<std::function<void()>> tape;
   bool saving = false;
+  // the forward in flight has passed a source of gradients: an adapted layer, or an attention whose k|v are differentiated.
+  // (Downstream of the first one every tensor of the trunk takes a gradient; a model that also differentiates an input
+  // which reaches the trunk EARLIER -- the UNet's pooled embedding -- asks this to tell what took one without it.)
+  bool grad_src = false;
   int64_t pack_launches = 0;  // weight-packing kernels launched so far (creation only: a replan must not add any)
   const float* lora_down = nullptr;  // parameters of the forward in flight
   const float* lora_up = nullptr;
@@ -846,6 +850,7 @@ struct smi_engine {
       p.with_lora(xa, L.rows_pad, lora_up + L.off_up, L.rank, L.nseg > 1 ? L.out / L.nseg : 0, lscale, (int)x->arow0);
     run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), gemm_bytes(p), true, "linear");
     y->arow0 = x->arow0;
+    if (lon) grad_src = true;
     if (lon && L.dora && MA(x) > 0) {  // adapted rows: y += x dW^T (dW holds lscale), accumulated onto the main result
       const GemmParams d = gemm_nt(dtype, PA(x), x->cols, dora_sites[L.dora_idx].dW, PA(y), L.out, (int)MA(x), L.out, L.in)
                                .with_res(PA(y), L.out);
@@ -1046,8 +1051,10 @@ struct smi_engine {
 
   // self-attention on a fused [M, 3C] q|k|v tensor, or cross-attention on q [M, C] and kv [n*L, 2C] -- or on k|v at
   // `kv_ext` (leading dimension ld_ext) inside a tensor of the caller's; kvg: that tensor, when it takes a gradient
+  // dq_apart (with kvg): dK|dV by a launch of their own, as where q takes no gradient, and dQ by a second one -- the bits
+  // of dK|dV then do not depend on whether dQ is wanted (a dQ kernel forms delta in another order than attn_delta_kernel)
   Ten* attention(Ten* qkv, Ten* q, Ten* kv, int heads, int C, int nbatch, int Nq, int Nk, bool causal,
-                 const void* kv_ext = nullptr, int64_t ld_ext = 0, Ten* kvg = nullptr) {
+                 const void* kv_ext = nullptr, int64_t ld_ext = 0, Ten* kvg = nullptr, bool dq_apart = false) {
     Ten* src_q = qkv ? qkv : q;
     Ten* o = new_ten(src_q->rows, C, src_q->n, src_q->H, src_q->W);
     float* lse = alloc_f32((size_t)nbatch * heads * Nq);
@@ -1078,6 +1085,7 @@ struct smi_engine {
     RUNP(SMI_PROF_ATTN, 4.0 * nbatch * heads * (double)Nq * Nk * p.D, 0.0, launch_attn_fwd(p, stream));
     // external k|v with a gradient owner: dK|dV go to this block's columns of the owner's gradient
     o->ng = qkv ? qkv->ng : (q->ng || (kv && kv->ng) || kvg);
+    if ((kv && kv->ng) || kvg) grad_src = true;
     if (saving && o->ng) {
       tape.push_back([=]() {
         if (!o->g) return;
@@ -1127,14 +1135,30 @@ struct smi_engine {
           snprintf(tag, sizeof(tag), "attn_bwd dK|dV%s B=%d H=%d Nq=%d Nk=%d D=%d", b.dQ ? "" : " (no dQ)", b.B, heads, Nq, Nk, b.D);
           next_tag = tag;
         }
+        if (dq_apart && kvg && b.dQ) {
+          AttnParams kvp = b, qp = b;
+          kvp.dQ = nullptr;
+          qp.dK = qp.dV = nullptr;
+          RUNP(SMI_PROF_ATTN, 6.0 * b.B * heads * (double)Nq * Nk * b.D, 0.0, launch_attn_bwd(kvp, stream));
+          RUNP(SMI_PROF_ATTN, 6.0 * b.B * heads * (double)Nq * Nk * b.D, 0.0, launch_attn_bwd(qp, stream));
+          return;
+        }
         RUNP(SMI_PROF_ATTN, 10.0 * b.B * heads * (double)Nq * Nk * b.D, 0.0, launch_attn_bwd(b, stream));
       });
     }
     return o;
   }
 
+  // the gradient of a row vector added to a map of HW pixels is stored x 2^-k, k = rowvec_shift(HW) ~ log2(HW) / 2
+  static int rowvec_shift(int HW) {
+    int k = 0;
+    while ((1 << (2 * (k + 1))) <= HW) ++k;
+    return k;
+  }
   // 3x3 conv (pad 1): mode 0 stride 1, 1 stride 2, 2 nearest-2x upsample then stride 1
-  Ten* conv3x3(Ten* x, const Conv& c, Ten* rowvec, Ten* res, int64_t ld_rowvec = 0) {
+  // rvg: the tensor `rowvec` is a column block of (leading dimension ld_rowvec), when that tensor takes the gradient:
+  // d(rowvec) lands in the block's columns of rvg->g, x the block's own 2^-k (whoever reads rvg->g divides it out per block)
+  Ten* conv3x3(Ten* x, const Conv& c, Ten* rowvec, Ten* res, int64_t ld_rowvec = 0, Ten* rvg = nullptr) {
     const int Hin = x->H, Win = x->W;
     const int Hout = conv3x3_out(Hin, c.mode), Wout = conv3x3_out(Win, c.mode);
     Ten* y = new_ten((int64_t)x->n * Hout * Wout, c.Cout, x->n, Hout, Wout);
@@ -1148,6 +1172,7 @@ struct smi_engine {
     const float lscale = mult * c.scale;
     float* xa = nullptr;
     if (lon) {
+      grad_src = true;
       xa = alloc_f32((size_t)MA(y) * c.rows_pad);
       const GemmParams g = conv3x3_fwd(dtype, PA(x), shadow_ptr(c.sh_down), xa, ad_samples(x, Hin * Win), Hin, Win, c.Cin,
                                        c.rows_pad, c.mode, c.pad).f32_out();
@@ -1167,13 +1192,20 @@ struct smi_engine {
         if (rowvec && rowvec->ng) {
           // d(rowvec)[n][c] = sum over the pixels of sample n of dy; stored x 2^-k (k ~ log2(HW) / 2) so that a coherent sum
           // cannot leave the fp16 range -- linear_bwd divides it out again (Ten::gmul)
-          int k = 0;
-          while ((1 << (2 * (k + 1))) <= Hout * Wout) ++k;
-          rowvec->gmul = exp2f((float)-k);
-          rowvec->g = alloc_t(MA(rowvec), rowvec->cols);
+          rowvec->gmul = exp2f((float)-rowvec_shift(Hout * Wout));
+          if (rvg) {  // every block writes its own columns; zeroed once in case a block's gradient never arrives
+            if (!rvg->g) {
+              rvg->g = alloc_t(MA(rvg), rvg->cols);
+              if (!dry && !err) (void)hipMemsetAsync(rvg->g, 0, (size_t)MA(rvg) * rvg->cols * esz(), stream);
+            }
+            rowvec->g = (char*)rvg->g + ((const char*)rowvec->p - (const char*)rvg->p);
+          } else {
+            rowvec->g = alloc_t(MA(rowvec), rowvec->cols);
+          }
           float* cs_scratch = alloc_f32(colsum_scratch_floats(nb_ad, cp->Cout));
           RUNP(SMI_PROF_ELEM, 0.0, 0.0,
-               launch_colsum(dtype, dy, rowvec->g, cs_scratch, nb_ad, Hout * Wout, cp->Cout, rowvec->gmul, stream));
+               launch_colsum(dtype, dy, rowvec->g, cs_scratch, nb_ad, Hout * Wout, cp->Cout, rowvec->gmul, stream,
+                             rvg ? ld_rowvec : 0));
         }
         float* dxa = nullptr;
         if (lon) {
@@ -1272,10 +1304,11 @@ struct smi_engine {
     return y;
   }
 
-  // t: the projected time embedding, one row per sample with leading dimension ldt (0: dense); null where there is none
-  Ten* resnet(Ten* x, const Resnet& r, Ten* t, int64_t ldt, bool keep_out = false) {
+  // t: the projected time embedding, one row per sample with leading dimension ldt (0: dense); null where there is none;
+  // tg: the wider tensor t is a column block of, when it takes t's gradient (conv3x3's rvg)
+  Ten* resnet(Ten* x, const Resnet& r, Ten* t, int64_t ldt, bool keep_out = false, Ten* tg = nullptr) {
     Ten* h = groupnorm(x, r.n1, true);
-    h = conv3x3(h, r.c1, t, nullptr, ldt);
+    h = conv3x3(h, r.c1, t, nullptr, ldt, tg);
     h = groupnorm(h, r.n2, true);
     Ten* sc = r.has_sc ? linear(x, r.sc) : x;
     if (keep_out) keep_next_output();  // (conv3x3 creates its output tensor first)

@@ -34,6 +34,16 @@ __global__ void fill_kernel(float* p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
+// columns [col0, col0 + cols) of w [rows][ld] times s, a power of two (exact): a block of a packed weight copy
+template <typename T>
+__global__ void scale_cols_kernel(T* w, int ld, int rows, int col0, int cols, float s) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)rows * cols) return;
+  const int64_t r = i / cols, c = i - r * cols;
+  T* p = w + r * ld + col0 + c;
+  *p = from_f<T>(to_f(*p) * s);
+}
+
 struct TBlock {
   Norm n1, n2, n3;
   Lin qkv1, out1, q2, kv2, out2, ff1, ff2;
@@ -90,6 +100,67 @@ struct UNet : Model {
   Lin temb_all;  // every resnet's time_emb_proj stacked (they all read silu(emb)): one GEMM per pass
   bool temb_grouped = false;
   Ten* temb_all_out = nullptr;
+  // gradient with respect to the pooled embedding text_embeds (smi_unet_pooled_grad_*, smi_unet_backward_cond): on top of
+  // the context gradient.  The chain has no trainable weight on it: text_embeds -> cat[:, :P] -> add_embedding.linear_1 ->
+  // SiLU -> linear_2 -> (+ time embedding) -> SiLU -> every resnet's time_emb_proj -> added to every pixel of conv1's
+  // output.  Backward: every resnet's column sum of d(conv1 output) lands in its column block of ONE 16-bit gradient of
+  // the grouped projection, [adapted samples, sum C]; one fp32-output GEMM against the transposed grouped weight adds all
+  // the terms in one fp32 accumulation, and the rest of the chain stays in fp32 (launch_silu_bwd_f32, launch_vecmat_f32).
+  // Block b's sums are stored x 2^-k_b (Ten::gmul, k_b from its map size): the transposed copy of its weight rows is
+  // built x 2^k_b -- exact, a power of two -- so the product is the unscaled sum whatever mix of levels K runs over.  That
+  // copy and the (again larger) saved-pass arena live in one more buffer of the caller's (`tpack` + arena 1).
+  Arena tpack;
+  bool pool_cap = false, pool_want = false, bw_pool = false;
+  float* d_pooled = nullptr;  // the output of the backward in flight, fp32 [adapted samples, P]
+  bool d_pooled_written = false;
+  int pooled_dim() const { return cfg.projection_class_embeddings_input_dim - 6 * cfg.addition_time_embed_dim; }
+  // every resnet with the pixels of the map its conv1 writes, for the engine's current latent shape
+  template <typename F>
+  void for_each_resnet_hw(F f) {
+    int h = lat_h, w = lat_w;
+    for (auto& lv : down) {
+      for (auto& r : lv.res) f(r, h * w);
+      if (lv.has_samp) h = conv3x3_out(h, 1), w = conv3x3_out(w, 1);
+    }
+    for (auto& r : mid.res) f(r, h * w);
+    for (auto& lv : up) {
+      for (auto& r : lv.res) f(r, h * w);
+      if (lv.has_samp) h = conv3x3_out(h, 2), w = conv3x3_out(w, 2);
+    }
+  }
+  // why this engine has no pooled-embedding gradient (nullptr: it has one); an adaptor on a time_emb_proj is named
+  const char* pooled_refusal(std::string& site) {
+    if (!cfg.addition_embed) return "this UNet has no added conditioning (addition_embed): there is no pooled embedding to differentiate";
+    if (temb_grouped) return nullptr;
+    for_each_resnet([&](Resnet& r) {
+      if (site.empty() && r.temb.nsite > 0) site = r.temb.name;
+    });
+    return site.empty() ? "it needs the grouped time_emb_proj projection, which is off (SMI_TEMB_GROUP=0)"
+                        : "not implemented through an adaptor on a time_emb_proj";
+  }
+  int build_pooled_grad(smi_engine& e) {
+    std::string site;
+    if (const char* why = pooled_refusal(site)) {
+      set_error("pooled-embedding gradient: %s%s%s", why, site.empty() ? "" : ": ", site.c_str());
+      return -1;
+    }
+    tpack.reset();
+    const int ted = temb_all.in, SC = temb_all.out;
+    void* t = tpack.alloc((size_t)ted * SC * e.esz());
+    e.transpose_into(temb_all.W, t, SC, ted, SC, 0, false);  // [ted, sum C]: the K-contiguous operand of d(temb_act) = G W_all
+    for_each_resnet_hw([&](Resnet& r, int hw) {
+      const int k = smi_engine::rowvec_shift(hw);
+      if (k == 0 || e.dry || e.err) return;
+      const int64_t total = (int64_t)ted * r.temb.out;
+      const int grid = (int)((total + 255) / 256);
+      if (e.dtype == DT_F16)
+        hipLaunchKernelGGL(scale_cols_kernel<f16>, dim3(grid), dim3(256), 0, e.stream, (f16*)t, SC, ted, (int)r.temb_col, r.temb.out, exp2f((float)k));
+      else
+        hipLaunchKernelGGL(scale_cols_kernel<bf16>, dim3(grid), dim3(256), 0, e.stream, (bf16*)t, SC, ted, (int)r.temb_col, r.temb.out, exp2f((float)k));
+    });
+    temb_all.Wt = t;
+    return 0;
+  }
 
   // model
   Conv conv_in, conv_out;
@@ -283,8 +354,9 @@ struct UNet : Model {
     temb_all.out = (int)total;
   }
 
-  // a resnet with its projected time embedding: a column block of the grouped projection (no gradient flows into it),
-  // or this resnet's own time_emb_proj
+  // a resnet with its projected time embedding: a column block of the grouped projection (a gradient flows into it only
+  // where the pooled embedding is differentiated: then into the block's columns of the grouped gradient), or this resnet's
+  // own time_emb_proj
   Ten* resnet(smi_engine& e, Ten* x, const Resnet& r, Ten* temb_act, bool keep_out = false) {
     if (!temb_all_out) return e.resnet(x, r, e.linear(temb_act, r.temb), 0, keep_out);
     e.tens->emplace_back();
@@ -293,7 +365,9 @@ struct UNet : Model {
     t->rows = temb_all_out->rows;
     t->cols = r.temb.out;
     t->n = temb_all_out->n;
-    return e.resnet(x, r, t, temb_all.out, keep_out);
+    t->arow0 = temb_all_out->arow0;
+    t->ng = temb_all_out->ng;
+    return e.resnet(x, r, t, temb_all.out, keep_out, t->ng ? temb_all_out : nullptr);
   }
 
   Ten* transformer(smi_engine& e, Ten* x, const Transformer& t, Ten* ctx, bool keep_out = false) {
@@ -308,9 +382,11 @@ struct UNet : Model {
       nrm = e.layernorm(h, tb.n2);
       Ten* q = e.linear(nrm, tb.q2);
       if (kv_grouped) {  // with the context differentiated, dK|dV go to this block's columns of the grouped gradient
+        // (a q that takes a gradient for the pooled embedding's sake alone: dK|dV keep the bits of a pass without it)
+        const bool dq_apart = temb_all_out && temb_all_out->ng && !e.grad_src && !e.lora_active(tb.q2);
         o = e.attention(nullptr, q, nullptr, t.heads, C, nb, Nq, ctx_len, false,
                         (const char*)kv_all_out->p + (size_t)tb.kv_col * e.esz(), kv_all.out,
-                        kv_all_out->ng ? kv_all_out : nullptr);
+                        kv_all_out->ng ? kv_all_out : nullptr, dq_apart);
       } else {
         Ten* kv = e.linear(ctx, tb.kv2);
         o = e.attention(nullptr, q, kv, t.heads, C, nb, Nq, ctx_len, false);
@@ -347,11 +423,14 @@ struct UNet : Model {
     e.tens = &e.tens_[save ? 1 : 0];
     e.tens->clear();
     e.saving = save;
+    e.grad_src = false;
     const int H = lat_h, Wd_ = lat_w, HW = H * Wd_;
     const int C0 = cfg.block_out_channels[0];
     const int ted = C0 * 4;
 
-    // ---- time / added-condition embedding (no gradient flows here: not adapted under lierla)
+    // ---- time / added-condition embedding (not adapted under lierla; the one gradient that flows here is the pooled
+    // embedding's, by the closure below the grouped projection: these ops push none of their own)
+    Ten* add_pre = nullptr;  // add_embedding.linear_1's output, the pre-activation of its SiLU
     float* tvals = e.alloc_f32(n);
     if (!e.dry && !e.err) hipLaunchKernelGGL(fill_kernel, dim3(1), dim3(64), 0, e.stream, tvals, timestep, n);
     Ten* te = e.new_ten(n, C0, n, 1, 1);  // [n, C] tensors carry n, H = W = 1: the adapted samples are the last rows
@@ -366,7 +445,8 @@ struct UNet : Model {
       pooled.p = const_cast<void*>(text_embeds);
       RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(e.dtype, pooled.p, P, cat->p, cat->cols, 0, n, P, e.stream));
       RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(e.dtype, tid->p, tid->cols, cat->p, cat->cols, P, n, tid->cols, e.stream));
-      Ten* aug = e.linear(e.silu(e.linear(cat, add1)), add2);
+      add_pre = e.linear(cat, add1);
+      Ten* aug = e.linear(e.silu(add_pre), add2);
       Ten* sum = e.new_ten(n, ted, n, 1, 1);
       RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_add(e.dtype, emb->p, aug->p, sum->p, (int64_t)n * ted, e.stream));
       emb = sum;
@@ -413,6 +493,27 @@ struct UNet : Model {
     }
     // (only while nothing upstream of emb is trained: the column-block views carry no gradient)
     temb_all_out = (temb_grouped && !temb_act->ng) ? e.linear(temb_act, temb_all) : nullptr;
+    const bool pool_grad = ctx_grad && pool_want && temb_all_out && add_pre;
+    if (pool_grad) {  // runs after every resnet's backward: the whole chain back to text_embeds (see `tpack`)
+      Ten* tao = temb_all_out;
+      Ten* emb_pre = emb;  // the pre-activation of temb_act; d(emb) = d(aug): the time branch takes no gradient
+      tao->ng = true;
+      e.tape.push_back([=, &e]() {
+        if (!tao->g || !d_pooled) return;
+        const int M = (int)e.MA(tao), P = pooled_dim();
+        float* ga = e.alloc_f32((size_t)M * ted);
+        const GemmParams p = gemm_nt(e.dtype, tao->g, temb_all.out, temb_all.Wt, ga, ted, M, ted, temb_all.out).f32_out();
+        e.run_gemm(SMI_PROF_GEMM, p, e.gemm_flops(p), e.gemm_bytes(p), true, "d_temb_act");
+        RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_silu_bwd_f32(e.dtype, e.PA(emb_pre), ga, (int64_t)M * ted, e.stream));
+        float* gh = e.alloc_f32((size_t)M * ted);
+        RUNP(SMI_PROF_GEMM, 2.0 * M * ted * ted, 2.0 * ted * ted,
+             launch_vecmat_f32(e.dtype, ga, add2.W, gh, M, add2.out, add2.in, add2.in, ted, e.stream));
+        RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_silu_bwd_f32(e.dtype, e.PA(add_pre), gh, (int64_t)M * ted, e.stream));
+        RUNP(SMI_PROF_GEMM, 2.0 * M * ted * P, 2.0 * ted * P,
+             launch_vecmat_f32(e.dtype, gh, add1.W, d_pooled, M, add1.out, add1.in, P, P, e.stream));
+        d_pooled_written = true;
+      });
+    }
 
     // ---- conv_in (MFMA implicit GEMM on the 64-channel zero-padded latent)
     Ten* x0 = e.new_ten((int64_t)n * HW, 64, n, H, Wd_);
@@ -499,6 +600,7 @@ struct UNet : Model {
       e.bw_mult = e.mult;
       e.bw_samp_on = e.samp_on;
       bw_ctx = ctx_grad;
+      bw_pool = pool_grad;
       tape_valid = true;
     }
     e.saving = false;
@@ -522,9 +624,12 @@ struct UNet : Model {
     e.tens_[1].clear();
     out_ten = nullptr;
   }
-  int backward(smi_engine& e, const float* d_eps, float* dd, float* du, int n_live, float* dctx = nullptr) {
+  int backward(smi_engine& e, const float* d_eps, float* dd, float* du, int n_live, float* dctx = nullptr,
+               float* dpool = nullptr) {
     e.d_ctx = dctx;
     e.d_ctx_written = false;
+    d_pooled = dpool;
+    d_pooled_written = false;
     if (!tape_valid && !e.dry) {
       set_error("smi_unet_backward: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
       return -4;
@@ -602,7 +707,13 @@ struct UNet : Model {
       if (e.d_ctx_written) RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_row_scale_f32(e.d_ctx, D, n * L, D, e.gscale + e.MAXS, L, e.stream));
       else (void)hipMemsetAsync(e.d_ctx, 0, (size_t)n * L * D * sizeof(float), e.stream);
     }
+    if (d_pooled && !e.dry && !e.err) {  // one row per sample: the same unscale; no term at all: the gradient is zero
+      const int P = pooled_dim();
+      if (d_pooled_written) RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_row_scale_f32(d_pooled, P, n, P, e.gscale + e.MAXS, 1, e.stream));
+      else (void)hipMemsetAsync(d_pooled, 0, (size_t)n * P * sizeof(float), e.stream);
+    }
     e.d_ctx = nullptr;
+    d_pooled = nullptr;
     drop_tape(e);
     return e.end_pass("the backward (");
   }
@@ -657,7 +768,7 @@ UNet* setup(smi_engine* e, const smi_unet_config* cfg, const smi_weight* weights
 // ctx_bytes != NULL: the plan of an engine that differentiates the context -- *ctx_bytes receives the bytes of its extra
 // transposed weights and out[2] is the saved-pass arena of a forward + backward with the context gradient on
 int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int batch_adapted, int h, int w,
-         int ctx_len, size_t out[5], size_t* ctx_bytes = nullptr) {
+         int ctx_len, size_t out[5], size_t* ctx_bytes = nullptr, size_t* pool_bytes = nullptr) {
   smi_engine e;
   e.dry = true;
   UNet& u = *setup(&e, cfg, nullptr, 0, sites, n_sites, batch, batch_adapted, h, w, ctx_len);
@@ -668,6 +779,11 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
     *ctx_bytes = align_up(u.xpack.peak, 4096);
     u.ctx_want = true;
   }
+  if (pool_bytes) {  // (with ctx_bytes) ... that also differentiates the pooled embedding: its transposed grouped weight
+    if (u.build_pooled_grad(e)) return -1;
+    *pool_bytes = align_up(u.tpack.peak, 4096);
+    u.pool_want = true;
+  }
   out[0] = align_up(e.wpack.peak, 4096);
   u.dry_forward(e);
   // arena 0 = [persistent | scratch 0 | scratch 1] (no-grad liveness, smi_engine::begin_block)
@@ -676,7 +792,8 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   out[1] = out[3] + 2 * out[4];
   u.forward(e, batch, batch_adapted, nullptr, 0.f, nullptr, nullptr, nullptr, true, nullptr);
   // sized for the full backward: a tail backward needs less
-  u.backward(e, nullptr, nullptr, nullptr, u.bw_n_ad, ctx_bytes ? reinterpret_cast<float*>(16) : nullptr);
+  u.backward(e, nullptr, nullptr, nullptr, u.bw_n_ad, ctx_bytes ? reinterpret_cast<float*>(16) : nullptr,
+             pool_bytes ? reinterpret_cast<float*>(16) : nullptr);
   out[2] = align_up(e.arena[1].peak, 4096);
   return e.err ? -1 : 0;
 }
@@ -767,6 +884,7 @@ int smi_replan(smi_engine* e, int batch, int batch_adapted, int h, int w, int ct
   e->arena[1].cap = r[2];
   e->set_arena0_regions(r[3], r[4]);
   u->ctx_cap = u->ctx_want = false;  // the context-gradient arena was sized for the old shape: attach one for the new
+  u->pool_cap = u->pool_want = false;  // (and so was the pooled-gradient buffer, whose weight copy folds the map sizes)
   e->tens_[0].clear();
   ++u->replans;
   return 0;
@@ -796,6 +914,9 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
   SMI_CHECK(!u->cfg.addition_embed || (text_embeds && time_ids), "SD-XL engine needs text_embeds and time_ids");
   SMI_CHECK(!(save_for_backward && u->ctx_want) || u->ctx_cap,
             "context gradient asked for, but no buffer is attached for this shape (smi_unet_ctx_grad_attach)");
+  SMI_CHECK(!(save_for_backward && u->pool_want) || (u->pool_cap && u->ctx_want),
+            "pooled-embedding gradient asked for, but the context gradient is off or no buffer is attached for this shape "
+            "(smi_unet_ctx_grad, smi_unet_pooled_grad_attach)");
   e->err = false;
   e->lora_down = lora_down_flat;
   e->lora_up = lora_up_flat;
@@ -941,6 +1062,7 @@ int smi_unet_ctx_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes) {
   e->arena[1].cap = r[2];
   u->forget_saved_pass(*e);  // the saved activations lived in the old arena
   u->ctx_cap = true;
+  u->pool_cap = u->pool_want = false;  // a pooled-gradient buffer held arena 1 until now: attach it again after this one
   return 0;
 }
 
@@ -950,6 +1072,7 @@ int smi_unet_ctx_grad(smi_engine* e, int on) {
   SMI_CHECK(!on || (u && u->ctx_cap), "smi_unet_ctx_grad: no context-gradient buffer is attached for the engine's current shape "
                                       "(smi_unet_ctx_grad_attach; smi_replan detaches it)");
   if (u) u->ctx_want = on != 0;
+  if (u && !on) u->pool_want = false;  // the pooled-embedding gradient rides on the context gradient's pass
   return 0;
 }
 
@@ -969,12 +1092,88 @@ int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_
   return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out);
 }
 
+int smi_unet_pooled_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
+                               int batch_adapted, int h, int w, int ctx_len, size_t* bytes) {
+  if (check_cfg(cfg)) return -1;
+  SMI_CHECK(bytes && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
+            "bad arguments");
+  size_t r[5], x = 0, t = 0;
+  if (plan(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, r, &x, &t)) return -1;
+  *bytes = t + r[2] + 2 * 4096;
+  return 0;
+}
+
+int smi_unet_pooled_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes) {
+  SMI_CHECK(e && buffer, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "smi_unet_pooled_grad_attach: only UNet engines differentiate a pooled embedding");
+  UNet* u = unet(e);
+  SMI_CHECK(u->ctx_cap, "smi_unet_pooled_grad_attach: attach the context-gradient buffer first (smi_unet_ctx_grad_attach): "
+                        "the pooled-embedding gradient rides on the context gradient's pass");
+  size_t r[5], x = 0, t = 0;
+  if (plan(&u->cfg, e->sites.data(), (int)e->sites.size(), e->max_n, u->max_n_ad, u->lat_h, u->lat_w, u->ctx_len, r, &x, &t))
+    return -1;
+  char* base = (char*)align_up((size_t)buffer, 4096);
+  const size_t have = (size_t)((char*)buffer + buffer_bytes - base);
+  SMI_CHECK((char*)buffer + buffer_bytes >= base && t + r[2] <= have,
+            "smi_unet_pooled_grad_attach: buffer too small: need %zu bytes, got %zu", t + r[2] + 2 * 4096, buffer_bytes);
+  e->err = false;
+  u->tpack = Arena();
+  u->tpack.base = base;
+  u->tpack.cap = t;
+  if (u->build_pooled_grad(*e)) return -1;
+  SMI_HIP(hipGetLastError());
+  SMI_CHECK(!e->err && !u->tpack.overflow, "smi_unet_pooled_grad_attach: packing the transposed time_emb_proj weights failed");
+  e->arena[1] = Arena();  // the saved pass of a forward + backward with both gradients on: larger again
+  e->arena[1].base = base + t;
+  e->arena[1].cap = r[2];
+  u->forget_saved_pass(*e);  // the saved activations lived in the old arena
+  u->pool_cap = true;
+  return 0;
+}
+
+int smi_unet_pooled_grad(smi_engine* e, int on) {
+  SMI_CHECK(e != nullptr, "NULL argument");
+  UNet* u = unet(e);
+  if (!on) {
+    if (u) u->pool_want = false;
+    return 0;
+  }
+  SMI_CHECK(u, "smi_unet_pooled_grad: only UNet engines differentiate a pooled embedding");
+  std::string site;
+  const char* why = u->pooled_refusal(site);
+  SMI_CHECK(!why, "smi_unet_pooled_grad: %s%s%s", why ? why : "", site.empty() ? "" : ": ", site.c_str());
+  SMI_CHECK(u->pool_cap, "smi_unet_pooled_grad: no pooled-gradient buffer is attached for the engine's current shape "
+                         "(smi_unet_pooled_grad_attach; smi_replan and smi_unet_ctx_grad_attach detach it)");
+  SMI_CHECK(u->ctx_want, "smi_unet_pooled_grad: the context gradient is off (smi_unet_ctx_grad(e, 1) first): the "
+                         "pooled-embedding gradient rides on its pass");
+  u->pool_want = true;
+  return 0;
+}
+
+int smi_unet_backward_cond(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
+                           float* d_ctx_out, float* d_text_embeds_out) {
+  SMI_CHECK(e && d_eps && d_ctx_out && d_text_embeds_out, "NULL argument");
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
+  UNet* u = unet(e);
+  SMI_CHECK(u->tape_valid, "smi_unet_backward_cond: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  SMI_CHECK(u->bw_ctx && u->bw_pool, "smi_unet_backward_cond: the saved pass does not differentiate the pooled embedding "
+                                     "(smi_unet_ctx_grad(e, 1) and smi_unet_pooled_grad(e, 1) before the saving forward)");
+  const bool adapted = e->bw_down && e->bw_up && e->bw_mult != 0.f && !e->sites.empty();
+  SMI_CHECK(!adapted || (d_lora_down_flat && d_lora_up_flat),
+            "smi_unet_backward_cond: the saved pass ran with the adaptor on: its gradient buffers are required");
+  e->err = false;
+  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
+  return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out, d_text_embeds_out);
+}
+
 int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
                            float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps_live && d_lora_down_flat && d_lora_up_flat, "NULL argument");
   SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
   UNet* u = unet(e);
   SMI_CHECK(u->tape_valid, "smi_unet_backward_tail: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  SMI_CHECK(!u->bw_pool, "smi_unet_backward_tail: the saved pass differentiates the pooled embedding; a tail backward is not "
+                         "offered there (use smi_unet_backward_cond)");
   SMI_CHECK(!u->bw_ctx, "smi_unet_backward_tail: the saved pass differentiates the context; a tail backward is not offered "
                         "there (use smi_unet_backward_ctx)");
   SMI_CHECK(n_live >= 1 && n_live <= u->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",

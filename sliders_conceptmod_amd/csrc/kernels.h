@@ -315,8 +315,15 @@ int launch_chan_mix(int dtype, const float* x, const void* W, const void* b, flo
                     hipStream_t stream);
 // out[n][c] = mul * sum over the HW rows of sample n of x[n][hw][c]   (deterministic)
 size_t colsum_scratch_floats(int Nb, int C);  // fp32 scratch launch_colsum needs
+// ldo: row stride of out in elements (0 = C): a column block of a wider matrix
 int launch_colsum(int dtype, const void* x, void* out, float* scratch, int Nb, int HW, int C, float mul,
-                  hipStream_t stream);
+                  hipStream_t stream, int64_t ldo = 0);
+// g[i] *= silu'(x[i]) in place: g fp32, x the 16-bit pre-activation
+int launch_silu_bwd_f32(int dtype, const void* x, float* g, int64_t n, hipStream_t stream);
+// dx[m][j] (fp32, row stride lddx) = sum_i dy[m][i] W[i][j] for j < J: the input gradient of a Linear for a few fp32 rows
+// dy [M, I], read from the layer's own weight W T [I, ldw] (its first J input columns); fixed-order sums
+int launch_vecmat_f32(int dtype, const float* dy, const void* W, float* dx, int M, int I, int64_t ldw, int J, int64_t lddx,
+                      hipStream_t stream);
 // dst[M][cpad] (T) = src[M][0..cols) (fp32, row stride lds) * mul, zero padded
 int launch_f32_to_padded(int dtype, const float* src, int lds, int cols, void* dst, int cpad, int64_t M, float mul,
                          hipStream_t stream);

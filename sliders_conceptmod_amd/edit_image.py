@@ -12,8 +12,7 @@ Differences from the notebook, on purpose: the UNet computes in 16-bit storage (
 embedding being optimised and its Adam state stay fp32; rank, alpha and the train method are read from the LoRA file, as
 generate_images reads them, instead of being typed into a cell; the inversion runs before the adaptor is attached (the
 notebook's network is attached but switched off there); the strip is a plain PIL image, not a matplotlib figure; `--image_size`
-(default 512, the notebook's) is an argument.  SD-XL (`--base xl`) is refused: null-text inversion does not pass the added
-conditioning through yet."""
+(default 512, the notebook's) is an argument.  SD-XL (`--base xl`) is refused: that is the command `edit_image_xl`."""
 from __future__ import annotations
 
 import argparse
@@ -46,8 +45,8 @@ def output_paths(save_path: str, name: str, scales, image_path: str) -> Tuple[st
 def edit(args) -> List[str]:
     from PIL import Image
     if args.base == "xl":
-        raise ValueError("edit_image supports SD-1.x (--base 1.4): null-text inversion does not pass SD-XL's added "
-                         "conditioning through yet")
+        raise ValueError("edit_image supports SD-1.x (--base 1.4); for an SD-XL slider use the command "
+                         "python -m sliders_conceptmod_amd.edit_image_xl")
     device = torch.device(args.device if not str(args.device).isdigit() else f"cuda:{args.device}")
     if device.type != "cuda":
         raise ValueError("the product path has no CPU fallback: pass a cuda device")

@@ -19,7 +19,8 @@ Differences from the notebook: the UNet computes in fp16 / bf16 storage (the emb
 embedding is rounded for each UNet call); `next_step` / `prev_step` are two coefficients computed on the host and one
 affine kernel (smi_sched_step's arithmetic) instead of five tensor ops; prompts are encoded by a callable the caller passes
 (`encode_prompt`), not by a pipeline object; prompt-to-prompt attention control is not part of this package.
-SD-XL is refused: its added conditioning (`text_embeds`, `time_ids`) is not passed through this loop yet."""
+SD-XL is refused here: its added conditioning (`text_embeds`, `time_ids`) goes through the loop of
+null_inversion_xl.NullInversionXL."""
 from __future__ import annotations
 
 from typing import Callable, List, Optional, Sequence
@@ -83,8 +84,9 @@ class NullInversion:
             raise _native.SmiError("null-text inversion runs only on an MI355X through the HIP engine; move the UNet to a "
                                    "cuda device with unet.to(device, dtype) (there is no CPU fallback)")
         if unet.cfg.addition_embed_type == "text_time":
-            raise _native.SmiError("null-text inversion is implemented for SD-1.x UNets; an SD-XL UNet needs its added "
-                                   "conditioning (text_embeds, time_ids) passed through the loop, which is not done yet")
+            raise _native.SmiError("NullInversion is the SD-1.x class; an SD-XL UNet needs its added conditioning "
+                                   "(text_embeds, time_ids) passed through the loop: use "
+                                   "null_inversion_xl.NullInversionXL")
         if not isinstance(scheduler, model_util.DDIMScheduler) or type(scheduler) is not model_util.DDIMScheduler:
             raise ValueError("null-text inversion needs the deterministic DDIM scheduler (scheduler_name='ddim')")
         self.unet, self.scheduler, self.vae, self.vae_decoder = unet, scheduler, vae, vae_decoder

@@ -74,7 +74,8 @@ def diffusion_xl(unet, scheduler, latents, text_embeddings, add_text_embeddings,
 @torch.no_grad()
 def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, scale: float, start_noise: int,
                          guidance_scale: float = 7.5, num_inference_steps: int = 50, added_cond=None,
-                         uncond_per_step=None, adapted_embeddings=None, adapted_added_cond=None):
+                         uncond_per_step=None, adapted_embeddings=None, adapted_added_cond=None,
+                         uncond_pooled_per_step=None):
     """The inference-side slider loop of the eval scripts (eval-scripts/generate_images_sd1.py:170-190,
     generate_images_xl.py:327-343): denoise from `latents` (already x init_noise_sigma) with classifier-free guidance, the
     adaptor OFF (set_lora_slider(0)) while t > start_noise and at `scale` afterwards, every UNet call inside `with network`.
@@ -82,6 +83,9 @@ def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, sca
     `uncond_per_step` (real-image editing, demo_image_editing.ipynb): one unconditional embedding [1, L, D] per step, as
     null-text inversion returns them -- step k runs on cat([uncond_per_step[k] expanded to the batch, cond]), `cond` being
     the second half of `text_embeddings`; None: `text_embeddings` as given at every step.
+    `uncond_pooled_per_step` (SD-XL real-image editing, with `uncond_per_step` and `added_cond`): one unconditional pooled
+    embedding [1, P] per step, as NullInversionXL returns them -- step k runs with text_embeds = cat([uncond_pooled_per_step[k]
+    expanded to the batch, the conditional half of added_cond[0]]).
     `adapted_embeddings` / `adapted_added_cond` (a text-encoder LoRA, conceptmod/notrigger): the same two things encoded under
     the text-encoder adaptor at `scale`; they replace `text_embeddings` / `added_cond` at the steps where the UNet slider is
     on (t <= start_noise) -- the same flip.  `network` may then be None: a text-encoder-only sweep.
@@ -91,6 +95,12 @@ def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, sca
     plain_embeddings, plain_added = text_embeddings, added_cond
     if uncond_per_step is not None and len(uncond_per_step) != len(scheduler.timesteps):
         raise ValueError(f"{len(uncond_per_step)} unconditional embeddings for {len(scheduler.timesteps)} steps")
+    if uncond_pooled_per_step is not None:
+        if uncond_per_step is None or added_cond is None:
+            raise ValueError("uncond_pooled_per_step goes with uncond_per_step and added_cond (SD-XL)")
+        if len(uncond_pooled_per_step) != len(scheduler.timesteps):
+            raise ValueError(f"{len(uncond_pooled_per_step)} unconditional pooled embeddings for "
+                             f"{len(scheduler.timesteps)} steps")
     cond = text_embeddings.chunk(2)[1]
     for k, t in enumerate(scheduler.timesteps):
         on = not (t > start_noise)
@@ -102,6 +112,10 @@ def slider_sweep_latents(unet, network, scheduler, latents, text_embeddings, sca
             cond = text_embeddings.chunk(2)[1]
             u = uncond_per_step[k].to(cond.device, cond.dtype)
             text_embeddings = torch.cat([u.expand(*cond.shape), cond])
+        if uncond_pooled_per_step is not None:
+            pooled_cond = added_cond[0].chunk(2)[1]
+            pu = uncond_pooled_per_step[k].to(pooled_cond.device, pooled_cond.dtype)
+            added_cond = (torch.cat([pu.expand(*pooled_cond.shape), pooled_cond]), added_cond[1])
         with (network if network is not None else contextlib.nullcontext()):
             if added_cond is None:
                 noise_pred = predict_noise(unet, scheduler, t, latents, text_embeddings, guidance_scale=guidance_scale)

@@ -201,26 +201,33 @@ class _UNetFn(torch.autograd.Function):
     """Autograd bookkeeping only: forward and backward are single calls into the HIP engine."""
 
     @staticmethod
-    def forward(ctx, save, engine, sample, timestep, ehs, text_embeds, time_ids, flat, n_down, multiplier, ctx_grad):
-        # `save` / `ctx_grad` are decided by the caller: grad mode is always off inside Function.forward
+    def forward(ctx, save, engine, sample, timestep, ehs, text_embeds, time_ids, flat, n_down, multiplier, ctx_grad,
+                pooled_grad=False):
+        # `save` / `ctx_grad` / `pooled_grad` are decided by the caller: grad mode is always off inside Function.forward
         down = up = None
         if flat is not None:
             down, up = flat[:n_down], flat[n_down:]
         ehs_t = ehs.detach().to(engine.dtype).contiguous()  # the engine's operand; the gradient goes back to `ehs` in fp32
-        engine.set_ctx_grad(bool(save and ctx_grad))
-        eps = engine.forward(sample, timestep, ehs_t, text_embeds, time_ids, down, up, multiplier, save)
+        te_t = None if text_embeds is None else text_embeds.detach().to(engine.dtype).contiguous()
+        pooled_grad = bool(save and pooled_grad)
+        # the pooled embedding's gradient rides on the context gradient's pass (a d_ctx nobody asked for is dropped)
+        engine.set_ctx_grad(bool(save and ctx_grad) or pooled_grad)
+        engine.set_pooled_grad(pooled_grad)
+        eps = engine.forward(sample, timestep, ehs_t, te_t, time_ids, down, up, multiplier, save)
         ctx.engine = engine if save else None
         ctx.gen = engine.tape_generation() if save else 0
         ctx.n_down = n_down
         ctx.ctx_grad = bool(save and ctx_grad)
+        ctx.pooled_grad = pooled_grad
         ctx.ehs_meta = (tuple(ehs.shape), ehs.dtype)
-        ctx.keep = (sample, ehs_t, text_embeds, time_ids, flat)  # borrowed by the engine until backward
+        ctx.te_meta = None if text_embeds is None else (tuple(text_embeds.shape), text_embeds.dtype)
+        ctx.keep = (sample, ehs_t, te_t, time_ids, flat)  # borrowed by the engine until backward
         return eps
 
     @staticmethod
     def backward(ctx, d_eps):
         if ctx.engine is None:
-            return (None,) * 11
+            return (None,) * 12
         flat = ctx.keep[4]
         # the engine holds ONE tape: a later saved forward, a change of shape (replan) or an earlier backward drops it
         if ctx.engine.tape_generation() != ctx.gen:
@@ -230,15 +237,22 @@ class _UNetFn(torch.autograd.Function):
                 "previous backward released it). Call backward before the next grad-enabled UNet call.")
         g = torch.zeros_like(flat) if flat is not None else None
         gd, gu = (g[:ctx.n_down], g[ctx.n_down:]) if g is not None else (None, None)
-        g_ehs = None
-        if ctx.ctx_grad:
+        g_ehs = g_te = None
+        if ctx.pooled_grad:  # time_ids gets no gradient
+            shape, dt = ctx.ehs_meta
+            d_ctx = torch.empty(shape, dtype=torch.float32, device=d_eps.device)
+            d_te = torch.empty(ctx.te_meta[0], dtype=torch.float32, device=d_eps.device)
+            ctx.engine.backward_cond(d_eps.contiguous().float(), gd, gu, d_ctx, d_te)
+            g_ehs = d_ctx.to(dt) if ctx.ctx_grad else None
+            g_te = d_te.to(ctx.te_meta[1])
+        elif ctx.ctx_grad:
             shape, dt = ctx.ehs_meta
             d_ctx = torch.empty(shape, dtype=torch.float32, device=d_eps.device)
             ctx.engine.backward_ctx(d_eps.contiguous().float(), gd, gu, d_ctx)
             g_ehs = d_ctx.to(dt)
         else:
             ctx.engine.backward(d_eps.contiguous().float(), gd, gu)
-        return None, None, None, None, g_ehs, None, None, g, None, None, None
+        return None, None, None, None, g_ehs, g_te, None, g, None, None, None, None
 
 
 class UNet2DConditionModel(nn.Module):
@@ -331,9 +345,14 @@ class UNet2DConditionModel(nn.Module):
         ehs = encoder_hidden_states
         eng = self._ensure_engine(n, h, w, ehs.shape[1])
         text_embeds = time_ids = None
+        pooled_grad = False
         if self.cfg.addition_embed_type == "text_time":
-            text_embeds = added_cond_kwargs["text_embeds"].to(self.dtype).contiguous()
-            time_ids = added_cond_kwargs["time_ids"].float().contiguous()
+            text_embeds = added_cond_kwargs["text_embeds"]
+            # a pooled embedding that requires a gradient (SD-XL null-text optimisation) is differentiated like the context
+            pooled_grad = bool(torch.is_grad_enabled() and text_embeds.requires_grad)
+            if not pooled_grad:
+                text_embeds = text_embeds.detach().to(self.dtype).contiguous()
+            time_ids = added_cond_kwargs["time_ids"].detach().float().contiguous()
         t = float(timestep)
         net = self._lora_network
         flat, n_down, mult = None, 0, 0.0
@@ -344,14 +363,15 @@ class UNet2DConditionModel(nn.Module):
             grid = net.engine_compose(n)
             if grid is not None:  # one multiplier per (sample, slider): smi_unet_forward_compose, nothing saved
                 ranks, rows = grid
+                te = None if text_embeds is None else text_embeds.detach().to(eng.dtype).contiguous()
                 eps = eng.forward_compose(sample.float().contiguous(), t, ehs.detach().to(eng.dtype).contiguous(),
-                                          text_embeds, time_ids, flat[:n_down], flat[n_down:], ranks, rows, n_adapted=n)
+                                          te, time_ids, flat[:n_down], flat[n_down:], ranks, rows, n_adapted=n)
                 return UNetOutput(eps)
         lora_grad = bool(torch.is_grad_enabled() and mult != 0 and flat is not None and flat.requires_grad)
         # an embedding that requires a gradient (null-text optimisation) is differentiated with or without a LoRA network
         ctx_grad = bool(torch.is_grad_enabled() and ehs.requires_grad)
-        eps = _UNetFn.apply(lora_grad or ctx_grad, eng, sample.float().contiguous(), t, ehs, text_embeds, time_ids,
-                            flat, n_down, float(mult), ctx_grad)
+        eps = _UNetFn.apply(lora_grad or ctx_grad or pooled_grad, eng, sample.float().contiguous(), t, ehs, text_embeds,
+                            time_ids, flat, n_down, float(mult), ctx_grad, pooled_grad)
         return UNetOutput(eps)
 
 
