@@ -462,6 +462,47 @@ int smi_clip_adamw(float* param, const float* grad, float* exp_avg, float* exp_a
                    float beta1, float beta2, float eps, float weight_decay, int step, float max_norm, float* scratch,
                    void* stream);
 
+/* clip_grad_norm_(max_norm) (max_norm <= 0: no clipping) followed by one Lion step (the reference's `lion` optimiser,
+ * train_util.py:1027-1032: lion_pytorch.Lion) over flat fp32 buffers; exp_avg starts at zero:
+ *   p <- p (1 - lr weight_decay);  c = beta1 exp_avg + (1 - beta1) g;  p <- p - lr sign(c)   (sign(0) = 0, as torch.sign)
+ *   exp_avg <- beta2 exp_avg + (1 - beta2) g
+ * One grid-stride kernel after the optional norm reduction.  The hyper-parameters are doubles (the package's Python
+ * floats): 1 - beta and 1 - lr weight_decay are formed in double and rounded to fp32 once, as torch rounds a Python scalar.
+ * scratch: >= 1025 floats (only read when clipping). */
+int smi_clip_lion(float* param, const float* grad, float* exp_avg, int64_t n, double lr, double beta1, double beta2,
+                  double weight_decay, float max_norm, float* scratch, void* stream);
+
+/* Prodigy (the reference's `prodigy` optimiser, train_util.py:1033-1038: prodigyopt.Prodigy) over flat fp32 buffers.
+ * Hyper-parameters as doubles (the package's Python floats); beta3 is passed resolved (sqrt(beta2) for the default). */
+typedef struct smi_prodigy_hyper {
+  double lr, beta1, beta2, beta3, eps, weight_decay, d0, d_coef, growth_rate; /* growth_rate: INFINITY for none */
+  int decouple, use_bias_correction, safeguard_warmup;
+} smi_prodigy_hyper;
+/* The state of a fresh Prodigy group: p0 = param (a copy), exp_avg = exp_avg_sq = s = 0 (n floats each), and `state`, 8
+ * device doubles: [0] d = d0, [1] d_max = d0, [2] d_numerator = 0, [3] k = 0, and what a step's finalize leaves for its
+ * apply: [4] dlr (old), [5] d (new), [6] skip flag, [7] reserved. */
+int smi_prodigy_init(const float* param, float* p0, float* exp_avg, float* exp_avg_sq, float* s, int64_t n, double d0,
+                     double* state, void* stream);
+/* clip_grad_norm_(max_norm) (max_norm <= 0: none), then one Prodigy step.  d, d_max, d_numerator, k and the two sums are
+ * doubles on the device; the host reads none of them:
+ *   bc = use_bias_correction ? sqrt(1 - beta2^(k+1)) / (1 - beta1^(k+1)) : 1;   dlr = d lr bc
+ *   d_numerator <- beta3 d_numerator;   if weight_decay != 0 and not decouple: g <- g + weight_decay p
+ *   if lr > 0: d_numerator += (d / d0) dlr sum(g (p0 - p))
+ *   exp_avg <- beta1 exp_avg + d (1 - beta1) g;   exp_avg_sq <- beta2 exp_avg_sq + d^2 (1 - beta2) g^2
+ *   s <- beta3 s + (d / d0) (safeguard_warmup ? d : dlr) g;   d_denom = sum |s|
+ *   if d_denom == 0: stop here (p, d, d_max and k keep their values)
+ *   if lr > 0: d_hat = d_coef d_numerator / d_denom;  if d == d0: d <- max(d, d_hat);  d_max <- max(d_max, d_hat);
+ *              d <- min(d_max, d growth_rate)
+ *   if weight_decay != 0 and decouple: p <- p - weight_decay dlr p          (the OLD dlr)
+ *   p <- p - dlr exp_avg / (sqrt(exp_avg_sq) + d eps)                        (the OLD dlr, the NEW d);   k <- k + 1
+ * Three launches ordered by the stream (accumulate with one partial per workgroup of each sum; finalize, one wave, the
+ * partials added in double, each lane its run of consecutive partials in index order and the lane sums in lane order;
+ * apply): no atomics, no grid barrier, a fixed summation order, so two runs and two ranks give the same bits.
+ * scratch: >= 3073 floats. */
+int smi_clip_prodigy(float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq, float* s,
+                     int64_t n, const smi_prodigy_hyper* hyper, float max_norm, double* state, float* scratch,
+                     void* stream);
+
 /* x = c_x * x + c_eps * eps + c_noise * noise   -- the update of scheduler.step(...).prev_sample
  * (train_util.py:324,705) for DDIM (eta = 0; noise = NULL) and Euler-ancestral; coefficients computed on the host. */
 int smi_sched_step(float* x, const float* eps, const float* noise, float c_x, float c_eps, float c_noise, int64_t n,

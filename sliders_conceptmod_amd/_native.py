@@ -122,6 +122,13 @@ class LoraStackJobC(C.Structure):
                 ("coef", C.c_float), ("reserved", C.c_int)]
 
 
+class ProdigyHyperC(C.Structure):
+    """include/smi.h smi_prodigy_hyper: Prodigy's hyper-parameters, beta3 resolved."""
+    _fields_ = [(k, C.c_double) for k in ("lr", "beta1", "beta2", "beta3", "eps", "weight_decay", "d0", "d_coef",
+                                          "growth_rate")] + [("decouple", C.c_int), ("use_bias_correction", C.c_int),
+                                                             ("safeguard_warmup", C.c_int)]
+
+
 _lib = None
 
 _SIGS = {
@@ -199,6 +206,10 @@ _SIGS = {
                                                      C.c_void_p]),
     "smi_clip_adamw": (C.c_int, [C.c_void_p] * 4 + [C.c_int64] + [C.c_float] * 5 + [C.c_int, C.c_float, C.c_void_p,
                                                                                     C.c_void_p]),
+    "smi_clip_lion": (C.c_int, [C.c_void_p] * 3 + [C.c_int64] + [C.c_double] * 4 + [C.c_float, C.c_void_p, C.c_void_p]),
+    "smi_prodigy_init": (C.c_int, [C.c_void_p] * 5 + [C.c_int64, C.c_double, C.c_void_p, C.c_void_p]),
+    "smi_clip_prodigy": (C.c_int, [C.c_void_p] * 6 + [C.c_int64, C.POINTER(ProdigyHyperC), C.c_float, C.c_void_p,
+                                                      C.c_void_p, C.c_void_p]),
     "smi_sched_step": (C.c_int, [C.c_void_p] * 3 + [C.c_float] * 3 + [C.c_int64, C.c_void_p]),
     "smi_op_gemm_scratch": (C.c_int, [C.c_void_p, C.c_size_t]),
     "smi_op_gemm": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
@@ -605,6 +616,42 @@ def clip_adamw(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, 
 def adam_step(param, grad, exp_avg, exp_avg_sq, lr: float, step: int, scratch, beta1=0.9, beta2=0.999, eps=1e-8):
     """One torch.optim.Adam step on flat fp32 tensors: clip_adamw with weight_decay 0 and no clipping."""
     clip_adamw(param, grad, exp_avg, exp_avg_sq, lr, step, scratch, (beta1, beta2), eps, 0.0, 0.0)
+
+
+def clip_lion(param, grad, exp_avg, lr: float, scratch, betas=(0.9, 0.99), weight_decay=0.0, max_grad_norm=0.0):
+    """smi_clip_lion on flat fp32 tensors: clip_grad_norm_(max_grad_norm) (0: no clipping), then one Lion step.  scratch:
+    >= 1025 floats.  No allocation, no synchronisation."""
+    check(lib().smi_clip_lion(ptr(param), ptr(grad), ptr(exp_avg), param.numel(), float(lr), float(betas[0]),
+                              float(betas[1]), float(weight_decay), float(max_grad_norm), ptr(scratch), stream_ptr()),
+          "smi_clip_lion")
+
+
+PRODIGY_STATE_DOUBLES = 8  # include/smi.h smi_prodigy_init: d, d_max, d_numerator, k, dlr, d (new), skip, reserved
+
+
+def prodigy_hyper(lr=1.0, betas=(0.9, 0.999), beta3=None, eps=1e-8, weight_decay=0.0, decouple=True,
+                  use_bias_correction=False, safeguard_warmup=False, d0=1e-6, d_coef=1.0,
+                  growth_rate=float("inf")) -> ProdigyHyperC:
+    """smi_prodigy_hyper from the package's keyword arguments (beta3 None -> sqrt(beta2))."""
+    b3 = float(betas[1]) ** 0.5 if beta3 is None else float(beta3)
+    return ProdigyHyperC(float(lr), float(betas[0]), float(betas[1]), b3, float(eps), float(weight_decay), float(d0),
+                         float(d_coef), float(growth_rate), int(bool(decouple)), int(bool(use_bias_correction)),
+                         int(bool(safeguard_warmup)))
+
+
+def prodigy_init(param, p0, exp_avg, exp_avg_sq, s, state, d0: float = 1e-6):
+    """smi_prodigy_init: p0 = param, zero moments, `state` (PRODIGY_STATE_DOUBLES float64 on the device) = a fresh group."""
+    assert state.dtype == torch.float64 and state.numel() >= PRODIGY_STATE_DOUBLES
+    check(lib().smi_prodigy_init(ptr(param), ptr(p0), ptr(exp_avg), ptr(exp_avg_sq), ptr(s), param.numel(), float(d0),
+                                 ptr(state), stream_ptr()), "smi_prodigy_init")
+
+
+def clip_prodigy(param, grad, p0, exp_avg, exp_avg_sq, s, state, scratch, hyper: ProdigyHyperC, max_grad_norm=0.0):
+    """smi_clip_prodigy on flat fp32 tensors: clip_grad_norm_(max_grad_norm) (0: no clipping), then one Prodigy step with
+    d and k on the device.  scratch: >= 3073 floats.  No allocation, no synchronisation."""
+    check(lib().smi_clip_prodigy(ptr(param), ptr(grad), ptr(p0), ptr(exp_avg), ptr(exp_avg_sq), ptr(s), param.numel(),
+                                 C.byref(hyper), float(max_grad_norm), ptr(state), ptr(scratch), stream_ptr()),
+          "smi_clip_prodigy")
 
 
 def _weight_table(state: dict, dtype, device):

@@ -453,6 +453,230 @@ __global__ void clip_adamw_kernel(float* __restrict__ p, const float* __restrict
   }
 }
 
+// ---- Lion and Prodigy (include/smi.h states both algorithms).  Flat fp32 vectors; whole 4-packs go through 16-byte accesses
+// when every pointer is 16-byte aligned (VEC), the n % 4 tail -- or, unaligned, every element -- one thread each.
+__device__ __forceinline__ float clip_coef(float max_norm, const float* __restrict__ norm_sq_dev) {
+  if (!(max_norm > 0.f)) return 1.f;
+  return fminf(max_norm / (sqrtf(norm_sq_dev[0]) + 1e-6f), 1.f);
+}
+
+// The roundings are spelled out (fmaf where one is meant, contraction off for the rest) as torch's CPU kernels round
+// the same updates -- x.mul_(b).add_(g, alpha=a) is fma(a, g, fl(b x)) -- so that the fp32 emulation of the tests is THIS
+// arithmetic and a one-element vector agrees with it to the bit.
+// The sum of np <= 1024 fp32 workgroup partials in double by ONE wave (blockDim.x == 64), in a fixed order: lane l adds
+// its run of consecutive partials in index order, then the 64 lane sums are added in lane order.  Every lane gets the total.
+__device__ __forceinline__ double ordered_sum_f64(const float* __restrict__ part, int np, double* sh) {
+  const int lane = threadIdx.x, per = (np + 63) / 64;
+  const int end = (lane + 1) * per < np ? (lane + 1) * per : np;
+  double acc = 0.0;
+  for (int i = lane * per; i < end; ++i) acc += (double)part[i];
+  sh[lane] = acc;
+  __syncthreads();
+  double total = 0.0;
+  for (int l = 0; l < 64; ++l) total += sh[l];
+  __syncthreads();  // sh is free for the next sum
+  return total;
+}
+// sum g^2 for Lion and Prodigy: the partials of reduce_partial_kernel<1>, added in double.  (sum_finalize_kernel adds them
+// one by one in fp32; at 1024 partials that sum is ~5e-7 off, the clip coefficient 2.5e-7, and every clipped gradient with
+// it -- 4.4 to 4.8 times the error of an fp32 step with an accurate norm, measured: DESIGN.md section 16.  AdamW keeps it:
+// its bits are pinned.)
+__global__ __launch_bounds__(64) void sum_finalize_f64_kernel(const float* __restrict__ partial, int np,
+                                                              float* __restrict__ out) {
+  __shared__ double sh[64];
+  const double s = ordered_sum_f64(partial, np, sh);
+  if (threadIdx.x == 0) out[0] = (float)s;
+}
+
+struct LionArgs {  // coefficients rounded to fp32 once on the host, from the doubles of the C ABI
+  float lr, b1, b2, one_minus_b1, one_minus_b2, decay, max_norm;  // decay = 1 - lr * weight_decay
+};
+__device__ __forceinline__ void lion_elem(float& p, float g, float& m, const LionArgs& a, float coef) {
+#pragma clang fp contract(off)
+  const float gi = g * coef;
+  const float c = fmaf(a.one_minus_b1, gi, m * a.b1);
+  const float sgn = (float)((c > 0.f) - (c < 0.f));  // three-way, as torch.sign: an exactly zero c leaves p to the decay alone
+  p = fmaf(-a.lr, sgn, p * a.decay);
+  m = fmaf(a.one_minus_b2, gi, m * a.b2);
+}
+template <bool VEC>
+__global__ __launch_bounds__(256) void clip_lion_kernel(float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ m, int64_t n, LionArgs a,
+                                                        const float* __restrict__ norm_sq_dev) {
+  const float coef = clip_coef(a.max_norm, norm_sq_dev);
+  const int64_t n4 = VEC ? n / 4 : 0;
+  GSTRIDE(i, n4) {
+    float4 pv = reinterpret_cast<const float4*>(p)[i], mv = reinterpret_cast<const float4*>(m)[i];
+    const float4 gv = reinterpret_cast<const float4*>(g)[i];
+    lion_elem(pv.x, gv.x, mv.x, a, coef);
+    lion_elem(pv.y, gv.y, mv.y, a, coef);
+    lion_elem(pv.z, gv.z, mv.z, a, coef);
+    lion_elem(pv.w, gv.w, mv.w, a, coef);
+    reinterpret_cast<float4*>(p)[i] = pv;
+    reinterpret_cast<float4*>(m)[i] = mv;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float pi = p[i], mi = m[i];
+    lion_elem(pi, g[i], mi, a, coef);
+    p[i] = pi;
+    m[i] = mi;
+  }
+}
+
+// Prodigy's device state block (doubles): what the group carries from step to step, and what one step's finalize leaves
+// for its apply
+enum { PS_D = 0, PS_DMAX = 1, PS_NUM = 2, PS_K = 3, PS_DLR = 4, PS_DNEW = 5, PS_SKIP = 6, PS_COUNT = 8 };
+struct ProdigyArgs {
+  double lr, b1, b2, b3, eps, wd, d0, d_coef, growth;
+  float max_norm;
+  int decouple, bias_corr, safeguard;
+};
+// dlr = d * lr * bc of the step that begins at state (d, k): formed on the device, identically by every thread that needs it
+__device__ __forceinline__ double prodigy_dlr(const double* __restrict__ st, const ProdigyArgs& a) {
+  double bc = 1.0;
+  if (a.bias_corr) {
+    const double k1 = st[PS_K] + 1.0;
+    bc = sqrt(1.0 - pow(a.b2, k1)) / (1.0 - pow(a.b1, k1));
+  }
+  return st[PS_D] * a.lr * bc;
+}
+
+__global__ void prodigy_init_kernel(const float* __restrict__ p, float* __restrict__ p0, float* __restrict__ m,
+                                    float* __restrict__ v, float* __restrict__ s, int64_t n, double d0,
+                                    double* __restrict__ st) {
+  GSTRIDE(i, n) {
+    p0[i] = p[i];
+    m[i] = 0.f;
+    v[i] = 0.f;
+    s[i] = 0.f;
+  }
+  if (blockIdx.x == 0 && threadIdx.x < PS_COUNT)
+    st[threadIdx.x] = (threadIdx.x == PS_D || threadIdx.x == PS_DMAX || threadIdx.x == PS_DNEW) ? d0 : 0.0;
+}
+
+struct ProdigyCoef {  // the step's scalars, rounded to fp32 once (the reference package hands Python floats to fp32 tensor ops)
+  float coef, wd_l2, b1, b2, b3, cm, cv, cs;
+};
+__device__ __forceinline__ void prodigy_acc_elem(float p, float g, float p0, float& m, float& v, float& s,
+                                                 const ProdigyCoef& c, float& num, float& den) {
+#pragma clang fp contract(off)
+  const float gi = fmaf(c.wd_l2, p, g * c.coef);  // clip, then the coupled decay (0 when decoupled or none)
+  num += gi * (p0 - p);
+  m = fmaf(c.cm, gi, m * c.b1);
+  v = fmaf(c.cv * gi, gi, v * c.b2);
+  s = fmaf(c.cs, gi, s * c.b3);
+  den += fabsf(s);
+}
+// accumulate: the three state updates per element, one partial per workgroup of sum g (p0 - p) and of sum |s|
+template <bool VEC>
+__global__ __launch_bounds__(256) void prodigy_accum_kernel(const float* __restrict__ p, const float* __restrict__ g,
+                                                            const float* __restrict__ p0, float* __restrict__ m,
+                                                            float* __restrict__ v, float* __restrict__ s, int64_t n,
+                                                            ProdigyArgs a, const double* __restrict__ st,
+                                                            const float* __restrict__ norm_sq_dev,
+                                                            float* __restrict__ part_num, float* __restrict__ part_den) {
+  __shared__ float sh[8];
+  const double d = st[PS_D], dlr = prodigy_dlr(st, a);
+  ProdigyCoef c;
+  c.coef = clip_coef(a.max_norm, norm_sq_dev);
+  c.wd_l2 = (a.wd != 0.0 && !a.decouple) ? (float)a.wd : 0.f;
+  c.b1 = (float)a.b1, c.b2 = (float)a.b2, c.b3 = (float)a.b3;
+  c.cm = (float)(d * (1.0 - a.b1));
+  c.cv = (float)(d * d * (1.0 - a.b2));
+  c.cs = (float)((d / a.d0) * (a.safeguard ? d : dlr));
+  float num = 0.f, den = 0.f;
+  const int64_t n4 = VEC ? n / 4 : 0;
+  GSTRIDE(i, n4) {
+    const float4 pv = reinterpret_cast<const float4*>(p)[i], gv = reinterpret_cast<const float4*>(g)[i];
+    const float4 qv = reinterpret_cast<const float4*>(p0)[i];
+    float4 mv = reinterpret_cast<const float4*>(m)[i], vv = reinterpret_cast<const float4*>(v)[i];
+    float4 sv = reinterpret_cast<const float4*>(s)[i];
+    prodigy_acc_elem(pv.x, gv.x, qv.x, mv.x, vv.x, sv.x, c, num, den);
+    prodigy_acc_elem(pv.y, gv.y, qv.y, mv.y, vv.y, sv.y, c, num, den);
+    prodigy_acc_elem(pv.z, gv.z, qv.z, mv.z, vv.z, sv.z, c, num, den);
+    prodigy_acc_elem(pv.w, gv.w, qv.w, mv.w, vv.w, sv.w, c, num, den);
+    reinterpret_cast<float4*>(m)[i] = mv;
+    reinterpret_cast<float4*>(v)[i] = vv;
+    reinterpret_cast<float4*>(s)[i] = sv;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    float mi = m[i], vi = v[i], si = s[i];
+    prodigy_acc_elem(p[i], g[i], p0[i], mi, vi, si, c, num, den);
+    m[i] = mi;
+    v[i] = vi;
+    s[i] = si;
+  }
+  num = wave_sum(num);
+  den = wave_sum(den);
+  if ((threadIdx.x & 63) == 0) {
+    sh[threadIdx.x >> 6] = num;
+    sh[4 + (threadIdx.x >> 6)] = den;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    part_num[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    part_den[blockIdx.x] = (sh[4] + sh[5]) + (sh[6] + sh[7]);
+  }
+}
+// finalize: one wave adds the partials in double (ordered_sum_f64); lane 0 applies the rules for d_numerator, d, d_max, k
+__global__ __launch_bounds__(64) void prodigy_finalize_kernel(const float* __restrict__ part_num,
+                                                              const float* __restrict__ part_den, int np, ProdigyArgs a,
+                                                              double* __restrict__ st) {
+  __shared__ double sh[64];
+  const double sum_num = ordered_sum_f64(part_num, np, sh);
+  const double den = ordered_sum_f64(part_den, np, sh);
+  if (threadIdx.x != 0) return;
+  double d = st[PS_D], d_max = st[PS_DMAX];
+  const double dlr = prodigy_dlr(st, a);
+  double num = a.b3 * st[PS_NUM];
+  if (a.lr > 0.0) num += (d / a.d0) * dlr * sum_num;
+  st[PS_NUM] = num;
+  st[PS_DLR] = dlr;
+  if (den == 0.0) {  // no gradient has arrived yet: the moments above are updated, p, d and k are not
+    st[PS_DNEW] = d;
+    st[PS_SKIP] = 1.0;
+    return;
+  }
+  if (a.lr > 0.0) {
+    const double d_hat = a.d_coef * num / den;
+    if (d == a.d0) d = fmax(d, d_hat);
+    d_max = fmax(d_max, d_hat);
+    d = fmin(d_max, d * a.growth);
+  }
+  st[PS_D] = d;
+  st[PS_DMAX] = d_max;
+  st[PS_K] = st[PS_K] + 1.0;
+  st[PS_DNEW] = d;
+  st[PS_SKIP] = 0.0;
+}
+// apply: p -= wd dlr p (decoupled);  p -= dlr exp_avg / (sqrt(exp_avg_sq) + d eps) with the step's OLD dlr and NEW d
+template <bool VEC>
+__global__ __launch_bounds__(256) void prodigy_apply_kernel(float* __restrict__ p, const float* __restrict__ m,
+                                                            const float* __restrict__ v, int64_t n, ProdigyArgs a,
+                                                            const double* __restrict__ st) {
+#pragma clang fp contract(off)
+  if (st[PS_SKIP] != 0.0) return;
+  const float dlr = (float)st[PS_DLR], deps = (float)(st[PS_DNEW] * a.eps);
+  const float wdl = (a.wd != 0.0 && a.decouple) ? (float)(a.wd * st[PS_DLR]) : 0.f;
+  const int64_t n4 = VEC ? n / 4 : 0;
+  // p.add_(p, alpha=-wd dlr) is fma(-wdl, p, p); p.addcdiv_(m, denom, value=-dlr) is p + fl(fl(-dlr m) / denom)
+#define PRODIGY_APPLY(P_, M_, V_) (fmaf(-wdl, (P_), (P_)) + (-dlr * (M_)) / (sqrtf(V_) + deps))
+  GSTRIDE(i, n4) {
+    float4 pv = reinterpret_cast<const float4*>(p)[i];
+    const float4 mv = reinterpret_cast<const float4*>(m)[i], vv = reinterpret_cast<const float4*>(v)[i];
+    pv.x = PRODIGY_APPLY(pv.x, mv.x, vv.x);
+    pv.y = PRODIGY_APPLY(pv.y, mv.y, vv.y);
+    pv.z = PRODIGY_APPLY(pv.z, mv.z, vv.z);
+    pv.w = PRODIGY_APPLY(pv.w, mv.w, vv.w);
+    reinterpret_cast<float4*>(p)[i] = pv;
+  }
+  for (int64_t i = n4 * 4 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const float pi = p[i];
+    p[i] = PRODIGY_APPLY(pi, m[i], v[i]);
+  }
+#undef PRODIGY_APPLY
+}
+
 __global__ void sched_affine_kernel(float* __restrict__ x, const float* __restrict__ eps,
                                     const float* __restrict__ noise, float cx, float ce, float cn, int64_t n) {
   GSTRIDE(i, n) {
@@ -664,6 +888,74 @@ int launch_clip_adamw(float* p, const float* g, float* m, float* v, int64_t n, f
   const float bc2 = 1.f - powf(beta2, (float)step);
   hipLaunchKernelGGL(clip_adamw_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, g, m, v, n, lr, beta1, beta2, eps,
                      weight_decay, bc1, sqrtf(bc2), max_norm, scratch);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+namespace {
+// sum g^2 into scratch[0] through scratch[1 .. 1024]: the partials of launch_clip_adamw, the last stage in double
+void launch_grad_norm_sq(const float* g, int64_t n, float* scratch, hipStream_t stream) {
+  const int np = ew_grid(n) > 1024 ? 1024 : ew_grid(n);
+  hipLaunchKernelGGL(reduce_partial_kernel<1>, dim3(np), dim3(256), 0, stream, g, n, scratch + 1);
+  hipLaunchKernelGGL(sum_finalize_f64_kernel, dim3(1), dim3(64), 0, stream, scratch + 1, np, scratch);
+}
+inline bool aligned16(std::initializer_list<const void*> ptrs) {
+  uintptr_t bits = 0;
+  for (const void* q : ptrs) bits |= (uintptr_t)q;
+  return (bits & 15) == 0;
+}
+// workgroups of an optimiser kernel over n elements, 4 per thread where vectorised; the cap is also the partial count
+inline int optim_grid(int64_t n, bool vec) {
+  const int g = ew_grid(vec ? (n + 3) / 4 : n);
+  return g > 1024 ? 1024 : g;
+}
+}  // namespace
+
+// scratch: >= 1 + 1024 floats
+int launch_clip_lion(float* p, const float* g, float* m, int64_t n, double lr, double beta1, double beta2,
+                     double weight_decay, float max_norm, float* scratch, hipStream_t stream) {
+  SMI_CHECK(p && g && m && n > 0 && (max_norm <= 0.f || scratch), "lion: bad arguments");
+  if (max_norm > 0.f) launch_grad_norm_sq(g, n, scratch, stream);
+  const LionArgs a{(float)lr,           (float)beta1, (float)beta2, (float)(1.0 - beta1), (float)(1.0 - beta2),
+                   (float)(1.0 - lr * weight_decay), max_norm};
+  const bool vec = aligned16({p, g, m});
+  if (vec)
+    hipLaunchKernelGGL(clip_lion_kernel<true>, dim3(optim_grid(n, true)), dim3(256), 0, stream, p, g, m, n, a, scratch);
+  else
+    hipLaunchKernelGGL(clip_lion_kernel<false>, dim3(optim_grid(n, false)), dim3(256), 0, stream, p, g, m, n, a, scratch);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int launch_prodigy_init(const float* p, float* p0, float* m, float* v, float* s, int64_t n, double d0, double* state,
+                        hipStream_t stream) {
+  SMI_CHECK(p && p0 && m && v && s && state && n > 0 && d0 > 0.0, "prodigy_init: bad arguments");
+  hipLaunchKernelGGL(prodigy_init_kernel, dim3(ew_grid(n)), dim3(256), 0, stream, p, p0, m, v, s, n, d0, state);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+// scratch: >= 1 + 3 * 1024 floats ([0] = sum g^2, then 1024 partials each of sum g^2, sum g (p0 - p), sum |s|)
+int launch_clip_prodigy(float* p, const float* g, const float* p0, float* m, float* v, float* s, int64_t n,
+                        const ProdigyHyper* h, float max_norm, double* state, float* scratch, hipStream_t stream) {
+  SMI_CHECK(p && g && p0 && m && v && s && h && state && scratch && n > 0 && ((uintptr_t)state & 7) == 0, "prodigy: bad arguments");
+  SMI_CHECK(h->d0 > 0.0 && h->beta3 > 0.0, "prodigy: d0 and beta3 must be positive (beta3: pass sqrt(beta2) for the default)");
+  if (max_norm > 0.f) launch_grad_norm_sq(g, n, scratch, stream);
+  const ProdigyArgs a{h->lr,     h->beta1,       h->beta2,    h->beta3,          h->eps,
+                      h->weight_decay, h->d0,    h->d_coef,   h->growth_rate,    max_norm,
+                      h->decouple, h->use_bias_correction, h->safeguard_warmup};
+  float* part_num = scratch + 1 + 1024;
+  float* part_den = scratch + 1 + 2048;
+  const bool vec = aligned16({p, g, p0, m, v, s});
+  const int grid = optim_grid(n, vec);
+  if (vec) {
+    hipLaunchKernelGGL(prodigy_accum_kernel<true>, dim3(grid), dim3(256), 0, stream, p, g, p0, m, v, s, n, a, state, scratch,
+                       part_num, part_den);
+    hipLaunchKernelGGL(prodigy_finalize_kernel, dim3(1), dim3(64), 0, stream, part_num, part_den, grid, a, state);
+    hipLaunchKernelGGL(prodigy_apply_kernel<true>, dim3(grid), dim3(256), 0, stream, p, m, v, n, a, state);
+  } else {
+    hipLaunchKernelGGL(prodigy_accum_kernel<false>, dim3(grid), dim3(256), 0, stream, p, g, p0, m, v, s, n, a, state, scratch,
+                       part_num, part_den);
+    hipLaunchKernelGGL(prodigy_finalize_kernel, dim3(1), dim3(64), 0, stream, part_num, part_den, grid, a, state);
+    hipLaunchKernelGGL(prodigy_apply_kernel<false>, dim3(grid), dim3(256), 0, stream, p, m, v, n, a, state);
+  }
   SMI_HIP(hipGetLastError());
   return 0;
 }

@@ -498,6 +498,19 @@ int launch_axpby(float* y, const float* x, float a, float b, int64_t n, hipStrea
 int launch_clip_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                       float eps, float weight_decay, int step, float max_norm, float* scratch /*>= 1024+2 floats*/,
                       hipStream_t stream);
+// global-norm clip + Lion (include/smi.h smi_clip_lion); state m; scratch >= 1 + 1024 floats
+int launch_clip_lion(float* p, const float* g, float* m, int64_t n, double lr, double beta1, double beta2,
+                     double weight_decay, float max_norm, float* scratch, hipStream_t stream);
+// Prodigy (include/smi.h smi_prodigy_init / smi_clip_prodigy; the fields of smi_prodigy_hyper): state p0, m, v, s and
+// the 8-double device block; scratch >= 1 + 3 * 1024 floats
+struct ProdigyHyper {
+  double lr, beta1, beta2, beta3, eps, weight_decay, d0, d_coef, growth_rate;
+  int decouple, use_bias_correction, safeguard_warmup;
+};
+int launch_prodigy_init(const float* p, float* p0, float* m, float* v, float* s, int64_t n, double d0, double* state,
+                        hipStream_t stream);
+int launch_clip_prodigy(float* p, const float* g, const float* p0, float* m, float* v, float* s, int64_t n,
+                        const ProdigyHyper* h, float max_norm, double* state, float* scratch, hipStream_t stream);
 // DDIM (eta=0): x = c0*x + c1*eps ; Euler-a: x = x + eps*dt + noise*sigma_up
 int launch_sched_affine(float* x, const float* eps, const float* noise, float c_x, float c_eps, float c_noise,
                         int64_t n, hipStream_t stream);

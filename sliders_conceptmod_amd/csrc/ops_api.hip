@@ -45,6 +45,26 @@ int smi_clip_adamw(float* param, const float* grad, float* exp_avg, float* exp_a
   return launch_clip_adamw(param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step, max_norm,
                            scratch, (hipStream_t)stream);
 }
+int smi_clip_lion(float* param, const float* grad, float* exp_avg, int64_t n, double lr, double beta1, double beta2,
+                  double weight_decay, float max_norm, float* scratch, void* stream) {
+  return launch_clip_lion(param, grad, exp_avg, n, lr, beta1, beta2, weight_decay, max_norm, scratch, (hipStream_t)stream);
+}
+int smi_prodigy_init(const float* param, float* p0, float* exp_avg, float* exp_avg_sq, float* s, int64_t n, double d0,
+                     double* state, void* stream) {
+  return launch_prodigy_init(param, p0, exp_avg, exp_avg_sq, s, n, d0, state, (hipStream_t)stream);
+}
+int smi_clip_prodigy(float* param, const float* grad, const float* p0, float* exp_avg, float* exp_avg_sq, float* s,
+                     int64_t n, const smi_prodigy_hyper* hyper, float max_norm, double* state, float* scratch,
+                     void* stream) {
+  if (!hyper) {
+    set_error("smi_clip_prodigy: hyper is NULL");
+    return 1;
+  }
+  const ProdigyHyper h{hyper->lr,     hyper->beta1,  hyper->beta2,       hyper->beta3,    hyper->eps, hyper->weight_decay,
+                       hyper->d0,     hyper->d_coef, hyper->growth_rate, hyper->decouple, hyper->use_bias_correction,
+                       hyper->safeguard_warmup};
+  return launch_clip_prodigy(param, grad, p0, exp_avg, exp_avg_sq, s, n, &h, max_norm, state, scratch, (hipStream_t)stream);
+}
 int smi_sched_step(float* x, const float* eps, const float* noise, float c_x, float c_eps, float c_noise, int64_t n,
                    void* stream) {
   return launch_sched_affine(x, eps, noise, c_x, c_eps, c_noise, n, (hipStream_t)stream);

@@ -21,6 +21,7 @@ from typing import Dict, Optional
 import torch
 
 from . import _native, parallel
+from .optim import OptimSpec
 
 
 def tail_backward_ok(guidance_scale: float, allowed: bool = True) -> bool:
@@ -49,11 +50,13 @@ def _doubled_cond(unet, batch_size: int, first, second, first_pooled=None, poole
 
 class _FusedStep:
     """What the two steps share: the step's ONE message, [flat fp32 LoRA gradient | n_loss loss
-    scalars] -- the losses ride on the gradient's all-reduce -- the AdamW state, the adaptor snapshot, the backward
-    through the CFG mix and the all-reduce / clip / AdamW tail."""
+    scalars] -- the losses ride on the gradient's all-reduce -- the optimiser state, the adaptor snapshot, the backward
+    through the CFG mix and the all-reduce / clip / optimiser tail (AdamW, Lion or Prodigy: one native call each)."""
 
     def __init__(self, unet, network, scheduler, n_loss: int, lr, betas, eps, weight_decay, max_grad_norm,
-                 process_group):
+                 process_group, optimizer: Optional[OptimSpec] = None):
+        """`optimizer`: an optim.OptimSpec ("adamw", "lion" or "prodigy" with its hyper-parameters); None = AdamW with
+        `betas`, `eps` and `weight_decay`.  The step owns the state vectors of that optimiser only."""
         self.unet, self.network, self.scheduler = unet, network, scheduler
         self.lr, self.betas, self.eps, self.weight_decay = lr, betas, eps, weight_decay
         self.max_grad_norm = max_grad_norm
@@ -61,8 +64,16 @@ class _FusedStep:
         flat = network.flat
         self.msg = torch.zeros(flat.numel() + n_loss, dtype=flat.dtype, device=flat.device)
         self.grad = self.msg[:flat.numel()]
+        self.optimizer = OptimSpec.adamw(betas, eps, weight_decay) if optimizer is None else optimizer
+        if self.optimizer.name not in ("adamw", "lion", "prodigy"):
+            raise ValueError(f"the fused step has no native {self.optimizer.name} (adamw, lion, prodigy)")
         self.exp_avg = torch.zeros_like(flat)
-        self.exp_avg_sq = torch.zeros_like(flat)
+        if self.optimizer.name in ("adamw", "prodigy"):
+            self.exp_avg_sq = torch.zeros_like(flat)
+        if self.optimizer.name == "prodigy":
+            self.p0, self.s = torch.empty_like(flat), torch.empty_like(flat)
+            self.prodigy_state = torch.zeros(_native.PRODIGY_STATE_DOUBLES, dtype=torch.float64, device=flat.device)
+            self._prodigy_hyper = _native.prodigy_hyper(lr=lr, **self.optimizer.hyper)
         self.scratch = torch.empty(4096, dtype=torch.float32, device=flat.device)
         self.step_count = 0
 
@@ -86,16 +97,40 @@ class _FusedStep:
     def _optimizer_tail(self, lr: Optional[float]):
         parallel.allreduce_mean_(self.msg, self.pg)  # gradient + losses in one collective; no-op on a single rank
         self.step_count += 1
-        _native.clip_adamw(self.network.flat, self.grad, self.exp_avg, self.exp_avg_sq, self.lr if lr is None else lr,
-                           self.step_count, self.scratch, self.betas, self.eps, self.weight_decay, self.max_grad_norm)
+        lr = self.lr if lr is None else lr
+        flat, opt = self.network.flat, self.optimizer
+        if opt.name == "adamw":
+            _native.clip_adamw(flat, self.grad, self.exp_avg, self.exp_avg_sq, lr, self.step_count, self.scratch,
+                               opt.hyper["betas"], opt.hyper["eps"], opt.hyper["weight_decay"], self.max_grad_norm)
+        elif opt.name == "lion":
+            _native.clip_lion(flat, self.grad, self.exp_avg, lr, self.scratch, opt.hyper["betas"],
+                              opt.hyper["weight_decay"], self.max_grad_norm)
+        else:  # prodigy: p0 is the parameter vector as the first step finds it; d and k live on the device
+            if self.step_count == 1:
+                _native.prodigy_init(flat, self.p0, self.exp_avg, self.exp_avg_sq, self.s, self.prodigy_state,
+                                     opt.hyper["d0"])
+            self._prodigy_hyper.lr = float(lr)
+            _native.clip_prodigy(flat, self.grad, self.p0, self.exp_avg, self.exp_avg_sq, self.s, self.prodigy_state,
+                                 self.scratch, self._prodigy_hyper, self.max_grad_norm)
+
+    def prodigy_d(self) -> float:
+        """Prodigy's current step-size estimate d, for logging: ONE device read (a synchronisation) -- call it where the
+        trainer already waits for the loss."""
+        if self.optimizer.name != "prodigy":
+            raise ValueError(f"prodigy_d(): the step's optimiser is {self.optimizer.name}")
+        if self.step_count == 0:
+            return float(self.optimizer.hyper["d0"])
+        return float(self.prodigy_state[0].item())
 
 
 class SliderStep(_FusedStep):
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, cfg_scale: float = 1.0,
                  skip_dead_cfg_half: bool = False, process_group=None, batch_passes: bool = True,
-                 dedup_uncond: bool = False, preroll_skip_dead_half: bool = True, tail_backward: bool = True):
-        super().__init__(unet, network, scheduler, 1, lr, betas, eps, weight_decay, max_grad_norm, process_group)
+                 dedup_uncond: bool = False, preroll_skip_dead_half: bool = True, tail_backward: bool = True,
+                 optimizer: Optional[OptimSpec] = None):
+        super().__init__(unet, network, scheduler, 1, lr, betas, eps, weight_decay, max_grad_norm, process_group,
+                         optimizer)
         self.loss = self.msg[self.grad.numel():]
         self.cfg_scale = cfg_scale
         # With CFG scale 1 the unconditional half of the doubled batch is algebraically dead (u + 1*(t-u) == t).
@@ -281,8 +316,9 @@ class ImageSliderStep(_FusedStep):
 
     def __init__(self, unet, network, scheduler, *, lr: float = 1e-4, betas=(0.9, 0.999), eps: float = 1e-8,
                  weight_decay: float = 1e-2, max_grad_norm: float = 0.0, process_group=None, one_pass: bool = True,
-                 tail_backward: bool = True):
-        super().__init__(unet, network, scheduler, 2, lr, betas, eps, weight_decay, max_grad_norm, process_group)
+                 tail_backward: bool = True, optimizer: Optional[OptimSpec] = None):
+        super().__init__(unet, network, scheduler, 2, lr, betas, eps, weight_decay, max_grad_norm, process_group,
+                         optimizer)
         self.losses = self.msg[self.grad.numel():]  # (high side, low side); mean over ranks after the step's all-reduce
         self.one_pass = one_pass  # both sides in one UNet pass where the adaptor set allows it (see _one_pass_ok)
         self._one_pass_cached = None

@@ -8,6 +8,7 @@ from pathlib import Path
 import torch
 
 from . import parallel, train_util
+from .optim import LION_DEFAULTS, PRODIGY_DEFAULTS, OptimSpec
 
 
 def apply_cli_overrides(config, args) -> list:
@@ -70,13 +71,46 @@ def fused_step_choice(fused_step, optimizer_name: str, kwargs: dict):
     return fusable and fused_step is not False, wd
 
 
+def native_optimizer(optimizer_name: str, kwargs: dict):
+    """The optim.OptimSpec of the fused step's native kernel for this optimiser, or None where it has none.  Adam / AdamW:
+    the rule of adam_fusable.  Lion / Prodigy: whenever `kwargs` holds only the algorithm's own hyper-parameters
+    (optim.LION_DEFAULTS / PRODIGY_DEFAULTS); `fsdp_in_use`, `slice_p` or anything unknown leaves it to the torch class."""
+    name = optimizer_name.lower()
+    if name in ("lion", "prodigy"):
+        return None if _refused_arguments(name, kwargs) else OptimSpec.of(name, kwargs)
+    fusable, wd = adam_fusable(optimizer_name, kwargs)
+    if not fusable:
+        return None
+    return OptimSpec.adamw(kwargs.get("betas", (0.9, 0.999)), kwargs.get("eps", 1e-8), wd)
+
+
+def _refused_arguments(name: str, kwargs: dict) -> list:
+    return sorted(set(kwargs) - set(LION_DEFAULTS if name == "lion" else PRODIGY_DEFAULTS))
+
+
+def step_choice(fused_step, optimizer_name: str, kwargs: dict):
+    """The trainers' `fused_step` argument -> (run the fused step?, its optim.OptimSpec or None): None = whenever the
+    optimiser has a native kernel (native_optimizer), True = fused or ValueError naming what stands in the way, False = the
+    reference-style autograd loop.  Adam / AdamW and every unknown name go through fused_step_choice."""
+    name = optimizer_name.lower()
+    if name not in ("lion", "prodigy"):
+        fused, _ = fused_step_choice(fused_step, optimizer_name, kwargs)
+        return fused, (native_optimizer(optimizer_name, kwargs) if fused else None)
+    refused = _refused_arguments(name, kwargs)
+    if fused_step and refused:
+        raise ValueError(f"--fused_step: the native {name} step does not take {', '.join(refused)} "
+                         f"(it takes {', '.join(sorted(LION_DEFAULTS if name == 'lion' else PRODIGY_DEFAULTS))})")
+    fused = not refused and fused_step is not False
+    return fused, (OptimSpec.of(name, kwargs) if fused else None)
+
+
 def add_fused_step_flags(parser):
     """Shared by the four trainers: the fused step is the default, `--no_fused_step` keeps the reference-style loop."""
     g = parser.add_mutually_exclusive_group()
     g.add_argument("--fused_step", dest="fused_step", action="store_true", default=None,
                    help="insist on the fused step (pre-roll + 4-pass step through step.SliderStep / ImageSliderStep: one "
-                        "batched UNet pass, native loss / clip / AdamW, no autograd graph -- the path bench.py measures); "
-                        "it is the default whenever the optimiser is Adam / AdamW")
+                        "batched UNet pass, native loss / clip / optimiser, no autograd graph -- the path bench.py "
+                        "measures); it is the default whenever the optimiser is Adam / AdamW, Lion or Prodigy")
     g.add_argument("--no_fused_step", dest="fused_step", action="store_false",
                    help="the reference-style loop: one UNet call per guidance pass, torch autograd and optimiser")
     parser.add_argument("--no_dedup_uncond", action="store_true",

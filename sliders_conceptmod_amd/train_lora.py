@@ -30,7 +30,8 @@ def encode(text_encoder, tokenizer, prompt, device, dtype):
 def train(config: RootConfig, prompts: list, device, models=None, on_step_complete=None, save_file=True,
           fused_step=None, dedup_uncond: bool = True):
     """`fused_step` (not in the reference signature): None (default) = the fused path whenever the configured optimiser is
-    Adam / AdamW, else the reference-style autograd loop; True = fused or ValueError; False = the reference-style loop.
+    Adam / AdamW, Lion or Prodigy with arguments the native step takes (train_common.step_choice), else the reference-style
+    autograd loop; True = fused or ValueError; False = the reference-style loop.
     `dedup_uncond`: inside the fused step, run each distinct frozen sample once (bit-identical results, step.py)."""
     metadata = {"prompts": ",".join([p.model_dump_json() for p in prompts]), "config": config.model_dump_json()}
     # train_lora.py:44-46: `modules = DEFAULT_TARGET_REPLACE; modules += UNET_TARGET_REPLACE_MODULE_CONV` mutates the list
@@ -57,7 +58,8 @@ def train(config: RootConfig, prompts: list, device, models=None, on_step_comple
     parallel.broadcast_(network.flat.data)
     optimizer_module = train_util.get_optimizer(config.train.optimizer)
     optimizer_kwargs = train_common.parse_optimizer_args(config.train.optimizer_args)  # train_lora.py:82-87
-    optimizer = optimizer_module(network.prepare_optimizer_params(), lr=config.train.lr, **optimizer_kwargs)
+    fused, spec = train_common.step_choice(fused_step, config.train.optimizer, optimizer_kwargs)  # may refuse: before any work
+    optimizer =optimizer_module(network.prepare_optimizer_params(), lr=config.train.lr, **optimizer_kwargs)
     lr_scheduler = train_util.get_lr_scheduler(config.train.lr_scheduler, optimizer,
                                                max_iterations=config.train.iterations, lr_min=config.train.lr / 100)
     criteria = torch.nn.MSELoss()
@@ -75,15 +77,14 @@ def train(config: RootConfig, prompts: list, device, models=None, on_step_comple
     del tokenizer, text_encoder
 
     # The fused step (default): the pre-roll and the 4-pass step run through SliderStep (one batched UNet pass, native loss /
-    # AdamW, no autograd graph) -- the path bench.py measures.  Same arithmetic and RNG draw order as the reference-style
-    # arms below (tested); `--no_fused_step` keeps those.
+    # AdamW, Lion or Prodigy, no autograd graph) -- the path bench.py measures.  Same arithmetic and RNG draw order as the
+    # reference-style arms below (tested); `--no_fused_step` keeps those.
     stepper = None
-    fused, wd = train_common.fused_step_choice(fused_step, config.train.optimizer, optimizer_kwargs)
     if fused:
         from .step import SliderStep
-        stepper = SliderStep(unet, network, noise_scheduler, lr=config.train.lr, weight_decay=wd,
-                             eps=optimizer_kwargs.get("eps", 1e-8), betas=optimizer_kwargs.get("betas", (0.9, 0.999)),
-                             max_grad_norm=0.0, cfg_scale=1.0, dedup_uncond=dedup_uncond)
+        stepper = SliderStep(unet, network, noise_scheduler, lr=config.train.lr, optimizer=spec, max_grad_norm=0.0,
+                             cfg_scale=1.0, dedup_uncond=dedup_uncond)
+    prodigy = config.train.optimizer.lower() == "prodigy"
     cond_cache = {}  # fused path: conditioning tensors per (prompt pair, batch)
 
     pbar = tqdm(range(config.train.iterations), disable=rank != 0)
@@ -136,13 +137,17 @@ def train(config: RootConfig, prompts: list, device, models=None, on_step_comple
             optimizer.step()
         lr_scheduler.step()
         lv = float(loss.item())  # the one host sync per step, as the reference's loss.item() (train_lora.py:292)
-        pbar.set_description(f"Loss*1k: {lv * 1000:.4f}")
+        desc = f"Loss*1k: {lv * 1000:.4f}"
+        if prodigy:  # the step-size estimate; fused: one more device read, right after loss.item() has synchronised
+            desc += f" d: {stepper.prodigy_d() if stepper is not None else optimizer.d:.3e}"
+        pbar.set_description(desc)
         if on_step_complete is not None:
             on_step_complete(i, lv)
         if save_file and rank == 0 and train_common.checkpoint_due(i, config):
             train_common.save_checkpoint(network, config, f"{i}steps", ".pt", save_weight_dtype)
     if save_file and rank == 0:
         train_common.save_checkpoint(network, config, "last", ".pt", save_weight_dtype)
+    network.fused_stepper = stepper  # the run's SliderStep (None: autograd loop), e.g. for prodigy_d()
     return network
 
 

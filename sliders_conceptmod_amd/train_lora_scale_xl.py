@@ -75,8 +75,9 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
     `image_size` is what the pairs are resized to (the reference hard-codes (512, 512) for SD-XL,
     I/train_lora-scale-xl.py:220, and (256, 256) for SD-1.x, I/train_lora-scale.py:219).  `xl=False` is the SD-1.x twin
     (train_lora_scale.py).  `fused_step` runs the two-sided step through step.ImageSliderStep (no autograd graph, native
-    AdamW) -- same arithmetic, tested against the autograd loop: None (default) = whenever the configured optimiser is
-    Adam / AdamW without amsgrad, True = fused or ValueError, False = the reference-style autograd loop."""
+    AdamW, Lion or Prodigy) -- same arithmetic, tested against the autograd loop: None (default) = whenever the configured
+    optimiser is Adam / AdamW without amsgrad, Lion or Prodigy (train_common.step_choice), True = fused or ValueError,
+    False = the reference-style autograd loop."""
     weight_dtype = config_util.parse_precision(config.train.precision)
     tokenizers, text_encoders, unet, noise_scheduler = models or model_util.load_models(
         config.pretrained_model.name_or_path, scheduler_name=config.train.noise_scheduler, xl=xl)
@@ -91,6 +92,7 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
                                                                                                    dtype=weight_dtype)
     parallel.broadcast_(network.flat.data)
     optimizer_kwargs = train_common.parse_optimizer_args(config.train.optimizer_args)  # I/train_lora-scale-xl.py:110-117
+    fused, spec = train_common.step_choice(fused_step, config.train.optimizer, optimizer_kwargs)  # may refuse: before any work
     optimizer = train_util.get_optimizer(config.train.optimizer)(network.prepare_optimizer_params(),
                                                                  lr=config.train.lr, **optimizer_kwargs)
     lr_scheduler = train_util.get_lr_scheduler(config.train.lr_scheduler, optimizer,
@@ -133,14 +135,14 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
     size = image_size or ((512, 512) if xl else (256, 256))
     save_dtype = config_util.parse_precision(config.train.precision)
     stepper = None
-    fused, wd = train_common.fused_step_choice(fused_step, config.train.optimizer, optimizer_kwargs)
     if fused:
         from .step import ImageSliderStep
-        stepper = ImageSliderStep(unet, network, noise_scheduler, lr=config.train.lr, weight_decay=wd,
-                                  eps=optimizer_kwargs.get("eps", 1e-8), betas=optimizer_kwargs.get("betas", (0.9, 0.999)))
+        stepper = ImageSliderStep(unet, network, noise_scheduler, lr=config.train.lr, optimizer=spec)
+    prodigy = config.train.optimizer.lower() == "prodigy"
     cond_cache = {}
     network.training_losses = []
-    for i in tqdm(range(config.train.iterations), disable=rank_ != 0):
+    pbar = tqdm(range(config.train.iterations), disable=rank_ != 0)
+    for i in pbar:
         noise_scheduler.set_timesteps(config.train.max_denoising_steps, device=device)
         optimizer.zero_grad()
         settings, pos, neu, unc = pairs[torch.randint(0, len(pairs), (1,)).item()]
@@ -199,12 +201,15 @@ def train(config, prompts, device, folder_main, folders, scales, models=None, ra
         optimizer.step()  # fused: no gradients, a no-op that keeps torch's "optimizer before scheduler" order
         lr_scheduler.step()
         network.training_losses.append((lh, ll))
+        if prodigy:  # the step-size estimate; fused: one more device read, right after the losses' read has synchronised
+            pbar.set_description(f"d: {stepper.prodigy_d() if stepper is not None else optimizer.d:.3e}")
         if on_step_complete is not None:
             on_step_complete(i, lh, ll)
         if rank_ == 0 and train_common.checkpoint_due(i, config):  # I/train_lora-scale-xl.py:402-412
             train_common.save_checkpoint(network, config, f"{i}steps", ".pt", save_dtype)
     if rank_ == 0:
         train_common.save_checkpoint(network, config, "last", ".pt", save_dtype)
+    network.fused_stepper = stepper  # the run's ImageSliderStep (None: autograd loop), e.g. for prodigy_d()
     return network
 
 

@@ -33,8 +33,10 @@ def encode_xl(text_encoder, tokenizer, prompt, device, dtype) -> PromptEmbedsXL:
 
 
 def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft_type="lora", rank=4, save_file=True,
-          models=None, fused_step=None, optimizer_kwargs=None, dedup_uncond=True):
-    """`fused_step` (not in the reference signature): None / True = the fused path (the script's optimiser is a hard-coded
+          models=None, fused_step=None, optimizer_kwargs=None, dedup_uncond=True, optimizer=None):
+    """`optimizer` (not in the reference signature; `--optimizer`): None = the script's hard-coded AdamW(lr 1e-4, wd 1e-6),
+    else a train_util.get_optimizer name (adam, adamw, lion, prodigy) built from `optimizer_kwargs` alone; Lion and Prodigy
+    run fused like AdamW (train_common.step_choice).  `fused_step` (not in the reference signature): None / True = the fused path (the script's optimiser is a hard-coded
     AdamW, train_lora_xl.py:104; with `optimizer_kwargs` the native AdamW cannot express, train_common.adam_fusable, None
     takes the autograd loop and True raises), False = the reference-style autograd loop; `dedup_uncond`: inside the fused step, each
     distinct frozen sample runs once (bit-identical results, step.py).  `optimizer_kwargs` (not in the reference signature) overrides keyword arguments of the hard-coded AdamW
@@ -60,9 +62,17 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
                          prefix="lora_unet", train_method=config.network.training_method).to(device,
                                                                                              dtype=weight_dtype)
     parallel.broadcast_(network.flat.data)
-    okw = dict(lr=1e-4, weight_decay=1e-6)
-    okw.update(optimizer_kwargs or {})
-    optimizer = torch.optim.AdamW(network.parameters(), **okw)
+    if optimizer is None:
+        optimizer_name = "adamw"
+        okw = dict(lr=1e-4, weight_decay=1e-6)
+        okw.update(optimizer_kwargs or {})
+        optimizer = torch.optim.AdamW(network.parameters(), **okw)
+    else:  # `--optimizer`: the named class at ITS default learning rate unless optimizer_kwargs sets one
+        optimizer_name = optimizer
+        okw = dict(optimizer_kwargs or {})
+        optimizer = train_util.get_optimizer(optimizer_name)(network.parameters(), **okw)
+        okw.setdefault("lr", optimizer.defaults["lr"])
+    fused, spec = train_common.step_choice(fused_step, optimizer_name, okw)
     lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=50, eta_min=1e-6)
     criteria = torch.nn.MSELoss()
 
@@ -81,11 +91,11 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
     del tokenizers, text_encoders
 
     stepper = None
-    if train_common.fused_step_choice(fused_step, "adamw", okw)[0]:
+    if fused:
         from .step import SliderStep
-        stepper = SliderStep(unet, network, noise_scheduler, lr=okw["lr"], weight_decay=okw["weight_decay"],
-                             eps=okw.get("eps", 1e-8), betas=okw.get("betas", (0.9, 0.999)), max_grad_norm=0.2,
+        stepper = SliderStep(unet, network, noise_scheduler, lr=okw["lr"], optimizer=spec, max_grad_norm=0.2,
                              cfg_scale=guidance_scale, dedup_uncond=dedup_uncond)
+    prodigy = optimizer_name.lower() == "prodigy"
     cond_cache = {}  # fused path: conditioning tensors per (prompt pair, batch, size); rebuilt only with dynamic crops
     network.training_losses = []
     pbar = tqdm(range(config.train.iterations), disable=rank_ != 0)
@@ -155,11 +165,15 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
         lr_scheduler.step()
         lv = float(loss.item())  # the one host sync per step, as the reference's loss.item() (train_lora_xl.py:346)
         network.training_losses.append(lv)
-        pbar.set_description(f"Loss*1k: {lv * 1000:.4f}")
+        desc = f"Loss*1k: {lv * 1000:.4f}"
+        if prodigy:  # the step-size estimate; fused: one more device read, right after loss.item() has synchronised
+            desc += f" d: {stepper.prodigy_d() if stepper is not None else optimizer.d:.3e}"
+        pbar.set_description(desc)
         if save_file and rank_ == 0 and train_common.checkpoint_due(i, config):
             train_common.save_checkpoint(network, config, f"{i}steps", ".safetensors", save_weight_dtype)
         if on_step_complete is not None:
             on_step_complete(i)
+    network.fused_stepper = stepper  # the run's SliderStep (None: autograd loop), e.g. for prodigy_d()
     if save_file:
         if rank_ == 0:
             train_common.save_checkpoint(network, config, "last", ".safetensors", save_weight_dtype)
@@ -189,7 +203,7 @@ def main(args):
     prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
     device = train_common.launch_device(args)
     train(config, prompts, device, None, args.peft_type, args.rank, True, None, args.fused_step,
-          dedup_uncond=not args.no_dedup_uncond)
+          dedup_uncond=not args.no_dedup_uncond, optimizer=getattr(args, "optimizer", None))
 
 
 def build_parser():
@@ -201,6 +215,9 @@ def build_parser():
     parser.add_argument("--name", type=str, required=False, default=None, help="Name of the slider.")
     parser.add_argument("--attributes", type=str, required=False, default=None)
     parser.add_argument("--peft_type", type=str, required=False, default="lora")
+    parser.add_argument("--optimizer", type=str, required=False, default=None,
+                        help="adam, adamw, lion or prodigy at the class's own defaults instead of the script's hard-coded "
+                             "AdamW(lr 1e-4, weight_decay 1e-6)")
     train_common.add_fused_step_flags(parser)
     return parser
 

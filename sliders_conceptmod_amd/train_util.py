@@ -268,8 +268,14 @@ def get_optimizer(name: str):
         return torch.optim.Adam
     if name == "adamw":
         return torch.optim.AdamW
-    if name.startswith("dadapt") or name.endswith("8bit") or name in ("lion", "prodigy"):
-        # the reference imports dadaptation / bitsandbytes / lion_pytorch / prodigyopt here; none is in this image
+    if name == "lion":  # the reference imports lion_pytorch / prodigyopt here; optim.py holds classes of our own
+        from .optim import Lion
+        return Lion
+    if name == "prodigy":
+        from .optim import Prodigy
+        return Prodigy
+    if name.startswith("dadapt") or name.endswith("8bit"):
+        # the reference imports dadaptation / bitsandbytes here; neither is in this image
         raise ValueError(f"optimizer '{name}' needs a package that is not installed; use adam or adamw")
     raise ValueError("Optimizer must be adam, adamw, lion or Prodigy")
 
