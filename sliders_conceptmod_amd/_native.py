@@ -446,19 +446,25 @@ class Engine(_EngineBase):
         self._ctx_buf, self._ctx_on = None, False  # smi_replan detaches the context-gradient buffer
         self._pool_buf, self._pool_on = None, False  # ... and the pooled-gradient buffer
 
+    def _attach_grad_buffer(self, what: str) -> torch.Tensor:
+        """Sizes (smi_unet_{what}_grad_bytes), allocates and attaches (smi_unet_{what}_grad_attach) the gradient buffer
+        `what` ("ctx" / "pooled") of the current shape; the caller keeps the tensor it returns alive."""
+        size_fn, attach_fn = f"smi_unet_{what}_grad_bytes", f"smi_unet_{what}_grad_attach"
+        sarr, _keep = make_sites(self.sites)
+        out = C.c_size_t(0)
+        check(getattr(lib(), size_fn)(C.byref(self.cfg_c), sarr, len(self.sites), self.batch, self.batch_adapted, self.h,
+                                      self.w, self.ctx_len, C.byref(out)), size_fn)
+        buf = torch.empty(out.value, dtype=torch.uint8, device=self.workspace.device)
+        with torch.cuda.device(self.workspace.device):
+            check(getattr(lib(), attach_fn)(self.handle, ptr(buf), out.value), attach_fn)
+        return buf
+
     def set_ctx_grad(self, on: bool):
         """Saving forwards from here on also differentiate the context of their adapted samples (smi_unet_ctx_grad); the
         extra buffer (transposed k|v weights + a larger saved-pass arena) is attached on first use for the current shape."""
         on = bool(on)
         if on and self._ctx_buf is None:
-            sarr, _keep = make_sites(self.sites)
-            out = C.c_size_t(0)
-            check(lib().smi_unet_ctx_grad_bytes(C.byref(self.cfg_c), sarr, len(self.sites), self.batch, self.batch_adapted,
-                                                self.h, self.w, self.ctx_len, C.byref(out)), "smi_unet_ctx_grad_bytes")
-            buf = torch.empty(out.value, dtype=torch.uint8, device=self.workspace.device)
-            with torch.cuda.device(self.workspace.device):
-                check(lib().smi_unet_ctx_grad_attach(self.handle, ptr(buf), out.value), "smi_unet_ctx_grad_attach")
-            self._ctx_buf = buf
+            self._ctx_buf = self._attach_grad_buffer("ctx")
         if on != self._ctx_on:
             check(lib().smi_unet_ctx_grad(self.handle, int(on)), "smi_unet_ctx_grad")
             self._ctx_on = on
@@ -474,15 +480,7 @@ class Engine(_EngineBase):
             if self._ctx_buf is None:
                 raise SmiError("set_pooled_grad(True) needs set_ctx_grad(True) first: the pooled-embedding gradient rides "
                                "on the context gradient's pass")
-            sarr, _keep = make_sites(self.sites)
-            out = C.c_size_t(0)
-            check(lib().smi_unet_pooled_grad_bytes(C.byref(self.cfg_c), sarr, len(self.sites), self.batch,
-                                                   self.batch_adapted, self.h, self.w, self.ctx_len, C.byref(out)),
-                  "smi_unet_pooled_grad_bytes")
-            buf = torch.empty(out.value, dtype=torch.uint8, device=self.workspace.device)
-            with torch.cuda.device(self.workspace.device):
-                check(lib().smi_unet_pooled_grad_attach(self.handle, ptr(buf), out.value), "smi_unet_pooled_grad_attach")
-            self._pool_buf = buf
+            self._pool_buf = self._attach_grad_buffer("pooled")
         if on != self._pool_on:
             check(lib().smi_unet_pooled_grad(self.handle, int(on)), "smi_unet_pooled_grad")
             self._pool_on = on

@@ -798,6 +798,76 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   return e.err ? -1 : 0;
 }
 
+// the refusal of the UNet-only entry points that take any engine; `why` completes the sentence
+int refuse_other_kind(const smi_engine* e, const char* why) {
+  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder%s", why);
+  return 0;
+}
+
+// smi_unet_ctx_grad_bytes / smi_unet_pooled_grad_bytes (pooled): the transposed weights of that gradient + the saved-pass
+// arena of a forward + backward with it on
+int grad_buffer_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int batch_adapted, int h,
+                      int w, int ctx_len, size_t* bytes, bool pooled) {
+  if (check_cfg(cfg)) return -1;
+  SMI_CHECK(bytes && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
+            "bad arguments");
+  size_t r[5], x = 0, t = 0;
+  if (plan(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, r, &x, pooled ? &t : nullptr)) return -1;
+  *bytes = (pooled ? t : x) + r[2] + 2 * 4096;
+  return 0;
+}
+
+// smi_unet_ctx_grad_attach / smi_unet_pooled_grad_attach (pooled) after their own refusals: the buffer becomes
+// [pack arena of the transposed weights (xpack / tpack), built here | arena 1, sized for that gradient's saved pass]
+int attach_grad_buffer(smi_engine* e, void* buffer, size_t buffer_bytes, bool pooled) {
+  UNet* u = unet(e);
+  const char* name = pooled ? "smi_unet_pooled_grad_attach" : "smi_unet_ctx_grad_attach";
+  size_t r[5], x = 0, t = 0;
+  if (plan(&u->cfg, e->sites.data(), (int)e->sites.size(), e->max_n, u->max_n_ad, u->lat_h, u->lat_w, u->ctx_len, r, &x,
+           pooled ? &t : nullptr))
+    return -1;
+  const size_t pack_bytes = pooled ? t : x;
+  Arena& pack = pooled ? u->tpack : u->xpack;
+  char* base = (char*)align_up((size_t)buffer, 4096);
+  const size_t have = (size_t)((char*)buffer + buffer_bytes - base);
+  SMI_CHECK((char*)buffer + buffer_bytes >= base && pack_bytes + r[2] <= have, "%s: buffer too small: need %zu bytes, got %zu",
+            name, pack_bytes + r[2] + 2 * 4096, buffer_bytes);
+  e->err = false;
+  pack = Arena();
+  pack.base = base;
+  pack.cap = pack_bytes;
+  if (!pooled) u->build_ctx_grad(*e);
+  else if (u->build_pooled_grad(*e)) return -1;
+  SMI_HIP(hipGetLastError());
+  SMI_CHECK(!e->err && !pack.overflow, "%s: packing the transposed %s weights failed", name, pooled ? "time_emb_proj" : "k|v");
+  e->arena[1] = Arena();  // the saved pass of a forward + backward with this gradient on is larger than the plain one
+  e->arena[1].base = base + pack_bytes;
+  e->arena[1].cap = r[2];
+  u->forget_saved_pass(*e);  // the saved activations lived in the old arena
+  return 0;
+}
+
+// Every backward entry point begins here, after its NULL check: another kind of engine is refused, and so is, under
+// `name`, an engine without a saved pass (name NULL: smi_unet_backward, which leaves that to UNet::backward's own refusal)
+int backward_begin(const smi_engine* e, const char* name) {
+  if (refuse_other_kind(e, ": it has no backward")) return -1;
+  SMI_CHECK(!name || unet(e)->tape_valid, "%s: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)", name);
+  return 0;
+}
+
+// ... and, after the refusals of its own, ends here.  d_ctx / d_pooled: smi_unet_backward_ctx / _cond, which take the
+// adaptor's gradient buffers only when the saved pass ran with the adaptor on
+int backward_launch(smi_engine* e, const char* name, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
+                    int n_live, float* d_ctx = nullptr, float* d_pooled = nullptr) {
+  UNet* u = unet(e);
+  const bool adapted = e->bw_down && e->bw_up && e->bw_mult != 0.f && !e->sites.empty();
+  SMI_CHECK(!adapted || (d_lora_down_flat && d_lora_up_flat),
+            "%s: the saved pass ran with the adaptor on: its gradient buffers are required", name);
+  e->err = false;
+  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
+  return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, n_live, d_ctx, d_pooled);
+}
+
 }  // namespace
 
 extern "C" {
@@ -904,9 +974,7 @@ int smi_unet_forward_batched(smi_engine* e, int n, int n_adapted, const float* s
                              const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                              const float* lora_up_flat, float multiplier, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && sample && ctx && eps_out, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET,
-            "this engine is a VAE encoder / decoder or a CLIP text / vision encoder (use smi_vae_encode / smi_vae_decode / "
-            "smi_clip_encode / smi_clip_vision_encode)");
+  if (refuse_other_kind(e, " (use smi_vae_encode / smi_vae_decode / smi_clip_encode / smi_clip_vision_encode)")) return -1;
   UNet* u = unet(e);
   SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
   SMI_CHECK(n_adapted >= 0 && n_adapted <= n && n_adapted <= u->max_n_ad,
@@ -929,7 +997,7 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
                            const void* text_embeds, const float* time_ids, const float* lora_down_flat,
                            const float* lora_up_flat, const float* multipliers, int save_for_backward, float* eps_out) {
   SMI_CHECK(e && multipliers, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: no UNet forward");
+  if (refuse_other_kind(e, ": no UNet forward")) return -1;
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "per-sample multipliers: 1..%d adapted samples", smi_engine::MAXS);
   float mref = 0.f;
   bool same = true;
@@ -965,7 +1033,7 @@ int smi_unet_forward_compose(smi_engine* e, int n, int n_adapted, const float* s
                              const float* lora_up_flat, int n_sliders, const int* ranks, const float* multipliers,
                              float* eps_out) {
   SMI_CHECK(e && ranks && multipliers && lora_down_flat && lora_up_flat, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: no UNet forward");
+  if (refuse_other_kind(e, ": no UNet forward")) return -1;
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "slider composition: 1..%d adapted samples, got %d",
             smi_engine::MAXS, n_adapted);
   SMI_CHECK(n_sliders >= 1 && n_sliders <= smi_engine::MAX_SLIDERS, "slider composition: 1..%d sliders, got %d",
@@ -1021,46 +1089,20 @@ int smi_unet_forward(smi_engine* e, int n, const float* sample, float timestep, 
 
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
-  UNet* u = unet(e);
-  e->err = false;
-  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
-  return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad);
+  if (backward_begin(e, nullptr)) return -1;
+  return backward_launch(e, "smi_unet_backward", d_eps, d_lora_down_flat, d_lora_up_flat, unet(e)->bw_n_ad);
 }
 
 int smi_unet_ctx_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
                             int batch_adapted, int h, int w, int ctx_len, size_t* bytes) {
-  if (check_cfg(cfg)) return -1;
-  SMI_CHECK(bytes && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
-            "bad arguments");
-  size_t r[5], x = 0;
-  if (plan(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, r, &x)) return -1;
-  *bytes = x + r[2] + 2 * 4096;
-  return 0;
+  return grad_buffer_bytes(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, bytes, false);
 }
 
 int smi_unet_ctx_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes) {
   SMI_CHECK(e && buffer, "NULL argument");
   SMI_CHECK(e->kind == smi_engine::UNET, "smi_unet_ctx_grad_attach: only UNet engines differentiate a context");
   UNet* u = unet(e);
-  size_t r[5], x = 0;
-  if (plan(&u->cfg, e->sites.data(), (int)e->sites.size(), e->max_n, u->max_n_ad, u->lat_h, u->lat_w, u->ctx_len, r, &x))
-    return -1;
-  char* base = (char*)align_up((size_t)buffer, 4096);
-  const size_t have = (size_t)((char*)buffer + buffer_bytes - base);
-  SMI_CHECK((char*)buffer + buffer_bytes >= base && x + r[2] <= have,
-            "smi_unet_ctx_grad_attach: buffer too small: need %zu bytes, got %zu", x + r[2] + 2 * 4096, buffer_bytes);
-  e->err = false;
-  u->xpack = Arena();
-  u->xpack.base = base;
-  u->xpack.cap = x;
-  u->build_ctx_grad(*e);
-  SMI_HIP(hipGetLastError());
-  SMI_CHECK(!e->err && !u->xpack.overflow, "smi_unet_ctx_grad_attach: packing the transposed k|v weights failed");
-  e->arena[1] = Arena();
-  e->arena[1].base = base + x;
-  e->arena[1].cap = r[2];
-  u->forget_saved_pass(*e);  // the saved activations lived in the old arena
+  if (const int rc = attach_grad_buffer(e, buffer, buffer_bytes, false)) return rc;
   u->ctx_cap = true;
   u->pool_cap = u->pool_want = false;  // a pooled-gradient buffer held arena 1 until now: attach it again after this one
   return 0;
@@ -1079,28 +1121,16 @@ int smi_unet_ctx_grad(smi_engine* e, int on) {
 int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
                           float* d_ctx_out) {
   SMI_CHECK(e && d_eps && d_ctx_out, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
-  UNet* u = unet(e);
-  SMI_CHECK(u->tape_valid, "smi_unet_backward_ctx: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  if (backward_begin(e, "smi_unet_backward_ctx")) return -1;
+  const UNet* u = unet(e);
   SMI_CHECK(u->bw_ctx, "smi_unet_backward_ctx: the saved pass does not differentiate the context (smi_unet_ctx_grad(e, 1) "
                        "before the saving forward)");
-  const bool adapted = e->bw_down && e->bw_up && e->bw_mult != 0.f && !e->sites.empty();
-  SMI_CHECK(!adapted || (d_lora_down_flat && d_lora_up_flat),
-            "smi_unet_backward_ctx: the saved pass ran with the adaptor on: its gradient buffers are required");
-  e->err = false;
-  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
-  return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out);
+  return backward_launch(e, "smi_unet_backward_ctx", d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out);
 }
 
 int smi_unet_pooled_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
                                int batch_adapted, int h, int w, int ctx_len, size_t* bytes) {
-  if (check_cfg(cfg)) return -1;
-  SMI_CHECK(bytes && batch > 0 && batch_adapted >= 0 && batch_adapted <= batch && h > 0 && w > 0 && ctx_len > 0,
-            "bad arguments");
-  size_t r[5], x = 0, t = 0;
-  if (plan(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, r, &x, &t)) return -1;
-  *bytes = t + r[2] + 2 * 4096;
-  return 0;
+  return grad_buffer_bytes(cfg, sites, n_sites, batch, batch_adapted, h, w, ctx_len, bytes, true);
 }
 
 int smi_unet_pooled_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes) {
@@ -1109,24 +1139,7 @@ int smi_unet_pooled_grad_attach(smi_engine* e, void* buffer, size_t buffer_bytes
   UNet* u = unet(e);
   SMI_CHECK(u->ctx_cap, "smi_unet_pooled_grad_attach: attach the context-gradient buffer first (smi_unet_ctx_grad_attach): "
                         "the pooled-embedding gradient rides on the context gradient's pass");
-  size_t r[5], x = 0, t = 0;
-  if (plan(&u->cfg, e->sites.data(), (int)e->sites.size(), e->max_n, u->max_n_ad, u->lat_h, u->lat_w, u->ctx_len, r, &x, &t))
-    return -1;
-  char* base = (char*)align_up((size_t)buffer, 4096);
-  const size_t have = (size_t)((char*)buffer + buffer_bytes - base);
-  SMI_CHECK((char*)buffer + buffer_bytes >= base && t + r[2] <= have,
-            "smi_unet_pooled_grad_attach: buffer too small: need %zu bytes, got %zu", t + r[2] + 2 * 4096, buffer_bytes);
-  e->err = false;
-  u->tpack = Arena();
-  u->tpack.base = base;
-  u->tpack.cap = t;
-  if (u->build_pooled_grad(*e)) return -1;
-  SMI_HIP(hipGetLastError());
-  SMI_CHECK(!e->err && !u->tpack.overflow, "smi_unet_pooled_grad_attach: packing the transposed time_emb_proj weights failed");
-  e->arena[1] = Arena();  // the saved pass of a forward + backward with both gradients on: larger again
-  e->arena[1].base = base + t;
-  e->arena[1].cap = r[2];
-  u->forget_saved_pass(*e);  // the saved activations lived in the old arena
+  if (const int rc = attach_grad_buffer(e, buffer, buffer_bytes, true)) return rc;
   u->pool_cap = true;
   return 0;
 }
@@ -1153,34 +1166,26 @@ int smi_unet_pooled_grad(smi_engine* e, int on) {
 int smi_unet_backward_cond(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat,
                            float* d_ctx_out, float* d_text_embeds_out) {
   SMI_CHECK(e && d_eps && d_ctx_out && d_text_embeds_out, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
-  UNet* u = unet(e);
-  SMI_CHECK(u->tape_valid, "smi_unet_backward_cond: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  if (backward_begin(e, "smi_unet_backward_cond")) return -1;
+  const UNet* u = unet(e);
   SMI_CHECK(u->bw_ctx && u->bw_pool, "smi_unet_backward_cond: the saved pass does not differentiate the pooled embedding "
                                      "(smi_unet_ctx_grad(e, 1) and smi_unet_pooled_grad(e, 1) before the saving forward)");
-  const bool adapted = e->bw_down && e->bw_up && e->bw_mult != 0.f && !e->sites.empty();
-  SMI_CHECK(!adapted || (d_lora_down_flat && d_lora_up_flat),
-            "smi_unet_backward_cond: the saved pass ran with the adaptor on: its gradient buffers are required");
-  e->err = false;
-  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
-  return u->backward(*e, d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out, d_text_embeds_out);
+  return backward_launch(e, "smi_unet_backward_cond", d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out,
+                         d_text_embeds_out);
 }
 
 int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, float* d_lora_down_flat,
                            float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps_live && d_lora_down_flat && d_lora_up_flat, "NULL argument");
-  SMI_CHECK(e->kind == smi_engine::UNET, "this engine is a VAE encoder / decoder or a CLIP text / vision encoder: it has no backward");
-  UNet* u = unet(e);
-  SMI_CHECK(u->tape_valid, "smi_unet_backward_tail: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
+  if (backward_begin(e, "smi_unet_backward_tail")) return -1;
+  const UNet* u = unet(e);
   SMI_CHECK(!u->bw_pool, "smi_unet_backward_tail: the saved pass differentiates the pooled embedding; a tail backward is not "
                          "offered there (use smi_unet_backward_cond)");
   SMI_CHECK(!u->bw_ctx, "smi_unet_backward_tail: the saved pass differentiates the context; a tail backward is not offered "
                         "there (use smi_unet_backward_ctx)");
   SMI_CHECK(n_live >= 1 && n_live <= u->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
             n_live, u->bw_n_ad);
-  e->err = false;
-  GemmScratchScope scratch(u->splitk_ws, UNet::SPLITK_WS_BYTES);
-  return u->backward(*e, d_eps_live, d_lora_down_flat, d_lora_up_flat, n_live);
+  return backward_launch(e, "smi_unet_backward_tail", d_eps_live, d_lora_down_flat, d_lora_up_flat, n_live);
 }
 
 int smi_profile_enable(smi_engine* e, int enable) {

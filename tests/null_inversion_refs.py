@@ -29,34 +29,42 @@ def ddim_scheduler(steps=STEPS):
 GOLDEN = "null_inversion_oracle.json"  # under tests/golden/: {"timesteps": [...], "losses": [[...], ...]} of this recipe
 
 
-def oracle_null_optimization(ou, x0, uncond, cond, steps=STEPS, inner=INNER, g=GUIDANCE, epsilon=NO_EARLY_STOP,
-                             only_first=False):
-    """-> (losses [timestep][inner step], timesteps); only_first: stop after the first timestep's inner loop"""
+XL_TIME_IDS = [64.0, 64.0, 0.0, 0.0, 64.0, 64.0]  # of the SD-XL recipe (tests/null_inversion_xl_refs.py: a 64 x 64 image)
+
+
+def oracle_null_optimization(ou, x0, uncond, cond, pooled_u=None, pooled_c=None, optimize_pooled=False, steps=STEPS,
+                             inner=INNER, g=GUIDANCE, epsilon=NO_EARLY_STOP, only_first=False):
+    """-> (losses [timestep][inner step], timesteps); only_first: stop after the first timestep's inner loop.
+    pooled_u / pooled_c None: SD-1.x.  Given (SD-XL): they and XL_TIME_IDS go through every UNet call, and optimize_pooled
+    makes pooled_u a second Adam parameter."""
     sched = ddim_scheduler(steps)
-    unet = lambda x, t, c: ou(x, float(t), c, None).sample
+    tid = torch.tensor([XL_TIME_IDS])
+    unet = lambda x, t, c, p: ou(x, float(t), c, None if p is None else {"text_embeds": p, "time_ids": tid}).sample
     with torch.no_grad():
         latents = [x0]
         lat = x0.clone()
         for i in range(steps):
             t = int(sched.timesteps[len(sched.timesteps) - i - 1])
             cx, ce = step_coefficients(sched, t, True)
-            lat = cx * lat + ce * unet(lat, t, cond)
+            lat = cx * lat + ce * unet(lat, t, cond, pooled_c)
             latents.append(lat)
     losses, ts = [], []
     cur = latents[-1]
-    u = uncond
+    u, p = uncond, pooled_u
     for i in range(steps):
         u = u.clone().detach().requires_grad_(True)
-        opt = torch.optim.Adam([u], lr=1e-2 * (1. - i / 100.))
+        if p is not None:
+            p = p.clone().detach().requires_grad_(optimize_pooled)
+        opt = torch.optim.Adam([u, p] if optimize_pooled else [u], lr=1e-2 * (1. - i / 100.))
         prev = latents[len(latents) - i - 2]
         t = int(sched.timesteps[i])
         cx, ce = step_coefficients(sched, t, False)
         with torch.no_grad():
-            eps_c = unet(cur, t, cond)
+            eps_c = unet(cur, t, cond, pooled_c)
         losses.append([])
         ts.append(t)
         for _j in range(inner):
-            eps_u = unet(cur, t, u)
+            eps_u = unet(cur, t, u, p)
             rec = cx * cur + ce * (eps_u + g * (eps_c - eps_u))
             loss = nnf.mse_loss(rec, prev)
             opt.zero_grad()
@@ -68,8 +76,7 @@ def oracle_null_optimization(ou, x0, uncond, cond, steps=STEPS, inner=INNER, g=G
         if only_first:
             break
         with torch.no_grad():
-            ud = u.detach()
-            e_u, e_c = unet(cur, t, ud), unet(cur, t, cond)
+            e_u, e_c = unet(cur, t, u.detach(), None if p is None else p.detach()), unet(cur, t, cond, pooled_c)
             cur = cx * cur + ce * (e_u + g * (e_c - e_u))
     return losses, ts
 

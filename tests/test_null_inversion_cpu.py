@@ -127,3 +127,16 @@ def test_null_inversion_needs_the_gpu():
     unet = PU.UNet2DConditionModel(PU.UNetConfig(**dataclasses.asdict(OU.tiny_sd1x_config()))).half()
     with pytest.raises(_native.SmiError, match="runs only on an MI355X"):
         NI.NullInversion(unet, N.ddim_scheduler())
+
+
+def test_the_inversion_loops_are_defined_once():
+    """NullInversionXL reuses NullInversion's loops: a second definition in either module is the fork coming back."""
+    import ast
+    import inspect
+    from sliders_conceptmod_amd import null_inversion_xl as NX
+    names = ("_null_optimization_fused", "_null_optimization_autograd", "ddim_loop", "image2latent", "latent2image")
+    defined = [n.name for mod in (NI, NX) for n in ast.walk(ast.parse(inspect.getsource(mod)))
+               if isinstance(n, (ast.FunctionDef, ast.AsyncFunctionDef))]
+    for name in names:
+        assert defined.count(name) == 1, f"def {name}: {defined.count(name)} definitions"
+        assert getattr(NX.NullInversionXL, name) is getattr(NI.NullInversion, name)

@@ -97,6 +97,25 @@ def test_two_fused_runs_give_equal_bits():
     assert all(torch.equal(x, y) for x, y in zip(a[1], b[1])) and all(torch.equal(x, y) for x, y in zip(a[2], b[2]))
 
 
+def test_fused_sequence_only_optimisation_returns_the_encoders_pooled():
+    """optimize_pooled=False through the shared fused loop: the flat parameter is the sequence embedding alone"""
+    _losses, embs, pooleds, _ts, enc = run(True, False)
+    assert len(embs) == len(pooleds) == N.STEPS
+    assert all(torch.isfinite(e).all() for e in embs)
+    assert all(not torch.equal(a, b) for a, b in zip(embs, embs[1:]))
+    assert all(torch.equal(p, enc) for p in pooleds)
+
+
+@pytest.mark.parametrize("pooled", [True, False])
+@pytest.mark.parametrize("fused", [True, False])
+def test_early_stop_ends_the_inner_loop(fused, pooled):
+    inv, x0 = make_inversion(fused)
+    latents = inv.ddim_loop(x0)
+    embs, pooleds = inv.null_optimization(latents, N.INNER, 1e9, optimize_pooled=pooled)  # above any loss: one inner step per timestep
+    assert [len(l) for l in inv.losses] == [1] * N.STEPS
+    assert len(embs) == len(pooleds) == N.STEPS
+
+
 def test_refusals():
     from sliders_conceptmod_amd import model_util
     from sliders_conceptmod_amd._native import SmiError
