@@ -85,6 +85,7 @@ typedef struct smi_vae_config {
   int block_out_channels[SMI_MAX_LEVELS]; /* (128, 256, 512, 512) */
   int layers_per_block; /* 2 */
   int norm_num_groups;  /* 32 */
+  int no_post_quant_conv; /* decoder only: != 0 skips post_quant_conv (SD3's 16-channel VAE has none); 0 everywhere else */
 } smi_vae_config;
 
 /* Architecture of a transformers CLIPTextModel / CLIPTextModelWithProjection (the prompt front end:
@@ -124,6 +125,24 @@ typedef struct smi_lpips_config {
   int dtype;
   int channels[5]; /* (64, 192, 384, 256, 256) */
 } smi_lpips_config;
+
+/* Architecture of a diffusers SD3Transformer2DModel (the MMDiT of Stable Diffusion 3 medium; what
+ * conceptmod/textsliders/train_lora_sd3.py and predict_noise_sd3 drive).  Width d = num_heads x attention_head_dim. */
+typedef struct smi_mmdit_config {
+  int dtype;
+  int patch_size;             /* 2 */
+  int in_channels;            /* 16: in_channels x patch_size^2 must be a multiple of 64 (the patch GEMM's K) */
+  int out_channels;           /* 16 */
+  int num_layers;             /* 24: the last block is context_pre_only */
+  int num_heads;              /* 24 */
+  int attention_head_dim;     /* 64 (the only one built) */
+  int joint_attention_dim;    /* 4096: width of encoder_hidden_states */
+  int pooled_projection_dim;  /* 2048 */
+  int pos_embed_max_size;     /* 192: pos_embed.pos_embed is [1, 192 x 192, d] */
+  int context_len;            /* tokens per sample of encoder_hidden_states (77 + the T5 block, e.g. 333): fixed at creation */
+  int dual_attention_layers;  /* number of blocks with a second, image-only attention (SD3.5): must be 0 */
+  int qk_norm;                /* 0 none; 1 rms_norm (SD3.5): refused */
+} smi_mmdit_config;
 
 typedef struct smi_engine smi_engine;
 
@@ -180,7 +199,8 @@ int smi_vae_encode(smi_engine* e, int n, const float* image, float* moments_out)
  * image = decoder(post_quant_conv(latents)): replaces `vae.decode(latents / scaling_factor).sample` and the eval scripts'
  * post-processing (eval-scripts/generate_images_sd1.py:195-200).
  *   weights  diffusers AutoencoderKL state_dict entries `decoder.*` and `post_quant_conv.*`, dtype T (same size rule as
- *            the encoder: h, w multiples of f = 2^(n_levels-1); w also a multiple of 4; in_channels <= 4)
+ *            the encoder: h, w multiples of f = 2^(n_levels-1); w also a multiple of 4; in_channels <= 4; latent_channels
+ *            up to 16 here (SD3), and no `post_quant_conv.*` entries when cfg.no_post_quant_conv is set)
  *   latents  f32 [n, latent_channels, h/f, w/f]: what `vae.decode(z)` receives, i.e. ALREADY divided by scaling_factor
  *   image    f32 [n, in_channels, h, w]: `vae.decode(z).sample`, unclamped
  *   rgb8     optional (NULL: skipped) uint8 [n, h, w, in_channels] = round_half_even(clamp(sample/2 + 0.5, 0, 1) * 255)
@@ -277,6 +297,40 @@ int smi_lpips_create(const smi_lpips_config* cfg, const smi_weight* weights, int
                      void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
 int smi_lpips_distance(smi_engine* e, int n, const uint8_t* rgb8_a, const uint8_t* rgb8_b, const float* img_a,
                        const float* img_b, float* dist, float* per_layer, void* const* feats);
+
+/* ---- SD3 MMDiT, forward with LoRA sites (sweeping an SD3 slider) -------------------------------------------------------
+ * Replaces `transformer(hidden_states, timestep, encoder_hidden_states, pooled_projections).sample`
+ * (conceptmod/textsliders/train_util.py predict_noise_sd3).  Patch embedding (a GEMM on the patch matrix, columns (c, py, px))
+ * + the centre-cropped window of pos_embed.pos_embed; temb = timestep MLP(256-wide sinusoid, cos first) + pooled-text MLP;
+ * num_layers joint blocks: each stream is LN(h) (1 + scale) + shift under its own norm1[_context].linear(silu(temb)) chunks
+ * (shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp; the last block's context stream: scale, shift only), the two
+ * streams' q|k|v packed per sample into ONE non-causal attention over image tokens followed by context tokens, then
+ * h += gate_msa to_out(attn), h += gate_mlp ff(LN(h) (1 + scale_mlp) + shift_mlp) with tanh-GELU; the last block drops its
+ * context output.  norm_out (scale, shift) + proj_out, un-patchified with columns (py, px, c).
+ *   weights      the diffusers state_dict (`pos_embed.proj.*`, `pos_embed.pos_embed`, `context_embedder.*`,
+ *                `time_text_embed.*`, `transformer_blocks.<i>.*`, `norm_out.linear.*`, `proj_out.*`), dtype T
+ *   sites        Linear LoRA sites (rank <= 16) on attn.to_q/to_k/to_v (all three of a block or none, adjacent in the flat
+ *                buffers in that order: one fused GEMM), attn.add_q_proj/add_k_proj/add_v_proj (likewise), attn.to_out.0 and
+ *                attn.to_add_out; n_sites 0: a frozen network.  DoRA sites and other targets are refused by name.
+ *   h, w         the LATENT size, multiples of patch_size, grid <= pos_embed_max_size; fixed at creation, as context_len is
+ *   sample       f32 [n, in_channels, h, w]
+ *   timesteps    f32 [n], HOST memory: the scheduler's 1000 sigma, one per sample
+ *   ctx          T [n, context_len, joint_attention_dim]
+ *   pooled       T [n, pooled_projection_dim]
+ *   multipliers  f32 [n], HOST memory: sample i runs at W + m_i (alpha / r) up down.  NULL flat buffers, NULL multipliers or
+ *                all multipliers 0 give the bits of an engine created without sites.
+ *   out          f32 [n, out_channels, h, w]
+ * workspace = [packed weights | arena], sized by a dry forward.  n may be smaller than the creation batch.  No split-K
+ * scratch is lent to the GEMMs and every other sum is ordered by the shape: a sample gives the same bits alone or anywhere
+ * in a batch.  The config check refuses d % 64, d > 2048, attention_head_dim != 64, in_channels x patch_size^2 % 64, h or w
+ * not a multiple of patch_size, a grid above pos_embed_max_size, and dual_attention_layers / qk_norm (SD3.5) by name. */
+int smi_mmdit_workspace_bytes(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w,
+                              size_t* bytes);
+int smi_mmdit_create(const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                     int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                     smi_engine** out);
+int smi_mmdit_forward(smi_engine* e, int n, const float* sample, const float* timesteps, const void* ctx, const void* pooled,
+                      const float* lora_down_flat, const float* lora_up_flat, const float* multipliers, float* out);
 
 /* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)
@@ -591,8 +645,8 @@ int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const v
                                 const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
                                 int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                                 int64_t lddk, int64_t lddv, float scale, void* stream);
-/* The CLIP MLP activation, kind 0 quick_gelu / 1 erf-gelu: y = act(x) when y is given (n % 8 == 0), dx = dy * act'(x) when
- * dy is given (any n >= 1). */
+/* The MLP activations, kind 0 quick_gelu / 1 erf-gelu (CLIP) / 2 tanh-gelu (MMDiT; forward only): y = act(x) when y is
+ * given (n % 8 == 0), dx = dy * act'(x) when dy is given (any n >= 1; kinds 0 and 1). */
 int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream);
 int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
                      float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream);
@@ -650,6 +704,26 @@ int smi_op_nchw_to_nhwc(int dtype, const void* src, int src_f32, void* dst, int 
                         void* stream);
 int smi_op_nchw_to_nhwc_scaled(int dtype, const float* src, void* dst, int nb, int c, int hw, int cpad, const float* scale_dev,
                                void* stream);
+/* The MMDiT kernels, one launch each (tests/test_mmdit_kernels_gpu.py).  T is the 16-bit type, arithmetic fp32, one rounding
+ * at the store.  scale / shift / gate are c columns of row r / rows_per_sample of mod T [n, ldm], at column offsets that are
+ * multiples of 8 (as ldm is).
+ *   adaln_modulate  y [m, c] = LN(x) (1 + scale) + shift, LayerNorm without affine; c % 8 == 0, c <= 2048;
+ *                   mean_rstd f32 [m, 2] (may be NULL)
+ *   gate_residual   y [m, c] = h + gate f; y may alias h
+ *   joint_rows_pack / _split  joint [n (nx + nc), w] = per sample the nx rows of a [n nx, w], then the nc rows of b [n nc, w];
+ *                   the split is the inverse and a or b may be NULL there; w % 8 == 0
+ *   sd3_patchify    out T [n (h/p) (w/p), cin p p], columns (c, py, px), from latents f32 [n, cin, h, w]; cin p p % 64 == 0
+ *   sd3_add_pos     y [n gh gw, d] = x + the centre-cropped gh x gw window of pos T [s s, d] (top (s - gh) / 2, left (s - gw) / 2)
+ *   sd3_unpatchify  out f32 [n, cout, gh p, gw p] from rows T [n gh gw, p p cout], columns (py, px, c) */
+int smi_op_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int m, int c,
+                          int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, void* stream);
+int smi_op_gate_residual(int dtype, const void* h, const void* f, const void* mod, void* y, int64_t m, int c,
+                         int rows_per_sample, int64_t ldm, int off_gate, void* stream);
+int smi_op_joint_rows_pack(int dtype, const void* a, const void* b, void* joint, int n, int nx, int nc, int w, void* stream);
+int smi_op_joint_rows_split(int dtype, const void* joint, void* a, void* b, int n, int nx, int nc, int w, void* stream);
+int smi_op_sd3_patchify(int dtype, const float* latents, void* out, int n, int cin, int h, int w, int p, void* stream);
+int smi_op_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n, int gh, int gw, int d, int s, void* stream);
+int smi_op_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream);
 int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream);
 /* ff.net.0 with the GEGLU gate fused into the GEMM epilogue (the engine's forward path for
  * diffusers GEGLU: proj = x W^T + b [M, N]; out[M, N/2] = proj[:, :N/2] * gelu(proj[:, N/2:])).  Rows >= proj_row0 of

@@ -34,7 +34,7 @@ class UNetConfigC(C.Structure):
 class VaeConfigC(C.Structure):
     _fields_ = [("dtype", C.c_int), ("in_channels", C.c_int), ("latent_channels", C.c_int), ("n_levels", C.c_int),
                 ("block_out_channels", C.c_int * SMI_MAX_LEVELS), ("layers_per_block", C.c_int),
-                ("norm_num_groups", C.c_int)]
+                ("norm_num_groups", C.c_int), ("no_post_quant_conv", C.c_int)]
 
 
 class ClipConfigC(C.Structure):
@@ -52,6 +52,12 @@ class ClipVisionConfigC(C.Structure):
 
 class LpipsConfigC(C.Structure):
     _fields_ = [("dtype", C.c_int), ("channels", C.c_int * 5)]
+
+
+class MMDiTConfigC(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("dtype", "patch_size", "in_channels", "out_channels", "num_layers", "num_heads",
+                                       "attention_head_dim", "joint_attention_dim", "pooled_projection_dim",
+                                       "pos_embed_max_size", "context_len", "dual_attention_layers", "qk_norm")]
 
 
 class WeightC(C.Structure):
@@ -183,6 +189,12 @@ _SIGS = {
     "smi_lpips_create": (C.c_int, [C.POINTER(LpipsConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_int, C.c_int,
                                    C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_lpips_distance": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.POINTER(C.c_void_p)]),
+    "smi_mmdit_workspace_bytes": (C.c_int, [C.POINTER(MMDiTConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_mmdit_create": (C.c_int, [C.POINTER(MMDiTConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_mmdit_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 4 +
+                          [C.POINTER(C.c_float), C.c_void_p]),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -240,6 +252,15 @@ _SIGS = {
     "smi_op_colsum": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_float, C.c_void_p]),
     "smi_op_timestep_embed": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "smi_op_softmax_rows": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "smi_op_adaln_modulate": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 3 + [C.c_int64, C.c_int, C.c_int, C.c_float,
+                                                                                       C.c_void_p]),
+    "smi_op_gate_residual": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                                                      C.c_void_p]),
+    "smi_op_joint_rows_pack": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "smi_op_joint_rows_split": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
+    "smi_op_sd3_patchify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "smi_op_sd3_add_pos": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
+    "smi_op_sd3_unpatchify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "smi_op_chan_mix": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_conv3x3_small": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "smi_op_nchw_to_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),
@@ -693,6 +714,7 @@ def vae_config_c(cfg, dtype: torch.dtype) -> VaeConfigC:
     for i, v in enumerate(cfg.block_out_channels):
         c.block_out_channels[i] = v
     c.layers_per_block, c.norm_num_groups = cfg.layers_per_block, cfg.norm_num_groups
+    c.no_post_quant_conv = int(not getattr(cfg, "use_post_quant_conv", True))
     return c
 
 

@@ -51,7 +51,14 @@ __global__ void geglu_bwd_kernel(const T* __restrict__ proj, const T* __restrict
   }
 }
 
-template <typename T, int OP>  // 0: silu(a)   1: a + b   2: quick_gelu(a) = a * sigmoid(1.702 a)   3: gelu(a) (erf)
+// tanh-GELU 0.5 x (1 + tanh(u)), u = sqrt(2 / pi) (x + 0.044715 x^3), as x sigmoid(2 u): one v_exp and one division
+__device__ __forceinline__ float gelu_tanh_f(float x) {
+  const float u2 = 1.5957691216057308f * x * __builtin_fmaf(0.044715f * x, x, 1.f);
+  return x / (1.f + __expf(-u2));
+}
+
+// 0: silu(a)   1: a + b   2: quick_gelu(a) = a * sigmoid(1.702 a)   3: gelu(a) (erf)   4: gelu(a) (tanh form)
+template <typename T, int OP>
 __global__ void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, int64_t n8) {
   GSTRIDE(i, n8) {
     Pack8<T> x, z, o;
@@ -60,8 +67,11 @@ __global__ void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* _
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const float v = to_f(x.e[e]);
-      o.e[e] = from_f<T>(OP == 0 ? silu_f(v) : OP == 1 ? v + to_f(z.e[e]) : OP == 2 ? v / (1.f + __expf(-1.702f * v))
-                                                                                      : gelu_f(v));
+      o.e[e] = from_f<T>(OP == 4   ? gelu_tanh_f(v)
+                         : OP == 0 ? silu_f(v)
+                         : OP == 1 ? v + to_f(z.e[e])
+                         : OP == 2 ? v / (1.f + __expf(-1.702f * v))
+                                   : gelu_f(v));
     }
     *reinterpret_cast<u32x4*>(y + i * 8) = o.u;
   }
@@ -719,13 +729,13 @@ int launch_silu(int dtype, const void* x, void* y, int64_t n, hipStream_t stream
   return 0;
 }
 int launch_act(int dtype, const void* x, void* y, int64_t n, int kind, hipStream_t stream) {
-  SMI_CHECK(n % 8 == 0 && (kind == 0 || kind == 1), "act: n %% 8, kind 0 (quick_gelu) or 1 (gelu)");
+  SMI_CHECK(n % 8 == 0 && kind >= 0 && kind <= 2, "act: n %% 8, kind 0 (quick_gelu), 1 (gelu) or 2 (tanh gelu)");
   const int grid = ew_grid(n / 8);
 #define L(TT_, OP_) hipLaunchKernelGGL((ew_kernel<TT_, OP_>), dim3(grid), dim3(256), 0, stream, (const TT_*)x, nullptr, (TT_*)y, n / 8)
   if (dtype == DT_F16) {
-    if (kind == 0) L(f16, 2); else L(f16, 3);
+    if (kind == 0) L(f16, 2); else if (kind == 1) L(f16, 3); else L(f16, 4);
   } else {
-    if (kind == 0) L(bf16, 2); else L(bf16, 3);
+    if (kind == 0) L(bf16, 2); else if (kind == 1) L(bf16, 3); else L(bf16, 4);
   }
 #undef L
   SMI_HIP(hipGetLastError());

@@ -135,7 +135,7 @@ struct Model {
 
 struct smi_engine {
   // which model the engine holds: set once, by hold(); every entry point accepts one kind and refuses the others
-  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS };
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS, MMDIT };
   Kind kind = UNET;
   std::unique_ptr<Model> model;  // (also keeps a lambda from copying an engine it names through a reference parameter)
   int dtype = 0;
@@ -1288,7 +1288,7 @@ struct smi_engine {
     return y;
   }
 
-  // the CLIP MLP activation: kind 0 quick_gelu, 1 erf-gelu
+  // the CLIP MLP activation: kind 0 quick_gelu, 1 erf-gelu; 2 tanh-gelu (MMDiT feed-forward, no backward yet)
   Ten* act(Ten* x, int kind) {
     Ten* y = new_ten(x->rows, x->cols, x->n, x->H, x->W);
     RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(dtype, x->p, y->p, x->rows * x->cols, kind, stream));

@@ -175,10 +175,12 @@ struct VaeDecoder : Model {
     const int L = cfg.n_levels;
     const int* boc = cfg.block_out_channels;
     const int lc = cfg.latent_channels, co = cfg.in_channels;
-    pq_w = e.Wd("post_quant_conv.weight");
-    pq_b = e.Wd("post_quant_conv.bias");
-    e.check_shape("post_quant_conv.weight", {lc, lc, 1, 1});
-    e.check_shape("post_quant_conv.bias", {lc});
+    if (!cfg.no_post_quant_conv) {
+      pq_w = e.Wd("post_quant_conv.weight");
+      pq_b = e.Wd("post_quant_conv.bias");
+      e.check_shape("post_quant_conv.weight", {lc, lc, 1, 1});
+      e.check_shape("post_quant_conv.bias", {lc});
+    }
     const int top = boc[L - 1];
     conv_in = e.make_conv_in("decoder.conv_in", lc, top);
     build_vae_mid(e, mid, cfg, "decoder.mid_block", top);
@@ -225,8 +227,11 @@ struct VaeDecoder : Model {
     float* zt = e.alloc_f32((size_t)M0 * lc);
     // NCHW -> NHWC: the NHWC -> NCHW kernel with the roles of C and HW swapped
     RUN(launch_nhwc_to_nchw_f32(latents, zt, n, h0 * w0, lc, e.stream));
-    float* zq = e.alloc_f32((size_t)M0 * lc);
-    RUN(launch_chan_mix(e.dtype, zt, pq_w, pq_b, zq, M0, lc, e.stream));
+    float* zq = zt;  // (a VAE without post_quant_conv: SD3's)
+    if (!cfg.no_post_quant_conv) {
+      zq = e.alloc_f32((size_t)M0 * lc);
+      RUN(launch_chan_mix(e.dtype, zt, pq_w, pq_b, zq, M0, lc, e.stream));
+    }
     Ten* x0 = e.new_ten(M0, 64, n, h0, w0);
     RUN(launch_f32_to_padded(e.dtype, zq, lc, lc, x0->p, 64, M0, 1.f, e.stream));
     Ten* h = e.conv3x3(x0, conv_in, nullptr, nullptr);
@@ -260,11 +265,11 @@ struct VaeDecoder : Model {
   }
 };
 
-int check_vae_cfg(const smi_vae_config* c, int batch, int h, int w) {
+int check_vae_cfg(const smi_vae_config* c, int batch, int h, int w, int max_latent = 8) {
   SMI_CHECK(c != nullptr, "config is NULL");
   SMI_CHECK(c->dtype == SMI_DTYPE_F16 || c->dtype == SMI_DTYPE_BF16, "dtype must be f16 (0) or bf16 (1)");
   SMI_CHECK(c->n_levels >= 1 && c->n_levels <= SMI_MAX_LEVELS && c->in_channels >= 1 && c->in_channels <= 16 &&
-                c->latent_channels >= 1 && c->latent_channels <= 8 && c->layers_per_block >= 1,
+                c->latent_channels >= 1 && c->latent_channels <= max_latent && c->layers_per_block >= 1,
             "VAE config out of range");
   for (int i = 0; i < c->n_levels; ++i)
     SMI_CHECK(c->block_out_channels[i] % 64 == 0 && c->block_out_channels[i] % c->norm_num_groups == 0,
@@ -297,7 +302,7 @@ int64_t vae_dec_image_operand_bytes(const smi_vae_config* c, int h, int w) {
   return m * 2;
 }
 int check_vae_dec_cfg(const smi_vae_config* c, int batch, int h, int w) {
-  if (check_vae_cfg(c, batch, h, w)) return -1;
+  if (check_vae_cfg(c, batch, h, w, 16)) return -1;  // 16: SD3's latents (the 1x1 post_quant_conv kernel takes up to 16)
   SMI_CHECK(c->in_channels <= 4, "VAE decoder: %d image channels (the fused conv_out takes at most 4)", c->in_channels);
   SMI_CHECK(c->block_out_channels[0] <= 512, "VAE decoder: block_out_channels[0] = %d > 512", c->block_out_channels[0]);
   SMI_CHECK(w % 4 == 0, "VAE decoder: image width %d must be a multiple of 4", w);

@@ -288,7 +288,8 @@ int launch_geglu_fwd(int dtype, const void* proj, void* out, int M, int C4, hipS
 int launch_geglu_bwd(int dtype, const void* proj, const void* dout, void* dproj, int M, int C4, hipStream_t stream);
 int launch_silu(int dtype, const void* x, void* y, int64_t n, hipStream_t stream);
 int launch_add(int dtype, const void* a, const void* b, void* y, int64_t n, hipStream_t stream);  // y = a + b
-// CLIP text encoder pieces: y = quick_gelu(x) (kind 0) / gelu(x) (kind 1); token + position embedding lookup; row gather
+// CLIP text encoder pieces: y = quick_gelu(x) (kind 0) / gelu(x) (kind 1) / tanh-form gelu(x) (kind 2: the MMDiT's
+// feed-forward; forward only); token + position embedding lookup; row gather
 int launch_act(int dtype, const void* x, void* y, int64_t n, int kind, hipStream_t stream);
 // dx = dy * act'(x) in fp32, one 16-bit rounding at the store; any n (x, dy, dx 16-byte aligned)
 int launch_act_bwd(int dtype, const void* x, const void* dy, void* dx, int64_t n, int kind, hipStream_t stream);
@@ -353,6 +354,31 @@ int launch_vit_embed_ln(int dtype, const void* patch_out, const void* cls, const
 // logits_per_image f32 [ni, nt] = exp(logit_scale) <i, t> / (|i| |t|) from T [ni, dim], T [nt, dim]; dim % 8 == 0
 int launch_clip_logits(int dtype, const void* image_embeds, int ni, const void* text_embeds, int nt, int dim,
                        float logit_scale, float* logits_per_image, hipStream_t stream);
+
+// MMDiT (SD3) around the GEMMs and the attention (mmdit.hip).  T is 16-bit, arithmetic fp32, one rounding at the store.
+// scale / shift / gate are C columns of a row of one modulation tensor mod T [n, ldm], at column offsets that are multiples
+// of 8; row r of the activations belongs to sample r / rows_per_sample.
+// y[r, :] = LN(x[r, :]) (1 + scale[s, :]) + shift[s, :]: LayerNorm without affine, C % 8 == 0, C <= 2048, one pass over x;
+// mean_rstd f32 [M, 2] (may be NULL): what a backward needs
+int launch_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int M, int C,
+                          int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, hipStream_t stream);
+// y[r, :] = h[r, :] + gate[s, :] f[r, :]; y may alias h
+int launch_gate_residual(int dtype, const void* h, const void* f, const void* mod, void* y, int64_t M, int C,
+                         int rows_per_sample, int64_t ldm, int off_gate, hipStream_t stream);
+// joint T [n (Nx + Nc), W]: per sample the Nx rows of a [n Nx, W], then the Nc rows of b [n Nc, W]; W % 8 == 0.
+// The split is the inverse; a or b may be NULL there (that stream is dropped)
+int launch_joint_rows_pack(int dtype, const void* a, const void* b, void* joint, int n, int Nx, int Nc, int W,
+                           hipStream_t stream);
+int launch_joint_rows_split(int dtype, const void* joint, void* a, void* b, int n, int Nx, int Nc, int W, hipStream_t stream);
+// out T [n (H/p) (W/p), Cin p p], columns (c, py, px) as the rows of pos_embed.proj.weight.reshape(d, -1), from latents
+// f32 [n, Cin, H, W]; Cin p p % 64 == 0
+int launch_sd3_patchify(int dtype, const float* latents, void* out, int n, int Cin, int H, int W, int p, hipStream_t stream);
+// y[(i, gy, gx), :] = x[...] + pos[(top + gy) S + left + gx, :], pos T [S S, d], top = (S - gh) / 2, left = (S - gw) / 2:
+// the centre-cropped window of the position table; y may alias x
+int launch_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n, int gh, int gw, int d, int S,
+                       hipStream_t stream);
+// out f32 [n, Cout, gh p, gw p] from rows T [n gh gw, p p Cout] with columns (py, px, c)
+int launch_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int Cout, int gh, int gw, int p, hipStream_t stream);
 
 // LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
 // applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.

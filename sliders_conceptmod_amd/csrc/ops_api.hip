@@ -323,6 +323,31 @@ int smi_op_colsum(int dtype, const void* x, void* out, float* scratch, int nb, i
 int smi_op_timestep_embed(int dtype, const float* vals, void* out, int n, int dim, void* stream) {
   return launch_timestep_embed(dtype, vals, out, n, dim, (hipStream_t)stream);
 }
+// the MMDiT kernels (mmdit.hip)
+int smi_op_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int m, int c,
+                          int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, void* stream) {
+  return launch_adaln_modulate(dtype, x, mod, y, mean_rstd, m, c, rows_per_sample, ldm, off_scale, off_shift, eps,
+                               (hipStream_t)stream);
+}
+int smi_op_gate_residual(int dtype, const void* h, const void* f, const void* mod, void* y, int64_t m, int c,
+                         int rows_per_sample, int64_t ldm, int off_gate, void* stream) {
+  return launch_gate_residual(dtype, h, f, mod, y, m, c, rows_per_sample, ldm, off_gate, (hipStream_t)stream);
+}
+int smi_op_joint_rows_pack(int dtype, const void* a, const void* b, void* joint, int n, int nx, int nc, int w, void* stream) {
+  return launch_joint_rows_pack(dtype, a, b, joint, n, nx, nc, w, (hipStream_t)stream);
+}
+int smi_op_joint_rows_split(int dtype, const void* joint, void* a, void* b, int n, int nx, int nc, int w, void* stream) {
+  return launch_joint_rows_split(dtype, joint, a, b, n, nx, nc, w, (hipStream_t)stream);
+}
+int smi_op_sd3_patchify(int dtype, const float* latents, void* out, int n, int cin, int h, int w, int p, void* stream) {
+  return launch_sd3_patchify(dtype, latents, out, n, cin, h, w, p, (hipStream_t)stream);
+}
+int smi_op_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n, int gh, int gw, int d, int s, void* stream) {
+  return launch_sd3_add_pos(dtype, x, pos, y, n, gh, gw, d, s, (hipStream_t)stream);
+}
+int smi_op_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream) {
+  return launch_sd3_unpatchify(dtype, rows, out, n, cout, gh, gw, p, (hipStream_t)stream);
+}
 int smi_op_softmax_rows(int dtype, const float* s, void* p, int rows, int cols, float scale, void* stream) {
   return launch_softmax_rows(dtype, s, p, rows, cols, scale, (hipStream_t)stream);
 }

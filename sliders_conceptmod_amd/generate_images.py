@@ -23,7 +23,17 @@ at multiplier = scale on every prompt the sweep encodes, conditional and uncondi
 the un-adapted embeddings and the later steps the adapted ones -- the flip the UNet slider makes.  `--model_name` may be
 left out: a text-encoder-only sweep.  On a `synthetic://` model the text front end is then a pair of seeded CLIP towers
 (`train_notrigger.synthetic_towers`) instead of the hashed-embedding stand-in; `--synthetic_towers` asks for them without a
-file (the images a text-encoder file at scale 0 must reproduce)."""
+file (the images a text-encoder file at scale 0 must reproduce).
+
+`--base sd3`: the sweep of an SD3 slider (conceptmod/textsliders/train_lora_sd3.py writes them) on the native MMDiT: per CSV
+row and scale a CFG pair per sample through `train_util.predict_noise_sd3` steps of the flow-matching Euler schedule, the
+slider off while t > start_noise and at `scale` below it; the 16-channel VAE decodes latents / scaling_factor + shift_factor.
+Prompts are encoded as the pipeline does with text_encoder_3=None (`train_util.encode_prompts_sd3`, `--t5_tokens` zero rows).
+Defaults: 28 steps, guidance 7.0, 1024 x 1024, bf16 decode, start_noise 750 on the 1000 sigma axis.  Further differences, on
+purpose: the reference has no SD3 sweep script, so neither start_noise 750 nor guidance 7.0 comes from it (750 is the SD-XL
+sweep's value carried over, 7.0 the published pipeline's default); whether the file adapts the context stream too
+(add_q_proj ... to_add_out, which the reference's own LoRANetwork leaves out) is read from its keys; `--te_model_name` is
+refused with `--base sd3`."""
 from __future__ import annotations
 
 import argparse
@@ -96,9 +106,11 @@ def lora_file_params(state: Dict[str, torch.Tensor], unet) -> Tuple[int, float, 
         raise ValueError(f"LoRA file mixes alphas {sorted(alphas)}")
     alpha = alphas.pop() if alphas else float(ranks.copy().pop())
     names = {k[:-len(".lora_down.weight")] for k in downs}
+    ctx_stream = any("_attn_add_" in k or "_attn_to_add_out" in k for k in names)  # an SD3 file with the context stream's sites
     for target_replace in (LM.DEFAULT_TARGET_REPLACE, LM.DEFAULT_TARGET_REPLACE + LM.UNET_TARGET_REPLACE_MODULE_CONV):
         for method in TRAIN_METHODS:
-            got = {t[0] for t in LM.select_targets(unet, method, target_replace, LM.LORA_PREFIX_UNET, "_")}
+            got = {t[0] for t in LM.select_targets(unet, method, target_replace, LM.LORA_PREFIX_UNET, "_",
+                                                   context_stream=ctx_stream)}
             if got == names:
                 return ranks.pop(), alpha, method, list(target_replace)
     raise ValueError("the LoRA file's layers match no train method of this UNet (wrong --base or --pretrained_model?)")
@@ -141,8 +153,9 @@ def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: i
 
 def lora_network_from_state(unet, state: Dict[str, torch.Tensor], device):
     rank, alpha, method, target_replace = lora_file_params(state, unet)
+    ctx_stream = any("_attn_add_" in k or "_attn_to_add_out" in k for k in state)
     net = LM.LoRANetwork(unet, rank=rank, multiplier=1.0, alpha=alpha, train_method=method,
-                         target_replace=target_replace).to(device)
+                         target_replace=target_replace, context_stream=ctx_stream).to(device)
     net.load_state_dict(state)
     return net
 
@@ -183,8 +196,71 @@ def strip(images) -> "Image.Image":
     return out
 
 
+def generate_sd3(args) -> List[str]:
+    """`--base sd3` (module docstring)."""
+    from PIL import Image
+    if parse_te_names(args.te_model_name) or args.synthetic_towers:
+        raise ValueError("--base sd3 takes no --te_model_name / --synthetic_towers: text-encoder LoRA sweeps are not built for SD3")
+    if not args.model_name:
+        raise ValueError("--base sd3 needs --model_name (an SD3 slider file)")
+    if args.scheduler is not None:
+        raise ValueError("--base sd3 samples with the flow-matching Euler schedule only (leave --scheduler out)")
+    device = torch.device(args.device if not str(args.device).isdigit() else f"cuda:{args.device}")
+    if device.type != "cuda":
+        raise ValueError("the product path has no CPU fallback: pass a cuda device")
+    dtype = torch.float16
+    vae_dtype = DTYPES[args.vae_dtype] if args.vae_dtype else torch.bfloat16
+    start_noise = args.start_noise if args.start_noise is not None else 750
+    tokenizers, text_encoders, transformer, scheduler = model_util.load_models_sd3(args.pretrained_model, weight_dtype=dtype)
+    transformer = transformer.to(device, dtype).requires_grad_(False).eval()
+    for te in text_encoders:
+        te.to(device, dtype)
+    network = lora_network_from_state(transformer, load_lora_state(args.model_name), device)
+    if args.rank is not None and args.rank != network.lora_dim:
+        raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
+    network.__exit__(None, None, None)  # the sweep sets the multiplier per step
+    vae = model_util.load_vae_decoder_sd3(args.pretrained_model).to(device, vae_dtype)
+    scales = parse_scales(args.scales)
+    name = os.path.splitext(os.path.basename(args.model_name))[0]
+    folder = os.path.join(args.save_path, name)
+    for d in [scale_str(s) for s in scales] + ["all"]:
+        os.makedirs(os.path.join(folder, d), exist_ok=True)
+    h = w = args.image_size
+    jd = transformer.cfg.joint_attention_dim
+    written = []
+    for row in read_prompts(args.prompts_path):
+        case = row["case_number"]
+        if not (args.from_case <= case <= args.till_case):
+            continue
+        c, cp = train_util.encode_prompts_sd3(None, tokenizers, text_encoders, row["prompt"], 1, args.t5_tokens, jd)
+        u, up = train_util.encode_prompts_sd3(None, tokenizers, text_encoders, args.negative_prompts or "", 1, args.t5_tokens, jd)
+        te = train_util.concat_embeddings_sd3(u, c, args.num_samples)
+        pooled = train_util.concat_embeddings_sd3(up, cp, args.num_samples)
+        images = []
+        for scale in scales:
+            scheduler.set_timesteps(args.ddim_steps)
+            lat = train_util.get_initial_latents_sd3(scheduler, args.num_samples, h, w, 1,
+                                                     generator=torch.manual_seed(row["evaluation_seed"])).to(device)
+            lat = train_util.slider_sweep_latents_sd3(transformer, network, scheduler, lat, te, pooled, scale, start_noise,
+                                                      args.guidance_scale)
+            z = lat.float() / vae.config.scaling_factor + vae.config.shift_factor
+            rgb = vae.decode_to_uint8(z).cpu().numpy()
+            images.append([Image.fromarray(rgb[i]) for i in range(rgb.shape[0])])
+        for num in range(args.num_samples):
+            per_scale, all_path = output_paths(args.save_path, name, scales, case, num)
+            for i, p in enumerate(per_scale):
+                images[i][num].save(p)
+                written.append(p)
+            strip([images[i][num] for i in range(len(scales))]).save(all_path)
+            written.append(all_path)
+    return written
+
+
 def generate(args) -> List[str]:
     from PIL import Image
+    fill_defaults(args)
+    if args.base == "sd3":
+        return generate_sd3(args)
     xl = args.base == "xl"
     device = torch.device(args.device if not str(args.device).isdigit() else f"cuda:{args.device}")
     if device.type != "cuda":
@@ -297,13 +373,15 @@ def build_parser():
     p.add_argument("--pretrained_model", default="synthetic://sd1x",
                    help="local diffusers directory or synthetic://(tiny_)sd1x | sdxl")
     p.add_argument("--negative_prompts", default=None, help="negative prompt (default: the empty prompt)")
-    p.add_argument("--base", choices=["1.4", "xl"], default="1.4")
-    p.add_argument("--guidance_scale", type=float, default=7.5)
+    p.add_argument("--base", choices=["1.4", "xl", "sd3"], default="1.4")
+    p.add_argument("--guidance_scale", type=float, default=None, help="default 7.5 (SD-1.x, SD-XL) / 7.0 (SD3)")
+    p.add_argument("--t5_tokens", type=int, default=256, help="--base sd3: zero rows that stand in for the T5 block of the "
+                   "context (256: the published pipeline's max_sequence_length; 77: its first release)")
     p.add_argument("--image_size", type=int, default=None, help="default 512 (SD-1.x) / 1024 (SD-XL)")
     p.add_argument("--from_case", type=int, default=0)
     p.add_argument("--till_case", type=int, default=1000000)
     p.add_argument("--num_samples", type=int, default=5)
-    p.add_argument("--ddim_steps", type=int, default=50)
+    p.add_argument("--ddim_steps", type=int, default=None, help="default 50 (SD-1.x, SD-XL) / 28 (SD3)")
     p.add_argument("--rank", type=int, default=None, help="optional check: the rank is read from the file")
     p.add_argument("--start_noise", type=int, default=None, help="default 850 (SD-1.x) / 750 (SD-XL)")
     p.add_argument("--scales", default="-2,-1,0,1,2", help="comma-separated; write --scales=-1,0,1 (a leading '-' "
@@ -316,10 +394,19 @@ def build_parser():
     return p
 
 
-def main(argv=None):
-    args = build_parser().parse_args(argv)
+def fill_defaults(args):
+    """The defaults that depend on --base."""
     if args.image_size is None:
-        args.image_size = 1024 if args.base == "xl" else 512
+        args.image_size = 512 if args.base == "1.4" else 1024
+    if args.guidance_scale is None:
+        args.guidance_scale = 7.0 if args.base == "sd3" else 7.5
+    if args.ddim_steps is None:
+        args.ddim_steps = 28 if args.base == "sd3" else 50
+    return args
+
+
+def main(argv=None):
+    args = fill_defaults(build_parser().parse_args(argv))
     for path in generate(args):
         print(path)
 

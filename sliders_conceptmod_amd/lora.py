@@ -92,8 +92,13 @@ class LoRAModule:
 
 
 def select_targets(root_module: nn.Module, train_method: str, target_replace_modules, prefix: str, delimiter: str,
-                   with_duplicates: bool = False):
+                   with_duplicates: bool = False, context_stream: bool = False):
     """The name / class-name walk of lora.py:194-251, returning (lora_name, dotted path, child module).
+
+    The walk leaves out every child whose name contains 'add_' (lora.py:227), which on an SD3 `Attention` are the context
+    stream's add_q_proj / add_k_proj / add_v_proj and to_add_out: the reference's class adapts to_q, to_k, to_v and to_out.0
+    of a joint block only.  `context_stream=True` keeps them (all eight projections of a block, seven in the last); nothing
+    else changes, and a UNet has no such child.
 
     With the conv classes in `target_replace_modules` (c3lier) a resnet conv is reached twice -- through its
     DownBlock2D / UpBlock2D and again through its ResnetBlock2D; the reference BUILDS a LoRAModule both times (drawing
@@ -119,7 +124,7 @@ def select_targets(root_module: nn.Module, train_method: str, target_replace_mod
             raise NotImplementedError(f"train_method: {train_method} is not implemented.")
         if module.__class__.__name__ in target_replace_modules:
             for child_name, child_module in module.named_modules():
-                if "add_" in child_name:
+                if "add_" in child_name and not context_stream:
                     continue
                 if child_module.__class__.__name__ in ["Linear", "Conv2d", "LoRACompatibleLinear",
                                                        "LoRACompatibleConv"]:
@@ -142,35 +147,50 @@ def select_targets(root_module: nn.Module, train_method: str, target_replace_mod
 
 CLIP_TARGET_REPLACE = ["CLIPAttention", "CLIPSdpaAttention"]  # notrigger/train_notrigger.py:186
 _CLIP_QKV = {"q_proj": 0, "k_proj": 1, "v_proj": 2}
+_SD3_ADD_QKV = {"add_q_proj": 0, "add_k_proj": 1, "add_v_proj": 2}  # diffusers declares add_k_proj, add_v_proj, add_q_proj
+
+
+def _fused_slot(path):
+    """(parent, position) of a projection the engine fuses with its two siblings into one q|k|v GEMM but the walk meets out
+    of the engine's order; None for every other target."""
+    parent, _, leaf = path.rpartition(".")
+    if leaf in _CLIP_QKV and parent.endswith("self_attn"):
+        return parent, _CLIP_QKV[leaf]
+    if leaf in _SD3_ADD_QKV:
+        return parent + ".add", _SD3_ADD_QKV[leaf]
+    return None
 
 
 def flat_order(targets):
     """The order in which the targets' matrices are laid out in the flat buffers: the order of the walk, except that the
     q_proj / k_proj / v_proj of one CLIP `self_attn` lie in that order wherever the walk met them (transformers declares
-    k, v, q): the engine fuses the three into one q|k|v GEMM and wants their sites adjacent and in its order.  File keys,
-    `unet_loras` and the RNG draws keep the order of the walk; UNet targets (to_q, to_k, to_v, ...) are not touched."""
+    k, v, q): the engine fuses the three into one q|k|v GEMM and wants their sites adjacent and in its order; likewise the
+    add_q_proj / add_k_proj / add_v_proj of an SD3 joint attention (diffusers declares k, v, q).  File keys, `unet_loras`
+    and the RNG draws keep the order of the walk; UNet targets (to_q, to_k, to_v, ...) are not touched."""
     first = {}
     for i, (_name, path, _child) in enumerate(targets):
-        parent, _, leaf = path.rpartition(".")
-        if leaf in _CLIP_QKV and parent.endswith("self_attn"):
-            first.setdefault(parent, i)
+        slot = _fused_slot(path)
+        if slot:
+            first.setdefault(slot[0], i)
 
     def key(i):
-        parent, _, leaf = targets[i][1].rpartition(".")
-        return (first[parent], _CLIP_QKV[leaf]) if parent in first and leaf in _CLIP_QKV else (i, 0)
+        slot = _fused_slot(targets[i][1])
+        return (first[slot[0]], slot[1]) if slot else (i, 0)
     return sorted(range(len(targets)), key=key)
 
 
 class LoRANetwork(nn.Module):
     def __init__(self, unet, rank: int = 4, multiplier: float = 1.0, delimiter: str = "_", alpha: float = 1.0,
                  target_replace=DEFAULT_TARGET_REPLACE, prefix=LORA_PREFIX_UNET,
-                 train_method: TRAINING_METHODS = "full") -> None:
+                 train_method: TRAINING_METHODS = "full", context_stream: bool = False) -> None:
+        """context_stream: on an SD3 transformer, adapt the context stream's projections too (select_targets)."""
         super().__init__()
         self.lora_scale = 1
         self.multiplier = multiplier
         self.lora_dim = rank
         self.alpha = alpha
-        visits = select_targets(unet, train_method, target_replace, prefix, delimiter, with_duplicates=True)
+        visits = select_targets(unet, train_method, target_replace, prefix, delimiter, with_duplicates=True,
+                                context_stream=context_stream)
         targets = [v[:3] for v in visits if not v[3]]
         n_down = sum(math.prod(lora_shapes(c, rank)[1]) for _, _, c in targets)
         n_up = sum(math.prod(lora_shapes(c, rank)[2]) for _, _, c in targets)

@@ -244,6 +244,52 @@ def create_noise_scheduler(scheduler_name: AVAILABLE_SCHEDULERS = "ddpm", predic
     raise ValueError(f"Unknown scheduler name: {name}")
 
 
+class FlowMatchEulerDiscreteScheduler:
+    """The flow-matching Euler scheduler SD3 samples with (the published diffusers class, restated from its documented
+    behaviour; `diffusers` is not a dependency here, so the restatement is unpinned -- DESIGN.md section 17).
+    Base sigmas linspace(1, N, N)[::-1] / N, shifted by s' = shift s / (1 + (shift - 1) s).  `set_timesteps(n)`:
+    t = linspace(N s'_max, N s'_min, n), sigma = t / N SHIFTED ONCE MORE, timesteps = N sigma, a final sigma 0 appended.
+    `step`: x + (sigma_{i+1} - sigma_i) v in fp32.  init_noise_sigma 1, scale_model_input the identity.  The model is fed
+    the timestep N sigma."""
+
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps: int = 1000, shift: float = 3.0):
+        self.num_train_timesteps, self.shift = num_train_timesteps, float(shift)
+        base = torch.linspace(1, num_train_timesteps, num_train_timesteps, dtype=torch.float64).flip(0) / num_train_timesteps
+        self._train_sigmas = self.shift_sigma(base)
+        self.sigma_max, self.sigma_min = float(self._train_sigmas[0]), float(self._train_sigmas[-1])
+        self.set_timesteps(num_train_timesteps)
+
+    def shift_sigma(self, s):
+        return self.shift * s / (1 + (self.shift - 1) * s)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n = self.num_train_timesteps
+        t = torch.linspace(self.sigma_max * n, self.sigma_min * n, num_inference_steps, dtype=torch.float64)
+        sig = self.shift_sigma(t / n)
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = (sig * n).to(torch.float32)
+        self.sigmas = torch.cat([sig, torch.zeros(1, dtype=torch.float64)]).to(torch.float32)
+        self._step_index = None
+
+    def scale_model_input(self, sample, timestep=None):
+        return sample
+
+    def index_for_timestep(self, timestep) -> int:
+        t = float(timestep)
+        hits = (self.timesteps == torch.tensor(t, dtype=torch.float32)).nonzero()
+        if hits.numel() == 0:
+            raise ValueError(f"timestep {t} is not one of this schedule's (call set_timesteps and pass scheduler.timesteps[i])")
+        return int(hits[0])
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict: bool = True):
+        i = self.index_for_timestep(timestep)
+        dt = float(self.sigmas[i + 1]) - float(self.sigmas[i])
+        prev = (sample.float() + dt * model_output.float()).to(sample.dtype)
+        return _StepOutput(prev) if return_dict else (prev,)
+
+
 # ----------------------------------------------------------------------------------------------------------------
 # model factory (reference: conceptmod/textsliders/model_util.py:27-137, 170-385 -- hub / checkpoint loaders)
 # ----------------------------------------------------------------------------------------------------------------
@@ -524,6 +570,135 @@ def load_clip(name: str):
         return model, CLIPTokenizer.from_pretrained(name), vc.image_size
     raise ValueError(f"cannot load '{name}': no network in this environment; pass a local transformers directory or "
                      f"synthetic://tiny_clip | synthetic://vit_b32 | synthetic://vit_l14")
+
+
+def _sd3_from_dir(path: str):
+    """<path>/transformer/config.json + diffusion_pytorch_model.safetensors (safe loader only) -> SD3Transformer2DModel."""
+    import json
+    from safetensors.torch import load_file
+    from . import mmdit as PM
+    cj = json.load(open(os.path.join(path, "transformer", "config.json")))
+    cfg = PM.SD3Config(patch_size=cj.get("patch_size", 2), in_channels=cj.get("in_channels", 16),
+                       out_channels=cj.get("out_channels") or cj.get("in_channels", 16), num_layers=cj.get("num_layers", 24),
+                       num_attention_heads=cj.get("num_attention_heads", 24),
+                       attention_head_dim=cj.get("attention_head_dim", 64),
+                       joint_attention_dim=cj.get("joint_attention_dim", 4096),
+                       pooled_projection_dim=cj.get("pooled_projection_dim", 2048),
+                       pos_embed_max_size=cj.get("pos_embed_max_size", 192), sample_size=cj.get("sample_size", 128),
+                       dual_attention_layers=tuple(cj.get("dual_attention_layers") or ()), qk_norm=cj.get("qk_norm"))
+    if cfg.dual_attention_layers or cfg.qk_norm:
+        raise ValueError(f"{path}: dual_attention_layers / qk_norm (SD3.5) are not built")
+    model = PM.SD3Transformer2DModel(cfg)
+    model.load_state_dict(load_file(os.path.join(path, "transformer", "diffusion_pytorch_model.safetensors")))
+    return model
+
+
+class SyntheticClipTower:
+    """Offline stand-in for one CLIPTextModelWithProjection of `synthetic://tiny_sd3`, in the spirit of SyntheticTextEncoder:
+    token ids map to seeded normal features keyed by a hash of the ids (equal prompts share embeddings).  The native CLIP
+    engine needs a hidden size that is a multiple of 64, and two such towers would not fit tiny_sd3's 64-wide context."""
+
+    class _Config:
+        def __init__(self, hidden_size, projection_dim):
+            self.hidden_size, self.projection_dim = hidden_size, projection_dim
+
+    def __init__(self, hidden_size: int, projection_dim: int, salt: int):
+        self.config, self.salt = self._Config(hidden_size, projection_dim), salt
+        self.device, self.dtype = torch.device("cpu"), torch.float32
+
+    def to(self, device=None, dtype=None):
+        self.device = torch.device(device) if device is not None else self.device
+        self.dtype = dtype or self.dtype
+        return self
+
+    def __call__(self, input_ids, output_hidden_states: bool = False, **_):
+        import hashlib
+        hs, pooled = [], []
+        for row in input_ids.cpu().tolist():
+            seed = int.from_bytes(hashlib.sha256(repr((self.salt, row)).encode()).digest()[:8], "little") % (2 ** 31)
+            g = torch.Generator().manual_seed(seed)
+            hs.append(torch.randn(len(row), self.config.hidden_size, generator=g))
+            pooled.append(torch.randn(self.config.projection_dim, generator=g))
+        pen = torch.stack(hs).to(self.device, self.dtype)
+        pool = torch.stack(pooled).to(self.device, self.dtype)
+
+        class _Out:
+            hidden_states = (None, pen, None)
+
+            def __getitem__(_self, i):
+                return (pool,)[i]
+        return _Out()
+
+
+def synthetic_sd3_towers(tiny: bool):
+    """(tokenizers, text encoders) of SD3's two CLIP towers: CLIP-L and OpenCLIP-bigG (both WithProjection) with seeded
+    weights on the native engine, or for tiny_sd3 two hashed stand-ins (hidden 32, projection 32 each)."""
+    from . import clip as PC
+    if tiny:
+        encs = [SyntheticClipTower(32, 32, 1), SyntheticClipTower(32, 32, 2)]
+        return [SyntheticClipTokenizer(1000, 999), SyntheticClipTokenizer(1000, 999)], encs
+    c1 = PC.CLIPTextConfig(**{**PC.clip_l_config().__dict__, "projection_dim": 768})
+    c2 = PC.open_clip_bigg_config()
+    encs = [init_synthetic_clip_(PC.CLIPTextModelWithProjection(c1), seed=1),
+            init_synthetic_clip_(PC.CLIPTextModelWithProjection(c2), seed=2)]
+    toks = [SyntheticClipTokenizer(e.config.vocab_size, e.config.eos_token_id) for e in encs]
+    return toks, encs
+
+
+def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float16):
+    """(tokenizers, text_encoders, transformer, scheduler) of an SD3 pipeline loaded with text_encoder_3=None, as the
+    reference loads it (conceptmod/textsliders/train_lora_sd3.py).  `synthetic://sd3 | tiny_sd3`: the architecture with
+    seeded weights.  A local diffusers directory is read with the safetensors loader from transformer/, text_encoder/ and
+    text_encoder_2/; text_encoder_3 (T5) is never loaded."""
+    from . import mmdit as PM
+    name = pretrained_model_name_or_path
+    scheduler = FlowMatchEulerDiscreteScheduler(num_train_timesteps=1000, shift=3.0)
+    if name.startswith("synthetic://"):
+        kind = name[len("synthetic://"):]
+        if kind not in ("sd3", "tiny_sd3"):
+            raise ValueError(f"unknown synthetic model '{name}': synthetic://sd3 | synthetic://tiny_sd3")
+        tiny = kind == "tiny_sd3"
+        model = PM.init_synthetic_(PM.SD3Transformer2DModel(PM.tiny_sd3_config() if tiny else PM.sd3_medium_config()), seed=0)
+        toks, encs = synthetic_sd3_towers(tiny)
+        return toks, encs, model, scheduler
+    if os.path.isdir(name):
+        import json
+        sj = os.path.join(name, "scheduler", "scheduler_config.json")
+        if os.path.exists(sj):
+            cj = json.load(open(sj))
+            scheduler = FlowMatchEulerDiscreteScheduler(cj.get("num_train_timesteps", 1000), cj.get("shift", 3.0))
+        from transformers import CLIPTokenizer
+        toks = [CLIPTokenizer.from_pretrained(name, subfolder="tokenizer"),
+                CLIPTokenizer.from_pretrained(name, subfolder="tokenizer_2")]
+        encs = [_clip_from_dir(name, "text_encoder"), _clip_from_dir(name, "text_encoder_2")]
+        return toks, encs, _sd3_from_dir(name), scheduler
+    raise ValueError(f"cannot load '{name}': pass a local diffusers directory or synthetic://sd3 | synthetic://tiny_sd3")
+
+
+def load_vae_decoder_sd3(pretrained_model_name_or_path: str):
+    """The 16-channel AutoencoderKL decoder of SD3 (no post_quant_conv; scaling 1.5305, shift 0.0609): seeded for
+    `synthetic://(tiny_)sd3`, else read from the directory's `vae/` with the safetensors loader."""
+    import json
+    from . import vae as PV
+    from . import vae_decoder as PD
+    name = pretrained_model_name_or_path
+    if name.startswith("synthetic://"):
+        cfg = PV.sd3_vae_config()
+        if "tiny" in name:
+            cfg = PV.VAEConfig(**{**cfg.__dict__, "block_out_channels": (64, 128, 128, 128), "norm_num_groups": 16})
+        return PD.init_synthetic_(PD.AutoencoderKLDecoder(cfg), seed=11)
+    if os.path.isdir(name):
+        from safetensors.torch import load_file
+        cj = json.load(open(os.path.join(name, "vae", "config.json")))
+        cfg = PV.VAEConfig(in_channels=cj.get("out_channels", cj.get("in_channels", 3)),
+                           latent_channels=cj.get("latent_channels", 16), block_out_channels=tuple(cj["block_out_channels"]),
+                           layers_per_block=cj.get("layers_per_block", 2), norm_num_groups=cj.get("norm_num_groups", 32),
+                           scaling_factor=cj.get("scaling_factor", 1.5305), shift_factor=cj.get("shift_factor") or 0.0,
+                           use_post_quant_conv=cj.get("use_post_quant_conv", True))
+        vae = PD.AutoencoderKLDecoder(cfg)
+        vae.load_state_dict(load_file(os.path.join(name, "vae", "diffusion_pytorch_model.safetensors")))
+        return vae
+    raise ValueError(f"cannot load a VAE decoder from '{name}': a local diffusers directory or synthetic://sd3 | tiny_sd3")
 
 
 # ----------------------------------------------------------------------------------------------------------------

@@ -50,6 +50,81 @@ def diffusion(unet, scheduler, latents, text_embeddings, total_timesteps: int = 
     return latents
 
 
+# ---- SD3 (conceptmod/textsliders/train_util.py get_initial_latents_sd3, concat_embeddings_sd3, predict_noise_sd3,
+# diffusion_sd3, encode_prompts_sd3): re-written from their documented behaviour on the native MMDiT -------------------------
+SD3_LATENT_CHANNELS = 16
+
+
+def get_initial_latents_sd3(scheduler, n_imgs: int, height: int, width: int, n_prompts: int, generator=None):
+    """randn [n_imgs, 16, height / 8, width / 8] (the reference draws it on the device; here on the CPU from `generator`, as
+    the other get_initial_latents do: the caller moves it).  init_noise_sigma is 1 and n_prompts is not used, as there."""
+    return torch.randn((n_imgs, SD3_LATENT_CHANNELS, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR),
+                       generator=generator, device="cpu")
+
+
+def concat_embeddings_sd3(unconditional, conditional, n_imgs: int):
+    return torch.cat([unconditional, conditional]).repeat_interleave(n_imgs, dim=0)
+
+
+def encode_prompts_sd3(pipeline, tokenizers, text_encoders, prompt: str, num_images_per_prompt: int = 1,
+                       t5_tokens: int = 256, joint_attention_dim: int = 4096):
+    """(prompt_embeds [n, 77 + t5_tokens, joint_attention_dim], pooled [n, p1 + p2]) as the SD3 pipeline encodes a prompt
+    with text_encoder_3=None: hidden_states[-2] of the two CLIP towers concatenated on the feature axis and zero-padded to
+    joint_attention_dim, then t5_tokens zero rows appended on the sequence axis (256: the published pipeline's
+    max_sequence_length; 77 reproduces its first release); pooled: the two projected pooled embeddings concatenated.
+    `pipeline` is the reference's first argument and is not used (there is no pipeline object here)."""
+    del pipeline
+    embeds, pooled = [], []
+    for tok, enc in zip(tokenizers, text_encoders):
+        ids = tok(prompt, padding="max_length", max_length=tok.model_max_length, truncation=True,
+                  return_tensors="pt").input_ids
+        out = enc(ids.to(enc.device), output_hidden_states=True)
+        pooled.append(out[0])
+        embeds.append(out.hidden_states[-2])
+    clip = torch.cat(embeds, dim=-1)
+    if clip.shape[-1] > joint_attention_dim:
+        raise ValueError(f"the CLIP towers are {clip.shape[-1]} wide, the transformer's context {joint_attention_dim}")
+    clip = torch.nn.functional.pad(clip, (0, joint_attention_dim - clip.shape[-1]))
+    zeros = torch.zeros(clip.shape[0], t5_tokens, joint_attention_dim, dtype=clip.dtype, device=clip.device)
+    prompt_embeds = torch.cat([clip, zeros], dim=1).repeat_interleave(num_images_per_prompt, dim=0)
+    return prompt_embeds, torch.cat(pooled, dim=-1).repeat_interleave(num_images_per_prompt, dim=0)
+
+
+def predict_noise_sd3(transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+                      guidance_scale=7.5, multipliers=None):
+    """One CFG step: returns the STEPPED latents, not the prediction (as the reference does).  The network is fed the
+    scheduler's timestep (1000 sigma).  `multipliers` (not in the reference signature): one adaptor multiplier per sample
+    of the doubled batch, for a transformer with an attached LoRANetwork."""
+    latent_model_input = torch.cat([latents] * 2)
+    v = transformer(hidden_states=latent_model_input, timestep=[float(timestep)] * latent_model_input.shape[0],
+                    encoder_hidden_states=text_embeddings, pooled_projections=add_text_embeddings,
+                    multipliers=multipliers, return_dict=False)[0]
+    guided = _cfg(v, guidance_scale)
+    return scheduler.step(guided, timestep, latents, return_dict=False)[0]
+
+
+@torch.no_grad()
+def diffusion_sd3(transformer, scheduler, latents, text_embeddings, add_text_embeddings, guidance_scale: float = 1.0,
+                  total_timesteps: int = 1000, start_timesteps=0):
+    for timestep in scheduler.timesteps[start_timesteps:total_timesteps]:
+        latents = predict_noise_sd3(transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+                                    guidance_scale=guidance_scale)
+    return latents
+
+
+@torch.no_grad()
+def slider_sweep_latents_sd3(transformer, network, scheduler, latents, text_embeddings, add_text_embeddings, scale: float,
+                             start_noise: float, guidance_scale: float):
+    """diffusion_sd3 over the whole schedule with the slider off while t > start_noise (on the 1000 sigma axis) and at
+    `scale` below it."""
+    for timestep in scheduler.timesteps:
+        on = network is not None and float(timestep) <= start_noise
+        m = [float(scale) if on else 0.0] * (2 * latents.shape[0]) if network is not None else None
+        latents = predict_noise_sd3(transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+                                    guidance_scale=guidance_scale, multipliers=m)
+    return latents
+
+
 def predict_noise_xl(unet, scheduler, timestep, latents, text_embeddings, add_text_embeddings, add_time_ids,
                      guidance_scale=7.5, guidance_rescale=0.7):
     latent_model_input = torch.cat([latents] * 2)

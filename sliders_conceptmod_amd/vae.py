@@ -26,6 +26,8 @@ class VAEConfig:
     layers_per_block: int = 2
     norm_num_groups: int = 32
     scaling_factor: float = 0.18215
+    shift_factor: float = 0.0          # SD3: the caller decodes latents / scaling_factor + shift_factor
+    use_post_quant_conv: bool = True   # SD3's VAE has none (decoder only: the encoder engine keeps its quant_conv)
 
 
 def sd_vae_config() -> VAEConfig:
@@ -34,6 +36,10 @@ def sd_vae_config() -> VAEConfig:
 
 def sdxl_vae_config() -> VAEConfig:
     return VAEConfig(scaling_factor=0.13025)
+
+
+def sd3_vae_config() -> VAEConfig:  # stabilityai/stable-diffusion-3-medium-diffusers vae/config.json
+    return VAEConfig(latent_channels=16, scaling_factor=1.5305, shift_factor=0.0609, use_post_quant_conv=False)
 
 
 class _Resnet(nn.Module):

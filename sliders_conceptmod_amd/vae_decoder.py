@@ -84,16 +84,17 @@ class AutoencoderKLDecoder(EngineCacheMixin, nn.Module):
         super().__init__()
         self.config = cfg
         self.decoder = _Decoder(cfg)
-        self.post_quant_conv = nn.Conv2d(cfg.latent_channels, cfg.latent_channels, 1)
+        if cfg.use_post_quant_conv:
+            self.post_quant_conv = nn.Conv2d(cfg.latent_channels, cfg.latent_channels, 1)
         self._engines = {}
 
     @property
     def dtype(self):
-        return self.post_quant_conv.weight.dtype
+        return self.decoder.conv_in.weight.dtype
 
     @property
     def device(self):
-        return self.post_quant_conv.weight.device
+        return self.decoder.conv_in.weight.device
 
     def load_state_dict(self, state_dict, strict: bool = True):
         """Accepts a full diffusers AutoencoderKL state dict: the encoder / quant_conv entries are not used."""
