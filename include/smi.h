@@ -591,6 +591,19 @@ int smi_op_gemm_epilogue(int dtype, const void* A, const void* W, void* C, int M
 int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin,
                    int win, int cin, int cout, int stride, int upsample, int transposed, int hout, int wout,
                    void* stream);
+/* The UNets' up-sampler conv (nearest-2x, then 3x3 / pad 1) in the engine's phase form:
+ * out [nb, 2h, 2w, cout] from in [nb, h, w, cin], the torch filter w [cout, cin, 3, 3] and bias [cout] (may be NULL).
+ * Packs the four summed 2x2 filters into wph (16 * cout * cin elements), runs the four phase convs into planes
+ * (4 * nb * h * w * cout elements) on the tile with tuner code tile_code (0: the launcher's own choice; a tile that cannot
+ * take the launch is replaced as in smi_op_gemm_epilogue) and un-shuffles the planes into out with the concat's copy.
+ * ran_code (may be NULL): int [4], the code of the tile each phase ran on. */
+int smi_op_upconv_phase(int dtype, const void* in, const void* w, const void* bias, void* wph, void* planes, void* out, int nb,
+                        int h, int w_, int cin, int cout, int tile_code, int* ran_code, void* stream);
+/* Process-wide override of SMI_UPCONV_PHASE (parity tests): -1 = the environment (default on), 0 = every up-sampler conv
+ * as one 3x3 conv on the 2x grid, 1 = as four 2x2 phase convs where the layer allows it (UNet up-samplers without an
+ * adaptor) at EVERY map size; the default form takes only input maps of at least SMI_UPCONV_PHASE_MIN_PIXELS (1024) pixels
+ * per sample.  Read when an engine is planned and created (the phase filters are packed then) and at every forward. */
+int smi_set_upconv_phase(int on);
 int smi_op_attention_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
                          int nq, int nk, int d, float scale, void* stream);
 int smi_op_attention_bwd(int dtype, const void* q, const void* k, const void* v, const void* o, const float* lse,

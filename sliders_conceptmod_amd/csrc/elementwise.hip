@@ -111,6 +111,25 @@ __global__ void copy_cols_kernel(const T* __restrict__ src, int64_t lds, T* __re
   }
 }
 
+// the same copy out of the four phase planes of an up-sampler conv: destination row (n, oy, ox) of the 2H x 2W map reads row
+// (n, oy >> 1, ox >> 1) of plane 2 (oy & 1) + (ox & 1); walked in destination order, the same bytes as copy_cols moves
+template <typename T>
+__global__ void copy_cols_phase_kernel(const T* __restrict__ src, T* __restrict__ dst, int64_t ldd, int col0, int Nb, int H,
+                                       int W, int C) {
+  const int c8 = C / 8;
+  const int64_t plane = (int64_t)Nb * H * W;
+  GSTRIDE(i, 4 * plane * c8) {
+    const int64_t m = i / c8;
+    const int c = (int)(i - m * c8) * 8;
+    const int ox = (int)(m % (2 * W));
+    const int64_t t = m / (2 * W);
+    const int oy = (int)(t % (2 * H));
+    const int64_t n = t / (2 * H);
+    const int64_t s = (2 * (oy & 1) + (ox & 1)) * plane + (n * H + (oy >> 1)) * W + (ox >> 1);
+    *reinterpret_cast<u32x4*>(dst + m * ldd + col0 + c) = *reinterpret_cast<const u32x4*>(src + s * C + c);
+  }
+}
+
 // NCHW (T or f32) -> token-major [Nb, HW, Cpad] T (channels >= C zero filled), value * scale (or * *scale_dev)
 template <typename T>
 __global__ void nchw_to_nhwc_kernel(const void* __restrict__ src, int src_f32, T* __restrict__ dst, int Nb, int C,
@@ -792,6 +811,17 @@ int launch_copy_cols(int dtype, const void* src, int64_t lds, void* dst, int64_t
   SMI_CHECK(C % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && col0 % 8 == 0, "copy_cols: 16-byte alignment");
   const int grid = ew_grid((int64_t)M * C / 8);
   hipLaunchKernelGGL(copy_cols_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)src, lds, (f16*)dst, ldd, col0, (int64_t)M, C);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int launch_copy_cols_phase(int dtype, const void* src, void* dst, int64_t ldd, int col0, int Nb, int H, int W, int C,
+                           hipStream_t stream) {
+  (void)dtype;
+  SMI_CHECK(C % 8 == 0 && ldd % 8 == 0 && col0 % 8 == 0, "copy_cols_phase: 16-byte alignment");
+  SMI_CHECK(Nb > 0 && H > 0 && W > 0 && col0 >= 0 && col0 + C <= ldd, "copy_cols_phase: bad shape");
+  const int grid = ew_grid((int64_t)4 * Nb * H * W * C / 8);
+  hipLaunchKernelGGL(copy_cols_phase_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)src, (f16*)dst, ldd, col0, Nb, H,
+                     W, C);
   SMI_HIP(hipGetLastError());
   return 0;
 }

@@ -64,6 +64,9 @@ struct Ten {
   // of the FORWARD only (xa)
   int64_t bskip = 0;
   bool ng = false;
+  // phase-major output of an up-sampler conv: p holds four planes [n, H/2, W/2, cols], plane 2 a + b the pixels
+  // (2 i + a, 2 j + b).  Only concat reads it (as its first part); g is in ordinary row order
+  bool phase = false;
   bool f32g = false;  // the context of a pass that differentiates it: its gradient is summed in fp32 in the caller's buffer
   float gmul = 1.f;  // the stored gradient g is gmul x the (loss-scaled) gradient; a power of two, 1 but for row vectors
 };
@@ -91,6 +94,8 @@ struct Lin {
 struct Conv {
   const void* Wp = nullptr;   // forward pack [Cout][9*Cin]
   const void* Wg = nullptr;   // gradient pack [Cin][9*Cout]
+  const void* Wph = nullptr;  // mode 2 without an adaptor, where the model asks for it: phase pack [4][Cout][4*Cin]
+  bool phase = false;         // ... and that it was packed (Wph itself may be offset 0 of a dry run)
   const void* b = nullptr;
   int Cin = 0, Cout = 0;
   int mode = 0;  // 0 stride 1, 1 stride-2 downsample, 2 nearest-2x upsample + conv
@@ -462,7 +467,15 @@ struct smi_engine {
   // the next tensor created is the current block's output and must outlive the scratch regions (a skip connection)
   void keep_next_output() { persist_next = in_block; }
 
+  // the phase-major tensor (Ten::phase) no concat has read yet.  Every op creates its output through new_ten, so an op other
+  // than that concat running while one is live is caught here instead of misreading the four planes as rows
+  Ten* phase_live = nullptr;
   Ten* new_ten(int64_t rows, int cols, int n = 0, int H = 0, int W = 0, size_t elt = 0) {
+    if (phase_live && !err) {
+      set_error("a phase-major up-sampler output (%d x %d x %d) reached an op other than the concat of the next up block",
+                phase_live->H, phase_live->W, phase_live->cols);
+      err = true;
+    }
     tens->emplace_back();
     Ten* t = &tens->back();
     t->rows = rows;
@@ -561,6 +574,7 @@ struct smi_engine {
   // (engine.hip, next to their kernels)
   void transpose_into(const void* src, void* dst, int R, int C, int ldd, int col0, bool packing = true);
   void pack_conv_into(const void* src, void* dst, int Cout, int Cin, int mode, int pad = 0);
+  void pack_conv_phase_into(const void* src, void* dst, int Cout, int Cin);  // phase pack [4][Cout][4 * Cin] of a mode-2 layer
 
   void attach_lora(Lin& L, const std::vector<std::string>& targets) {
     // targets: the module paths fused into this GEMM (1, 2 (k|v) or 3 (q|k|v)); all adapted or none
@@ -744,7 +758,8 @@ struct smi_engine {
     }
     return b;
   }
-  Conv make_conv(const std::string& name, int Cin, int Cout, int mode, bool grad_pack) {
+  // phase: a mode-2 layer whose output only a concat reads (the UNets' up-samplers) may run as four 2x2 phase convs
+  Conv make_conv(const std::string& name, int Cin, int Cout, int mode, bool grad_pack, bool phase = false) {
     Conv c;
     c.Cin = Cin;
     c.Cout = Cout;
@@ -760,6 +775,13 @@ struct smi_engine {
       void* wg = pack_alloc((size_t)Cout * Cin * 9 * esz());
       pack_conv_into(Wd(name + ".weight"), wg, Cout, Cin, mode == 1 ? 1 : 2);
       c.Wg = wg;
+    }
+    // an adaptor keeps the layer on the 3x3 form: its xa / delta / weight-gradient jobs are written for that one
+    if (phase && mode == 2 && c.rank == 0 && upconv_phase_on()) {
+      void* wph = pack_alloc((size_t)16 * Cout * Cin * esz());
+      pack_conv_phase_into(Wd(name + ".weight"), wph, Cout, Cin);
+      c.Wph = wph;
+      c.phase = true;
     }
     return c;
   }
@@ -1179,8 +1201,20 @@ struct smi_engine {
       run_gemm(SMI_PROF_LORA, g, 2.0 * g.M * c.rank * g.K, 0.0, false, "conv3x3 xa");
       p.with_lora(xa, c.rows_pad, lora_up + c.off_up, c.rank, 0, lscale, (int)y->arow0);
     }
-    run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 2.0 * ((double)x->rows * c.Cin + (double)p.N * p.K + (double)p.M * p.N), true,
-             "conv3x3");
+    if (c.phase && !rowvec && !res && upconv_phase_takes(Hin * Win)) {
+      // four 2x2 phase convs on the low-res grid (4/9 of the FLOPs, which is what the profile is told), one output plane
+      // each: y is phase-major and the next op -- the up path's concat -- puts the rows back in order as it copies them
+      for (int ph = 0; ph < 4; ++ph) {
+        const GemmParams q = conv2x2_phase(dtype, x->p, c.Wph, y->p, x->n, Hin, Win, c.Cin, c.Cout, ph).with_bias(c.b);
+        run_gemm(SMI_PROF_CONV, q, gemm_flops(q), 2.0 * ((double)x->rows * c.Cin + (double)q.N * q.K + (double)q.M * q.N), true,
+                 "conv3x3 phase");
+      }
+      y->phase = true;
+      phase_live = y;
+    } else {
+      run_gemm(SMI_PROF_CONV, p, gemm_flops(p), 2.0 * ((double)x->rows * c.Cin + (double)p.N * p.K + (double)p.M * p.N), true,
+               "conv3x3");
+    }
     y->ng = lon || x->ng || (res && res->ng) || (rowvec && rowvec->ng);
     if (saving && y->ng) {
       const Conv* cp = &c;
@@ -1259,8 +1293,13 @@ struct smi_engine {
   }
 
   Ten* concat(Ten* a, Ten* b) {
+    if (a->phase && a == phase_live) phase_live = nullptr;  // the one reader of a phase-major tensor (new_ten checks)
     Ten* y = new_ten(a->rows, a->cols + b->cols, a->n, a->H, a->W);
-    RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, a->p, a->cols, y->p, y->cols, 0, (int)a->rows, a->cols, stream));
+    if (a->phase)
+      RUNP(SMI_PROF_ELEM, 0.0, 0.0,
+           launch_copy_cols_phase(dtype, a->p, y->p, y->cols, 0, a->n, a->H / 2, a->W / 2, a->cols, stream));
+    else
+      RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, a->p, a->cols, y->p, y->cols, 0, (int)a->rows, a->cols, stream));
     RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_copy_cols(dtype, b->p, b->cols, y->p, y->cols, a->cols, (int)a->rows, b->cols, stream));
     y->ng = a->ng || b->ng;
     if (saving && y->ng) {

@@ -44,7 +44,44 @@ __global__ void pack_conv_kernel(const T* __restrict__ src, T* __restrict__ dst,
     }
   }
 }
+// conv weight [Cout, Cin, 3, 3] of a nearest-2x up-sampler -> phase pack dst[2 a + b][co][(2 p + q) * Cin + ci]: on the 2x
+// grid, output row 2 i + a sees low-res row i - 1 + a + p through the 3x3 rows {0} | {1, 2} (a = 0) or {0, 1} | {2} (a = 1)
+// for p = 0 | 1; columns alike.  The up to four weights are summed in fp32 and rounded once.
+template <typename T>
+__global__ void pack_conv_phase_kernel(const T* __restrict__ src, T* __restrict__ dst, int Cout, int Cin) {
+  const int64_t total = (int64_t)16 * Cout * Cin;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+    const int ci = (int)(i % Cin);
+    const int tap = (int)((i / Cin) % 4);
+    const int co = (int)((i / (4 * (int64_t)Cin)) % Cout);
+    const int ph = (int)(i / (4 * (int64_t)Cin * Cout));
+    const int a = ph >> 1, b = ph & 1, p = tap >> 1, q = tap & 1;
+    const int ky0 = p == 0 ? 0 : 1 + a, ky1 = p == 0 ? a : 2;
+    const int kx0 = q == 0 ? 0 : 1 + b, kx1 = q == 0 ? b : 2;
+    const T* w = src + ((int64_t)co * Cin + ci) * 9;
+    float s = 0.f;
+    for (int ky = ky0; ky <= ky1; ++ky)
+      for (int kx = kx0; kx <= kx1; ++kx) s += to_f(w[ky * 3 + kx]);
+    dst[i] = from_f<T>(s);
+  }
+}
 }  // namespace
+
+int smi::launch_pack_conv_phase(int dtype, const void* src, void* dst, int Cout, int Cin, hipStream_t stream) {
+  const int64_t total = (int64_t)16 * Cout * Cin;
+  const int grid = (int)std::min<int64_t>((total + 255) / 256, 8192);
+  if (dtype == DT_F16)
+    hipLaunchKernelGGL(pack_conv_phase_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)src, (f16*)dst, Cout, Cin);
+  else
+    hipLaunchKernelGGL(pack_conv_phase_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)src, (bf16*)dst, Cout, Cin);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+void smi_engine::pack_conv_phase_into(const void* src, void* dst, int Cout, int Cin) {
+  if (dry || err || !src) return;
+  ++pack_launches;
+  if (launch_pack_conv_phase(dtype, src, dst, Cout, Cin, stream) != 0) err = true;
+}
 
 void smi_engine::transpose_into(const void* src, void* dst, int R, int C, int ldd, int col0, bool packing) {
   if (dry || err || !src) return;

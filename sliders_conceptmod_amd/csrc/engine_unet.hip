@@ -255,7 +255,8 @@ struct UNet : Model {
                                             cfg.num_heads[L - 1 - i], cfg.transformer_layers[L - 1 - i]));
       }
       lv.has_samp = i != L - 1;
-      if (lv.has_samp) lv.samp = e.make_conv(b + ".upsamplers.0.conv", out_ch, out_ch, 2, true);
+      // (phase form: the up-sampler's output goes to the next level's first concat and nowhere else, see forward)
+      if (lv.has_samp) lv.samp = e.make_conv(b + ".upsamplers.0.conv", out_ch, out_ch, 2, true, true);
     }
     norm_out = e.make_norm("conv_norm_out", boc[0], 1e-5f, G);
     conv_out = e.make_conv("conv_out", boc[0], cfg.out_channels, 0, false);
@@ -424,6 +425,7 @@ struct UNet : Model {
     e.tens->clear();
     e.saving = save;
     e.grad_src = false;
+    e.phase_live = nullptr;
     const int H = lat_h, Wd_ = lat_w, HW = H * Wd_;
     const int C0 = cfg.block_out_channels[0];
     const int ted = C0 * 4;

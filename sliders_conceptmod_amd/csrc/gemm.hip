@@ -97,7 +97,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmParams p) {
     if (CONV) {
       const int tap = k0 / p.Cin;
       const int c0 = k0 - tap * p.Cin;
-      const int ky = tap / 3, kx = tap - ky * 3;
+      int ky, kx;
+      conv_tap_yx(p, tap, ky, kx);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         int iy, ix;
@@ -109,8 +110,8 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(GemmParams p) {
           ok = (ty >= 0) && (tx >= 0) && (iy * p.stride == ty) && (ix * p.stride == tx) && (iy < p.Hin) &&
                (ix < p.Win);
         } else {
-          iy = crow[i].oy * p.stride + ky - p.pad;
-          ix = crow[i].ox * p.stride + kx - p.pad;
+          iy = crow[i].oy * p.stride + ky + p.tap_oy;
+          ix = crow[i].ox * p.stride + kx + p.tap_ox;
           if (p.upsample) {
             ok = (iy >= 0) && (ix >= 0) && (iy < 2 * p.Hin) && (ix < 2 * p.Win);
             iy >>= 1;
@@ -489,8 +490,12 @@ int launch_candidate(const GemmParams& p, GemmTile cand, hipStream_t stream) {
 }
 GemmTile tuned_choice(const GemmParams& p, hipStream_t stream) {
   TuneKey key;
+  // (the tap grid shares the gather slot, 0 for the 3x3 grid with origin -pad, so that persisted 18-integer keys stay valid)
+  const int taps = p.conv && (p.tap_w != 3 || p.tap_oy != -p.pad || p.tap_ox != -p.pad)
+                       ? 16 * (p.tap_w * 64 + (p.tap_oy + 4) * 8 + (p.tap_ox + 4))
+                       : 0;
   const int kv[18] = {(int)p.dtype, (int)p.conv, p.M, p.N, p.K, (int)(p.conv ? p.Cin : p.lda),
-                      (int)(p.stride * 4 + p.upsample * 2 + p.transposed), (int)(p.res != nullptr), p.lora_r,
+                      (int)(p.stride * 4 + p.upsample * 2 + p.transposed + taps), (int)(p.res != nullptr), p.lora_r,
                       (int)(p.geglu_out != nullptr), (int)p.out_f32, (int)(p.bias != nullptr),
                       (int)(p.rowvec != nullptr), (int)(p.conv ? p.Hin * 65536 + p.Win : p.ldc),
                       (int)(p.res ? p.ldr : 0), p.lora_seg, p.pad, (int)(p.res == p.C) + 2 * (int)(p.lora_r > 0 && p.up_sn == 1)};
@@ -680,6 +685,25 @@ int launch_splitk(const GemmParams& p, int S, GemmTile slice, hipStream_t stream
 }
 }  // namespace
 
+namespace {
+int g_upconv_phase_sel = -1;
+}
+void set_upconv_phase(int on) { g_upconv_phase_sel = on; }
+bool upconv_phase_on() {
+  static const bool env_on = []() { const char* e = getenv("SMI_UPCONV_PHASE"); return !(e && !strcmp(e, "0")); }();
+  return g_upconv_phase_sel < 0 ? env_on : g_upconv_phase_sel != 0;
+}
+// Four launches for one only pay where the one is long: below 32 x 32 low-res pixels per sample a pre-roll forward at UNet
+// batch 2 turns one 20-90 us launch into four of about the same latency (SD-1.4 pre-roll 175.6 -> 177.8 ms with every
+// up-sampler in the phase form).  The floor is on the SAMPLE's map, never on the launch's rows, so that a sample's bits do
+// not depend on the batch it travels in.
+bool upconv_phase_takes(int lowres_pixels) {
+  if (!upconv_phase_on()) return false;
+  if (g_upconv_phase_sel > 0) return true;
+  static const int floor_px = []() { const char* e = getenv("SMI_UPCONV_PHASE_MIN_PIXELS"); return e ? atoi(e) : 1024; }();
+  return lowres_pixels >= floor_px;
+}
+
 void set_gemm_scratch(void* ws, size_t bytes) {
   t_scratch = ws;
   t_scratch_bytes = ws ? bytes : 0;
@@ -689,8 +713,10 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
   SMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
   SMI_CHECK(!p.geglu_out || gemm_geglu_supported(p), "gemm: fused GEGLU not available for this shape/layout");
   if (p.conv) {
-    SMI_CHECK(p.K == 9 * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
+    SMI_CHECK(p.K == p.tap_w * p.tap_w * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
               "conv: inconsistent geometry");
+    SMI_CHECK(p.tap_w == 3 || (p.tap_w == 2 && p.stride == 1 && !p.upsample && !p.transposed),
+              "conv: a %d-wide tap grid (2 takes a plain stride-1 conv only)", p.tap_w);
   }
   // SMI_SPLITK_DEBUG (tools/bench_splitk.py): slice count and slice kernel (a tile code) of THIS call from SMI_SPLITK_S / _V
   static const bool splitk_debug = getenv("SMI_SPLITK_DEBUG") != nullptr;
@@ -759,7 +785,8 @@ int launch_v1(const GemmParams& p, hipStream_t stream) {
   SMI_CHECK(p.lora_seg % 4 == 0, "gemm: lora_seg %% 4 != 0");
   SMI_CHECK(p.res == nullptr || p.ldr % 4 == 0, "gemm: ldr %% 4 != 0");
   if (p.conv) {
-    SMI_CHECK(p.Cin % 64 == 0 && p.K == 9 * p.Cin, "conv: Cin %% 64 != 0 or K != 9*Cin (Cin=%d K=%d)", p.Cin, p.K);
+    SMI_CHECK(p.Cin % 64 == 0 && p.K == p.tap_w * p.tap_w * p.Cin, "conv: Cin %% 64 != 0 or K != taps*Cin (Cin=%d K=%d)",
+              p.Cin, p.K);
     SMI_CHECK(p.M == p.Nb * p.Hout * p.Wout, "conv: M != Nb*Hout*Wout");
     SMI_CHECK((int64_t)p.Nb * p.Hin * p.Win * p.Cin * 2 < 0xFFFFFFF0ll, "conv: input larger than 4 GiB");
     SMI_CHECK(p.stride == 1 || p.stride == 2, "conv: stride");

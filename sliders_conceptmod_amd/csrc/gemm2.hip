@@ -186,12 +186,14 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
     if (CONV) {
       const int tap = k0 / p.Cin;
       const int c0 = k0 - tap * p.Cin;
-      const int ky = tap / 3, kx = tap - ky * 3;
+      int ky, kx;
+      conv_tap_yx(p, tap, ky, kx);
       if (conv_fast) {
-        const int toff = ((ky - 1) * p.Win + (kx - 1)) * p.Cin + c0;  // wave-uniform
+        const int dy = ky + p.tap_oy, dx = kx + p.tap_ox;  // wave-uniform
+        const int toff = (dy * p.Win + dx) * p.Cin + c0;
 #pragma unroll
         for (int j = 0; j < A_INSTR; ++j) {
-          const int iy = c_oy[j] + ky - 1, ix = c_ox[j] + kx - 1;
+          const int iy = c_oy[j] + dy, ix = c_ox[j] + dx;
           const bool ok = ((unsigned)iy < (unsigned)p.Hin) && ((unsigned)ix < (unsigned)p.Win);
           const void* src = ok ? (const void*)(a_ptr[j] + toff) : (const void*)zero;
           glds16(src, As + (wave * A_INSTR + j) * 1024);
@@ -208,8 +210,8 @@ __global__ __launch_bounds__((NL >= 2 ? 4 : 2) * WM * 64) void gemm_glds_kernel(
           ok = (ty >= 0) && (tx >= 0) && (iy * p.stride == ty) && (ix * p.stride == tx) && (iy < p.Hin) &&
                (ix < p.Win);
         } else {
-          iy = c_oy[j] * p.stride + ky - p.pad;
-          ix = c_ox[j] * p.stride + kx - p.pad;
+          iy = c_oy[j] * p.stride + ky + p.tap_oy;
+          ix = c_ox[j] * p.stride + kx + p.tap_ox;
           if (p.upsample) {
             ok = (iy >= 0) && (ix >= 0) && (iy < 2 * p.Hin) && (ix < 2 * p.Win);
             iy >>= 1;

@@ -83,8 +83,9 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx) {
-            const bool ok = (unsigned)(oy + ky - 1) < (unsigned)p.Hin && (unsigned)(ox + kx - 1) < (unsigned)p.Win;
-            mk |= ok ? (1 << (3 * ky + kx)) : 0;
+            const bool ok = ky < p.tap_w && kx < p.tap_w && (unsigned)(oy + ky + p.tap_oy) < (unsigned)p.Hin &&
+                            (unsigned)(ox + kx + p.tap_ox) < (unsigned)p.Win;
+            mk |= ok ? (1 << (p.tap_w * ky + kx)) : 0;
           }
         amask[h][j] = mrow < p.M ? mk : 0;
         aS[h][j] = reinterpret_cast<const T*>(p.A) + (int64_t)m * p.Cin + chunk * 8;
@@ -104,8 +105,8 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
   // dst: half-tile base + (2 wave + j) KiB
   auto stage_a = [&](int h, unsigned char* dst) {
     if (CONV) {
-      const int toff = ((kyA[h] - 1) * p.Win + (kxA[h] - 1)) * p.Cin + cA[h];
-      const int tap = kyA[h] * 3 + kxA[h];
+      const int toff = ((kyA[h] + p.tap_oy) * p.Win + (kxA[h] + p.tap_ox)) * p.Cin + cA[h];
+      const int tap = kyA[h] * p.tap_w + kxA[h];
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         const void* src = ((amask[h][j] >> tap) & 1) ? (const void*)(aS[h][j] + toff) : (const void*)g_zero_page;
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(512) void gemm_8ph_kernel(GemmParams p) {
       cA[h] += BK;
       if (cA[h] == p.Cin) {
         cA[h] = 0;
-        if (++kxA[h] == 3) {
+        if (++kxA[h] == p.tap_w) {
           kxA[h] = 0;
           ++kyA[h];
         }
@@ -314,7 +315,7 @@ int launch_t(const GemmParams& p, hipStream_t stream) {
 bool gemm3_supported(const GemmParams& p) {
   if (!gemm2_supported(p)) return false;
   if (p.conv && (p.stride != 1 || p.upsample || p.transposed || p.Cin % BK != 0 || p.Hout != p.Hin || p.Wout != p.Win ||
-                 p.K != 9 * p.Cin || p.M != p.Nb * p.Hout * p.Wout))
+                 (p.tap_w != 2 && p.tap_w != 3) || p.K != p.tap_w * p.tap_w * p.Cin || p.M != p.Nb * p.Hout * p.Wout))
     return false;
   if (p.K % BK != 0 || p.N % 8 != 0 || p.lora_seg % 8 != 0) return false;
   if (p.out_f32 && p.ldc % 4 != 0) return false;

@@ -43,12 +43,18 @@ constexpr int SMEM4 = 2 * KBUF;          // 144 KiB
 // CONV = implicit-GEMM 3x3 / stride 1 / pad 1 (as gemm3.hip): K runs over (tap, channel); an A row is an output pixel,
 // its source for a K-tile is the pixel's own address + a wave-uniform tap offset, or the zero page when the tap falls
 // outside the image (one 9-bit mask per lane and A unit, for the current and for the next output tile).
-// MODE: 0 dense, 1 conv, 2 dense with the fused GEGLU epilogue, 3 conv with the 2x up-sampling folded into the gather
+// MODE: 0 dense, 1 conv, 2 dense with the fused GEGLU epilogue, 3 conv with the 2x up-sampling folded into the gather,
+// 4 conv on the 2x2 tap grid of an up-sampler's phase conv (kernels.h conv2x2_phase)
 // (separate instantiations: each keeps only its own epilogue,
 // which is what keeps the 160 accumulators + epilogue temporaries inside 256 registers)
 template <typename T, int MODE>
 __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
-  constexpr bool CONV = MODE == 1;
+  constexpr bool CONV = MODE == 1 || MODE == 4;
+  // tap grid of the plain conv gather: 3 x 3 with origin (-1, -1), or (MODE 4) the 2 x 2 grid of an up-sampler's phase conv
+  // with the launch's origin.  Compile-time, so that the 3 x 3 instantiation is the code it was before the 2 x 2 grid existed
+  // (with the grid as launch parameters it ran 8-10 % slower inside the step: 438 -> 482 us at 16384 x 1280 x 11520)
+  constexpr int TW = MODE == 4 ? 2 : 3;
+  const int toy = MODE == 4 ? p.tap_oy : -1, tox = MODE == 4 ? p.tap_ox : -1;
   constexpr bool GEGLU = MODE == 2;
   constexpr bool UPS = MODE == 3;  // 3x3 conv on the nearest-2x up-sampled input (the UNet's up-samplers), Wout % 64 == 0
   typedef typename TT<T>::v8 v8;
@@ -127,11 +133,11 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
       const int oy = rem / p.Win, ox = rem - oy * p.Win;
       int mk = 0;
 #pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
+      for (int ky = 0; ky < TW; ++ky)
 #pragma unroll
-        for (int kx = 0; kx < 3; ++kx) {
-          const bool ok = (unsigned)(oy + ky - 1) < (unsigned)p.Hin && (unsigned)(ox + kx - 1) < (unsigned)p.Win;
-          mk |= ok ? (1 << (3 * ky + kx)) : 0;
+        for (int kx = 0; kx < TW; ++kx) {
+          const bool ok = (unsigned)(oy + ky + toy) < (unsigned)p.Hin && (unsigned)(ox + kx + tox) < (unsigned)p.Win;
+          mk |= ok ? (1 << (TW * ky + kx)) : 0;
         }
       am[u] = mk;
     }
@@ -182,8 +188,8 @@ __global__ __launch_bounds__(512) void gemm_5ph_kernel(GemmParams p) {
       glds16(ok ? (const void*)(base + vo) : (const void*)g_zero_page, buf + u * UNIT + ldsw);
     } else if (CONV) {
       const int tap = (tt * cpt_magic) >> 16;
-      const int ky = (tap * 11) >> 5, kx = tap - 3 * ky;
-      const int64_t toff = ((int64_t)((ky - 1) * p.Win + (kx - 1)) * p.Cin + (tt - tap * cpt) * BK) * 2;
+      const int ky = TW == 2 ? tap >> 1 : (tap * 11) >> 5, kx = tap - TW * ky;
+      const int64_t toff = ((int64_t)((ky + toy) * p.Win + (kx + tox)) * p.Cin + (tt - tap * cpt) * BK) * 2;
       const int mk = nx ? am_nxt[u] : am_cur[u];
       const char* src = (nx ? a_nxt : a_cur) + u * a_unit + toff + voffA;
       glds16(((mk >> tap) & 1) ? (const void*)src : (const void*)g_zero_page, buf + u * UNIT + ldsw);
@@ -558,9 +564,12 @@ bool gemm4_supported(const GemmParams& p) {
   if (p.geglu_out && (p.conv || p.out_f32 || p.res || p.rowvec || p.lora_r > 0 ||
                       (reinterpret_cast<uintptr_t>(p.geglu_out) & 15) != 0))
     return false;
-  if (p.conv && (p.stride != 1 || p.pad != 1 || p.transposed || p.Cin % BK != 0 || p.K != 9 * p.Cin ||
+  if (p.conv && (p.stride != 1 || p.pad != 1 || p.transposed || p.Cin % BK != 0 || p.K != p.tap_w * p.tap_w * p.Cin ||
                  p.M != p.Nb * p.Hout * p.Wout))
     return false;
+  // the plain conv mode takes the 3x3 grid and the 2x2 grid of a phase conv; the up-sampling gather knows the 3x3 grid only
+  if (p.conv && p.tap_w != 3 && (p.tap_w != 2 || p.upsample)) return false;
+  if (p.conv && p.upsample && (p.tap_oy != -1 || p.tap_ox != -1)) return false;
   if (p.conv && !p.upsample && (p.Hout != p.Hin || p.Wout != p.Win)) return false;
   if (p.conv && p.upsample && (p.Hout != 2 * p.Hin || p.Wout != 2 * p.Win || p.Wout % 64 != 0)) return false;
   if (p.M % BM != 0 || p.N % BN != 0 || p.K % BK != 0 || p.K < 2 * BK) return false;
@@ -572,15 +581,17 @@ bool gemm4_supported(const GemmParams& p) {
 }
 
 int launch_gemm4(const GemmParams& p, hipStream_t stream) {
-  const int mode = p.conv ? (p.upsample ? 3 : 1) : (p.geglu_out ? 2 : 0);
+  const int mode = p.conv ? (p.upsample ? 3 : (p.tap_w == 2 ? 4 : 1)) : (p.geglu_out ? 2 : 0);
   if (p.dtype == DT_F16)
     return mode == 1   ? launch_t<f16, 1>(p, stream)
            : mode == 2 ? launch_t<f16, 2>(p, stream)
            : mode == 3 ? launch_t<f16, 3>(p, stream)
+           : mode == 4 ? launch_t<f16, 4>(p, stream)
                        : launch_t<f16, 0>(p, stream);
   return mode == 1   ? launch_t<bf16, 1>(p, stream)
          : mode == 2 ? launch_t<bf16, 2>(p, stream)
          : mode == 3 ? launch_t<bf16, 3>(p, stream)
+         : mode == 4 ? launch_t<bf16, 4>(p, stream)
                      : launch_t<bf16, 0>(p, stream);
 }
 

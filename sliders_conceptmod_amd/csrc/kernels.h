@@ -10,7 +10,8 @@ namespace smi {
 
 // ---------------------------------------------------------------------------------------------------------------
 // C[M,N] = A[M,K] * W[N,K]^T  (+ epilogue), W rows K-contiguous (torch nn.Linear layout).
-// With conv != 0, A is gathered on the fly from an NHWC image (implicit GEMM, K = 9*Cin ordered (kh,kw,ci)).
+// With conv != 0, A is gathered on the fly from an NHWC image (implicit GEMM, K = 9*Cin ordered (kh,kw,ci); 4*Cin on the
+// 2x2 tap grid of an up-sampler's phase conv).
 // Epilogue (all fp32, one rounding at the store):  + bias[n] + rowvec[m / rows_per_vec][n]
 //     + lora_scale * sum_q xa[m][q] * up[n][q] + res[m][n]
 // ---------------------------------------------------------------------------------------------------------------
@@ -57,6 +58,9 @@ struct GemmParams {
   // split-K (internal to launch_gemm, gemm2 kernels only): the workgroups of slice s accumulate K-tiles
   // [s nk / ksplit, (s + 1) nk / ksplit) and store fp32 partials to C + s * M * ldc (out_f32 form, no epilogue)
   int ksplit = 0;
+  // conv tap grid: tap_w x tap_w taps (3, or 2 for a phase conv of an up-sampler), K = tap_w^2 * Cin ordered (ky, kx, ci);
+  // tap (0, 0) of output pixel (oy, ox) reads input pixel (oy * stride + tap_oy, ox * stride + tap_ox): -pad for the 3x3 layers
+  int tap_w = 3, tap_oy = -1, tap_ox = -1;
 
   // epilogue setters, chained onto one of the constructors below
   GemmParams& f32_out() { out_f32 = 1; return *this; }
@@ -124,9 +128,15 @@ inline GemmParams conv3x3_geom(int dtype, const void* in, const void* w, void* o
   p.Wout = Wout;
   p.stride = stride;
   p.pad = pad;
+  p.tap_oy = p.tap_ox = -pad;
   p.upsample = upsample;
   p.transposed = transposed;
   return p;
+}
+// (ky, kx) of filter tap `tap` on the launch's tap grid (tap_w is 2 or 3)
+__host__ __device__ inline void conv_tap_yx(const GemmParams& p, int tap, int& ky, int& kx) {
+  ky = p.tap_w == 2 ? tap >> 1 : tap / 3;
+  kx = tap - ky * p.tap_w;
 }
 // forward conv of a layer: mode 0 stride 1, 1 stride 2, 2 nearest-2x upsample then stride 1
 inline int conv3x3_out(int in, int mode) { return mode == 1 ? (in + 1) / 2 : (mode == 2 ? in * 2 : in); }
@@ -134,6 +144,20 @@ inline GemmParams conv3x3_fwd(int dtype, const void* in, const void* w, void* ou
                               int Cout, int mode = 0, int pad = 1) {
   return conv3x3_geom(dtype, in, w, out, Nb, Hin, Win, Cin, Cout, conv3x3_out(Hin, mode), conv3x3_out(Win, mode),
                       mode == 1 ? 2 : 1, pad, mode == 2 ? 1 : 0, 0);
+}
+// Phase 2 a + b (a, b in {0, 1}) of a mode-2 layer: the output pixels (2 i + a, 2 j + b) of nearest-2x + 3x3 / pad 1 are a
+// same-size 2x2 conv over the low-res input with tap origin (a - 1, b - 1) and summed filters.  wph: the layer's phase pack
+// [4][Cout][4 * Cin] (16-bit), out: the phase-major result [4][Nb, Hin, Win, Cout] (16-bit) -- this launch fills plane `phase`
+inline GemmParams conv2x2_phase(int dtype, const void* in, const void* wph, void* out, int Nb, int Hin, int Win, int Cin,
+                                int Cout, int phase) {
+  const int64_t M = (int64_t)Nb * Hin * Win;
+  GemmParams p = conv3x3_geom(dtype, in, (const char*)wph + (int64_t)phase * Cout * 4 * Cin * 2,
+                              (char*)out + (int64_t)phase * M * Cout * 2, Nb, Hin, Win, Cin, Cout, Hin, Win, 1, 1, 0, 0);
+  p.K = 4 * Cin;
+  p.tap_w = 2;
+  p.tap_oy = (phase >> 1) - 1;
+  p.tap_ox = (phase & 1) - 1;
+  return p;
 }
 // gradient conv of that layer (Hin, Win, Cin, Cout are the FORWARD's): dy [Nb, Hout, Wout, Cout] against the gradient
 // pack wg [Cin][9 * Cout].  Mode 0: same size.  Mode 1: transposed stride 2, dx on the input grid.  Mode 2: dx on the 2x
@@ -299,6 +323,21 @@ int launch_gather_rows(int dtype, const void* src, const int* idx, void* out, in
 // copy [M, C] (src row stride lds) into dst columns [col0, col0+C) of a [M, ldd] tensor (concat / split)
 int launch_copy_cols(int dtype, const void* src, int64_t lds, void* dst, int64_t ldd, int col0, int M, int C,
                      hipStream_t stream);
+// the same copy from a phase-major up-sampler output (conv2x2_phase): src [4][Nb, H, W, C], plane 2 a + b holding the
+// pixels (2 i + a, 2 j + b), into columns [col0, col0 + C) of dst [Nb, 2 H, 2 W, ldd]
+int launch_copy_cols_phase(int dtype, const void* src, void* dst, int64_t ldd, int col0, int Nb, int H, int W, int C,
+                           hipStream_t stream);
+// Up-sampler convs as four 2x2 phase convs (SMI_UPCONV_PHASE, default 1).  Override of the parity tests, process-wide
+// like set_gn_select: -1 follows the environment, 0 / 1 force it off / on.  Read when an engine packs its weights and
+// again at every forward; a layer with an adaptor, and the VAE decoder, keep the 3x3 form either way.
+// phase pack [4][Cout][4 * Cin] of a torch filter [Cout, Cin, 3, 3] (engine.hip, next to the conv packs): per phase and
+// 2x2 tap the one, two or four 3x3 weights that land on the same low-res pixel, summed in fp32 and rounded once
+int launch_pack_conv_phase(int dtype, const void* src, void* dst, int Cout, int Cin, hipStream_t stream);
+void set_upconv_phase(int on);
+bool upconv_phase_on();
+// ... and for a layer whose input map has this many pixels per sample: by default only from SMI_UPCONV_PHASE_MIN_PIXELS
+// (1024 = 32 x 32) up; the override 1 takes every size (the parity tests run tiny maps)
+bool upconv_phase_takes(int lowres_pixels);
 int launch_nchw_to_nhwc(int dtype, const void* src, int src_f32, void* dst, int Nb, int C, int HW, int Cpad,
                         float scale, hipStream_t stream);
 // f32 NCHW -> T token-major, sample n multiplied by scale_dev[n] (backward entry: loss-scaled d_eps)

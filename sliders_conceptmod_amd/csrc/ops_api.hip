@@ -112,6 +112,27 @@ int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* 
                          .with_bias(bias),
                      (hipStream_t)stream);
 }
+// nearest-2x + 3x3 / pad 1 as the engine's phase form: pack, four 2x2 phase convs, un-shuffle (see include/smi.h)
+int smi_op_upconv_phase(int dtype, const void* in, const void* w, const void* bias, void* wph, void* planes, void* out, int nb,
+                        int h, int w_, int cin, int cout, int tile_code, int* ran_code, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!in || !w || !wph || !planes || !out || nb <= 0 || h <= 0 || w_ <= 0 || cin <= 0 || cout <= 0) {
+    set_error("smi_op_upconv_phase: bad arguments");
+    return -1;
+  }
+  if (int rc = launch_pack_conv_phase(dtype, w, wph, cout, cin, st)) return rc;
+  for (int ph = 0; ph < 4; ++ph) {
+    int ran = 0;
+    const GemmParams p = conv2x2_phase(dtype, in, wph, planes, nb, h, w_, cin, cout, ph).with_bias(bias);
+    if (int rc = launch_gemm_on_tile(p, tile_code, 0, &ran, st)) return rc;
+    if (ran_code) ran_code[ph] = ran;
+  }
+  return launch_copy_cols_phase(dtype, planes, out, cout, 0, nb, h, w_, cout, st);
+}
+int smi_set_upconv_phase(int on) {
+  set_upconv_phase(on);
+  return 0;
+}
 // dense [b, n, h, d] operands: every leading dimension is h * d
 static AttnParams attn_dense(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, int b, int h,
                              int nq, int nk, int d, float scale) {
