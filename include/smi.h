@@ -332,6 +332,30 @@ int smi_mmdit_create(const smi_mmdit_config* cfg, const smi_weight* weights, int
 int smi_mmdit_forward(smi_engine* e, int n, const float* sample, const float* timesteps, const void* ctx, const void* pooled,
                       const float* lora_down_flat, const float* lora_up_flat, const float* multipliers, float* out);
 
+/* ---- SD3 MMDiT with LoRA sites, differentiated to the LoRA parameters (training an SD3 slider: train_lora_sd3) ---------
+ * A trainable engine also keeps transposed copies of every Linear on the gradient path of both streams (the fused q|k|v,
+ * to_out.0 / to_add_out, ff.net.0.proj, ff.net.2, proj_out; the modulation Linears, the embedders and norm_out.linear get
+ * none) and a second arena for ONE saved pass and its backward: workspace = [packed weights | arena 0 (no-grad passes) |
+ * arena 1], sized by a dry forward + backward; n_sites 0 is refused by name.
+ *   smi_mmdit_forward       runs on a trainable engine too and leaves a saved pass intact
+ *   smi_mmdit_forward_save  the arguments of smi_mmdit_forward and the same bits in out; the pass is kept for ONE backward
+ *   smi_mmdit_backward      d_out f32 [n, out_channels, h, w] (device): the gradient of `out`.  The gradients of the LoRA
+ *                           parameters are ADDED to d_lora_down_flat / d_lora_up_flat (f32, the layout of the flat parameter
+ *                           buffers).  One power-of-two loss scale per sample keeps the 16-bit gradients in range.  Nothing
+ *                           else is differentiated: not the latents, the context, the pooled embedding or temb (scale, shift
+ *                           and gate depend on temb alone and no site sits upstream of them).  The backward consumes the
+ *                           saved pass: without one it returns -4.  A pass saved with all multipliers 0 or NULL flat
+ *                           buffers, or NULL gradient buffers here: returns 0 and adds nothing. */
+int smi_mmdit_train_workspace_bytes(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h,
+                                    int w, size_t* bytes);
+int smi_mmdit_train_create(const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                           int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                           smi_engine** out);
+int smi_mmdit_forward_save(smi_engine* e, int n, const float* sample, const float* timesteps, const void* ctx,
+                           const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
+                           const float* multipliers, float* out);
+int smi_mmdit_backward(smi_engine* e, const float* d_out, float* d_lora_down_flat, float* d_lora_up_flat);
+
 /* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)
  *   ctx         T   [n, ctx_len, cross_attention_dim]
@@ -658,8 +682,8 @@ int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const v
                                 const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
                                 int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                                 int64_t lddk, int64_t lddv, float scale, void* stream);
-/* The MLP activations, kind 0 quick_gelu / 1 erf-gelu (CLIP) / 2 tanh-gelu (MMDiT; forward only): y = act(x) when y is
- * given (n % 8 == 0), dx = dy * act'(x) when dy is given (any n >= 1; kinds 0 and 1). */
+/* The MLP activations, kind 0 quick_gelu / 1 erf-gelu (CLIP) / 2 tanh-gelu (MMDiT): y = act(x) when y is given
+ * (n % 8 == 0), dx = dy * act'(x) when dy is given (any n >= 1). */
 int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream);
 int smi_op_groupnorm(int dtype, const void* x, const void* gamma, const void* beta, void* y, const void* dy, void* dx,
                      float* scratch, int nb, int hw, int c, int g, float eps, int silu, void* stream);
@@ -727,11 +751,20 @@ int smi_op_nchw_to_nhwc_scaled(int dtype, const float* src, void* dst, int nb, i
  *                   the split is the inverse and a or b may be NULL there; w % 8 == 0
  *   sd3_patchify    out T [n (h/p) (w/p), cin p p], columns (c, py, px), from latents f32 [n, cin, h, w]; cin p p % 64 == 0
  *   sd3_add_pos     y [n gh gw, d] = x + the centre-cropped gh x gw window of pos T [s s, d] (top (s - gh) / 2, left (s - gw) / 2)
- *   sd3_unpatchify  out f32 [n, cout, gh p, gw p] from rows T [n gh gw, p p cout], columns (py, px, c) */
+ *   sd3_unpatchify  out f32 [n, cout, gh p, gw p] from rows T [n gh gw, p p cout], columns (py, px, c)
+ * and the backwards to the activations (tests/test_mmdit_bwd_kernels_gpu.py); scale, shift and gate take no gradient:
+ *   adaln_modulate_bwd  dx [m, c] = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ add), g = dy (1 + scale),
+ *                   xhat = (x - mean) rstd from the forward's mean_rstd; add [m, c] is optional and may alias dx
+ *   gate_residual_bwd   df [m, c] = gate dy (the gradient of h is dy itself)
+ * pack and split are each other's backward. */
 int smi_op_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int m, int c,
                           int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, void* stream);
 int smi_op_gate_residual(int dtype, const void* h, const void* f, const void* mod, void* y, int64_t m, int c,
                          int rows_per_sample, int64_t ldm, int off_gate, void* stream);
+int smi_op_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const void* mod, const float* mean_rstd, const void* add,
+                              void* dx, int m, int c, int rows_per_sample, int64_t ldm, int off_scale, void* stream);
+int smi_op_gate_residual_bwd(int dtype, const void* dy, const void* mod, void* df, int64_t m, int c, int rows_per_sample,
+                             int64_t ldm, int off_gate, void* stream);
 int smi_op_joint_rows_pack(int dtype, const void* a, const void* b, void* joint, int n, int nx, int nc, int w, void* stream);
 int smi_op_joint_rows_split(int dtype, const void* joint, void* a, void* b, int n, int nx, int nc, int w, void* stream);
 int smi_op_sd3_patchify(int dtype, const float* latents, void* out, int n, int cin, int h, int w, int p, void* stream);

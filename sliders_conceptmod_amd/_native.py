@@ -195,6 +195,14 @@ _SIGS = {
                                    C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_mmdit_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 4 +
                           [C.POINTER(C.c_float), C.c_void_p]),
+    "smi_mmdit_train_workspace_bytes": (C.c_int, [C.POINTER(MMDiTConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int,
+                                                  C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_mmdit_train_create": (C.c_int, [C.POINTER(MMDiTConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                         C.POINTER(C.c_void_p)]),
+    "smi_mmdit_forward_save": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 4 +
+                               [C.POINTER(C.c_float), C.c_void_p]),
+    "smi_mmdit_backward": (C.c_int, [C.c_void_p] * 4),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -258,6 +266,9 @@ _SIGS = {
                                                                                        C.c_void_p]),
     "smi_op_gate_residual": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int,
                                                                       C.c_void_p]),
+    "smi_op_adaln_modulate_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 3 + [C.c_int64, C.c_int, C.c_void_p]),
+    "smi_op_gate_residual_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_int, C.c_int64, C.c_int,
+                                                                          C.c_void_p]),
     "smi_op_joint_rows_pack": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
     "smi_op_joint_rows_split": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 4 + [C.c_void_p]),
     "smi_op_sd3_patchify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),

@@ -77,11 +77,25 @@ __global__ void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* _
   }
 }
 
-// dx = dy * act'(x): KIND 0 quick_gelu (x sigmoid(1.702 x))' = s (1 + 1.702 x (1 - s)), KIND 1 erf-gelu (dgelu_f).  Whole
-// 8-packs vectorised; the n % 8 tail elements one thread each
+// (x sigmoid(w))' with w = 2u = c x (1 + a x^2): s + x s (1 - s) w', w' = c (1 + 3 a x^2).  Through t = exp(-|w|) <= 1, so that
+// nothing overflows for large |x| (exp(+w) would at x = -12) and 1 - s is formed without a subtraction (s -> 1 at large x):
+// s = 1 / (1 + t) or t / (1 + t) by the sign of w, s (1 - s) = t / (1 + t)^2
+__device__ __forceinline__ float dgelu_tanh_f(float x) {
+  const float x2 = x * x;
+  const float w = 1.5957691216057308f * x * __builtin_fmaf(0.044715f, x2, 1.f);
+  const float t = __expf(-fabsf(w));
+  const float r = 1.f / (1.f + t);
+  const float s = w >= 0.f ? r : t * r;
+  const float dw = 1.5957691216057308f * __builtin_fmaf(3.f * 0.044715f, x2, 1.f);
+  return __builtin_fmaf(x * dw, t * r * r, s);
+}
+
+// dx = dy * act'(x): KIND 0 quick_gelu (x sigmoid(1.702 x))' = s (1 + 1.702 x (1 - s)), KIND 1 erf-gelu (dgelu_f), KIND 2
+// tanh-gelu (dgelu_tanh_f).  Whole 8-packs vectorised; the n % 8 tail elements one thread each
 template <typename T, int KIND>
 __device__ __forceinline__ float dact_f(float v) {
   if (KIND == 1) return dgelu_f(v);
+  if (KIND == 2) return dgelu_tanh_f(v);
   const float s = 1.f / (1.f + __expf(-1.702f * v));
   return s * (1.f + 1.702f * v * (1.f - s));
 }
@@ -761,14 +775,14 @@ int launch_act(int dtype, const void* x, void* y, int64_t n, int kind, hipStream
   return 0;
 }
 int launch_act_bwd(int dtype, const void* x, const void* dy, void* dx, int64_t n, int kind, hipStream_t stream) {
-  SMI_CHECK(n >= 1 && (kind == 0 || kind == 1), "act bwd: n >= 1, kind 0 (quick_gelu) or 1 (gelu)");
+  SMI_CHECK(n >= 1 && kind >= 0 && kind <= 2, "act bwd: n >= 1, kind 0 (quick_gelu), 1 (gelu) or 2 (tanh gelu)");
   SMI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "act bwd: x, dy and dx must be 16-byte aligned");
   const int grid = ew_grid(n / 8 > 0 ? n / 8 : 1);
 #define L(TT_, K_) hipLaunchKernelGGL((act_bwd_kernel<TT_, K_>), dim3(grid), dim3(256), 0, stream, (const TT_*)x, (const TT_*)dy, (TT_*)dx, n)
   if (dtype == DT_F16) {
-    if (kind == 0) L(f16, 0); else L(f16, 1);
+    if (kind == 0) L(f16, 0); else if (kind == 1) L(f16, 1); else L(f16, 2);
   } else {
-    if (kind == 0) L(bf16, 0); else L(bf16, 1);
+    if (kind == 0) L(bf16, 0); else if (kind == 1) L(bf16, 1); else L(bf16, 2);
   }
 #undef L
   SMI_HIP(hipGetLastError());

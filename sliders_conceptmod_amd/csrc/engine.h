@@ -1327,7 +1327,7 @@ struct smi_engine {
     return y;
   }
 
-  // the CLIP MLP activation: kind 0 quick_gelu, 1 erf-gelu; 2 tanh-gelu (MMDiT feed-forward, no backward yet)
+  // the MLP activations: kind 0 quick_gelu, 1 erf-gelu (CLIP); 2 tanh-gelu (MMDiT feed-forward)
   Ten* act(Ten* x, int kind) {
     Ten* y = new_ten(x->rows, x->cols, x->n, x->H, x->W);
     RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_act(dtype, x->p, y->p, x->rows * x->cols, kind, stream));

@@ -1,11 +1,13 @@
 // The SD3 MMDiT engine (diffusers SD3Transformer2DModel, SD3-medium's family): patch embedding with the centre-cropped
 // position table, the conditioning vector temb = time MLP + pooled-text MLP, joint blocks -- an image stream and a context
 // stream, each under adaLN-Zero modulation of temb, meeting in ONE attention over the packed (image | context) sequence --
-// and the modulated output projection, un-patchified.  Forward only, on the op core (engine.h); Linear LoRA sites on the
-// attention projections at one multiplier per sample, as the CLIP text tower takes them.
+// and the modulated output projection, un-patchified.  On the op core (engine.h); Linear LoRA sites on the attention
+// projections at one multiplier per sample, as the CLIP text tower takes them.  An engine made by smi_mmdit_train_create also
+// saves a pass and differentiates it to the LoRA parameters (MMDiT::backward).
 //
 // The four ops this model adds to the core's (adaln, gate_residual, joint_pack, joint_split) are the free functions below:
-// each allocates its output and launches one kernel of mmdit.hip.  A backward adds its tape closure there.
+// each allocates its output, launches one kernel of mmdit.hip and, in a saved pass, pushes its backward on the tape when
+// its output depends on an adapted layer.  The modulation tensors depend on temb alone: they take no gradient.
 #include "engine.h"
 
 namespace {
@@ -17,6 +19,9 @@ struct ValArgs {
 __global__ void mmdit_set_vals_kernel(float* dst, ValArgs a, int n) {
   const int i = threadIdx.x;
   if (i < n) dst[i] = a.v[i];
+}
+const void* mod_row(const smi_engine& e, const Ten* mod, const Ten* x) {  // mod's row of x's first adapted sample
+  return (const char*)mod->p + (size_t)(x->n > 0 ? x->arow0 / (x->rows / x->n) : 0) * mod->cols * e.esz();
 }
 int upload_vals(smi_engine& e, float* dst, const float* host, int n, float div) {
   for (int i0 = 0; i0 < n; i0 += 64) {
@@ -38,6 +43,19 @@ Ten* adaln(smi_engine& e, Ten* x, Ten* mod, int off_scale, int off_shift) {
   RUNP(SMI_PROF_NORM, 0.0, 4.0 * x->rows * x->cols,
        launch_adaln_modulate(e.dtype, x->p, mod->p, y->p, st, (int)x->rows, x->cols, (int)(x->rows / x->n), mod->cols, off_scale,
                              off_shift, 1e-6f, e.stream));
+  y->ng = x->ng;
+  if (e.saving && y->ng) {
+    smi_engine* ep = &e;
+    e.tape.push_back([=]() {
+      smi_engine& e = *ep;
+      if (!y->g) return;
+      // the stream's residual gradient, when it is already in x's slot, rides in the same launch (add may equal dx)
+      const smi_engine::Slot gs = e.grad_slot(x);
+      RUNP(SMI_PROF_NORM, 0.0, 6.0 * e.MA(x) * x->cols,
+           launch_adaln_modulate_bwd(e.dtype, e.PA(x), y->g, mod_row(e, mod, x), st + x->arow0 * 2, gs.add, gs.out, (int)e.MA(x),
+                                     x->cols, (int)(x->rows / x->n), mod->cols, off_scale, e.stream));
+    });
+  }
   return y;
 }
 // h + gate f, gate at column off_gate of mod
@@ -46,6 +64,21 @@ Ten* gate_residual(smi_engine& e, Ten* h, Ten* f, Ten* mod, int off_gate) {
   RUNP(SMI_PROF_ELEM, 0.0, 6.0 * h->rows * h->cols,
        launch_gate_residual(e.dtype, h->p, f->p, mod->p, y->p, h->rows, h->cols, (int)(h->rows / h->n), mod->cols, off_gate,
                             e.stream));
+  y->ng = h->ng || f->ng;
+  if (e.saving && y->ng) {
+    smi_engine* ep = &e;
+    e.tape.push_back([=]() {
+      smi_engine& e = *ep;
+      if (!y->g) return;
+      if (f->ng)
+        e.into_slot(e.grad_slot(f), e.MA(f), f->cols, [&](void* df) {
+          RUNP(SMI_PROF_ELEM, 0.0, 4.0 * e.MA(f) * f->cols,
+               launch_gate_residual_bwd(e.dtype, y->g, mod_row(e, mod, f), df, e.MA(f), f->cols, (int)(f->rows / f->n), mod->cols,
+                                        off_gate, e.stream));
+        });
+      if (h->ng) e.accumulate(h, y->g);  // dh is dy itself
+    });
+  }
   return y;
 }
 // per sample the rows of a (image stream), then the rows of b (context stream)
@@ -53,6 +86,19 @@ Ten* joint_pack(smi_engine& e, Ten* a, Ten* b) {
   const int n = a->n, Nx = (int)(a->rows / n), Nc = (int)(b->rows / n);
   Ten* j = e.new_ten(a->rows + b->rows, a->cols, n, Nx + Nc, 1);
   RUNP(SMI_PROF_ELEM, 0.0, 4.0 * j->rows * j->cols, launch_joint_rows_pack(e.dtype, a->p, b->p, j->p, n, Nx, Nc, a->cols, e.stream));
+  j->ng = a->ng || b->ng;
+  if (e.saving && j->ng) {
+    smi_engine* ep = &e;
+    e.tape.push_back([=]() {  // the split of the gradient; a and b have this one consumer: their slots are fresh
+      smi_engine& e = *ep;
+      if (!j->g) return;
+      const int n0 = e.ad_first(j, Nx + Nc);
+      void* ga = a->ng ? e.grad_slot(a).out : nullptr;  // (outside the launch macro: a dry run allocates them too)
+      void* gb = b->ng ? e.grad_slot(b).out : nullptr;
+      RUNP(SMI_PROF_ELEM, 0.0, 4.0 * e.MA(j) * j->cols,
+           launch_joint_rows_split(e.dtype, j->g, ga, gb, n - n0, Nx, Nc, j->cols, e.stream));
+    });
+  }
   return j;
 }
 // the inverse; want_b false: the context rows are dropped (the last block)
@@ -62,6 +108,28 @@ void joint_split(smi_engine& e, Ten* j, int Nx, int Nc, Ten** a, Ten** b, bool w
   *b = want_b ? e.new_ten((int64_t)n * Nc, j->cols, n, Nc, 1) : nullptr;
   RUNP(SMI_PROF_ELEM, 0.0, 4.0 * j->rows * j->cols,
        launch_joint_rows_split(e.dtype, j->p, (*a)->p, want_b ? (*b)->p : nullptr, n, Nx, Nc, j->cols, e.stream));
+  (*a)->ng = j->ng;
+  if (*b) (*b)->ng = j->ng;
+  if (e.saving && j->ng) {
+    smi_engine* ep = &e;
+    Ten *ta = *a, *tb = *b;
+    e.tape.push_back([=]() {  // the pack of the two gradients; a stream that was dropped, or that no gradient reached, packs zeros
+      smi_engine& e = *ep;
+      if (!ta->g && !(tb && tb->g)) return;
+      const int n0 = e.ad_first(j, Nx + Nc);
+      auto grad_or_zero = [&](Ten* t, int rows) -> void* {
+        if (t && t->g) return t->g;
+        void* z = e.alloc_t((int64_t)(n - n0) * rows, j->cols);
+        if (!e.dry && !e.err) (void)hipMemsetAsync(z, 0, (size_t)(n - n0) * rows * j->cols * e.esz(), e.stream);
+        return z;
+      };
+      void* ga = grad_or_zero(ta, Nx);
+      void* gb = grad_or_zero(tb, Nc);
+      e.into_slot(e.grad_slot(j), e.MA(j), j->cols, [&](void* dj) {
+        RUNP(SMI_PROF_ELEM, 0.0, 4.0 * e.MA(j) * j->cols, launch_joint_rows_pack(e.dtype, ga, gb, dj, n - n0, Nx, Nc, j->cols, e.stream));
+      });
+    });
+  }
 }
 
 // ---- the model --------------------------------------------------------------------------------------------------------
@@ -80,7 +148,16 @@ struct MMDiT : Model {
   std::vector<JointBlock> blocks;
   Lin patch, ctx_in, t1, t2, p1, p2, norm_out, proj_out;
   const void* pos = nullptr;
-  MMDiT(const smi_mmdit_config& c, int h, int w) : cfg(c), H(h), W(w) {}
+  // an engine made by smi_mmdit_train_create: transposed copies of the Linears on the gradient path, and arena 1 for the
+  // saved pass and its backward
+  bool trainable = false;
+  bool tape_valid = false;
+  int bw_n = 0;                          // samples of the saved pass (all adapted)
+  Ten* out_rows = nullptr;               // proj_out's output of the saved pass: where the backward starts
+  std::vector<WgradJob> wjobs_uploaded;  // the device table of the deferred weight-gradient jobs, as in the CLIP tower
+  WgradJob* wjobs_dev = nullptr;
+  size_t wjobs_cap = 0;
+  MMDiT(const smi_mmdit_config& c, int h, int w, bool train = false) : cfg(c), H(h), W(w), trainable(train) {}
   int d() const { return cfg.num_heads * cfg.attention_head_dim; }
   int gh() const { return H / cfg.patch_size; }
   int gw() const { return W / cfg.patch_size; }
@@ -107,29 +184,34 @@ struct MMDiT : Model {
       JointBlock& B = blocks[i];
       B.pre_only = i == cfg.num_layers - 1;
       B.x.mod = e.make_lin(b + ".norm1.linear", D, 6 * D, true, false);
-      B.x.qkv = e.make_fused(b + ".attn", {"to_q", "to_k", "to_v"}, D, D, false);
+      B.x.qkv = e.make_fused(b + ".attn", {"to_q", "to_k", "to_v"}, D, D, trainable);
       B.x.qkv.b = e.fused_bias(b + ".attn", {"to_q", "to_k", "to_v"}, D);
-      B.x.out = e.make_lin(b + ".attn.to_out.0", D, D, true, false, true);
-      B.x.ff1 = e.make_lin(b + ".ff.net.0.proj", D, 4 * D, true, false);
-      B.x.ff2 = e.make_lin(b + ".ff.net.2", 4 * D, D, true, false);
+      B.x.out = e.make_lin(b + ".attn.to_out.0", D, D, true, trainable, true);
+      B.x.ff1 = e.make_lin(b + ".ff.net.0.proj", D, 4 * D, true, trainable);
+      B.x.ff2 = e.make_lin(b + ".ff.net.2", 4 * D, D, true, trainable);
       B.c.mod = e.make_lin(b + ".norm1_context.linear", D, (B.pre_only ? 2 : 6) * D, true, false);
-      B.c.qkv = e.make_fused(b + ".attn", {"add_q_proj", "add_k_proj", "add_v_proj"}, D, D, false);
+      B.c.qkv = e.make_fused(b + ".attn", {"add_q_proj", "add_k_proj", "add_v_proj"}, D, D, trainable);
       B.c.qkv.b = e.fused_bias(b + ".attn", {"add_q_proj", "add_k_proj", "add_v_proj"}, D);
       if (!B.pre_only) {
-        B.c.out = e.make_lin(b + ".attn.to_add_out", D, D, true, false, true);
-        B.c.ff1 = e.make_lin(b + ".ff_context.net.0.proj", D, 4 * D, true, false);
-        B.c.ff2 = e.make_lin(b + ".ff_context.net.2", 4 * D, D, true, false);
+        B.c.out = e.make_lin(b + ".attn.to_add_out", D, D, true, trainable, true);
+        B.c.ff1 = e.make_lin(b + ".ff_context.net.0.proj", D, 4 * D, true, trainable);
+        B.c.ff2 = e.make_lin(b + ".ff_context.net.2", 4 * D, D, true, trainable);
       }
     }
     norm_out = e.make_lin("norm_out.linear", D, 2 * D, true, false);
-    proj_out = e.make_lin("proj_out", D, P * P * cfg.out_channels, true, false);
+    proj_out = e.make_lin("proj_out", D, P * P * cfg.out_channels, true, trainable);
   }
   // what the engine packs after the layers
   void build_all(smi_engine& e) {
     build(e);
     e.finish_lora();
-    e.gscale = (float*)e.pack_alloc(256 * sizeof(float));
+    // (a backward keeps its per-sample loss scales in the whole block)
+    e.gscale = (float*)e.pack_alloc((trainable ? (size_t)e.GSCALE_FLOATS : 256) * sizeof(float));
     e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
+    if (trainable) {
+      wjobs_cap = 2 * e.sites.size() + 8;  // a fused q|k|v pushes at most 4 jobs for its 3 sites, an output projection 2
+      wjobs_dev = (WgradJob*)e.pack_alloc(wjobs_cap * sizeof(WgradJob));
+    }
     for (size_t i = 0; i < e.sites.size(); ++i)
       if (!e.site_used[i] && !e.err) {
         set_error("LoRA target '%s' is not an attention projection of this transformer", e.site_names[i].c_str());
@@ -148,20 +230,32 @@ struct MMDiT : Model {
     return gate_residual(e, h, f, mod, 5 * D);
   }
 
-  // every sample under the adaptor (e.mult, the per-sample ratios already on the device), nothing saved
+  void drop_tape(smi_engine& e) {
+    e.pinned.clear();
+    e.tape.clear();
+    tape_valid = false;
+    e.bw_skip = 0;
+  }
+
+  // every sample under the adaptor (e.mult, the per-sample ratios already on the device).  save: the pass goes to arena 1 with
+  // a fresh tape and every tensor kept (no scratch alternation: begin_block does nothing while saving); else arena 0, and a
+  // saved pass stays as it is
   int forward(smi_engine& e, int n, const float* sample, const float* timesteps_host, const void* ctx, const void* pooled,
-              float* out) {
+              float* out, bool save = false) {
     const int D = d(), P = cfg.patch_size, Nx = gh() * gw(), Nc = cfg.context_len, heads = cfg.num_heads;
     e.n_ad = n;
-    e.cur = &e.arena[0];
+    e.cur = &e.arena[save ? 1 : 0];
     e.cur->reset();
-    e.scr[0].reset();
-    e.scr[1].reset();
-    if (e.dry) e.scr[0].cap = e.scr[1].cap = (size_t)-1;
+    if (!save) {
+      e.scr[0].reset();
+      e.scr[1].reset();
+      if (e.dry) e.scr[0].cap = e.scr[1].cap = (size_t)-1;
+    }
     e.in_block = e.persist_next = false;
-    e.tens = &e.tens_[0];
+    e.tens = &e.tens_[save ? 1 : 0];
     e.tens->clear();
-    e.saving = false;
+    if (save) drop_tape(e);
+    e.saving = save;
     if (!e.prep_sites.empty() && (e.dry || (e.lora_down && e.lora_up && e.mult != 0.f)))
       RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.lora_down, e.lora_up, e.lora_shadow, e.stream));
 
@@ -219,8 +313,76 @@ struct MMDiT : Model {
     Ten* y = e.linear(adaln(e, x, mo, 0, D), proj_out);
     RUN(launch_sd3_unpatchify(e.dtype, y->p, out, n, cfg.out_channels, gh(), gw(), P, e.stream));
     e.end_block();
-    if (!e.dry && (e.scr[0].overflow || e.scr[1].overflow)) e.err = true;
+    if (save) {
+      e.saving = false;
+      out_rows = y;
+      bw_n = n;
+      e.bw_down = e.lora_down;
+      e.bw_up = e.lora_up;
+      e.bw_mult = e.mult;
+      e.bw_samp_on = e.samp_on;
+      tape_valid = true;
+    }
+    if (!save && !e.dry && (e.scr[0].overflow || e.scr[1].overflow)) e.err = true;
     return e.end_pass("this call (");
+  }
+
+  // ClipText::backward for this model: one power-of-two loss scale per sample from d_out, un-patchify's inverse into the
+  // gradient of proj_out's rows, the 16-bit LoRA operands rebuilt from the SAVED parameters, the tape in reverse, one grouped
+  // weight-gradient launch (+= into dd / du).  A backward consumes the saved pass
+  int backward(smi_engine& e, const float* d_out, float* dd, float* du) {
+    if (!tape_valid && !e.dry) {
+      set_error("smi_mmdit_backward: no saved forward pass (call smi_mmdit_forward_save first)");
+      return -4;
+    }
+    e.cur = &e.arena[1];
+    e.tens = &e.tens_[1];
+    e.in_block = e.persist_next = false;
+    e.saving = false;
+    e.d_down = dd;
+    e.d_up = du;
+    e.d_ctx = nullptr;
+    e.n_ad = bw_n;
+    Ten* y = out_rows;
+    if (!y->ng || (!e.dry && (!dd || !du))) {  // adaptor off in the saved pass, or no buffers to add to: nothing to do
+      drop_tape(e);
+      return 0;
+    }
+    const int n = bw_n;
+    e.wjobs.clear();
+    e.pinned.clear();
+    e.bw_skip = 0;
+    RUN(launch_grad_scale(d_out, n, (int64_t)cfg.out_channels * H * W, e.gscale, e.MAXS, e.stream));
+    if (!e.prep_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f)
+      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.bw_down, e.bw_up, e.lora_shadow, e.stream));
+    e.mult = e.bw_mult;
+    y->g = e.alloc_t(e.MA(y), y->cols);
+    RUN(launch_sd3_unpatchify_bwd(e.dtype, d_out, y->g, n, cfg.out_channels, gh(), gw(), cfg.patch_size, e.gscale, e.stream));
+    for (auto it = e.tape.rbegin(); it != e.tape.rend(); ++it) (*it)();
+    if (!e.wjobs.empty() && !e.err) {
+      wgrad_grouped_finish(e.wjobs);
+      if (!e.dry) {
+        if (e.wjobs.size() > wjobs_cap) {
+          set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", e.wjobs.size(), wjobs_cap);
+          drop_tape(e);
+          return -1;
+        }
+        const bool same = wjobs_uploaded.size() == e.wjobs.size() &&
+                          memcmp(wjobs_uploaded.data(), e.wjobs.data(), e.wjobs.size() * sizeof(WgradJob)) == 0;
+        if (!same) {  // bump allocation gives the same addresses every step: uploaded once, then reused
+          wjobs_uploaded = e.wjobs;
+          if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), e.wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
+                             e.stream) != hipSuccess) {
+            set_error("hipMemcpyAsync (weight-gradient job table) failed");
+            drop_tape(e);
+            return -1;
+          }
+        }
+        RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_wgrad_grouped(e.dtype, e.wjobs, wjobs_dev, e.stream));
+      }
+    }
+    drop_tape(e);
+    return e.end_pass("the backward (");
   }
 };
 
@@ -269,8 +431,9 @@ int check_mmdit(const smi_mmdit_config* c, const smi_lora_site* sites, int n_sit
   return 0;
 }
 
-MMDiT* mmdit_setup(smi_engine* e, const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w) {
-  MMDiT* m = new MMDiT(*cfg, h, w);
+MMDiT* mmdit_setup(smi_engine* e, const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w,
+                   bool train = false) {
+  MMDiT* m = new MMDiT(*cfg, h, w, train);
   e->hold(smi_engine::MMDIT, m, cfg->dtype, batch);
   e->sites.assign(sites, sites + n_sites);
   e->site_names.resize(n_sites);
@@ -282,20 +445,64 @@ MMDiT* mmdit_setup(smi_engine* e, const smi_mmdit_config* cfg, const smi_lora_si
   for (int i = 0; i < n_sites; ++i) e->smap[e->site_names[i]] = &e->sites[i];
   return m;
 }
-// dry run: out = {packed weights, persistent region of the arena, one scratch region}; the arena is out[1] + 2 out[2]
-int mmdit_plan(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w, size_t out[3]) {
+// dry run: out = {packed weights, persistent region of arena 0, one scratch region, arena 1}; arena 0 is out[1] + 2 out[2];
+// out[3] (a saved pass and its backward) is 0 unless the engine is trainable
+int mmdit_plan(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w, size_t out[4],
+               bool train = false) {
   smi_engine e;
   e.dry = true;
-  MMDiT& m = *mmdit_setup(&e, cfg, sites, n_sites, batch, h, w);
+  MMDiT& m = *mmdit_setup(&e, cfg, sites, n_sites, batch, h, w, train);
   m.build_all(e);
   if (e.err) return -1;
   out[0] = align_up(e.wpack.peak, 4096);
   m.dry_forward(e);
   out[1] = align_up(e.arena[0].peak, 4096);
   out[2] = align_up(std::max(e.scr[0].peak, e.scr[1].peak), 4096);
+  out[3] = 0;
+  if (train) {
+    m.forward(e, batch, nullptr, nullptr, (void*)16, (void*)16, (float*)16, true);
+    m.backward(e, nullptr, nullptr, nullptr);
+    out[3] = align_up(e.arena[1].peak, 4096);
+  }
   return e.err ? -1 : 0;
 }
-size_t plan_bytes(const size_t r[3]) { return r[0] + r[1] + 2 * r[2] + 2 * 4096; }
+size_t plan_bytes(const size_t r[4]) { return r[0] + r[1] + 2 * r[2] + 2 * 4096 + (r[3] ? r[3] + 4096 : 0); }
+
+int check_mmdit_train(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w) {
+  if (check_mmdit(cfg, sites, n_sites, batch, h, w)) return -1;
+  SMI_CHECK(sites && n_sites > 0, "smi_mmdit_train: n_sites 0 -- no LoRA sites to train (a frozen network is smi_mmdit_create's)");
+  return 0;
+}
+
+// smi_mmdit_forward / smi_mmdit_forward_save: the adaptor's state from the arguments, then the pass
+int mmdit_run(smi_engine* e, const char* who, int n, const float* sample, const float* timesteps, const void* ctx,
+              const void* pooled, const float* lora_down_flat, const float* lora_up_flat, const float* multipliers, float* out,
+              bool save) {
+  SMI_CHECK(e && e->kind == smi_engine::MMDIT, "%s: NULL or not an MMDiT engine (create it with smi_mmdit_create)", who);
+  MMDiT* m = static_cast<MMDiT*>(e->model.get());
+  SMI_CHECK(!save || m->trainable, "%s: this engine keeps no pass (create it with smi_mmdit_train_create)", who);
+  SMI_CHECK(sample && timesteps && ctx && pooled && out, "%s: sample, timesteps, ctx, pooled and out are required", who);
+  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  e->err = false;
+  // the adaptor is on when both flat buffers and the multipliers are given and one multiplier is not 0; else the frozen net.
+  // Every adapted pass takes the per-sample route (sigma_i = m_i / max |m|): a sample gives the same bits alone and in a batch
+  float mref = 0.f;
+  if (lora_down_flat && lora_up_flat && multipliers && !e->prep_sites.empty())
+    for (int i = 0; i < n; ++i) mref = fmaxf(mref, fabsf(multipliers[i]));
+  if (mref != 0.f && upload_vals(*e, e->samp_mult_dev, multipliers, n, mref)) return -2;
+  // (slot 1 keeps the saved pass's ratios for its backward)
+  if (save && mref != 0.f && upload_vals(*e, e->samp_mult_dev + smi_engine::MAXS, multipliers, n, mref)) return -2;
+  e->lora_down = mref != 0.f ? lora_down_flat : nullptr;
+  e->lora_up = mref != 0.f ? lora_up_flat : nullptr;
+  e->mult = mref;
+  e->samp_on = mref != 0.f;
+  // no split-K scratch is lent to this model's GEMMs: the slice count follows the launch's row count, so with one the bits
+  // of a sample would depend on its batch
+  smi::set_gemm_scratch(nullptr, 0);
+  const int rc = m->forward(*e, n, sample, timesteps, ctx, pooled, out, save);
+  e->samp_on = false;
+  return rc;
+}
 
 }  // namespace
 
@@ -305,55 +512,79 @@ int smi_mmdit_workspace_bytes(const smi_mmdit_config* cfg, const smi_lora_site* 
                               size_t* bytes) {
   if (check_mmdit(cfg, sites, n_sites, batch, h, w)) return -1;
   SMI_CHECK(bytes != nullptr, "bad arguments");
-  size_t r[3];
+  size_t r[4];
   if (mmdit_plan(cfg, sites, n_sites, batch, h, w, r)) return -1;
   *bytes = plan_bytes(r);
   return 0;
 }
 
-int smi_mmdit_create(const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
-                     int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
-                     smi_engine** out) {
-  if (check_mmdit(cfg, sites, n_sites, batch, h, w)) return -1;
+int smi_mmdit_train_workspace_bytes(const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h,
+                                    int w, size_t* bytes) {
+  if (check_mmdit_train(cfg, sites, n_sites, batch, h, w)) return -1;
+  SMI_CHECK(bytes != nullptr, "bad arguments");
+  size_t r[4];
+  if (mmdit_plan(cfg, sites, n_sites, batch, h, w, r, true)) return -1;
+  *bytes = plan_bytes(r);
+  return 0;
+}
+
+// both create entries: train says which
+static int mmdit_create(bool train, const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights,
+                        const smi_lora_site* sites, int n_sites, int batch, int h, int w, void* workspace,
+                        size_t workspace_bytes, void* stream, smi_engine** out) {
   SMI_CHECK(out && workspace && weights && n_weights > 0, "bad arguments");
-  size_t r[3];
-  if (mmdit_plan(cfg, sites, n_sites, batch, h, w, r)) return -1;
+  size_t r[4];
+  if (mmdit_plan(cfg, sites, n_sites, batch, h, w, r, train)) return -1;
   SMI_CHECK(plan_bytes(r) <= workspace_bytes, "workspace too small: need %zu bytes, got %zu", plan_bytes(r), workspace_bytes);
   smi_engine* e = new smi_engine();
   e->stream = (hipStream_t)stream;
-  MMDiT* m = mmdit_setup(e, cfg, sites, n_sites, batch, h, w);
+  MMDiT* m = mmdit_setup(e, cfg, sites, n_sites, batch, h, w, train);
   for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
   char* base = (char*)align_up((size_t)workspace, 4096);
   e->wpack.base = base;
   e->wpack.cap = r[0];
   e->arena[0].base = base + r[0];
   e->set_arena0_regions(r[1], r[2]);
+  e->arena[1].base = base + r[0] + r[1] + 2 * r[2];
+  e->arena[1].cap = r[3];
   m->build_all(*e);
   return finish_create(e, "the MMDiT weights", out);
 }
 
+int smi_mmdit_create(const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                     int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                     smi_engine** out) {
+  if (check_mmdit(cfg, sites, n_sites, batch, h, w)) return -1;
+  return mmdit_create(false, cfg, weights, n_weights, sites, n_sites, batch, h, w, workspace, workspace_bytes, stream, out);
+}
+
+int smi_mmdit_train_create(const smi_mmdit_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                           int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                           smi_engine** out) {
+  if (check_mmdit_train(cfg, sites, n_sites, batch, h, w)) return -1;
+  return mmdit_create(true, cfg, weights, n_weights, sites, n_sites, batch, h, w, workspace, workspace_bytes, stream, out);
+}
+
 int smi_mmdit_forward(smi_engine* e, int n, const float* sample, const float* timesteps, const void* ctx, const void* pooled,
                       const float* lora_down_flat, const float* lora_up_flat, const float* multipliers, float* out) {
-  SMI_CHECK(e && e->kind == smi_engine::MMDIT, "smi_mmdit_forward: NULL or not an MMDiT engine (create it with smi_mmdit_create)");
-  SMI_CHECK(sample && timesteps && ctx && pooled && out, "smi_mmdit_forward: sample, timesteps, ctx, pooled and out are required");
-  SMI_CHECK(n >= 1 && n <= e->max_n, "batch %d outside [1, %d] the engine was created for", n, e->max_n);
+  return mmdit_run(e, "smi_mmdit_forward", n, sample, timesteps, ctx, pooled, lora_down_flat, lora_up_flat, multipliers, out,
+                   false);
+}
+
+int smi_mmdit_forward_save(smi_engine* e, int n, const float* sample, const float* timesteps, const void* ctx,
+                           const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
+                           const float* multipliers, float* out) {
+  return mmdit_run(e, "smi_mmdit_forward_save", n, sample, timesteps, ctx, pooled, lora_down_flat, lora_up_flat, multipliers,
+                   out, true);
+}
+
+int smi_mmdit_backward(smi_engine* e, const float* d_out, float* d_lora_down_flat, float* d_lora_up_flat) {
+  SMI_CHECK(e && e->kind == smi_engine::MMDIT && d_out, "smi_mmdit_backward: NULL argument or not an MMDiT engine");
+  MMDiT* m = static_cast<MMDiT*>(e->model.get());
+  SMI_CHECK(m->trainable, "smi_mmdit_backward: this engine keeps no pass (create it with smi_mmdit_train_create)");
   e->err = false;
-  // the adaptor is on when both flat buffers and the multipliers are given and one multiplier is not 0; else the frozen net.
-  // Every adapted pass takes the per-sample route (sigma_i = m_i / max |m|): a sample gives the same bits alone and in a batch
-  float mref = 0.f;
-  if (lora_down_flat && lora_up_flat && multipliers && !e->prep_sites.empty())
-    for (int i = 0; i < n; ++i) mref = fmaxf(mref, fabsf(multipliers[i]));
-  if (mref != 0.f && upload_vals(*e, e->samp_mult_dev, multipliers, n, mref)) return -2;
-  e->lora_down = mref != 0.f ? lora_down_flat : nullptr;
-  e->lora_up = mref != 0.f ? lora_up_flat : nullptr;
-  e->mult = mref;
-  e->samp_on = mref != 0.f;
-  // no split-K scratch is lent to this model's GEMMs: the slice count follows the launch's row count, so with one the bits
-  // of a sample would depend on its batch
   smi::set_gemm_scratch(nullptr, 0);
-  const int rc = static_cast<MMDiT*>(e->model.get())->forward(*e, n, sample, timesteps, ctx, pooled, out);
-  e->samp_on = false;
-  return rc;
+  return m->backward(*e, d_out, d_lora_down_flat, d_lora_up_flat);
 }
 
 }  // extern "C"

@@ -418,6 +418,17 @@ int launch_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n
                        hipStream_t stream);
 // out f32 [n, Cout, gh p, gw p] from rows T [n gh gw, p p Cout] with columns (py, px, c)
 int launch_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int Cout, int gh, int gw, int p, hipStream_t stream);
+// The backwards to the activations (scale, shift and gate take no gradient: they depend on temb alone).
+// dx[r, :] = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ add[r, :]), g = dy (1 + scale[s, :]), xhat = (x - mean) rstd with
+// mean_rstd from the forward; add is optional and may alias dx
+int launch_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const void* mod, const float* mean_rstd, const void* add,
+                              void* dx, int M, int C, int rows_per_sample, int64_t ldm, int off_scale, hipStream_t stream);
+// df[r, :] = gate[s, :] dy[r, :] (dh is dy)
+int launch_gate_residual_bwd(int dtype, const void* dy, const void* mod, void* df, int64_t M, int C, int rows_per_sample,
+                             int64_t ldm, int off_gate, hipStream_t stream);
+// rows T [n gh gw, p p Cout] = scale_dev[n] x d_out f32 [n, Cout, gh p, gw p]: un-patchify's inverse; Cout p p % 8 == 0
+int launch_sd3_unpatchify_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
+                              const float* scale_dev, hipStream_t stream);
 
 // LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
 // applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.

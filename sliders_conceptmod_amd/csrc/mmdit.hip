@@ -82,6 +82,61 @@ __global__ __launch_bounds__(256) void adaln_modulate_kernel(const T* __restrict
   }
 }
 
+// the backward to x: with g = dy (1 + scale[s, :]) and xhat = (x - mean) rstd from the forward's mean_rstd,
+// dx[r, :] = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ add[r, :]).  One wave per row; g and xhat stay in registers between
+// the two reductions and the apply.  add may alias dx (a lane reads its vector before it writes it); no restrict on the two
+template <typename T, int NV>
+__global__ __launch_bounds__(256) void adaln_modulate_bwd_kernel(const T* __restrict__ x, const T* __restrict__ dy,
+                                                                 const T* __restrict__ mod, const float* __restrict__ mean_rstd,
+                                                                 const T* add, T* dx, int M, int C, int rows_per_sample,
+                                                                 int64_t ldm, int off_scale) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= M) return;
+  const int nvec = C / 8;
+  const float inv_c = 1.f / (float)C;
+  const float mean = mean_rstd[(int64_t)row * 2], rstd = mean_rstd[(int64_t)row * 2 + 1];
+  const T* mrow = mod + (int64_t)(row / rows_per_sample) * ldm + off_scale;
+  float g[NV][8], xh[NV][8];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int v = lane + 64 * j;
+    if (v < nvec) {
+      Pack8<T> xv, dv, sc;
+      xv.u = *reinterpret_cast<const u32x4*>(x + (int64_t)row * C + v * 8);
+      dv.u = *reinterpret_cast<const u32x4*>(dy + (int64_t)row * C + v * 8);
+      sc.u = *reinterpret_cast<const u32x4*>(mrow + v * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        g[j][e] = to_f(dv.e[e]) * (1.f + to_f(sc.e[e]));
+        xh[j][e] = (to_f(xv.e[e]) - mean) * rstd;
+        s1 += g[j][e];
+        s2 = __builtin_fmaf(g[j][e], xh[j][e], s2);
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) g[j][e] = xh[j][e] = 0.f;
+    }
+  }
+  const float m1 = wave_sum_all(s1) * inv_c;
+  const float m2 = wave_sum_all(s2) * inv_c;
+#pragma unroll
+  for (int j = 0; j < NV; ++j) {
+    const int v = lane + 64 * j;
+    if (v < nvec) {
+      Pack8<T> av, o;
+      if (add) av.u = *reinterpret_cast<const u32x4*>(add + (int64_t)row * C + v * 8);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const float d = rstd * (g[j][e] - m1 - xh[j][e] * m2);
+        o.e[e] = from_f<T>(add ? d + to_f(av.e[e]) : d);
+      }
+      *reinterpret_cast<u32x4*>(dx + (int64_t)row * C + v * 8) = o.u;
+    }
+  }
+}
+
 // y[r, :] = h[r, :] + gate[s, :] f[r, :]; y may alias h (every vector is read before it is written, by the same lane)
 template <typename T>
 __global__ void gate_residual_kernel(const T* h, const T* __restrict__ f, const T* __restrict__ mod, T* y, int64_t M, int C8,
@@ -96,6 +151,22 @@ __global__ void gate_residual_kernel(const T* h, const T* __restrict__ f, const 
 #pragma unroll
     for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(__builtin_fmaf(to_f(gv.e[e]), to_f(fv.e[e]), to_f(hv.e[e])));
     *reinterpret_cast<u32x4*>(y + i * 8) = o.u;
+  }
+}
+
+// its backward to f: df[r, :] = gate[s, :] dy[r, :] (the gradient of h is dy itself: no kernel)
+template <typename T>
+__global__ void gate_residual_bwd_kernel(const T* __restrict__ dy, const T* __restrict__ mod, T* __restrict__ df, int64_t M,
+                                         int C8, int rows_per_sample, int64_t ldm, int off_gate) {
+  GSTRIDE(i, M * C8) {
+    const int64_t r = i / C8;
+    const int v = (int)(i - r * C8);
+    Pack8<T> dv, gv, o;
+    dv.u = *reinterpret_cast<const u32x4*>(dy + i * 8);
+    gv.u = *reinterpret_cast<const u32x4*>(mod + (r / rows_per_sample) * ldm + off_gate + v * 8);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(gv.e[e]) * to_f(dv.e[e]));
+    *reinterpret_cast<u32x4*>(df + i * 8) = o.u;
   }
 }
 
@@ -171,7 +242,90 @@ __global__ void sd3_unpatchify_kernel(const T* __restrict__ rows, float* __restr
   }
 }
 
+// the inverse, for the backward: rows[(n, gy, gx), (py, px, c)] = scale[n] d_out[n, c, gy p + py, gx p + px] (scale: the
+// sample's loss scale on the device); one lane writes 8 adjacent columns
+template <typename T>
+__global__ void sd3_unpatchify_bwd_kernel(const float* __restrict__ d_out, T* __restrict__ rows, int64_t nrows, int Cout, int gh,
+                                          int gw, int p, const float* __restrict__ scale) {
+  const int K8 = p * p * Cout / 8;
+  const int H = gh * p, W = gw * p;
+  GSTRIDE(i, nrows * K8) {
+    const int64_t r = i / K8;
+    const int k0 = (int)(i - r * K8) * 8;
+    const int gx = (int)(r % gw);
+    const int gy = (int)((r / gw) % gh);
+    const int64_t n = r / ((int64_t)gw * gh);
+    const float s = scale[n];
+    Pack8<T> o;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int k = k0 + e;
+      const int c = k % Cout, px = (k / Cout) % p, py = k / (Cout * p);
+      o.e[e] = from_f<T>(s * d_out[((n * Cout + c) * H + gy * p + py) * W + gx * p + px]);
+    }
+    *reinterpret_cast<u32x4*>(rows + i * 8) = o.u;
+  }
+}
+
 }  // namespace
+
+int launch_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const void* mod, const float* mean_rstd, const void* add,
+                              void* dx, int M, int C, int rows_per_sample, int64_t ldm, int off_scale, hipStream_t stream) {
+  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0 && C <= 512 * ADALN_MAXV, "adaln_modulate_bwd: C %% 8, C <= 2048 (got M=%d C=%d)", M, C);
+  SMI_CHECK(rows_per_sample >= 1 && ldm % 8 == 0 && off_scale % 8 == 0 && off_scale >= 0 && off_scale + C <= ldm,
+            "adaln_modulate_bwd: scale is C columns of a mod row at an offset that is a multiple of 8 (ldm=%lld, %d)",
+            (long long)ldm, off_scale);
+  SMI_CHECK(x && dy && mod && mean_rstd && dx, "adaln_modulate_bwd: NULL operand");
+  SMI_CHECK((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)mod | (uintptr_t)add | (uintptr_t)dx) & 15) == 0,
+            "adaln_modulate_bwd: x, dy, mod, add and dx must be 16-byte aligned");
+  const int nv = (C / 8 + 63) / 64;
+#define GO(T_, NV_)                                                                                                      \
+  hipLaunchKernelGGL((adaln_modulate_bwd_kernel<T_, NV_>), dim3(cdiv(M, 4)), dim3(256), 0, stream, (const T_*)x, (const T_*)dy, \
+                     (const T_*)mod, mean_rstd, (const T_*)add, (T_*)dx, M, C, rows_per_sample, ldm, off_scale)
+#define GO_T(T_)                  \
+  switch (nv) {                   \
+    case 1: GO(T_, 1); break;     \
+    case 2: GO(T_, 2); break;     \
+    case 3: GO(T_, 3); break;     \
+    default: GO(T_, 4); break;    \
+  }
+  if (dtype == DT_F16) { GO_T(f16) } else { GO_T(bf16) }
+#undef GO_T
+#undef GO
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_gate_residual_bwd(int dtype, const void* dy, const void* mod, void* df, int64_t M, int C, int rows_per_sample,
+                             int64_t ldm, int off_gate, hipStream_t stream) {
+  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0, "gate_residual_bwd: C %% 8 (got C=%d)", C);
+  SMI_CHECK(rows_per_sample >= 1 && ldm % 8 == 0 && off_gate % 8 == 0 && off_gate >= 0 && off_gate + C <= ldm,
+            "gate_residual_bwd: gate is C columns of a mod row at an offset that is a multiple of 8 (ldm=%lld, %d)",
+            (long long)ldm, off_gate);
+  SMI_CHECK(dy && mod && df && (((uintptr_t)dy | (uintptr_t)mod | (uintptr_t)df) & 15) == 0,
+            "gate_residual_bwd: dy, mod and df must be non-NULL and 16-byte aligned");
+  const int grid = ew_grid(M * (C / 8));
+  if (dtype == DT_F16)
+    hipLaunchKernelGGL(gate_residual_bwd_kernel<f16>, dim3(grid), dim3(256), 0, stream, (const f16*)dy, (const f16*)mod, (f16*)df, M, C / 8, rows_per_sample, ldm, off_gate);
+  else
+    hipLaunchKernelGGL(gate_residual_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)mod, (bf16*)df, M, C / 8, rows_per_sample, ldm, off_gate);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
+int launch_sd3_unpatchify_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
+                              const float* scale_dev, hipStream_t stream) {
+  SMI_CHECK(n >= 1 && Cout >= 1 && gh >= 1 && gw >= 1 && p >= 1 && (Cout * p * p) % 8 == 0 && scale_dev,
+            "sd3_unpatchify_bwd: Cout p p %% 8 and a scale per sample (got Cout=%d p=%d)", Cout, p);
+  const int64_t nrows = (int64_t)n * gh * gw;
+  const int grid = ew_grid(nrows * (Cout * p * p / 8));
+  if (dtype == DT_F16)
+    hipLaunchKernelGGL(sd3_unpatchify_bwd_kernel<f16>, dim3(grid), dim3(256), 0, stream, d_out, (f16*)rows, nrows, Cout, gh, gw, p, scale_dev);
+  else
+    hipLaunchKernelGGL(sd3_unpatchify_bwd_kernel<bf16>, dim3(grid), dim3(256), 0, stream, d_out, (bf16*)rows, nrows, Cout, gh, gw, p, scale_dev);
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
 
 int launch_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int M, int C,
                           int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, hipStream_t stream) {

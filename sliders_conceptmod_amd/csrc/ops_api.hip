@@ -354,6 +354,15 @@ int smi_op_gate_residual(int dtype, const void* h, const void* f, const void* mo
                          int rows_per_sample, int64_t ldm, int off_gate, void* stream) {
   return launch_gate_residual(dtype, h, f, mod, y, m, c, rows_per_sample, ldm, off_gate, (hipStream_t)stream);
 }
+int smi_op_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const void* mod, const float* mean_rstd, const void* add,
+                              void* dx, int m, int c, int rows_per_sample, int64_t ldm, int off_scale, void* stream) {
+  return launch_adaln_modulate_bwd(dtype, x, dy, mod, mean_rstd, add, dx, m, c, rows_per_sample, ldm, off_scale,
+                                   (hipStream_t)stream);
+}
+int smi_op_gate_residual_bwd(int dtype, const void* dy, const void* mod, void* df, int64_t m, int c, int rows_per_sample,
+                             int64_t ldm, int off_gate, void* stream) {
+  return launch_gate_residual_bwd(dtype, dy, mod, df, m, c, rows_per_sample, ldm, off_gate, (hipStream_t)stream);
+}
 int smi_op_joint_rows_pack(int dtype, const void* a, const void* b, void* joint, int n, int nx, int nc, int w, void* stream) {
   return launch_joint_rows_pack(dtype, a, b, joint, n, nx, nc, w, (hipStream_t)stream);
 }

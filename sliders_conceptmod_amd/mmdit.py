@@ -6,7 +6,9 @@ add_k_proj,add_v_proj,to_add_out}`, `.ff`, `.ff_context`, `norm_out.linear`, `pr
 `Attention`, so `lora.select_targets` finds it as the reference's `target_replace=["Attention"]` does
 (conceptmod/textsliders/train_lora_sd3.py).  No arithmetic happens here: `forward` runs csrc/engine_mmdit.hip.
 
-Forward only.  SD3.5's qk-norm and dual attention are not built (the engine refuses them by name)."""
+With grad enabled and a LoRANetwork attached, `forward` goes through a trainable engine (smi_mmdit_train_create) and an
+autograd Function whose backward is the engine's: gradients reach the network's flat parameter and nothing else.
+SD3.5's qk-norm and dual attention are not built (the engine refuses them by name)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -144,31 +146,61 @@ def workspace_bytes(cfg: SD3Config, dtype: torch.dtype, sites: Sequence[dict], b
     return out.value
 
 
+def train_workspace_bytes(cfg: SD3Config, dtype: torch.dtype, sites: Sequence[dict], batch: int, h: int, w: int,
+                          context_len: int) -> int:
+    """smi_mmdit_train_workspace_bytes: the host-only dry forward + backward of a trainable engine."""
+    arr, _keep = _native.make_sites(sites)
+    out = C.c_size_t(0)
+    _native.check(_native.lib().smi_mmdit_train_workspace_bytes(C.byref(engine_config_c(cfg, dtype, context_len)), arr,
+                                                                len(sites), batch, h, w, C.byref(out)),
+                  "smi_mmdit_train_workspace_bytes")
+    return out.value
+
+
 class MMDiTEngine(_native._EngineBase):
     """SD3 MMDiT on the HIP engine for one latent size and context length (smi_mmdit_*): the forward with Linear LoRA
-    sites at one multiplier per sample."""
+    sites at one multiplier per sample; `trainable=True` (smi_mmdit_train_*): also `forward_save` and `backward`, the
+    gradient of the output to the LoRA parameters."""
 
     def __init__(self, cfg: SD3Config, dtype: torch.dtype, state: dict, sites: Sequence[dict], batch: int, h: int,
-                 w: int, context_len: int, device):
+                 w: int, context_len: int, device, trainable: bool = False):
         self.cfg, self.dtype, self.batch, self.h, self.w, self.context_len = cfg, dtype, batch, h, w, context_len
+        self.trainable = trainable
         self.cfg_c = engine_config_c(cfg, dtype, context_len)
         arr, self._site_keep = _native.make_sites(sites)
         out = C.c_size_t(0)
-        _native.check(_native.lib().smi_mmdit_workspace_bytes(C.byref(self.cfg_c), arr, len(sites), batch, h, w,
-                                                              C.byref(out)), "smi_mmdit_workspace_bytes")
+        lib = _native.lib()
+        size_fn, create_fn, name = ((lib.smi_mmdit_train_workspace_bytes, lib.smi_mmdit_train_create, "smi_mmdit_train")
+                                    if trainable else (lib.smi_mmdit_workspace_bytes, lib.smi_mmdit_create, "smi_mmdit"))
+        _native.check(size_fn(C.byref(self.cfg_c), arr, len(sites), batch, h, w, C.byref(out)), name + "_workspace_bytes")
         self.workspace_bytes = out.value
         self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
         warr, self._keep = _native._weight_table(state, dtype, self.workspace.device)
         handle = C.c_void_p()
         with torch.cuda.device(self.workspace.device):
-            _native.check(_native.lib().smi_mmdit_create(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch, h, w,
-                                                         _native.ptr(self.workspace), out.value, _native.stream_ptr(),
-                                                         C.byref(handle)), "smi_mmdit_create")
+            _native.check(create_fn(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch, h, w,
+                                    _native.ptr(self.workspace), out.value, _native.stream_ptr(), C.byref(handle)),
+                          name + "_create")
         self.handle = handle
+        self._borrowed = None  # the operands of the saved pass: the engine reads the LoRA parameters again in its backward
+
+    def forward_save(self, sample, timesteps, ctx, pooled, lora_down, lora_up, multipliers, out=None) -> torch.Tensor:
+        """`forward`, with the pass kept for one `backward` (smi_mmdit_forward_save): the same bits in the output."""
+        return self.forward(sample, timesteps, ctx, pooled, lora_down, lora_up, multipliers, out, save=True)
+
+    def backward(self, d_out: torch.Tensor, d_down: Optional[torch.Tensor], d_up: Optional[torch.Tensor]) -> None:
+        """smi_mmdit_backward: d_out f32 [n, Cout, h, w]; the LoRA gradients are ADDED to d_down / d_up (f32, flat layout).
+        Consumes the saved pass (SmiError without one)."""
+        d_out = d_out.to(self.workspace.device, torch.float32).contiguous()
+        with torch.cuda.device(self.workspace.device):
+            rc = _native.lib().smi_mmdit_backward(self.handle, _native.ptr(d_out), _native.ptr(d_down), _native.ptr(d_up))
+        self._borrowed = None
+        _native.check(rc, "smi_mmdit_backward")
 
     def forward(self, sample: torch.Tensor, timesteps, ctx: torch.Tensor, pooled: torch.Tensor,
                 lora_down: Optional[torch.Tensor] = None, lora_up: Optional[torch.Tensor] = None,
-                multipliers: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                multipliers: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None,
+                save: bool = False) -> torch.Tensor:
         """sample [n, Cin, h, w] -> f32 [n, Cout, h, w].  timesteps: n floats (the scheduler's 1000 sigma), on the host."""
         n = sample.shape[0]
         cfg, dev = self.cfg, self.workspace.device
@@ -190,11 +222,38 @@ class MMDiTEngine(_native._EngineBase):
             out = torch.empty((n, cfg.out_channels, self.h, self.w), dtype=torch.float32, device=dev)
         tarr = (C.c_float * n)(*ts)
         marr = None if multipliers is None else (C.c_float * n)(*[float(m) for m in multipliers])
+        fn, name = ((_native.lib().smi_mmdit_forward_save, "smi_mmdit_forward_save") if save
+                    else (_native.lib().smi_mmdit_forward, "smi_mmdit_forward"))
         with torch.cuda.device(dev):
-            _native.check(_native.lib().smi_mmdit_forward(self.handle, n, _native.ptr(sample), tarr, _native.ptr(ctx),
-                                                          _native.ptr(pooled), _native.ptr(lora_down), _native.ptr(lora_up),
-                                                          marr, _native.ptr(out)), "smi_mmdit_forward")
+            _native.check(fn(self.handle, n, _native.ptr(sample), tarr, _native.ptr(ctx), _native.ptr(pooled),
+                             _native.ptr(lora_down), _native.ptr(lora_up), marr, _native.ptr(out)), name)
+        if save:
+            self._borrowed = (lora_down, lora_up)
         return out
+
+
+class _MMDiTFn(torch.autograd.Function):
+    """Autograd bookkeeping only: forward and backward are single calls into the trainable engine.  The one differentiable
+    input is the network's flat parameter."""
+
+    @staticmethod
+    def forward(ctx, engine, flat, n_down, sample, ts, ehs, pooled, multipliers):
+        flat_d = flat.detach()
+        out = engine.forward_save(sample, ts, ehs, pooled, flat_d[:n_down], flat_d[n_down:], multipliers)
+        ctx.engine, ctx.n_down, ctx.flat = engine, n_down, flat_d
+        engine._saved_by = ctx
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if getattr(ctx.engine, "_saved_by", None) is not ctx:
+            raise _native.SmiError(
+                "backward through an SD3 transformer output whose saved activations are gone: the engine keeps the pass of "
+                "the LAST grad-enabled forward only (a later grad-enabled forward or a previous backward released it)")
+        ctx.engine._saved_by = None
+        g = torch.zeros_like(ctx.flat)
+        ctx.engine.backward(d_out, g[:ctx.n_down], g[ctx.n_down:])
+        return None, g, None, None, None, None, None, None
 
 
 class SD3Transformer2DModel(EngineCacheMixin, nn.Module):
@@ -225,41 +284,50 @@ class SD3Transformer2DModel(EngineCacheMixin, nn.Module):
         net = self.__dict__.get("_lora_network")
         return net.engine_sites() if net is not None and net.unet_loras else []
 
-    def _new_engine(self, state, n, h, w, context_len, _net_id):
-        return MMDiTEngine(self.cfg, self.dtype, state, self._sites(), max(n, 1), h, w, context_len, self.device)
+    def _new_engine(self, state, n, h, w, context_len, trainable, _net_id):
+        return MMDiTEngine(self.cfg, self.dtype, state, self._sites(), max(n, 1), h, w, context_len, self.device,
+                           trainable=trainable)
 
-    def engine(self, n: int, h: int, w: int, context_len: int) -> MMDiTEngine:
+    def engine(self, n: int, h: int, w: int, context_len: int, trainable: bool = False) -> MMDiTEngine:
         """The engine for this latent size and context length, with the attached network's sites (fixed at creation: an engine
-        built for another network is closed first)."""
+        built for another network is closed first).  trainable: the engine that saves a pass and differentiates it."""
         net = self.__dict__.get("_lora_network")
         for key, e in list(self._engines.items()):
             if key[-1] != id(net):
                 e.close()
                 del self._engines[key]
-        return self._engine(n, h, w, context_len, id(net))
+        return self._engine(n, h, w, context_len, trainable, id(net))
 
-    @torch.no_grad()
     def forward(self, hidden_states, timestep, encoder_hidden_states, pooled_projections, multipliers=None,
                 return_dict: bool = True, **_):
         """diffusers' call.  `timestep`: a number or n of them.  An attached LoRANetwork runs at its current multiplier
-        (0 outside `with network:`) on every sample, or at `multipliers` (one per sample)."""
+        (0 outside `with network:`) on every sample, or at `multipliers` (one per sample).  With grad enabled and a network
+        whose parameter requires grad, the pass is saved and the output carries the gradient to that parameter."""
         n, _c, h, w = hidden_states.shape
         if torch.is_tensor(timestep):
             timestep = timestep.detach().float().cpu().reshape(-1).tolist()
         ts = list(timestep) if isinstance(timestep, (list, tuple)) else [float(timestep)]
         ts = ts * n if len(ts) == 1 else ts
-        e = self.engine(n, h, w, encoder_hidden_states.shape[1])
         net = self.__dict__.get("_lora_network")
         down = up = None
+        hidden_states, encoder_hidden_states = hidden_states.detach(), encoder_hidden_states.detach()
+        pooled_projections = pooled_projections.detach()
         if net is not None and net.unet_loras:
             flat, n_down, mult = net.engine_params()
-            flat = flat.detach()
-            down, up = flat[:n_down], flat[n_down:]
             if multipliers is None:
                 multipliers = [mult] * n
+            if torch.is_grad_enabled() and flat.requires_grad:
+                e = self.engine(n, h, w, encoder_hidden_states.shape[1], trainable=True)
+                out = _MMDiTFn.apply(e, flat, n_down, hidden_states, ts, encoder_hidden_states, pooled_projections,
+                                     [float(m) for m in multipliers])
+                return TransformerOutput(out) if return_dict else (out,)
+            flat = flat.detach()
+            down, up = flat[:n_down], flat[n_down:]
         else:
             multipliers = None
-        out = e.forward(hidden_states, ts, encoder_hidden_states, pooled_projections, down, up, multipliers)
+        e = self.engine(n, h, w, encoder_hidden_states.shape[1])
+        with torch.no_grad():
+            out = e.forward(hidden_states, ts, encoder_hidden_states, pooled_projections, down, up, multipliers)
         return TransformerOutput(out) if return_dict else (out,)
 
 

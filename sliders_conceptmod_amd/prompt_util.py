@@ -27,7 +27,16 @@ class PromptEmbedsXL:
         self.text_embeds, self.pooled_embeds = text_embeds, pooled_embeds
 
 
-PROMPT_EMBEDDING = Union[torch.Tensor, PromptEmbedsXL]
+class PromptEmbedsSD3:
+    """SD3 conditioning of one prompt: (the joint text embedding -- CLIP towers and the T5 block, [n, tokens,
+    joint_attention_dim] --, the pooled projections of the two CLIP towers concatenated)."""
+    __slots__ = ("text_embeds", "pooled_embeds")
+
+    def __init__(self, text_embeds, pooled_embeds) -> None:
+        self.text_embeds, self.pooled_embeds = text_embeds, pooled_embeds
+
+
+PROMPT_EMBEDDING = Union[torch.Tensor, PromptEmbedsXL, PromptEmbedsSD3]
 
 
 class PromptEmbedsCache:

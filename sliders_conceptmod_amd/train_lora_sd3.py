@@ -1,0 +1,220 @@
+"""Text-slider trainer for Stable Diffusion 3 on the native MMDiT (conceptmod/textsliders/train_lora_sd3.py, restated from
+its behaviour): five prompts encoded once, per iteration a prompt pair and `timesteps_to` in [1, max_denoising_steps), the
+adapted network's pre-roll from pure noise to `timesteps_to`, three frozen CFG steps (positive, neutral, negative), one
+adapted CFG step under autograd, `PromptEmbedsPair.loss` on the STEPPED latents, clip_grad_norm_ 0.2, AdamW(lr 1e-4,
+wd 1e-6), CosineAnnealingLR(T_max 50, eta_min 1e-6), `<name>_<i>steps.safetensors` / `<name>_last.safetensors`.
+
+    python -m sliders_conceptmod_amd.train_lora_sd3 --config_file data/config-sd3.yaml --alpha 1 --rank 4 --device 0 --name x
+
+The adapted step runs through the trainable MMDiT engine (`SD3Transformer2DModel.forward` with grad enabled: a saved forward
+and `smi_mmdit_backward`; gradients reach the LoRA matrices only).  The three frozen predictions share one no-grad pass
+(unconditional, positive, neutral, negative): a sample has the same bits alone or in a batch.  Clip + optimiser: the native
+fused step where train_common.step_choice allows it, else (`--no_fused_step`) torch's clip_grad_norm_ and optimiser class.
+
+What differs from the reference script, on purpose:
+  * `LoRANetwork(transformer)` adapts to_q / to_k / to_v / to_out.0 of every joint block, as the reference's name filter does
+    (96 modules on SD3-medium); `--context_stream` adds the context stream's projections (191).
+  * `--peft_type dora`, `network.type: c3lier` and SD3.5 checkpoints (qk_norm, dual attention) are refused by name: the
+    engine takes plain Linear LoRA sites on the attention projections of an SD3-medium-family transformer.
+  * keys use the `_` delimiter of this package's other trainers, which is what `generate_images --base sd3` reads.
+  * latents stay fp32 between the steps (the engine's output type), as in train_lora_xl here."""
+import argparse
+
+import torch
+from tqdm import tqdm
+
+from . import config_util, model_util, prompt_util, train_common, train_util
+from .config_util import RootConfig
+from .lora import LoRANetwork
+from .prompt_util import PromptEmbedsCache, PromptEmbedsPair, PromptEmbedsSD3
+
+NUM_IMAGES_PER_PROMPT = 1
+MAX_GRAD_NORM = 0.2
+
+
+def check_supported(config: RootConfig, peft_type: str) -> None:
+    """The refusals, by name, before anything is loaded."""
+    if peft_type == "dora":
+        raise ValueError("--peft_type dora: DoRA on the SD3 transformer is not built (the MMDiT engine takes plain LoRA sites)")
+    if peft_type != "lora":
+        raise ValueError(f"peft_type must be lora, got {peft_type}")
+    if config.network.type == "c3lier":
+        raise ValueError("network.type c3lier: the SD3 transformer has no conv layers to adapt; use network.type lierla")
+    name = str(config.pretrained_model.name_or_path).lower()
+    if "3.5" in name or "sd3_5" in name or "sd35" in name:
+        raise ValueError(f"'{config.pretrained_model.name_or_path}': SD3.5 (qk_norm, dual attention layers) is not built; "
+                         f"this trainer takes the SD3-medium family")
+
+
+def frozen_steps(transformer, scheduler, timestep, latents, pair: PromptEmbedsPair, bs: int, guidance_scale: float):
+    """(positive, neutral, negative) stepped latents of three `predict_noise_sd3` calls with the network off, from ONE pass
+    over (unconditional, positive, neutral, negative): the unconditional half is the same in all three."""
+    embs = (pair.unconditional, pair.positive, pair.neutral, pair.negative)
+    ctx = torch.cat([e.text_embeds.repeat_interleave(bs, dim=0) for e in embs])
+    pooled = torch.cat([e.pooled_embeds.repeat_interleave(bs, dim=0) for e in embs])
+    n = 4 * latents.shape[0]
+    with torch.no_grad():
+        v = transformer(hidden_states=torch.cat([latents] * 4), timestep=[float(timestep)] * n, encoder_hidden_states=ctx,
+                        pooled_projections=pooled, multipliers=[0.0] * n, return_dict=False)[0]
+        u, rest = v[:latents.shape[0]], v[latents.shape[0]:].chunk(3)
+        return tuple(scheduler.step(u + guidance_scale * (c - u), timestep, latents, return_dict=False)[0] for c in rest)
+
+
+def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft_type="lora", rank=4, save_file=True,
+          models=None, fused_step=None, optimizer_kwargs=None, optimizer=None, context_stream=False, t5_tokens=256):
+    """The reference's `train(config, prompts, device, on_step_complete, peft_type, rank, save_file)`; the other arguments
+    are this package's (train_lora_xl.train): `models` a preloaded load_models_sd3 tuple, `fused_step` / `optimizer` /
+    `optimizer_kwargs` the optimiser choice, `context_stream` the 191-module form, `t5_tokens` the zero rows that stand in
+    for the T5 block.  Per-step losses are left in `network.training_losses`; `network.first_step` keeps iteration 0's draws
+    (latents, timesteps_to, gradient) for the parity test."""
+    check_supported(config, peft_type)
+    weight_dtype = config_util.parse_precision(config.train.precision)
+    save_weight_dtype = config_util.parse_precision(config.train.precision)
+    guidance_scale = config.train.cfg
+    tokenizers, text_encoders, transformer, noise_scheduler = models or model_util.load_models_sd3(
+        config.pretrained_model.name_or_path, weight_dtype=weight_dtype)
+    for te in text_encoders:  # (the stand-in towers of synthetic://tiny_sd3 are no nn.Modules: nothing to freeze)
+        te.to(device, weight_dtype)
+        if isinstance(te, torch.nn.Module):
+            te.requires_grad_(False).eval()
+    transformer.to(device, dtype=weight_dtype).requires_grad_(False).eval()
+    network = LoRANetwork(transformer, rank=rank, multiplier=1.0, train_method=config.network.training_method,
+                          context_stream=context_stream).to(device, dtype=weight_dtype)
+    if optimizer is None:
+        optimizer_name = "adamw"
+        okw = dict(lr=1e-4, weight_decay=1e-6)
+        okw.update(optimizer_kwargs or {})
+        optimizer = torch.optim.AdamW(network.parameters(), **okw)
+    else:
+        optimizer_name = optimizer
+        okw = dict(optimizer_kwargs or {})
+        optimizer = train_util.get_optimizer(optimizer_name)(network.parameters(), **okw)
+        okw.setdefault("lr", optimizer.defaults["lr"])
+    fused, spec = train_common.step_choice(fused_step, optimizer_name, okw)
+    lr_scheduler = torch.optim.lr_scheduler.CosineAnnealingLR(optimizer, T_max=50, eta_min=1e-6)
+    criteria = torch.nn.MSELoss()
+
+    cache = PromptEmbedsCache()
+    prompt_pairs = []
+    jd = transformer.cfg.joint_attention_dim
+    with torch.no_grad():
+        for settings in prompts:
+            for prompt in [settings.target, settings.positive, settings.neutral, settings.unconditional, settings.negative]:
+                if prompt is not None and cache[prompt] is None:
+                    te, pooled = train_util.encode_prompts_sd3(None, tokenizers, text_encoders, prompt, NUM_IMAGES_PER_PROMPT,
+                                                               t5_tokens, jd)
+                    cache[prompt] = PromptEmbedsSD3(te.to(device, weight_dtype), pooled.to(device, weight_dtype))
+            neg = cache[settings.negative] if settings.negative is not None else None
+            prompt_pairs.append(PromptEmbedsPair(criteria, cache[settings.target], cache[settings.positive],
+                                                 cache[settings.unconditional], cache[settings.neutral], neg, settings))
+    del tokenizers, text_encoders
+
+    tail = None
+    if fused:  # the native clip + optimiser step on the flat parameter (step._FusedStep owns the optimiser state)
+        from .step import _FusedStep
+        tail = _FusedStep(transformer, network, noise_scheduler, 1, okw["lr"], (0.9, 0.999), 1e-8, 0.0, MAX_GRAD_NORM, None, spec)
+    network.training_losses = []
+    network.first_step = None
+    for i in tqdm(range(config.train.iterations)):
+        with torch.no_grad():
+            noise_scheduler.set_timesteps(config.train.max_denoising_steps, device=device)
+            optimizer.zero_grad()
+            prompt_pair = prompt_pairs[torch.randint(0, len(prompt_pairs), (1,)).item()]
+            timesteps_to = torch.randint(1, config.train.max_denoising_steps, (1,)).item()
+            height, width = prompt_pair.resolution, prompt_pair.resolution
+            if prompt_pair.dynamic_resolution:
+                height, width = train_util.get_random_resolution_in_bucket(prompt_pair.resolution)
+            bs = prompt_pair.batch_size
+            latents = train_util.get_initial_latents_sd3(noise_scheduler, bs, height, width, 1).to(device, torch.float32)
+
+            def cond(e):
+                return dict(text_embeddings=train_util.concat_embeddings_sd3(prompt_pair.unconditional.text_embeds,
+                                                                             e.text_embeds, bs),
+                            add_text_embeddings=train_util.concat_embeddings_sd3(prompt_pair.unconditional.pooled_embeds,
+                                                                                 e.pooled_embeds, bs))
+
+            with network:  # the slightly denoised latents, under the adaptor
+                denoised_latents = train_util.diffusion_sd3(transformer, noise_scheduler, latents, **cond(prompt_pair.target),
+                                                            start_timesteps=0, total_timesteps=timesteps_to,
+                                                            guidance_scale=guidance_scale)
+            current_timestep = noise_scheduler.timesteps[timesteps_to]
+            positive_latents, neutral_latents, negative_latents = frozen_steps(
+                transformer, noise_scheduler, current_timestep, denoised_latents, prompt_pair, bs, guidance_scale)
+        with network:
+            target_latents = train_util.predict_noise_sd3(transformer, noise_scheduler, current_timestep, denoised_latents,
+                                                          **cond(prompt_pair.target), guidance_scale=guidance_scale)
+        loss = prompt_pair.loss(target_latents=target_latents, positive_latents=positive_latents,
+                                neutral_latents=neutral_latents, negative_latents=negative_latents)
+        loss.backward()
+        if i == 0:
+            network.first_step = dict(latents=latents.cpu(), timesteps_to=timesteps_to, denoised=denoised_latents.cpu(),
+                                      grad=network.flat.grad.detach().clone().cpu(), loss=float(loss.item()))
+        if tail is not None:
+            tail.grad.copy_(network.flat.grad)
+            tail._optimizer_tail(lr_scheduler.get_last_lr()[0])
+            network.flat.grad = None
+            optimizer.step()  # no gradients: a no-op that keeps torch's "optimizer before scheduler" order
+        else:
+            torch.nn.utils.clip_grad_norm_(network.parameters(), max_norm=MAX_GRAD_NORM)
+            optimizer.step()
+        lr_scheduler.step()
+        lv = float(loss.item())
+        network.training_losses.append(lv)
+        if save_file and train_common.checkpoint_due(i, config):
+            train_common.save_checkpoint(network, config, f"{i}steps", ".safetensors", save_weight_dtype)
+        if on_step_complete is not None:
+            on_step_complete(i)
+    if save_file:
+        train_common.save_checkpoint(network, config, "last", ".safetensors", save_weight_dtype)
+        return network
+    return network.get_state_dict(save_weight_dtype)
+
+
+def train_lora(target, positive, negative, unconditional, alpha=1.0, device=0, name=None, attributes=None, batch_size=1,
+               config_file="data/config-sd3.yaml", resolution=512, steps=None, on_step_complete=None, peft_type="lora", rank=4,
+               save_file=False, models=None, **train_kwargs):
+    """Programmatic entry (the reference's train_lora): the prompt settings built in memory (neutral = target, action
+    enhance), trained without writing a file unless save_file."""
+    config = config_util.load_config_from_yaml(config_file)
+    if steps is not None:
+        config.train.iterations = steps
+    train_common.apply_cli_overrides(config, argparse.Namespace(name=name, alpha=alpha, rank=rank, attributes=None))
+    settings = prompt_util.PromptSettings(target=target, positive=positive, negative=negative, unconditional=unconditional,
+                                          neutral=target, action="enhance", resolution=resolution, dynamic_resolution=False,
+                                          batch_size=batch_size)
+    dev = torch.device(f"cuda:{device}") if not isinstance(device, torch.device) else device
+    return train(config, [settings], dev, on_step_complete, peft_type, rank, save_file, models, **train_kwargs)
+
+
+def main(args):
+    config = config_util.load_config_from_yaml(args.config_file)
+    attributes = train_common.apply_cli_overrides(config, args)
+    check_supported(config, args.peft_type)
+    prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
+    device = train_common.launch_device(args)
+    return train(config, prompts, device, None, args.peft_type, args.rank, True, None, args.fused_step,
+                 optimizer=args.optimizer, context_stream=args.context_stream, t5_tokens=args.t5_tokens)
+
+
+def build_parser():
+    parser = argparse.ArgumentParser()
+    parser.add_argument("--config_file", required=False, default="data/config-sd3.yaml")
+    parser.add_argument("--alpha", type=float, required=True, help="LoRA weight.")
+    parser.add_argument("--rank", type=int, required=False, default=4, help="Rank of LoRA.")
+    parser.add_argument("--device", required=False, default=0, help="Device to train on.")
+    parser.add_argument("--name", type=str, required=False, default=None, help="Name of the slider.")
+    parser.add_argument("--attributes", type=str, required=False, default=None)
+    parser.add_argument("--peft_type", type=str, required=False, default="lora", help="lora (dora is refused)")
+    parser.add_argument("--context_stream", action="store_true",
+                        help="also adapt the context stream's add_q_proj / add_k_proj / add_v_proj / to_add_out")
+    parser.add_argument("--t5_tokens", type=int, default=256,
+                        help="zero rows that stand in for the T5 block of the prompt embedding (text_encoder_3=None)")
+    parser.add_argument("--optimizer", type=str, required=False, default=None,
+                        help="adam, adamw, lion or prodigy at the class's own defaults instead of the script's hard-coded "
+                             "AdamW(lr 1e-4, weight_decay 1e-6)")
+    train_common.add_fused_step_flags(parser)
+    return parser
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())

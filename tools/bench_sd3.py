@@ -4,7 +4,14 @@ restatement of the same network in the same dtype on the same GPU (F.linear, F.l
 the two arms alternating in one process.  Prints one JSON line per (size, dtype) with the algorithmic FLOP of a forward
 (GEMMs and attention, from the shapes) and the TF/s both arms reach, and writes them to --out.  No threshold.
 
-    python tools/bench_sd3.py [--rounds 3] [--iters 5] [--sizes 1024,512] [--dtypes fp16,bf16] [--out profiles/sd3_forward.json]"""
+`--train`: the slider step's differentiated part instead -- the trainable engine's saved forward + backward to the rank-4
+LoRA matrices of the 96 image-stream sites (`--context_stream`: all 191) next to torch-ROCm autograd through the same
+restatement with the same adaptor, same dtype, arms alternating; per (size, dtype) the ms of both arms, the engine's split
+into forward_save and backward (forward_save timed alone; backward = the pair minus it), the workspace bytes and the
+relative L2 distance of the two gradient vectors.
+
+    python tools/bench_sd3.py [--rounds 3] [--iters 5] [--sizes 1024,512] [--dtypes fp16,bf16] [--out profiles/sd3_forward.json]
+    python tools/bench_sd3.py --train [--sizes 512,1024] [--out profiles/sd3_train_n2_ctx333.json]"""
 import argparse
 import json
 import math
@@ -45,13 +52,20 @@ def forward_flop(cfg, n, Nx, Nc):
     return f + 2.0 * n * d * 2 * d + 2.0 * n * Nx * d * cfg.patch_size ** 2 * cfg.out_channels
 
 
-def torch_forward(sd, cfg, x, ts, ctx, pooled):
-    """The network in torch ops, in the dtype of `sd` (tests/mmdit_refs.py is the float64 form of the same graph)."""
+def torch_forward(sd, cfg, x, ts, ctx, pooled, lora=None, mults=None):
+    """The network in torch ops, in the dtype of `sd` (tests/mmdit_refs.py is the float64 form of the same graph).
+    lora: {module path: (down [r, in], up [out, r], alpha / r)} fp32 leaves, applied in the network's dtype at mults [n]."""
     n, dt = x.shape[0], ctx.dtype
     p, d, heads = cfg.patch_size, cfg.inner_dim, cfg.num_attention_heads
     gh, gw = x.shape[2] // p, x.shape[3] // p
     Nx = gh * gw
-    lin = lambda t, k: F.linear(t, sd[k + ".weight"], sd[k + ".bias"])
+
+    def lin(t, k):
+        y = F.linear(t, sd[k + ".weight"], sd[k + ".bias"])
+        if lora is not None and k in lora:
+            down, up, sc = lora[k]
+            y = y + (mults.to(dt) * sc).reshape([n] + [1] * (t.dim() - 1)) * F.linear(F.linear(t, down.to(dt)), up.to(dt))
+        return y
     half = torch.exp(-math.log(10000.0) * torch.arange(128, device=x.device, dtype=torch.float32) / 128)
     a = ts[:, None] * half[None]
     te = lin(F.silu(lin(torch.cat([a.cos(), a.sin()], 1).to(dt), "time_text_embed.timestep_embedder.linear_1")),
@@ -89,8 +103,77 @@ def torch_forward(sd, cfg, x, ts, ctx, pooled):
     return y.reshape(n, gh, gw, p, p, C).permute(0, 5, 1, 3, 2, 4).reshape(n, C, gh * p, gw * p).float()
 
 
+def train_rows(a, cfg, model):
+    """--train (module docstring)."""
+    from sliders_conceptmod_amd import lora as L
+    n, Nc = 2, 77 + a.t5_tokens
+    rows = []
+    for dname in a.dtypes.split(","):
+        dt = {"fp16": torch.float16, "bf16": torch.bfloat16}[dname]
+        model = model.to("cuda", dt).requires_grad_(False)
+        sd = {k: v.detach() for k, v in model.state_dict().items()}
+        torch.manual_seed(0)
+        net = L.LoRANetwork(model, rank=4, multiplier=1.0, train_method="full", context_stream=a.context_stream).to("cuda")
+        with torch.no_grad():
+            net.flat[net._n_down:].normal_(0, 0.05)
+        flat, nd = net.flat.detach(), net._n_down
+        for size in (int(s) for s in a.sizes.split(",")):
+            lat = size // 8
+            g = torch.Generator().manual_seed(1)
+            x = torch.randn(n, cfg.in_channels, lat, lat, generator=g).cuda()
+            ctx = torch.randn(n, Nc, cfg.joint_attention_dim, generator=g).to(dt).cuda()
+            pooled = torch.randn(n, cfg.pooled_projection_dim, generator=g).to(dt).cuda()
+            d_out = torch.randn(n, cfg.out_channels, lat, lat, generator=g).cuda()
+            ts, mults = [500.0] * n, [1.0, -2.0]
+            tsd, md = torch.tensor(ts, device="cuda"), torch.tensor(mults, device="cuda")
+            eng = model.engine(n, lat, lat, Nc, trainable=True)
+            grad = torch.zeros_like(flat)
+
+            def engine_pair():
+                eng.forward_save(x, ts, ctx, pooled, flat[:nd], flat[nd:], mults)
+                eng.backward(d_out, grad[:nd], grad[nd:])
+
+            def leaves():
+                return {l.target_path: (flat[l.off_down:l.off_down + 4 * l.in_dim].view(4, l.in_dim).clone().requires_grad_(True),
+                                        flat[nd + l.off_up:nd + l.off_up + l.out_dim * 4].view(l.out_dim, 4).clone().requires_grad_(True),
+                                        float(l.scale)) for l in net.unet_loras}
+            lv = leaves()
+
+            def torch_pair():
+                for dn, up, _ in lv.values():
+                    dn.grad = up.grad = None
+                (torch_forward(sd, cfg, x, tsd, ctx, pooled, lv, md) * d_out).sum().backward()
+
+            grad.zero_()
+            engine_pair()
+            torch.cuda.reset_peak_memory_stats()  # (the torch arm's peak, on top of what is resident: weights, the workspace)
+            torch_pair()
+            tg = torch.zeros_like(flat)
+            for l in net.unet_loras:
+                dn, up, _ = lv[l.target_path]
+                tg[l.off_down:l.off_down + 4 * l.in_dim] = dn.grad.reshape(-1)
+                tg[nd + l.off_up:nd + l.off_up + l.out_dim * 4] = up.grad.reshape(-1)
+            rel = float((grad - tg).norm() / tg.norm())
+            e_ms, f_ms, t_ms = [], [], []
+            for _ in range(a.rounds):
+                e_ms.append(timed(engine_pair, a.iters))
+                f_ms.append(timed(lambda: eng.forward_save(x, ts, ctx, pooled, flat[:nd], flat[nd:], mults), a.iters))
+                t_ms.append(timed(torch_pair, a.iters))
+            row = {"model": a.model, "mode": "train", "image": size, "dtype": dname, "n": n, "context_tokens": Nc,
+                   "lora_modules": len(net.unet_loras), "engine_ms": e_ms, "engine_forward_save_ms": f_ms,
+                   "engine_backward_ms": min(e_ms) - min(f_ms), "torch_ms": t_ms, "engine_vs_torch_grad_rel_l2": rel,
+                   "workspace_bytes": eng.workspace_bytes, "torch_peak_bytes": torch.cuda.max_memory_allocated()}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+        model._close_engines()
+        model.__dict__.pop("_lora_network", None)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--train", action="store_true", help="saved forward + backward to the LoRA matrices instead of the forward")
+    ap.add_argument("--context_stream", action="store_true", help="--train: all 191 modules instead of the 96 image-stream ones")
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--sizes", default="1024,512")
@@ -101,6 +184,12 @@ def main():
     a = ap.parse_args()
     cfg = M.sd3_medium_config() if a.model == "sd3" else M.tiny_sd3_config()
     model = M.init_synthetic_(M.SD3Transformer2DModel(cfg), seed=0)
+    if a.train:
+        rows = train_rows(a, cfg, model)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            json.dump(rows, open(a.out, "w"), indent=1)
+        return rows
     n, Nc = 2, 77 + a.t5_tokens
     rows = []
     for dname in a.dtypes.split(","):
