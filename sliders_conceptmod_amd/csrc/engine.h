@@ -1,6 +1,6 @@
-// The op core of every engine: runs a model's forward -- and the activation/LoRA-gradient backward of the two models that
-// are differentiated, the UNet and the CLIP text tower with LoRA sites -- as a stream
-// of hand-written gfx950 kernels (gemm.hip, attention.hip, norm.hip, elementwise.hip, lora.hip).  It names no model: each
+// The op core of every engine: runs a model's forward -- and the activation/LoRA-gradient backward of the models that are
+// differentiated (the UNet, the CLIP text tower with LoRA sites, the MMDiT), whose saved pass and backward scaffold is
+// written once here -- as a stream of hand-written gfx950 kernels (gemm.hip, attention.hip, norm.hip, elementwise.hip, lora.hip).  It names no model: each
 // (engine_unet.hip, engine_vae.hip, engine_clip.hip, engine_lpips.hip) is a `Model` with its config, layers and forward over these ops.
 //
 // Structure
@@ -48,6 +48,12 @@ struct Arena {
     if (off > cap) overflow = true;
     return p;
   }
+};
+
+// up to 64 floats handed over BY VALUE in the kernel arguments (copied into the kernarg segment at launch): host values
+// reach the device without a host buffer that must outlive the call (smi_engine::upload_floats)
+struct F64Args {
+  float v[64];
 };
 
 struct Ten {
@@ -290,6 +296,26 @@ struct smi_engine {
   float* d_up = nullptr;
   int n_ad = 0;     // adapted samples of the pass in flight (the last n_ad of n)
   int bw_skip = 0;  // ... of which the backward in flight leaves out the first bw_skip (zero gradient: tail backward)
+  // the saved (differentiated) pass of a model that has a backward, and the device table of the deferred weight-gradient
+  // jobs with what it holds (bump allocation gives the same addresses every step of a plan: uploaded once, then reused)
+  struct SavedPass {
+    bool valid = false;
+    int n = 0;  // adapted samples of the saved pass
+    std::vector<WgradJob> uploaded;
+    WgradJob* dev = nullptr;
+    size_t cap = 0;
+  } saved;
+  void alloc_job_table(size_t cap) {  // at build time; the model knows how many jobs its sites can push
+    saved.cap = cap;
+    saved.dev = (WgradJob*)pack_alloc(cap * sizeof(WgradJob));
+  }
+  // a backward consumes the saved pass, also where it fails half way: a tail backward has moved the tensors' arow0
+  void drop_tape() {
+    pinned.clear();
+    tape.clear();
+    saved.valid = false;
+    bw_skip = 0;
+  }
 
   size_t esz() const { return 2; }
 
@@ -476,17 +502,21 @@ struct smi_engine {
                 phase_live->H, phase_live->W, phase_live->cols);
       err = true;
     }
+    const bool keep = persist_next;
+    persist_next = false;
+    return borrowed(arena_alloc((size_t)rows * cols * (elt ? elt : esz()), keep), rows, cols, n, H, W);
+  }
+  // a tensor of the pass in flight over memory that is not allocated here: a buffer of the caller's, a view into another tensor
+  Ten* borrowed(const void* p, int64_t rows, int cols, int n = 0, int H = 0, int W = 0) {
     tens->emplace_back();
     Ten* t = &tens->back();
+    t->p = const_cast<void*>(p);
     t->rows = rows;
     t->cols = cols;
     t->n = n;
     t->H = H;
     t->W = W;
     t->arow0 = n > 0 ? (int64_t)(n - n_ad) * (rows / n) : 0;
-    const bool keep = persist_next;
-    persist_next = false;
-    t->p = arena_alloc((size_t)rows * cols * (elt ? elt : esz()), keep);
     return t;
   }
   int64_t MA(const Ten* t) const { return t->rows - t->arow0; }  // adapted rows
@@ -1026,13 +1056,9 @@ struct smi_engine {
     if (lora_active(L) || !(dry || gemm_geglu_supported(p.with_geglu(probe, 0)))) return geglu(linear(x, L));  // generic path
     Ten* out = new_ten(x->rows, L.out / 2, x->n, x->H, x->W);
     // the projection buffer holds the adapted rows only; virtual base so that row m lands at (m - arow0)
-    tens->emplace_back();
-    Ten* pj = &tens->back();
-    *pj = *x;
-    pj->cols = L.out;
-    pj->g = nullptr;
     char* pbuf = (char*)arena_alloc((size_t)(need_proj ? MA(x) : 1) * L.out * esz());
-    pj->p = pbuf - (size_t)x->arow0 * L.out * esz();
+    Ten* pj = borrowed(pbuf - (size_t)x->arow0 * L.out * esz(), x->rows, L.out, x->n, x->H, x->W);
+    pj->arow0 = x->arow0;
     p.C = pj->p;
     p.with_geglu(out->p, need_proj ? (int)x->arow0 : p.M);
     run_gemm(SMI_PROF_GEMM, p, gemm_flops(p), 2.0 * ((double)p.M * p.K + (double)p.N * p.K + 0.5 * (double)p.M * p.N), true,
@@ -1354,7 +1380,35 @@ struct smi_engine {
     return conv3x3(h, r.c2, nullptr, sc);
   }
 
-  // ---- whole passes: how one begins (forward only: arena 0, nothing adapted, nothing saved) and how every one ends
+  // ---- whole passes: how one begins and how every one ends
+  // a pass whose last n_adapted samples run under the adaptor.  save: it goes to arena 1 with a fresh tape and every tensor
+  // kept (no scratch alternation: begin_block does nothing while saving); else arena 0, and a saved pass stays as it is
+  void begin_pass(int n_adapted, bool save) {
+    n_ad = n_adapted;
+    cur = &arena[save ? 1 : 0];
+    cur->reset();
+    tens = &tens_[save ? 1 : 0];
+    tens->clear();
+    in_block = persist_next = false;
+    if (!save) {
+      scr[0].reset();
+      scr[1].reset();
+      if (dry) scr[0].cap = scr[1].cap = (size_t)-1;
+    } else {
+      drop_tape();
+    }
+    saving = save;
+  }
+  // the end of a saving forward: what its backward needs of the adaptor's state (the model keeps its own output tensors)
+  void keep_saved_pass(int n_adapted) {
+    saved.n = n_adapted;
+    bw_down = lora_down;
+    bw_up = lora_up;
+    bw_mult = mult;
+    bw_samp_on = samp_on;
+    saved.valid = true;
+  }
+  // (forward only: arena 0, nothing adapted, nothing saved)
   void begin_forward_only_pass() {
     n_ad = 0;
     cur = &arena[0];
@@ -1373,6 +1427,26 @@ struct smi_engine {
     }
     return err ? -1 : 0;
   }
+
+  // ---- the backward of a saved pass (engine.hip): a model's backward is begin_backward, its own loss scales,
+  // rebuild_saved_operands, its own output gradient, run_tape_and_weight_grads, end_pass("the backward (")
+  // the refusal (-4, `no_pass`: the model's message) when nothing is saved; else arena 1, the gradient buffers, the last
+  // n_live adapted samples of the saved pass, empty job and pin lists
+  int begin_backward(const char* no_pass, float* dd, float* du, int n_live);
+  // the 16-bit LoRA operands belong to the SAVED forward: an adapted no-grad pass in between may have rebuilt them with
+  // other parameters or another multiplier
+  void rebuild_saved_operands();
+  // the tape in reverse, then every LoRA weight gradient of the pass as one grouped launch per accumulator class off the
+  // device job table.  Drops the tape; not 0: the table failed (message set)
+  int run_tape_and_weight_grads();
+
+  // host floats by kernel argument, 64 per launch, ordered on the stream: dst0[i] (and dst1[i] unless NULL) = host[i] / divisor
+  int upload_floats(float* dst0, float* dst1, const float* host, int n, float divisor);
+  // per-sample multipliers of the coming pass: *mref = max |m_i|, sigma_i = m_i / mref to slot 0 of samp_mult_dev and, for a
+  // pass that will be saved, to slot 1.  All zero: *mref = 0 and nothing is uploaded
+  int set_sample_multipliers(const float* multipliers, int n, bool save, float* mref);
+  // the engine's own copy of the caller's site list (targets re-pointed at strings it owns) and the map by target
+  void register_sites(const smi_lora_site* s, int n_sites);
 };
 
 // from here on (the models' methods) the engine is the parameter `e`
@@ -1382,6 +1456,10 @@ struct smi_engine {
 // (engine.hip)  the end of every create: wait for the packing kernels, turn a failure into a message (`what` names the weights in it),
 // drop the weight table, which is only borrowed during creation
 int finish_create(smi_engine* e, const char* what, smi_engine** out);
+// (engine.hip)  a site list of plain Linear LoRA on attention projections: no DoRA, rank in [1, 16], every target ends with
+// one of `suffixes`; `who` prefixes the messages, `where` completes the last one with the allowed targets
+int check_linear_lora_sites(const char* who, const smi_lora_site* sites, int n_sites, std::initializer_list<const char*> suffixes,
+                            const char* where);
 // the forward-only engines (VAE encoder, VAE decoder, CLIP text and image towers): `setup` fills a fresh engine with its
 // kind, dtype, largest batch and its model; the workspace is [packed weights | arena 0]
 using Setup = std::function<void(smi_engine*)>;

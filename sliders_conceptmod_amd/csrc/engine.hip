@@ -1,5 +1,5 @@
-// What the op core (engine.h) keeps out of line: the weight-packing kernels with their two launchers, and the create /
-// plan path that the forward-only engines share.
+// What the op core (engine.h) keeps out of line: the weight-packing kernels with their two launchers, the saved pass and
+// backward scaffold of the differentiated models, and the create / plan path that the forward-only engines share.
 #include "engine.h"
 
 namespace {
@@ -65,7 +65,118 @@ __global__ void pack_conv_phase_kernel(const T* __restrict__ src, T* __restrict_
     dst[i] = from_f<T>(s);
   }
 }
+__global__ void set_floats_kernel(float* dst0, float* dst1, F64Args a, int n) {
+  const int i = threadIdx.x;
+  if (i < n) {
+    dst0[i] = a.v[i];
+    if (dst1) dst1[i] = a.v[i];
+  }
+}
 }  // namespace
+
+// ---- the saved pass and its backward: what every differentiated model shares ------------------------------------------
+#undef SMI_ENG
+#define SMI_ENG (*this)
+int smi_engine::upload_floats(float* dst0, float* dst1, const float* host, int n, float divisor) {
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    F64Args a;
+    const int cnt = n - i0 < 64 ? n - i0 : 64;
+    for (int i = 0; i < 64; ++i) a.v[i] = i < cnt ? host[i0 + i] / divisor : 0.f;
+    hipLaunchKernelGGL(set_floats_kernel, dim3(1), dim3(64), 0, stream, dst0 + i0, dst1 ? dst1 + i0 : (float*)nullptr, a, cnt);
+  }
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+int smi_engine::set_sample_multipliers(const float* multipliers, int n, bool save, float* mref) {
+  float m = 0.f;
+  for (int i = 0; i < n; ++i) m = fmaxf(m, fabsf(multipliers[i]));
+  *mref = m;
+  return m != 0.f ? upload_floats(samp_mult_dev, save ? samp_mult_dev + MAXS : nullptr, multipliers, n, m) : 0;
+}
+
+void smi_engine::register_sites(const smi_lora_site* s, int n_sites) {
+  sites.assign(s, s + n_sites);
+  site_names.resize(n_sites);
+  site_used.assign(n_sites, 0);
+  for (int i = 0; i < n_sites; ++i) {
+    site_names[i] = s[i].target;
+    sites[i].target = site_names[i].c_str();
+  }
+  for (int i = 0; i < n_sites; ++i) smap[site_names[i]] = &sites[i];
+}
+int check_linear_lora_sites(const char* who, const smi_lora_site* sites, int n_sites, std::initializer_list<const char*> suffixes,
+                            const char* where) {
+  for (int i = 0; i < n_sites; ++i) {
+    const std::string t = sites[i].target ? sites[i].target : "";
+    SMI_CHECK(sites[i].off_dora < 0, "%s: DoRA site '%s' -- plain LoRA sites only", who, t.c_str());
+    SMI_CHECK(sites[i].rank >= 1 && sites[i].rank <= 16, "%s: rank %d of '%s' outside [1, 16]", who, sites[i].rank, t.c_str());
+    bool ok = false;
+    for (const char* suf : suffixes) {
+      const size_t m = strlen(suf);
+      ok = ok || (t.size() > m && t.compare(t.size() - m, m, suf) == 0);
+    }
+    SMI_CHECK(ok, "%s: target '%s' -- sites sit on %s", who, t.c_str(), where);
+  }
+  return 0;
+}
+
+int smi_engine::begin_backward(const char* no_pass, float* dd, float* du, int n_live) {
+  if (!saved.valid && !dry) {
+    set_error("%s", no_pass);
+    return -4;
+  }
+  cur = &arena[1];
+  tens = &tens_[1];
+  in_block = persist_next = false;
+  saving = false;
+  d_down = dd;
+  d_up = du;
+  n_ad = n_live;  // rows per sample of a gradient buffer = its rows / n_ad
+  wjobs.clear();
+  pinned.clear();
+  bw_skip = saved.n - n_live;
+  return 0;
+}
+void smi_engine::rebuild_saved_operands() {
+  if (!prep_sites.empty() && bw_down && bw_up && bw_mult != 0.f)
+    RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(dtype, prep_sites_dev, (int)prep_sites.size(), bw_down, bw_up, lora_shadow, stream));
+  mult = bw_mult;
+}
+int smi_engine::run_tape_and_weight_grads() {
+  for (auto it = tape.rbegin(); it != tape.rend(); ++it) (*it)();
+  int rc = 0;
+  if (!wjobs.empty() && !err) {
+    wgrad_grouped_finish(wjobs);
+    if (!dry) {
+      const bool same = saved.uploaded.size() == wjobs.size() &&
+                        memcmp(saved.uploaded.data(), wjobs.data(), wjobs.size() * sizeof(WgradJob)) == 0;
+      if (wjobs.size() > saved.cap) {
+        set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", wjobs.size(), saved.cap);
+        rc = -1;
+      } else if (!same) {
+        saved.uploaded = wjobs;
+        if (hipMemcpyAsync(saved.dev, saved.uploaded.data(), wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice, stream) !=
+            hipSuccess) {
+          set_error("hipMemcpyAsync (weight-gradient job table) failed");
+          saved.uploaded.clear();  // (the device table holds nothing that a later backward may take for its own)
+          rc = -1;
+        }
+      }
+      if (rc == 0) {
+        double bytes = 0.0, flops = 0.0;
+        for (const auto& j : wjobs) {
+          bytes += (double)(j.M - j.m_begin) * j.K * 2.0;
+          flops += 2.0 * (j.M - j.m_begin) * j.K * j.r;
+        }
+        RUNP(SMI_PROF_LORA, flops, bytes, launch_lora_wgrad_grouped(dtype, wjobs, saved.dev, stream));
+      }
+    }
+  }
+  drop_tape();
+  return rc;
+}
+#undef SMI_ENG
+#define SMI_ENG e
 
 int smi::launch_pack_conv_phase(int dtype, const void* src, void* dst, int Cout, int Cin, hipStream_t stream) {
   const int64_t total = (int64_t)16 * Cout * Cin;

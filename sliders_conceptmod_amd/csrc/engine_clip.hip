@@ -6,18 +6,6 @@
 
 namespace {
 
-// per-sample multiplier ratios travel in kernel arguments, 64 per launch, ordered on the engine's stream (as the UNet's)
-struct MultArgs {
-  float v[64];
-};
-__global__ void clip_set_mults_kernel(float* dst0, float* dst1, MultArgs a, int n) {
-  const int i = threadIdx.x;
-  if (i < n) {
-    dst0[i] = a.v[i];
-    if (dst1) dst1[i] = a.v[i];
-  }
-}
-
 struct CLayer {
   Norm n1, n2;
   Lin qkv, out, fc1, fc2;
@@ -61,12 +49,7 @@ struct ClipText : Model {
   const void* pos = nullptr;
   // a tower created with LoRA sites (smi_clip_lora_create): arena 1 holds the saved pass and its backward
   bool trainable = false;
-  bool tape_valid = false;
-  int bw_n = 0;                                      // samples of the saved pass (all adapted)
-  Ten *out_last = nullptr, *out_pen = nullptr;       // hidden_states[-1] (no final norm) and [-2] of the saved pass
-  std::vector<WgradJob> wjobs_uploaded;              // the device table of the deferred weight-gradient jobs, as in the UNet
-  WgradJob* wjobs_dev = nullptr;
-  size_t wjobs_cap = 0;
+  Ten *out_last = nullptr, *out_pen = nullptr;  // hidden_states[-1] (no final norm) and [-2] of the saved pass
   explicit ClipText(const smi_clip_config& c, bool train = false) : cfg(c), trainable(train) {}
 
   void build(smi_engine& e) override {
@@ -85,8 +68,7 @@ struct ClipText : Model {
     e.finish_lora();
     e.gscale = (float*)e.pack_alloc(e.GSCALE_FLOATS * sizeof(float));
     e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
-    wjobs_cap = 2 * e.sites.size() + 8;  // a fused q|k|v pushes at most 4 jobs for its 3 sites, out_proj 2
-    wjobs_dev = (WgradJob*)e.pack_alloc(wjobs_cap * sizeof(WgradJob));
+    e.alloc_job_table(2 * e.sites.size() + 8);  // a fused q|k|v pushes at most 4 jobs for its 3 sites, out_proj 2
     for (size_t i = 0; i < e.sites.size(); ++i)
       if (!e.site_used[i] && !e.err) {
         set_error("LoRA target '%s' is not a layer of this text tower", e.site_names[i].c_str());
@@ -98,7 +80,7 @@ struct ClipText : Model {
     forward(e, e.max_n, nullptr, nullptr, (void*)16, (void*)16, (void*)16);
   }
 
-  // the pass itself; whoever calls has begun it (begin_forward_only_pass / begin_adapted_pass)
+  // the pass itself; whoever calls has begun it (begin_forward_only_pass, or begin_pass with every sample adapted)
   int forward(smi_engine& e, int n, const int* ids, const int* eos_pos, void* last_hidden, void* penultimate,
               void* pooled, void* last_layer_out = nullptr) {
     const int L = cfg.max_positions, d = cfg.hidden_size;
@@ -118,12 +100,7 @@ struct ClipText : Model {
     if (e.saving) {
       out_last = h;
       out_pen = pen;
-      bw_n = n;
-      e.bw_down = e.lora_down;
-      e.bw_up = e.lora_up;
-      e.bw_mult = e.mult;
-      e.bw_samp_on = e.samp_on;
-      tape_valid = true;
+      e.keep_saved_pass(n);
     }
     {
       e.saving = false;  // neither output below is differentiated: the final norm and the projection stay off the tape
@@ -139,79 +116,25 @@ struct ClipText : Model {
     return e.end_pass("this call (");
   }
 
-  // an adapted pass of n samples, every one under the adaptor: arena 1 and a fresh tape when it is saved, else arena 0
-  void begin_adapted_pass(smi_engine& e, int n, bool save) {
-    e.n_ad = n;
-    e.cur = &e.arena[save ? 1 : 0];
-    e.cur->reset();
-    e.in_block = e.persist_next = false;
-    e.tens = &e.tens_[save ? 1 : 0];
-    e.tens->clear();
-    if (save) drop_tape(e);
-    e.saving = save;
-  }
-  void drop_tape(smi_engine& e) {
-    e.pinned.clear();
-    e.tape.clear();
-    tape_valid = false;
-    e.bw_skip = 0;
-  }
-
-  // UNet::backward without the UNet parts: one power-of-two loss scale per sample, the 16-bit LoRA operands rebuilt from
-  // the SAVED parameters, the tape in reverse, one grouped weight-gradient launch.  which 0: d_hidden is the gradient of
-  // hidden_states[-1] (the last layer's output, no final norm); 1: of hidden_states[-2], and the last layer's closures
-  // see no gradient -- its sites get none.  A backward consumes the saved pass.
+  // the shared backward (engine.h) with this model's two parts: which 0: d_hidden is the gradient of hidden_states[-1] (the
+  // last layer's output, no final norm); 1: of hidden_states[-2], and the last layer's closures see no gradient -- its
+  // sites get none.  One power-of-two loss scale per sample.  A backward consumes the saved pass.
   int backward(smi_engine& e, int which, const float* d_hidden, float* dd, float* du) {
-    if (!tape_valid && !e.dry) {
-      set_error("smi_clip_backward: no saved forward pass (call smi_clip_forward_lora with save_for_backward=1 first)");
-      return -4;
-    }
-    e.cur = &e.arena[1];
-    e.tens = &e.tens_[1];
-    e.d_down = dd;
-    e.d_up = du;
-    e.d_ctx = nullptr;
-    e.n_ad = bw_n;
+    if (const int rc = e.begin_backward("smi_clip_backward: no saved forward pass (call smi_clip_forward_lora with save_for_backward=1 first)",
+                                        dd, du, e.saved.n))
+      return rc;
     Ten* y = which == 0 ? out_last : out_pen;
     if (!y->ng) {  // adaptor off, or nothing adapted upstream of hidden_states[-2]: the gradient is zero
-      drop_tape(e);
+      e.drop_tape();
       return 0;
     }
-    const int n = bw_n, L = cfg.max_positions, d = cfg.hidden_size;
-    e.wjobs.clear();
-    e.pinned.clear();
-    e.bw_skip = 0;
+    const int n = e.saved.n, L = cfg.max_positions, d = cfg.hidden_size;
     RUN(launch_grad_scale(d_hidden, n, (int64_t)L * d, e.gscale, e.MAXS, e.stream));
-    if (!e.prep_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f)
-      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.bw_down, e.bw_up, e.lora_shadow, e.stream));
-    e.mult = e.bw_mult;
+    e.rebuild_saved_operands();
     y->g = e.alloc_t(e.MA(y), d);
     // f32 [n, L d] -> 16-bit rows, sample j x its loss scale: the cast of the UNet's d_eps with one "channel"
     RUN(launch_nchw_to_nhwc_scaled(e.dtype, d_hidden, y->g, n, 1, L * d, 1, e.gscale, e.stream));
-    for (auto it = e.tape.rbegin(); it != e.tape.rend(); ++it) (*it)();
-    if (!e.wjobs.empty() && !e.err) {
-      wgrad_grouped_finish(e.wjobs);
-      if (!e.dry) {
-        if (e.wjobs.size() > wjobs_cap) {
-          set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", e.wjobs.size(), wjobs_cap);
-          drop_tape(e);
-          return -1;
-        }
-        const bool same = wjobs_uploaded.size() == e.wjobs.size() &&
-                          memcmp(wjobs_uploaded.data(), e.wjobs.data(), e.wjobs.size() * sizeof(WgradJob)) == 0;
-        if (!same) {  // bump allocation gives the same addresses every step: uploaded once, then reused
-          wjobs_uploaded = e.wjobs;
-          if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), e.wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
-                             e.stream) != hipSuccess) {
-            set_error("hipMemcpyAsync (weight-gradient job table) failed");
-            drop_tape(e);
-            return -1;
-          }
-        }
-        RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_wgrad_grouped(e.dtype, e.wjobs, wjobs_dev, e.stream));
-      }
-    }
-    drop_tape(e);
+    if (e.run_tape_and_weight_grads()) return -1;
     return e.end_pass("the backward (");
   }
 };
@@ -308,30 +231,14 @@ int check_clip_lora(const smi_clip_config* c, const smi_lora_site* sites, int n_
             "smi_clip_lora: head_dim %d / %d positions -- the causal attention backward takes head_dim 64 and at most 128 "
             "positions", c->hidden_size / c->num_heads, c->max_positions);
   SMI_CHECK(batch <= smi_engine::MAXS, "smi_clip_lora: batch %d exceeds the %d per-sample multipliers", batch, smi_engine::MAXS);
-  for (int i = 0; i < n_sites; ++i) {
-    const std::string t = sites[i].target ? sites[i].target : "";
-    SMI_CHECK(sites[i].off_dora < 0, "smi_clip_lora: DoRA site '%s' -- the text tower takes plain LoRA sites only", t.c_str());
-    SMI_CHECK(sites[i].rank >= 1 && sites[i].rank <= 16, "smi_clip_lora: rank %d of '%s' outside [1, 16]", sites[i].rank, t.c_str());
-    bool ok = false;
-    for (const char* suf : {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj", ".self_attn.out_proj"}) {
-      const size_t m = strlen(suf);
-      ok = ok || (t.size() > m && t.compare(t.size() - m, m, suf) == 0);
-    }
-    SMI_CHECK(ok, "smi_clip_lora: target '%s' -- sites sit on self_attn.{q,k,v}_proj and self_attn.out_proj", t.c_str());
-  }
-  return 0;
+  return check_linear_lora_sites("smi_clip_lora", sites, n_sites,
+                                 {".self_attn.q_proj", ".self_attn.k_proj", ".self_attn.v_proj", ".self_attn.out_proj"},
+                                 "self_attn.{q,k,v}_proj and self_attn.out_proj");
 }
 ClipText* clip_lora_setup(smi_engine* e, const smi_clip_config* cfg, const smi_lora_site* sites, int n_sites, int batch) {
   ClipText* t = new ClipText(*cfg, true);
   e->hold(smi_engine::CLIP_TEXT, t, cfg->dtype, batch);
-  e->sites.assign(sites, sites + n_sites);
-  e->site_names.resize(n_sites);
-  e->site_used.assign(n_sites, 0);
-  for (int i = 0; i < n_sites; ++i) {
-    e->site_names[i] = sites[i].target;
-    e->sites[i].target = e->site_names[i].c_str();
-  }
-  for (int i = 0; i < n_sites; ++i) e->smap[e->site_names[i]] = &e->sites[i];
+  e->register_sites(sites, n_sites);
   return t;
 }
 // dry run: out = {packed weights, arena 0 (the largest no-grad pass), arena 1 (a saved pass and its backward)}
@@ -342,10 +249,10 @@ int clip_lora_plan(const smi_clip_config* cfg, const smi_lora_site* sites, int n
   t.build_trainable(e);
   if (e.err) return -1;
   out[0] = align_up(e.wpack.peak, 4096);
-  t.begin_adapted_pass(e, batch, false);  // the adapted no-grad pass allocates what the plain one does, and xa
+  e.begin_pass(batch, false);  // the adapted no-grad pass allocates what the plain one does, and xa
   t.forward(e, batch, nullptr, nullptr, (void*)16, (void*)16, (void*)16, (void*)16);
   out[1] = align_up(e.arena[0].peak, 4096);
-  t.begin_adapted_pass(e, batch, true);
+  e.begin_pass(batch, true);
   t.forward(e, batch, nullptr, nullptr, (void*)16, (void*)16, (void*)16, (void*)16);
   t.backward(e, 0, nullptr, nullptr, nullptr);
   out[2] = align_up(e.arena[1].peak, 4096);
@@ -460,21 +367,11 @@ int smi_clip_forward_lora(smi_engine* e, int n, const int32_t* ids, const int32_
   SMI_CHECK(lora_down_flat && lora_up_flat && multipliers, "smi_clip_forward_lora: lora_down_flat, lora_up_flat and multipliers are required");
   SMI_CHECK(!pooled || eos_pos, "pooled output needs eos_pos");
   e->err = false;
-  float mref = 0.f;
-  for (int i = 0; i < n; ++i) mref = fmaxf(mref, fabsf(multipliers[i]));
   // every adapted pass takes the per-sample route (sigma_i = m_i / max |m|), so that a sample gives the same bits alone and
   // in a batch; all multipliers 0 is the frozen tower
-  if (mref != 0.f) {
-    for (int i0 = 0; i0 < n; i0 += 64) {
-      MultArgs a;
-      const int cnt = n - i0 < 64 ? n - i0 : 64;
-      for (int i = 0; i < 64; ++i) a.v[i] = i < cnt ? multipliers[i0 + i] / mref : 0.f;
-      hipLaunchKernelGGL(clip_set_mults_kernel, dim3(1), dim3(64), 0, e->stream, e->samp_mult_dev + i0,
-                         save_for_backward ? e->samp_mult_dev + smi_engine::MAXS + i0 : (float*)nullptr, a, cnt);
-    }
-    SMI_HIP(hipGetLastError());
-  }
-  t->begin_adapted_pass(*e, n, save_for_backward != 0);
+  float mref = 0.f;
+  if (const int rc = e->set_sample_multipliers(multipliers, n, save_for_backward != 0, &mref)) return rc;
+  e->begin_pass(n, save_for_backward != 0);
   e->lora_down = lora_down_flat;
   e->lora_up = lora_up_flat;
   e->mult = mref;

@@ -12,26 +12,8 @@
 
 namespace {
 
-// per-sample host values (multiplier ratios, timesteps) travel in kernel arguments, 64 per launch, ordered on the stream
-struct ValArgs {
-  float v[64];
-};
-__global__ void mmdit_set_vals_kernel(float* dst, ValArgs a, int n) {
-  const int i = threadIdx.x;
-  if (i < n) dst[i] = a.v[i];
-}
 const void* mod_row(const smi_engine& e, const Ten* mod, const Ten* x) {  // mod's row of x's first adapted sample
   return (const char*)mod->p + (size_t)(x->n > 0 ? x->arow0 / (x->rows / x->n) : 0) * mod->cols * e.esz();
-}
-int upload_vals(smi_engine& e, float* dst, const float* host, int n, float div) {
-  for (int i0 = 0; i0 < n; i0 += 64) {
-    ValArgs a;
-    const int cnt = n - i0 < 64 ? n - i0 : 64;
-    for (int i = 0; i < 64; ++i) a.v[i] = i < cnt ? host[i0 + i] / div : 0.f;
-    hipLaunchKernelGGL(mmdit_set_vals_kernel, dim3(1), dim3(64), 0, e.stream, dst + i0, a, cnt);
-  }
-  SMI_HIP(hipGetLastError());
-  return 0;
 }
 
 // ---- ops --------------------------------------------------------------------------------------------------------------
@@ -151,12 +133,7 @@ struct MMDiT : Model {
   // an engine made by smi_mmdit_train_create: transposed copies of the Linears on the gradient path, and arena 1 for the
   // saved pass and its backward
   bool trainable = false;
-  bool tape_valid = false;
-  int bw_n = 0;                          // samples of the saved pass (all adapted)
-  Ten* out_rows = nullptr;               // proj_out's output of the saved pass: where the backward starts
-  std::vector<WgradJob> wjobs_uploaded;  // the device table of the deferred weight-gradient jobs, as in the CLIP tower
-  WgradJob* wjobs_dev = nullptr;
-  size_t wjobs_cap = 0;
+  Ten* out_rows = nullptr;  // proj_out's output of the saved pass: where the backward starts
   MMDiT(const smi_mmdit_config& c, int h, int w, bool train = false) : cfg(c), H(h), W(w), trainable(train) {}
   int d() const { return cfg.num_heads * cfg.attention_head_dim; }
   int gh() const { return H / cfg.patch_size; }
@@ -208,10 +185,8 @@ struct MMDiT : Model {
     // (a backward keeps its per-sample loss scales in the whole block)
     e.gscale = (float*)e.pack_alloc((trainable ? (size_t)e.GSCALE_FLOATS : 256) * sizeof(float));
     e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
-    if (trainable) {
-      wjobs_cap = 2 * e.sites.size() + 8;  // a fused q|k|v pushes at most 4 jobs for its 3 sites, an output projection 2
-      wjobs_dev = (WgradJob*)e.pack_alloc(wjobs_cap * sizeof(WgradJob));
-    }
+    // a fused q|k|v pushes at most 4 jobs for its 3 sites, an output projection 2
+    if (trainable) e.alloc_job_table(2 * e.sites.size() + 8);
     for (size_t i = 0; i < e.sites.size(); ++i)
       if (!e.site_used[i] && !e.err) {
         set_error("LoRA target '%s' is not an attention projection of this transformer", e.site_names[i].c_str());
@@ -230,48 +205,21 @@ struct MMDiT : Model {
     return gate_residual(e, h, f, mod, 5 * D);
   }
 
-  void drop_tape(smi_engine& e) {
-    e.pinned.clear();
-    e.tape.clear();
-    tape_valid = false;
-    e.bw_skip = 0;
-  }
-
-  // every sample under the adaptor (e.mult, the per-sample ratios already on the device).  save: the pass goes to arena 1 with
-  // a fresh tape and every tensor kept (no scratch alternation: begin_block does nothing while saving); else arena 0, and a
-  // saved pass stays as it is
+  // every sample under the adaptor (e.mult, the per-sample ratios already on the device); save: smi_engine::begin_pass
   int forward(smi_engine& e, int n, const float* sample, const float* timesteps_host, const void* ctx, const void* pooled,
               float* out, bool save = false) {
     const int D = d(), P = cfg.patch_size, Nx = gh() * gw(), Nc = cfg.context_len, heads = cfg.num_heads;
-    e.n_ad = n;
-    e.cur = &e.arena[save ? 1 : 0];
-    e.cur->reset();
-    if (!save) {
-      e.scr[0].reset();
-      e.scr[1].reset();
-      if (e.dry) e.scr[0].cap = e.scr[1].cap = (size_t)-1;
-    }
-    e.in_block = e.persist_next = false;
-    e.tens = &e.tens_[save ? 1 : 0];
-    e.tens->clear();
-    if (save) drop_tape(e);
-    e.saving = save;
+    e.begin_pass(n, save);
     if (!e.prep_sites.empty() && (e.dry || (e.lora_down && e.lora_up && e.mult != 0.f)))
       RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.lora_down, e.lora_up, e.lora_shadow, e.stream));
 
     // ---- conditioning vector: temb = time MLP(sinusoid(t)) + text MLP(pooled); every modulation reads silu(temb)
     float* tvals = e.alloc_f32(n);
-    if (!e.dry && !e.err && upload_vals(e, tvals, timesteps_host, n, 1.f) != 0) e.err = true;
+    if (!e.dry && !e.err && e.upload_floats(tvals, nullptr, timesteps_host, n, 1.f) != 0) e.err = true;
     Ten* ts = e.new_ten(n, 256, n, 1, 1);
     RUN(launch_timestep_embed(e.dtype, tvals, ts->p, n, 256, e.stream));
     Ten* te = e.linear(e.silu(e.linear(ts, t1)), t2);
-    e.tens->emplace_back();
-    Ten* pl = &e.tens->back();
-    pl->p = const_cast<void*>(pooled);
-    pl->rows = n;
-    pl->cols = cfg.pooled_projection_dim;
-    pl->n = n;
-    pl->H = pl->W = 1;
+    Ten* pl = e.borrowed(pooled, n, cfg.pooled_projection_dim, n, 1, 1);
     Ten* temb = e.linear(e.silu(e.linear(pl, p1)), p2, te);
     Ten* st = e.silu(temb);
 
@@ -281,14 +229,7 @@ struct MMDiT : Model {
     Ten* pe = e.linear(pm, patch);
     Ten* x = e.new_ten(pe->rows, D, n, Nx, 1);
     RUNP(SMI_PROF_ELEM, 0.0, 4.0 * x->rows * D, launch_sd3_add_pos(e.dtype, pe->p, pos, x->p, n, gh(), gw(), D, cfg.pos_embed_max_size, e.stream));
-    e.tens->emplace_back();
-    Ten* ci = &e.tens->back();
-    ci->p = const_cast<void*>(ctx);
-    ci->rows = (int64_t)n * Nc;
-    ci->cols = cfg.joint_attention_dim;
-    ci->n = n;
-    ci->H = Nc;
-    ci->W = 1;
+    Ten* ci = e.borrowed(ctx, (int64_t)n * Nc, cfg.joint_attention_dim, n, Nc, 1);
     Ten* c = e.linear(ci, ctx_in);
 
     // ---- joint blocks.  Block k allocates from scratch region k & 1 and reads block k - 1's two outputs in the other one
@@ -316,80 +257,31 @@ struct MMDiT : Model {
     if (save) {
       e.saving = false;
       out_rows = y;
-      bw_n = n;
-      e.bw_down = e.lora_down;
-      e.bw_up = e.lora_up;
-      e.bw_mult = e.mult;
-      e.bw_samp_on = e.samp_on;
-      tape_valid = true;
+      e.keep_saved_pass(n);
     }
     if (!save && !e.dry && (e.scr[0].overflow || e.scr[1].overflow)) e.err = true;
     return e.end_pass("this call (");
   }
 
-  // ClipText::backward for this model: one power-of-two loss scale per sample from d_out, un-patchify's inverse into the
-  // gradient of proj_out's rows, the 16-bit LoRA operands rebuilt from the SAVED parameters, the tape in reverse, one grouped
-  // weight-gradient launch (+= into dd / du).  A backward consumes the saved pass
+  // the shared backward (engine.h) with this model's part: one power-of-two loss scale per sample from d_out, and
+  // un-patchify's inverse into the gradient of proj_out's rows (+= into dd / du).  A backward consumes the saved pass
   int backward(smi_engine& e, const float* d_out, float* dd, float* du) {
-    if (!tape_valid && !e.dry) {
-      set_error("smi_mmdit_backward: no saved forward pass (call smi_mmdit_forward_save first)");
-      return -4;
-    }
-    e.cur = &e.arena[1];
-    e.tens = &e.tens_[1];
-    e.in_block = e.persist_next = false;
-    e.saving = false;
-    e.d_down = dd;
-    e.d_up = du;
-    e.d_ctx = nullptr;
-    e.n_ad = bw_n;
+    if (const int rc = e.begin_backward("smi_mmdit_backward: no saved forward pass (call smi_mmdit_forward_save first)", dd, du, e.saved.n))
+      return rc;
     Ten* y = out_rows;
     if (!y->ng || (!e.dry && (!dd || !du))) {  // adaptor off in the saved pass, or no buffers to add to: nothing to do
-      drop_tape(e);
+      e.drop_tape();
       return 0;
     }
-    const int n = bw_n;
-    e.wjobs.clear();
-    e.pinned.clear();
-    e.bw_skip = 0;
+    const int n = e.saved.n;
     RUN(launch_grad_scale(d_out, n, (int64_t)cfg.out_channels * H * W, e.gscale, e.MAXS, e.stream));
-    if (!e.prep_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f)
-      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.bw_down, e.bw_up, e.lora_shadow, e.stream));
-    e.mult = e.bw_mult;
+    e.rebuild_saved_operands();
     y->g = e.alloc_t(e.MA(y), y->cols);
     RUN(launch_sd3_unpatchify_bwd(e.dtype, d_out, y->g, n, cfg.out_channels, gh(), gw(), cfg.patch_size, e.gscale, e.stream));
-    for (auto it = e.tape.rbegin(); it != e.tape.rend(); ++it) (*it)();
-    if (!e.wjobs.empty() && !e.err) {
-      wgrad_grouped_finish(e.wjobs);
-      if (!e.dry) {
-        if (e.wjobs.size() > wjobs_cap) {
-          set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", e.wjobs.size(), wjobs_cap);
-          drop_tape(e);
-          return -1;
-        }
-        const bool same = wjobs_uploaded.size() == e.wjobs.size() &&
-                          memcmp(wjobs_uploaded.data(), e.wjobs.data(), e.wjobs.size() * sizeof(WgradJob)) == 0;
-        if (!same) {  // bump allocation gives the same addresses every step: uploaded once, then reused
-          wjobs_uploaded = e.wjobs;
-          if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), e.wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
-                             e.stream) != hipSuccess) {
-            set_error("hipMemcpyAsync (weight-gradient job table) failed");
-            drop_tape(e);
-            return -1;
-          }
-        }
-        RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_wgrad_grouped(e.dtype, e.wjobs, wjobs_dev, e.stream));
-      }
-    }
-    drop_tape(e);
+    if (e.run_tape_and_weight_grads()) return -1;
     return e.end_pass("the backward (");
   }
 };
-
-bool ends_with(const std::string& t, const char* suf) {
-  const size_t m = strlen(suf);
-  return t.size() > m && t.compare(t.size() - m, m, suf) == 0;
-}
 
 int check_mmdit(const smi_mmdit_config* c, const smi_lora_site* sites, int n_sites, int batch, int h, int w) {
   SMI_CHECK(c != nullptr, "config is NULL");
@@ -417,32 +309,18 @@ int check_mmdit(const smi_mmdit_config* c, const smi_lora_site* sites, int n_sit
             "MMDiT config: joint_attention_dim %% 8, pooled_projection_dim %% 8, context_len >= 1");
   SMI_CHECK(batch <= smi_engine::MAXS, "MMDiT: batch %d exceeds the %d per-sample multipliers", batch, smi_engine::MAXS);
   SMI_CHECK(n_sites == 0 || sites, "MMDiT: n_sites %d without sites", n_sites);
-  for (int i = 0; i < n_sites; ++i) {
-    const std::string t = sites[i].target ? sites[i].target : "";
-    SMI_CHECK(sites[i].off_dora < 0, "MMDiT: DoRA site '%s' -- the transformer takes plain LoRA sites only", t.c_str());
-    SMI_CHECK(sites[i].rank >= 1 && sites[i].rank <= 16, "MMDiT: rank %d of '%s' outside [1, 16]", sites[i].rank, t.c_str());
-    bool ok = false;
-    for (const char* suf : {".attn.to_q", ".attn.to_k", ".attn.to_v", ".attn.to_out.0", ".attn.add_q_proj", ".attn.add_k_proj",
-                            ".attn.add_v_proj", ".attn.to_add_out"})
-      ok = ok || ends_with(t, suf);
-    SMI_CHECK(ok, "MMDiT: target '%s' -- sites sit on the attention projections (attn.to_q/to_k/to_v/to_out.0, "
-              "attn.add_q_proj/add_k_proj/add_v_proj/to_add_out) only", t.c_str());
-  }
-  return 0;
+  return check_linear_lora_sites("MMDiT", sites, n_sites,
+                                 {".attn.to_q", ".attn.to_k", ".attn.to_v", ".attn.to_out.0", ".attn.add_q_proj",
+                                  ".attn.add_k_proj", ".attn.add_v_proj", ".attn.to_add_out"},
+                                 "the attention projections (attn.to_q/to_k/to_v/to_out.0, "
+                                 "attn.add_q_proj/add_k_proj/add_v_proj/to_add_out) only");
 }
 
 MMDiT* mmdit_setup(smi_engine* e, const smi_mmdit_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w,
                    bool train = false) {
   MMDiT* m = new MMDiT(*cfg, h, w, train);
   e->hold(smi_engine::MMDIT, m, cfg->dtype, batch);
-  e->sites.assign(sites, sites + n_sites);
-  e->site_names.resize(n_sites);
-  e->site_used.assign(n_sites, 0);
-  for (int i = 0; i < n_sites; ++i) {
-    e->site_names[i] = sites[i].target;
-    e->sites[i].target = e->site_names[i].c_str();
-  }
-  for (int i = 0; i < n_sites; ++i) e->smap[e->site_names[i]] = &e->sites[i];
+  e->register_sites(sites, n_sites);
   return m;
 }
 // dry run: out = {packed weights, persistent region of arena 0, one scratch region, arena 1}; arena 0 is out[1] + 2 out[2];
@@ -488,10 +366,7 @@ int mmdit_run(smi_engine* e, const char* who, int n, const float* sample, const 
   // Every adapted pass takes the per-sample route (sigma_i = m_i / max |m|): a sample gives the same bits alone and in a batch
   float mref = 0.f;
   if (lora_down_flat && lora_up_flat && multipliers && !e->prep_sites.empty())
-    for (int i = 0; i < n; ++i) mref = fmaxf(mref, fabsf(multipliers[i]));
-  if (mref != 0.f && upload_vals(*e, e->samp_mult_dev, multipliers, n, mref)) return -2;
-  // (slot 1 keeps the saved pass's ratios for its backward)
-  if (save && mref != 0.f && upload_vals(*e, e->samp_mult_dev + smi_engine::MAXS, multipliers, n, mref)) return -2;
+    if (const int rc = e->set_sample_multipliers(multipliers, n, save, &mref)) return rc;
   e->lora_down = mref != 0.f ? lora_down_flat : nullptr;
   e->lora_up = mref != 0.f ? lora_up_flat : nullptr;
   e->mult = mref;

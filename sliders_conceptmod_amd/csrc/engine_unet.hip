@@ -4,18 +4,6 @@
 
 namespace {
 
-// up to 64 floats handed over BY VALUE in the kernel arguments (copied into the kernarg segment at launch), written to one
-// or two device tables: host values reach the device without a host buffer that must outlive the call
-struct F64Args {
-  float v[64];
-};
-__global__ void set_floats_kernel(float* dst0, float* dst1, F64Args a, int n) {
-  const int i = threadIdx.x;
-  if (i < n) {
-    dst0[i] = a.v[i];
-    if (dst1) dst1[i] = a.v[i];
-  }
-}
 // the column table of a slider stack, rows [row0, row0 + rows) of dst [.][ld]: column c of sample i gets the multiplier of
 // the slider that owns rank column c (sliders in order, ranks.v[k] columns each); a.v = multipliers[rows][n_sliders]
 struct I16Args {
@@ -66,11 +54,6 @@ struct Level {
 struct UNet : Model {
   smi_unet_config cfg{};
   int max_n_ad = 0, lat_h = 0, lat_w = 0, ctx_len = 0;  // the shape the arenas are planned for (max_n: in the engine)
-  // the device table of the deferred weight-gradient jobs (smi_engine::wjobs) and what it holds (same addresses every
-  // step of a plan: no re-upload)
-  std::vector<WgradJob> wjobs_uploaded;
-  WgradJob* wjobs_dev = nullptr;
-  size_t wjobs_cap = 0;
   static constexpr size_t SPLITK_WS_BYTES = (size_t)512 * 128 * 128 * sizeof(float);  // 33.5 MB
   void* splitk_ws = nullptr;
   char* arena_home = nullptr;  // the arena region inside the creation workspace (smi_replan with arena == NULL)
@@ -168,13 +151,11 @@ struct UNet : Model {
   Lin time1, time2, add1, add2;
   std::vector<Level> down, up;
   Level mid;
-  bool tape_valid = false;
   // every saved forward gets a generation number; the caller keeps it with the output it will differentiate and
   // smi_unet_backward_checked refuses a stale one (a later saved forward, a replan or a backward dropped the tape)
   uint64_t tape_gen = 0;
   int64_t replans = 0;
   Ten* out_ten = nullptr;  // conv_out result (f32 [rows, 4])
-  int bw_n_ad = 0;         // adapted samples of the saved pass
 
   Transformer make_transformer(smi_engine& e, const std::string& name, int C, int heads, int layers) {
     Transformer t;
@@ -271,8 +252,7 @@ struct UNet : Model {
     e.gscale = (float*)e.pack_alloc(e.GSCALE_FLOATS * sizeof(float));
     e.samp_mult_dev = (float*)e.pack_alloc(2 * e.MAXS * sizeof(float));
     splitk_ws = e.pack_alloc(SPLITK_WS_BYTES);  // fp32 slabs of the split-K launches (gemm.hip: S x tiles <= 384 tiles)
-    wjobs_cap = 11 * (e.sites.size() + 8);  // a conv site pushes 10 jobs (d_up + one d_down job per filter tap)
-    wjobs_dev = (WgradJob*)e.pack_alloc(wjobs_cap * sizeof(WgradJob));
+    e.alloc_job_table(11 * (e.sites.size() + 8));  // a conv site pushes 10 jobs (d_up + one d_down job per filter tap)
     for (size_t i = 0; i < e.sites.size(); ++i)
       if (!e.site_used[i] && !e.err) {
         set_error("LoRA target '%s' is not a layer this engine adapts (attention projections; with c3lier: resnet "
@@ -360,13 +340,7 @@ struct UNet : Model {
   // own time_emb_proj
   Ten* resnet(smi_engine& e, Ten* x, const Resnet& r, Ten* temb_act, bool keep_out = false) {
     if (!temb_all_out) return e.resnet(x, r, e.linear(temb_act, r.temb), 0, keep_out);
-    e.tens->emplace_back();
-    Ten* t = &e.tens->back();
-    t->p = (char*)temb_all_out->p + (size_t)r.temb_col * e.esz();
-    t->rows = temb_all_out->rows;
-    t->cols = r.temb.out;
-    t->n = temb_all_out->n;
-    t->arow0 = temb_all_out->arow0;
+    Ten* t = e.borrowed((char*)temb_all_out->p + (size_t)r.temb_col * e.esz(), temb_all_out->rows, r.temb.out, temb_all_out->n);
     t->ng = temb_all_out->ng;
     return e.resnet(x, r, t, temb_all.out, keep_out, t->ng ? temb_all_out : nullptr);
   }
@@ -407,23 +381,8 @@ struct UNet : Model {
   void dry_forward(smi_engine& e) override { forward(e, e.max_n, max_n_ad, nullptr, 0.f, nullptr, nullptr, nullptr, false, nullptr); }
   int forward(smi_engine& e, int n, int n_adapted, const float* sample, float timestep, const void* ctxp, const void* text_embeds,
               const float* time_ids, bool save, float* eps_out) {
-    e.n_ad = n_adapted;
-    e.cur = &e.arena[save ? 1 : 0];
-    e.cur->reset();
-    e.in_block = e.persist_next = false;
-    if (!save) {
-      e.scr[0].reset();
-      e.scr[1].reset();
-      if (e.dry) e.scr[0].cap = e.scr[1].cap = (size_t)-1;
-    }
-    if (save) {
-      e.tape.clear();
-      tape_valid = false;
-      ++tape_gen;
-    }
-    e.tens = &e.tens_[save ? 1 : 0];
-    e.tens->clear();
-    e.saving = save;
+    e.begin_pass(n_adapted, save);
+    if (save) ++tape_gen;
     e.grad_src = false;
     e.phase_live = nullptr;
     const int H = lat_h, Wd_ = lat_w, HW = H * Wd_;
@@ -460,13 +419,7 @@ struct UNet : Model {
     if (e.lora_down && e.lora_up && e.mult != 0.f) e.dora_prepare(e.lora_down, e.lora_up, e.mult, e.saving, false);
 
     // ---- context as a [n*L, D] tensor (borrowed)
-    e.tens->emplace_back();
-    Ten* ctx = &e.tens->back();
-    ctx->p = const_cast<void*>(ctxp);
-    ctx->rows = (int64_t)n * ctx_len;
-    ctx->cols = cfg.cross_attention_dim;
-    ctx->n = n;
-    ctx->arow0 = (int64_t)(n - e.n_ad) * ctx_len;
+    Ten* ctx = e.borrowed(ctxp, (int64_t)n * ctx_len, cfg.cross_attention_dim, n);
     // The backward of adapted to_k / to_v reads the context again (d(down) = dxa^T ctx), possibly long after this call
     // returned: the saved pass keeps its own copy, so that it does not matter what the caller does with its buffer in
     // between (a temporary handed to the forward is free for reuse as soon as the call returns).
@@ -596,65 +549,43 @@ struct UNet : Model {
     }
     if (save) {
       out_ten = y;
-      bw_n_ad = n_adapted;
-      e.bw_down = e.lora_down;
-      e.bw_up = e.lora_up;
-      e.bw_mult = e.mult;
-      e.bw_samp_on = e.samp_on;
       bw_ctx = ctx_grad;
       bw_pool = pool_grad;
-      tape_valid = true;
+      e.keep_saved_pass(n_adapted);
     }
     e.saving = false;
     return e.end_pass(save ? "this call (arena 1 " : "this call (arena 0 ");
   }
 
-  // n_live: d_eps covers the LAST n_live adapted samples of the saved pass; the caller promises that the gradient with
-  // respect to the other adapted samples' output is exactly zero (then so is every gradient row of theirs, and they add
-  // exact zeros to the weight-gradient sums).  n_live == bw_n_ad is the full backward.
-  // a backward consumes the saved pass, also where it fails half way: a tail backward has moved the tensors' arow0
-  void drop_tape(smi_engine& e) {
-    e.pinned.clear();
-    e.tape.clear();
-    tape_valid = false;
-    e.bw_skip = 0;
-  }
   void forget_saved_pass(smi_engine& e) {  // arena 1 moves (re-plan, context-gradient buffer): what pointed into it goes
-    wjobs_uploaded.clear();
+    e.saved.uploaded.clear();
     e.tape.clear();
-    tape_valid = false;
+    e.saved.valid = false;
     e.tens_[1].clear();
     out_ten = nullptr;
   }
+  // n_live: d_eps covers the LAST n_live adapted samples of the saved pass; the caller promises that the gradient with
+  // respect to the other adapted samples' output is exactly zero (then so is every gradient row of theirs, and they add
+  // exact zeros to the weight-gradient sums).  n_live == e.saved.n is the full backward.
   int backward(smi_engine& e, const float* d_eps, float* dd, float* du, int n_live, float* dctx = nullptr,
                float* dpool = nullptr) {
     e.d_ctx = dctx;
     e.d_ctx_written = false;
     d_pooled = dpool;
     d_pooled_written = false;
-    if (!tape_valid && !e.dry) {
-      set_error("smi_unet_backward: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)");
-      return -4;
-    }
-    e.cur = &e.arena[1];
-    e.tens = &e.tens_[1];
-    e.d_down = dd;
-    e.d_up = du;
+    if (const int rc = e.begin_backward("smi_unet_backward: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)",
+                                        dd, du, n_live))
+      return rc;
     const int n = n_live, HW = lat_h * lat_w;  // d_eps covers the live adapted samples only
-    e.n_ad = n_live;  // rows per sample of a gradient buffer = its rows / n_ad
     Ten* y = out_ten;
     if (!y->ng) {  // adaptor off: nothing depends on the LoRA parameters
-      e.tape.clear();
-      tape_valid = false;
+      e.drop_tape();
       return 0;
     }
     if (n > e.MAXS && !e.dry) {
       set_error("smi_unet_backward: %d adapted samples exceed the %d per-sample loss scales", n, e.MAXS);
       return -1;
     }
-    e.wjobs.clear();
-    e.pinned.clear();
-    e.bw_skip = bw_n_ad - n_live;
     if (e.bw_skip > 0) {  // every closure works on rows [arow0, rows): start them at the first live sample (the tape and its
       for (Ten& t : *e.tens) {  // tensors do not outlive this call)
         if (t.n <= 0) continue;
@@ -665,45 +596,14 @@ struct UNet : Model {
     // one power-of-two loss scale PER SAMPLE (from max|d_eps[sample]|): a sample's backward arithmetic then does not
     // depend on which other samples share the batch -- W ranks on shards == one rank on the global batch
     RUN(launch_grad_scale(d_eps, n, (int64_t)cfg.out_channels * HW, e.gscale, e.MAXS, e.stream));
-    // the 16-bit LoRA operands / DoRA delta weights belong to the SAVED forward: an adapted no-grad pass in between
-    // (pre-roll) may have rebuilt them with other parameters or another multiplier -> rebuild from the saved ones
-    if (!e.prep_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f)
-      RUNP(SMI_PROF_LORA, 0.0, 0.0, launch_lora_prep(e.dtype, e.prep_sites_dev, (int)e.prep_sites.size(), e.bw_down, e.bw_up, e.lora_shadow, e.stream));
-    if (!e.dora_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f) {
+    e.rebuild_saved_operands();
+    if (!e.dora_sites.empty() && e.bw_down && e.bw_up && e.bw_mult != 0.f) {  // the DoRA delta weights likewise
       e.dora_prepare(e.bw_down, e.bw_up, e.bw_mult, true, true);
       RUN(launch_scale_min(e.gscale, n, e.gscale + 2 * e.MAXS, e.stream));
     }
-    e.mult = e.bw_mult;
     y->g = e.alloc_t(e.MA(y), 64);
     RUN(launch_nchw_to_nhwc_scaled(e.dtype, d_eps, y->g, n, cfg.out_channels, HW, 64, e.gscale, e.stream));
-    for (auto it = e.tape.rbegin(); it != e.tape.rend(); ++it) (*it)();
-    if (!e.wjobs.empty() && !e.err) {  // every LoRA weight gradient of this pass: one grouped launch per accumulator class
-      wgrad_grouped_finish(e.wjobs);
-      if (!e.dry) {
-        if (e.wjobs.size() > wjobs_cap) {
-          set_error("internal: %zu weight-gradient jobs exceed the table (%zu)", e.wjobs.size(), wjobs_cap);
-          drop_tape(e);
-          return -1;
-        }
-        const bool same = wjobs_uploaded.size() == e.wjobs.size() &&
-                          memcmp(wjobs_uploaded.data(), e.wjobs.data(), e.wjobs.size() * sizeof(WgradJob)) == 0;
-        if (!same) {  // bump allocation gives the same addresses every step of a plan: uploaded once, then reused
-          wjobs_uploaded = e.wjobs;
-          if (hipMemcpyAsync(wjobs_dev, wjobs_uploaded.data(), e.wjobs.size() * sizeof(WgradJob), hipMemcpyHostToDevice,
-                             e.stream) != hipSuccess) {
-            set_error("hipMemcpyAsync (weight-gradient job table) failed");
-            drop_tape(e);
-            return -1;
-          }
-        }
-        double bytes = 0.0, flops = 0.0;
-        for (const auto& j : e.wjobs) {
-          bytes += (double)(j.M - j.m_begin) * j.K * 2.0;
-          flops += 2.0 * (j.M - j.m_begin) * j.K * j.r;
-        }
-        RUNP(SMI_PROF_LORA, flops, bytes, launch_lora_wgrad_grouped(e.dtype, e.wjobs, wjobs_dev, e.stream));
-      }
-    }
+    if (e.run_tape_and_weight_grads()) return -1;
     if (e.d_ctx && !e.dry && !e.err) {  // the loss scale of each sample's rows divides out; no term at all: the gradient is zero
       const int L = ctx_len, D = cfg.cross_attention_dim;
       if (e.d_ctx_written) RUNP(SMI_PROF_ELEM, 0.0, 0.0, launch_row_scale_f32(e.d_ctx, D, n * L, D, e.gscale + e.MAXS, L, e.stream));
@@ -716,7 +616,6 @@ struct UNet : Model {
     }
     e.d_ctx = nullptr;
     d_pooled = nullptr;
-    drop_tape(e);
     return e.end_pass("the backward (");
   }
 };
@@ -755,14 +654,7 @@ UNet* setup(smi_engine* e, const smi_unet_config* cfg, const smi_weight* weights
   u->lat_w = w;
   u->ctx_len = ctx_len;
   for (int i = 0; i < n_weights; ++i) e->wmap[weights[i].name] = &weights[i];
-  e->sites.assign(sites, sites + n_sites);
-  e->site_names.resize(n_sites);
-  e->site_used.assign(n_sites, 0);
-  for (int i = 0; i < n_sites; ++i) {
-    e->site_names[i] = sites[i].target;
-    e->sites[i].target = e->site_names[i].c_str();
-  }
-  for (int i = 0; i < n_sites; ++i) e->smap[e->site_names[i]] = &e->sites[i];
+  e->register_sites(sites, n_sites);
   return u;
 }
 
@@ -794,7 +686,7 @@ int plan(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, in
   out[1] = out[3] + 2 * out[4];
   u.forward(e, batch, batch_adapted, nullptr, 0.f, nullptr, nullptr, nullptr, true, nullptr);
   // sized for the full backward: a tail backward needs less
-  u.backward(e, nullptr, nullptr, nullptr, u.bw_n_ad, ctx_bytes ? reinterpret_cast<float*>(16) : nullptr,
+  u.backward(e, nullptr, nullptr, nullptr, e.saved.n, ctx_bytes ? reinterpret_cast<float*>(16) : nullptr,
              pool_bytes ? reinterpret_cast<float*>(16) : nullptr);
   out[2] = align_up(e.arena[1].peak, 4096);
   return e.err ? -1 : 0;
@@ -853,7 +745,7 @@ int attach_grad_buffer(smi_engine* e, void* buffer, size_t buffer_bytes, bool po
 // `name`, an engine without a saved pass (name NULL: smi_unet_backward, which leaves that to UNet::backward's own refusal)
 int backward_begin(const smi_engine* e, const char* name) {
   if (refuse_other_kind(e, ": it has no backward")) return -1;
-  SMI_CHECK(!name || unet(e)->tape_valid, "%s: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)", name);
+  SMI_CHECK(!name || e->saved.valid, "%s: no saved forward pass (call smi_unet_forward with save_for_backward=1 first)", name);
   return 0;
 }
 
@@ -967,7 +859,7 @@ int smi_engine_stats(const smi_engine* e, int64_t out[4]) {
   const UNet* u = unet(e);  // (the other kinds neither re-plan nor save a pass)
   out[0] = e->pack_launches;
   out[1] = u ? u->replans : 0;
-  out[2] = u && u->tape_valid ? (int64_t)u->tape_gen : 0;
+  out[2] = u && e->saved.valid ? (int64_t)u->tape_gen : 0;
   out[3] = (int64_t)e->wpack.peak;
   return 0;
 }
@@ -1001,28 +893,18 @@ int smi_unet_forward_multi(smi_engine* e, int n, int n_adapted, const float* sam
   SMI_CHECK(e && multipliers, "NULL argument");
   if (refuse_other_kind(e, ": no UNet forward")) return -1;
   SMI_CHECK(n_adapted >= 1 && n_adapted <= smi_engine::MAXS, "per-sample multipliers: 1..%d adapted samples", smi_engine::MAXS);
-  float mref = 0.f;
   bool same = true;
-  for (int i = 0; i < n_adapted; ++i) {
-    if (fabsf(multipliers[i]) > mref) mref = fabsf(multipliers[i]);
-    same = same && multipliers[i] == multipliers[0];
-  }
-  if (same || mref == 0.f)
+  for (int i = 0; i < n_adapted; ++i) same = same && multipliers[i] == multipliers[0];
+  if (same)
     return smi_unet_forward_batched(e, n, n_adapted, sample, timestep, ctx, text_embeds, time_ids, lora_down_flat,
                                     lora_up_flat, multipliers[0], save_for_backward, eps_out);
   SMI_CHECK(e->n_conv_sites == 0 && e->dora_sites.empty(),
             "per-sample multipliers are implemented for Linear LoRA sites (attention projections, time_emb_proj, "
             "conv_shortcut); this network has conv or DoRA sites -- run the samples in separate passes");
-  // the per-sample ratios travel in kernel arguments, 64 per launch, ordered on the engine's stream (an async
-  // copy from a stack array is only correct while the runtime stages pageable sources before returning)
-  for (int i0 = 0; i0 < n_adapted; i0 += 64) {
-    F64Args a;
-    const int cnt = n_adapted - i0 < 64 ? n_adapted - i0 : 64;
-    for (int i = 0; i < 64; ++i) a.v[i] = i < cnt ? multipliers[i0 + i] / mref : 0.f;
-    hipLaunchKernelGGL(set_floats_kernel, dim3(1), dim3(64), 0, e->stream, e->samp_mult_dev + i0,
-                       save_for_backward ? e->samp_mult_dev + smi_engine::MAXS + i0 : (float*)nullptr, a, cnt);
-  }
-  SMI_HIP(hipGetLastError());
+  // the per-sample ratios travel in kernel arguments, ordered on the engine's stream (an async copy from a stack
+  // array is only correct while the runtime stages pageable sources before returning)
+  float mref = 0.f;  // (not 0: the multipliers differ)
+  if (const int rc = e->set_sample_multipliers(multipliers, n_adapted, save_for_backward != 0, &mref)) return rc;
   e->samp_on = true;
   const int rc = smi_unet_forward_batched(e, n, n_adapted, sample, timestep, ctx, text_embeds, time_ids, lora_down_flat,
                                           lora_up_flat, mref, save_for_backward, eps_out);
@@ -1060,7 +942,7 @@ int smi_unet_forward_compose(smi_engine* e, int n, int n_adapted, const float* s
             "slider composition: %d adapted samples x stacked rank %d exceed the %d entries of the multiplier table", n_adapted,
             R, smi_engine::COL_TABLE_FLOATS);
   UNet* u = unet(e);
-  u->drop_tape(*e);  // inference only: no earlier saved pass answers a backward after this one
+  e->drop_tape();  // inference only: no earlier saved pass answers a backward after this one
   // the table travels in kernel arguments, 64 multipliers per launch, ordered on the engine's stream (as the per-sample
   // ratios of smi_unet_forward_multi do: no asynchronous copy from pageable memory)
   const int per = 64 / n_sliders;
@@ -1092,7 +974,7 @@ int smi_unet_forward(smi_engine* e, int n, const float* sample, float timestep, 
 int smi_unet_backward(smi_engine* e, const float* d_eps, float* d_lora_down_flat, float* d_lora_up_flat) {
   SMI_CHECK(e && d_eps && d_lora_down_flat && d_lora_up_flat, "NULL argument");
   if (backward_begin(e, nullptr)) return -1;
-  return backward_launch(e, "smi_unet_backward", d_eps, d_lora_down_flat, d_lora_up_flat, unet(e)->bw_n_ad);
+  return backward_launch(e, "smi_unet_backward", d_eps, d_lora_down_flat, d_lora_up_flat, e->saved.n);
 }
 
 int smi_unet_ctx_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
@@ -1127,7 +1009,7 @@ int smi_unet_backward_ctx(smi_engine* e, const float* d_eps, float* d_lora_down_
   const UNet* u = unet(e);
   SMI_CHECK(u->bw_ctx, "smi_unet_backward_ctx: the saved pass does not differentiate the context (smi_unet_ctx_grad(e, 1) "
                        "before the saving forward)");
-  return backward_launch(e, "smi_unet_backward_ctx", d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out);
+  return backward_launch(e, "smi_unet_backward_ctx", d_eps, d_lora_down_flat, d_lora_up_flat, e->saved.n, d_ctx_out);
 }
 
 int smi_unet_pooled_grad_bytes(const smi_unet_config* cfg, const smi_lora_site* sites, int n_sites, int batch,
@@ -1172,7 +1054,7 @@ int smi_unet_backward_cond(smi_engine* e, const float* d_eps, float* d_lora_down
   const UNet* u = unet(e);
   SMI_CHECK(u->bw_ctx && u->bw_pool, "smi_unet_backward_cond: the saved pass does not differentiate the pooled embedding "
                                      "(smi_unet_ctx_grad(e, 1) and smi_unet_pooled_grad(e, 1) before the saving forward)");
-  return backward_launch(e, "smi_unet_backward_cond", d_eps, d_lora_down_flat, d_lora_up_flat, u->bw_n_ad, d_ctx_out,
+  return backward_launch(e, "smi_unet_backward_cond", d_eps, d_lora_down_flat, d_lora_up_flat, e->saved.n, d_ctx_out,
                          d_text_embeds_out);
 }
 
@@ -1185,8 +1067,8 @@ int smi_unet_backward_tail(smi_engine* e, int n_live, const float* d_eps_live, f
                          "offered there (use smi_unet_backward_cond)");
   SMI_CHECK(!u->bw_ctx, "smi_unet_backward_tail: the saved pass differentiates the context; a tail backward is not offered "
                         "there (use smi_unet_backward_ctx)");
-  SMI_CHECK(n_live >= 1 && n_live <= u->bw_n_ad, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
-            n_live, u->bw_n_ad);
+  SMI_CHECK(n_live >= 1 && n_live <= e->saved.n, "smi_unet_backward_tail: %d live samples outside [1, %d], the adapted samples of the saved pass",
+            n_live, e->saved.n);
   return backward_launch(e, "smi_unet_backward_tail", d_eps_live, d_lora_down_flat, d_lora_up_flat, n_live);
 }
 

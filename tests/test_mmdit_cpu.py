@@ -187,6 +187,24 @@ def test_site_refusals():
     assert _ws(cfg, [site("transformer_blocks.0.attn.to_add_out")]) > _ws(cfg)
 
 
+@pytest.mark.parametrize("plan", ["workspace_bytes", "train_workspace_bytes"])
+@pytest.mark.parametrize("change,gist", [
+    (dict(off_dora=0), r"DoRA site 'transformer_blocks\.0\.attn\.to_out\.0'"),
+    (dict(rank=0), r"rank 0 of 'transformer_blocks\.0\.attn\.to_out\.0' outside \[1, 16\]"),
+    (dict(rank=17), r"rank 17 of 'transformer_blocks\.0\.attn\.to_out\.0' outside \[1, 16\]"),
+    (dict(target="transformer_blocks.0.ff.net.0.proj"),
+     r"target 'transformer_blocks\.0\.ff\.net\.0\.proj'.*attention projections \(attn\.to_q/to_k/to_v/to_out\.0, "
+     r"attn\.add_q_proj/add_k_proj/add_v_proj/to_add_out\)"),
+], ids=["dora", "rank0", "rank17", "target"])
+def test_site_refusal_codes_and_messages(plan, change, gist):
+    """both dry runs return -1 with the model's prefix, the site and the reason in the message"""
+    cfg = M.tiny_sd3_config()
+    site = {"target": "transformer_blocks.0.attn.to_out.0", "off_down": 0, "off_up": 0, "rank": 4, "scale": 1.0}
+    with pytest.raises(_native.SmiError, match=r"failed \(-1\): MMDiT: " + gist):
+        getattr(M, plan)(cfg, torch.float16, [dict(site, **change)], 2, 8, 6, 5)
+    assert getattr(M, plan)(cfg, torch.float16, [site], 2, 8, 6, 5) > 0
+
+
 def test_generate_images_refuses_te_files_with_sd3(tmp_path):
     args = G.build_parser().parse_args(["--prompts_path", "p.csv", "--save_path", str(tmp_path), "--base", "sd3",
                                         "--model_name", "x.pt", "--te_model_name", "a.safetensors"])

@@ -207,3 +207,22 @@ def test_generate_images_text_encoder_flags():
     tok = SyntheticClipTokenizer(1000, 999)
     assert tok(["a b"], padding="max_length", max_length=77).input_ids.shape == (1, 77)
     assert tok(["a b"], padding=True).input_ids.shape == (1, 4) and tok("a b").input_ids.shape == (1, 4)
+
+
+# ---- the engine's site-list refusals, through the dry run (host only) ----------------------------------------------------
+@pytest.mark.parametrize("change,gist", [
+    (dict(off_dora=0), r"DoRA site 'text_model\.encoder\.layers\.0\.self_attn\.q_proj'"),
+    (dict(rank=0), r"rank 0 of 'text_model\.encoder\.layers\.0\.self_attn\.q_proj' outside \[1, 16\]"),
+    (dict(rank=17), r"rank 17 of 'text_model\.encoder\.layers\.0\.self_attn\.q_proj' outside \[1, 16\]"),
+    (dict(target="text_model.encoder.layers.0.mlp.fc1"), r"target 'text_model\.encoder\.layers\.0\.mlp\.fc1'.*self_attn\.\{q,k,v\}_proj and self_attn\.out_proj"),
+], ids=["dora", "rank0", "rank17", "target"])
+def test_clip_lora_plan_refuses_a_site(change, gist):
+    """smi_clip_lora_workspace_bytes returns -1 with the tower's prefix, the site and the reason in the message."""
+    from sliders_conceptmod_amd import _native
+    cfg = R.tiny_config()
+    sites, _, _ = R.flat_layout(R.site_names(cfg.num_hidden_layers), cfg.hidden_size, 4, 1.0)
+    q = next(i for i, s in enumerate(sites) if s["target"].endswith("layers.0.self_attn.q_proj"))
+    bad = [dict(s, **change) if i == q else s for i, s in enumerate(sites)]
+    with pytest.raises(_native.SmiError, match=r"failed \(-1\): smi_clip_lora: " + gist):
+        _native.clip_lora_workspace_bytes(cfg, torch.float16, bad, 2)
+    assert _native.clip_lora_workspace_bytes(cfg, torch.float16, sites, 2) > 0
