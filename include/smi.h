@@ -144,6 +144,24 @@ typedef struct smi_mmdit_config {
   int qk_norm;                /* 0 none; 1 rms_norm (SD3.5): refused */
 } smi_mmdit_config;
 
+/* Architecture of a diffusers FluxTransformer2DModel (FLUX.1-schnell / dev; what conceptmod/textsliders/train_lora_flux.py
+ * and predict_noise_flux drive).  Width d = num_heads x attention_head_dim; out_channels = in_channels. */
+typedef struct smi_flux_config {
+  int dtype;
+  int in_channels;            /* 16: in_channels x patch_size^2 (the packed width, 64) must be a multiple of 64 */
+  int patch_size;             /* 2 */
+  int num_layers;             /* 19 double (joint) blocks */
+  int num_single_layers;      /* 38 single blocks */
+  int num_heads;              /* 24 */
+  int attention_head_dim;     /* 128: a multiple of 16, at most 160 */
+  int joint_attention_dim;    /* 4096: width of encoder_hidden_states (T5) */
+  int pooled_projection_dim;  /* 768: CLIP-L's pooled row */
+  int guidance_embeds;        /* 0 schnell, 1 dev: a guidance embedder next to the timestep embedder */
+  int axes_dims_rope[3];      /* (16, 56, 56): even, summing to attention_head_dim */
+  int context_len;            /* tokens per sample of encoder_hidden_states: fixed at creation */
+  float rope_theta;           /* 10000 */
+} smi_flux_config;
+
 typedef struct smi_engine smi_engine;
 
 const char* smi_last_error(void);
@@ -355,6 +373,46 @@ int smi_mmdit_forward_save(smi_engine* e, int n, const float* sample, const floa
                            const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
                            const float* multipliers, float* out);
 int smi_mmdit_backward(smi_engine* e, const float* d_out, float* d_lora_down_flat, float* d_lora_up_flat);
+
+/* ---- Flux transformer, forward with LoRA sites (sweeping a Flux slider) ------------------------------------------------
+ * Replaces `transformer(hidden_states, timestep, guidance, pooled_projections, encoder_hidden_states, txt_ids, img_ids).sample`
+ * (conceptmod/textsliders/train_util.py predict_noise_flux) on UN-packed latents: the engine packs ([n, C, h, w] ->
+ * [n, (h/2)(w/2), 4 C], columns (c, py, px)) and un-packs itself, and builds the rotary table from (h, w, context_len) at
+ * creation, on the host in float64 (image ids (0, row, col), text ids 0; interleaved pairs).  x = x_embedder(pack),
+ * c = context_embedder(ctx), temb = timestep MLP(sinusoid256(t)) [+ guidance MLP(sinusoid256(1000 g))] + pooled-text MLP.
+ * num_layers double blocks: the SD3 joint block with q and k RMS-normalised per head (attn.norm_q / norm_k, and
+ * norm_added_q / norm_added_k on the context stream) and rotated, over the joint sequence CONTEXT rows first.
+ * num_single_layers single blocks on that joint sequence: z = LN(s) (1 + scale) + shift, attention(rope(rms(q)), rope(rms(k)), v)
+ * and gelu_tanh(proj_mlp z) side by side into one [rows, 5 d] operand of proj_out, s += gate proj_out([a | m]).  The image
+ * rows (the last of each sample) go through norm_out (scale, shift) + proj_out.
+ *   weights      the diffusers state_dict (`x_embedder.*`, `context_embedder.*`, `time_text_embed.*`,
+ *                `transformer_blocks.<i>.*`, `single_transformer_blocks.<i>.*`, `norm_out.linear.*`, `proj_out.*`), dtype T
+ *   sites        Linear LoRA sites (rank <= 16) on attn.to_q/to_k/to_v of double and single blocks (all three of a block or
+ *                none, adjacent in the flat buffers in that order: one fused GEMM), attn.add_q_proj/add_k_proj/add_v_proj
+ *                (likewise), attn.to_out.0 and attn.to_add_out; n_sites 0: a frozen network.  DoRA sites and other targets
+ *                (proj_mlp, proj_out, ff.*) are refused by name.
+ *   h, w         the LATENT size, even; fixed at creation, as context_len is
+ *   sample       f32 [n, in_channels, h, w]
+ *   timesteps    f32 [n], HOST memory: the scheduler's 1000 sigma, one per sample
+ *   guidance     f32 [n], HOST memory, for a guidance_embeds model; NULL for one without (either mismatch is refused)
+ *   ctx          T [n, context_len, joint_attention_dim]
+ *   pooled       T [n, pooled_projection_dim]
+ *   multipliers  f32 [n], HOST memory, as smi_mmdit_forward takes them: NULL flat buffers, NULL multipliers or all
+ *                multipliers 0 give the bits of an engine created without sites.
+ *   out          f32 [n, in_channels, h, w]
+ * workspace = [packed weights | persistent tensors | two block scratch regions], sized by a dry forward.  n may be smaller
+ * than the creation batch.  No split-K scratch is lent to the GEMMs: a sample gives the same bits alone or in a batch.  The
+ * config check refuses, by name: sum(axes_dims_rope) != attention_head_dim or an odd axis width, attention_head_dim not a
+ * multiple of 16 or above 160, d % 64, d > 3072 (the adaLN rows), patch_size != 2 (the pack is 2 x 2),
+ * in_channels x patch_size^2 % 64, h or w odd. */
+int smi_flux_workspace_bytes(const smi_flux_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w,
+                             size_t* bytes);
+int smi_flux_create(const smi_flux_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                    int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                    smi_engine** out);
+int smi_flux_forward(smi_engine* e, int n, const float* sample, const float* timesteps, const float* guidance,
+                     const void* ctx, const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
+                     const float* multipliers, float* out);
 
 /* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)
@@ -770,6 +828,16 @@ int smi_op_joint_rows_split(int dtype, const void* joint, void* a, void* b, int 
 int smi_op_sd3_patchify(int dtype, const float* latents, void* out, int n, int cin, int h, int w, int p, void* stream);
 int smi_op_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n, int gh, int gw, int d, int s, void* stream);
 int smi_op_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream);
+/* The Flux kernels, one launch each (tests/test_flux_kernels_gpu.py).
+ * qk_norm_rope: one stream's q|k|v rows src T [n tokens, lds] into rows [row_off, row_off + tokens) of every sample of the
+ * joint buffer dst T [n l, ldd]: q and k heads x rsqrt(mean(x^2) + eps) w (wq / wk T [d]) and rotated, interleaved pairs, by row
+ * (row_off + t) of table f32 [l, d] = cos[d / 2] | sin[d / 2]; v copied.  d % 16 == 0, d <= 160.  src == dst: in place.
+ * gelu_tanh_cols: y[m, 0..c) = gelu_tanh(x[m, 0..c)) with row strides ldx / ldy; y may alias x.
+ * flux_unpack: out f32 [n, cout, gh p, gw p] from rows T [n gh gw, cout p p] with columns (c, py, px). */
+int smi_op_qk_norm_rope(int dtype, const void* src, int64_t lds, void* dst, int64_t ldd, const void* wq, const void* wk,
+                        const float* table, int n, int tokens, int l, int row_off, int heads, int d, float eps, void* stream);
+int smi_op_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t m, int c, void* stream);
+int smi_op_flux_unpack(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream);
 int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream);
 /* ff.net.0 with the GEGLU gate fused into the GEMM epilogue (the engine's forward path for
  * diffusers GEGLU: proj = x W^T + b [M, N]; out[M, N/2] = proj[:, :N/2] * gelu(proj[:, N/2:])).  Rows >= proj_row0 of

@@ -60,6 +60,13 @@ class MMDiTConfigC(C.Structure):
                                        "pos_embed_max_size", "context_len", "dual_attention_layers", "qk_norm")]
 
 
+class FluxConfigC(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("dtype", "in_channels", "patch_size", "num_layers", "num_single_layers", "num_heads",
+                                       "attention_head_dim", "joint_attention_dim", "pooled_projection_dim",
+                                       "guidance_embeds")] + [("axes_dims_rope", C.c_int * 3), ("context_len", C.c_int),
+                                                              ("rope_theta", C.c_float)]
+
+
 class WeightC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -203,6 +210,12 @@ _SIGS = {
     "smi_mmdit_forward_save": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float)] + [C.c_void_p] * 4 +
                                [C.POINTER(C.c_float), C.c_void_p]),
     "smi_mmdit_backward": (C.c_int, [C.c_void_p] * 4),
+    "smi_flux_workspace_bytes": (C.c_int, [C.POINTER(FluxConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_flux_create": (C.c_int, [C.POINTER(FluxConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                  C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_flux_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)] +
+                         [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -274,6 +287,11 @@ _SIGS = {
     "smi_op_sd3_patchify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "smi_op_sd3_add_pos": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 5 + [C.c_void_p]),
     "smi_op_sd3_unpatchify": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "smi_op_qk_norm_rope": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_void_p] * 3 +
+                            [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "smi_op_gelu_tanh_cols": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
+                                        C.c_void_p]),
+    "smi_op_flux_unpack": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
     "smi_op_chan_mix": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_conv3x3_small": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "smi_op_nchw_to_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),

@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsmi_hip.so")
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm4.hip", "attention.hip", "attention_causal.hip", "norm.hip", "elementwise.hip", "lora.hip", "vae_decode.hip", "clip_vision.hip",
-           "lpips.hip", "mmdit.hip", "engine.hip", "engine_unet.hip", "engine_vae.hip", "engine_clip.hip", "engine_lpips.hip", "engine_mmdit.hip", "ops_api.hip"]
+           "lpips.hip", "mmdit.hip", "flux.hip", "engine.hip", "engine_unet.hip", "engine_vae.hip", "engine_clip.hip", "engine_lpips.hip", "engine_mmdit.hip", "engine_flux.hip", "ops_api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # attention: the softmax works on MFMA results every tile; with the default AGPR-form MFMA hipcc shuttles every
 # accumulator through v_accvgpr_read/write (481 moves per key tile, the kernel was VALU-bound at 91 % VALU busy).
@@ -31,7 +31,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
     hipcc = os.environ.get("HIPCC", "hipcc")
     objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, h) for h in ("smi_common.h", "kernels.h", "gemm_tile.h", "gemm_epilogue.h", "engine.h")] + [
+    headers = [os.path.join(CSRC, h) for h in ("smi_common.h", "kernels.h", "gemm_tile.h", "gemm_epilogue.h", "engine.h", "engine_joint_ops.h")] + [
         os.path.join(os.path.dirname(HERE), "include", "smi.h")]
     objs = []
     procs = []

@@ -1,7 +1,8 @@
 // The op core of every engine: runs a model's forward -- and the activation/LoRA-gradient backward of the models that are
 // differentiated (the UNet, the CLIP text tower with LoRA sites, the MMDiT), whose saved pass and backward scaffold is
 // written once here -- as a stream of hand-written gfx950 kernels (gemm.hip, attention.hip, norm.hip, elementwise.hip, lora.hip).  It names no model: each
-// (engine_unet.hip, engine_vae.hip, engine_clip.hip, engine_lpips.hip) is a `Model` with its config, layers and forward over these ops.
+// (engine_unet.hip, engine_vae.hip, engine_clip.hip, engine_lpips.hip, engine_mmdit.hip, engine_flux.hip) is a `Model` with its
+// config, layers and forward over these ops.
 //
 // Structure
 //   * Activations are token-major [n*H*W, C] in the model dtype (fp16/bf16); accumulation is fp32 everywhere.
@@ -146,7 +147,7 @@ struct Model {
 
 struct smi_engine {
   // which model the engine holds: set once, by hold(); every entry point accepts one kind and refuses the others
-  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS, MMDIT };
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS, MMDIT, FLUX };
   Kind kind = UNET;
   std::unique_ptr<Model> model;  // (also keeps a lambda from copying an engine it names through a reference parameter)
   int dtype = 0;
@@ -1461,7 +1462,8 @@ int finish_create(smi_engine* e, const char* what, smi_engine** out);
 int check_linear_lora_sites(const char* who, const smi_lora_site* sites, int n_sites, std::initializer_list<const char*> suffixes,
                             const char* where);
 // the forward-only engines (VAE encoder, VAE decoder, CLIP text and image towers): `setup` fills a fresh engine with its
-// kind, dtype, largest batch and its model; the workspace is [packed weights | arena 0]
+// kind, dtype, largest batch and its model; the workspace is [packed weights | arena 0 (| two block scratch regions, for a
+// model whose forward runs in begin_block / end_block pairs)]
 using Setup = std::function<void(smi_engine*)>;
 int workspace_bytes_forward_only(const Setup& setup, size_t* bytes);
 int create_forward_only(const Setup& setup, const char* what, const smi_weight* weights, int n_weights, void* workspace,

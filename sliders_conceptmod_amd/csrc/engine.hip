@@ -229,9 +229,10 @@ int finish_create(smi_engine* e, const char* what, smi_engine** out) {
 }
 
 // ---- the forward-only engines: one plan, one size, one create ---------------------------------------------------------
+// scratch: one of the two regions a model's blocks alternate between (smi_engine::begin_block); 0 for a model without blocks
 struct ForwardOnlyPlan {
-  size_t wpack = 0, arena = 0;
-  size_t bytes() const { return wpack + arena + 2 * 4096; }
+  size_t wpack = 0, arena = 0, scratch = 0;
+  size_t bytes() const { return wpack + arena + 2 * scratch + 2 * 4096; }
 };
 static void build_model(smi_engine& e) {  // the model's layers, then what every forward-only engine packs after them
   e.model->build(e);
@@ -247,6 +248,7 @@ static int plan_forward_only(const Setup& setup, ForwardOnlyPlan* p) {
   p->wpack = align_up(e.wpack.peak, 4096);
   e.model->dry_forward(e);
   p->arena = align_up(e.arena[0].peak, 4096);
+  p->scratch = align_up(std::max(e.scr[0].peak, e.scr[1].peak), 4096);
   return e.err ? -1 : 0;
 }
 int workspace_bytes_forward_only(const Setup& setup, size_t* bytes) {
@@ -271,6 +273,7 @@ int create_forward_only(const Setup& setup, const char* what, const smi_weight* 
   e->wpack.cap = p.wpack;
   e->arena[0].base = base + p.wpack;
   e->arena[0].cap = p.arena;
+  if (p.scratch) e->set_arena0_regions(p.arena, p.scratch);
   build_model(*e);
   return finish_create(e, what, out);
 }

@@ -397,8 +397,8 @@ int launch_clip_logits(int dtype, const void* image_embeds, int ni, const void* 
 // MMDiT (SD3) around the GEMMs and the attention (mmdit.hip).  T is 16-bit, arithmetic fp32, one rounding at the store.
 // scale / shift / gate are C columns of a row of one modulation tensor mod T [n, ldm], at column offsets that are multiples
 // of 8; row r of the activations belongs to sample r / rows_per_sample.
-// y[r, :] = LN(x[r, :]) (1 + scale[s, :]) + shift[s, :]: LayerNorm without affine, C % 8 == 0, C <= 2048, one pass over x;
-// mean_rstd f32 [M, 2] (may be NULL): what a backward needs
+// y[r, :] = LN(x[r, :]) (1 + scale[s, :]) + shift[s, :]: LayerNorm without affine, C % 8 == 0, C <= 3072 (the backward below:
+// C <= 2048), one pass over x; mean_rstd f32 [M, 2] (may be NULL): what a backward needs
 int launch_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int M, int C,
                           int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, hipStream_t stream);
 // y[r, :] = h[r, :] + gate[s, :] f[r, :]; y may alias h
@@ -429,6 +429,18 @@ int launch_gate_residual_bwd(int dtype, const void* dy, const void* mod, void* d
 // rows T [n gh gw, p p Cout] = scale_dev[n] x d_out f32 [n, Cout, gh p, gw p]: un-patchify's inverse; Cout p p % 8 == 0
 int launch_sd3_unpatchify_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
                               const float* scale_dev, hipStream_t stream);
+
+// Flux (flux.hip).  One stream's q|k|v rows src T [n tokens, lds] (q | k | v, H heads of D each) into the joint buffer
+// dst T [n L, ldd] at rows [row_off, row_off + tokens) of every sample: q and k heads x rsqrt(mean_D(x^2) + eps) w (wq / wk
+// T [D]) and rotated -- interleaved pairs -- by row (row_off + t) of table f32 [L, D] = cos[D / 2] | sin[D / 2]; v copied.
+// D % 16 == 0, D <= 160.  src == dst (tokens == L, row_off 0, lds == ldd): in place, v untouched
+int launch_qk_norm_rope(int dtype, const void* src, int64_t lds, void* dst, int64_t ldd, const void* wq, const void* wk,
+                        const float* table, int n, int tokens, int L, int row_off, int H, int D, float eps, hipStream_t stream);
+// y[m, 0..C) = gelu_tanh(x[m, 0..C)) with row strides ldx / ldy (column blocks of wider matrices); y may alias x; the bits of
+// launch_act kind 2
+int launch_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t M, int C, hipStream_t stream);
+// out f32 [n, Cout, gh p, gw p] from rows T [n gh gw, Cout p p] with columns (c, py, px): Flux's _unpack_latents
+int launch_flux_unpack(int dtype, const void* rows, float* out, int n, int Cout, int gh, int gw, int p, hipStream_t stream);
 
 // LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
 // applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.

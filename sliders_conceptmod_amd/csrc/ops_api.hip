@@ -378,6 +378,16 @@ int smi_op_sd3_add_pos(int dtype, const void* x, const void* pos, void* y, int n
 int smi_op_sd3_unpatchify(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream) {
   return launch_sd3_unpatchify(dtype, rows, out, n, cout, gh, gw, p, (hipStream_t)stream);
 }
+int smi_op_qk_norm_rope(int dtype, const void* src, int64_t lds, void* dst, int64_t ldd, const void* wq, const void* wk,
+                        const float* table, int n, int tokens, int l, int row_off, int heads, int d, float eps, void* stream) {
+  return launch_qk_norm_rope(dtype, src, lds, dst, ldd, wq, wk, table, n, tokens, l, row_off, heads, d, eps, (hipStream_t)stream);
+}
+int smi_op_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t m, int c, void* stream) {
+  return launch_gelu_tanh_cols(dtype, x, ldx, y, ldy, m, c, (hipStream_t)stream);
+}
+int smi_op_flux_unpack(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream) {
+  return launch_flux_unpack(dtype, rows, out, n, cout, gh, gw, p, (hipStream_t)stream);
+}
 int smi_op_softmax_rows(int dtype, const float* s, void* p, int rows, int cols, float scale, void* stream) {
   return launch_softmax_rows(dtype, s, p, rows, cols, scale, (hipStream_t)stream);
 }

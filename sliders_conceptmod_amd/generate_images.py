@@ -33,7 +33,17 @@ Defaults: 28 steps, guidance 7.0, 1024 x 1024, bf16 decode, start_noise 750 on t
 purpose: the reference has no SD3 sweep script, so neither start_noise 750 nor guidance 7.0 comes from it (750 is the SD-XL
 sweep's value carried over, 7.0 the published pipeline's default); whether the file adapts the context stream too
 (add_q_proj ... to_add_out, which the reference's own LoRANetwork leaves out) is read from its keys; `--te_model_name` is
-refused with `--base sd3`."""
+refused with `--base sd3`.
+
+`--base flux`: the sweep of a Flux slider (conceptmod/textsliders/train_lora_flux.py writes them, keys `lora_unet-...`) on the
+native Flux transformer, reusing the SD3 branch's helpers: ONE transformer pass per step and sample (no CFG pair) through
+`train_util.predict_noise_flux`; a guidance_embeds model (FLUX.1-dev) takes `--guidance_scale` (default 3.5) as its embedded
+guidance and FLUX.1-schnell ignores it; the 16-channel VAE decodes latents / scaling_factor + shift_factor of its config.
+Prompts: CLIP-L's pooled row and the T5 sequence (`model_util.load_models_flux`; `--no_t5`, or a directory without
+text_encoder_2: `--t5_tokens` zero rows).  Defaults, by the scheduler's config: 4 steps and 256 tokens without dynamic
+shifting (schnell), 28 steps and 512 tokens with it (dev); the slider is on where 1000 sigma <= `--start_noise` (750).
+These defaults are ours: the reference has no Flux sweep script (the step and token counts are the published pipelines',
+750 the SD-XL sweep's value carried over).  `--te_model_name` and DoRA files are refused with `--base flux`."""
 from __future__ import annotations
 
 import argparse
@@ -106,14 +116,24 @@ def lora_file_params(state: Dict[str, torch.Tensor], unet) -> Tuple[int, float, 
         raise ValueError(f"LoRA file mixes alphas {sorted(alphas)}")
     alpha = alphas.pop() if alphas else float(ranks.copy().pop())
     names = {k[:-len(".lora_down.weight")] for k in downs}
-    ctx_stream = any("_attn_add_" in k or "_attn_to_add_out" in k for k in names)  # an SD3 file with the context stream's sites
+    delim = file_delimiter(names)
+    ctx_stream = has_context_stream(names)  # an SD3 / Flux file with the context stream's sites
     for target_replace in (LM.DEFAULT_TARGET_REPLACE, LM.DEFAULT_TARGET_REPLACE + LM.UNET_TARGET_REPLACE_MODULE_CONV):
         for method in TRAIN_METHODS:
-            got = {t[0] for t in LM.select_targets(unet, method, target_replace, LM.LORA_PREFIX_UNET, "_",
+            got = {t[0] for t in LM.select_targets(unet, method, target_replace, LM.LORA_PREFIX_UNET, delim,
                                                    context_stream=ctx_stream)}
             if got == names:
                 return ranks.pop(), alpha, method, list(target_replace)
     raise ValueError("the LoRA file's layers match no train method of this UNet (wrong --base or --pretrained_model?)")
+
+
+def file_delimiter(keys) -> str:
+    """'-' for a file of the reference's Flux trainer (keys `lora_unet-transformer_blocks-0-attn-to_q...`), else '_'."""
+    return "-" if any(k.startswith(LM.LORA_PREFIX_UNET + "-") for k in keys) else "_"
+
+
+def has_context_stream(keys) -> bool:
+    return any(f"{d}attn{d}add_" in k or f"{d}attn{d}to_add_out" in k for k in keys for d in "_-")
 
 
 def load_lora_network(unet, path: str, device):
@@ -153,9 +173,8 @@ def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: i
 
 def lora_network_from_state(unet, state: Dict[str, torch.Tensor], device):
     rank, alpha, method, target_replace = lora_file_params(state, unet)
-    ctx_stream = any("_attn_add_" in k or "_attn_to_add_out" in k for k in state)
-    net = LM.LoRANetwork(unet, rank=rank, multiplier=1.0, alpha=alpha, train_method=method,
-                         target_replace=target_replace, context_stream=ctx_stream).to(device)
+    net = LM.LoRANetwork(unet, rank=rank, multiplier=1.0, alpha=alpha, train_method=method, delimiter=file_delimiter(state),
+                         target_replace=target_replace, context_stream=has_context_stream(state)).to(device)
     net.load_state_dict(state)
     return net
 
@@ -199,6 +218,7 @@ def strip(images) -> "Image.Image":
 def generate_sd3(args) -> List[str]:
     """`--base sd3` (module docstring)."""
     from PIL import Image
+    fill_defaults(args)  # (idempotent: a caller that parsed and came here directly gets --t5_tokens 256 and the rest too)
     if parse_te_names(args.te_model_name) or args.synthetic_towers:
         raise ValueError("--base sd3 takes no --te_model_name / --synthetic_towers: text-encoder LoRA sweeps are not built for SD3")
     if not args.model_name:
@@ -256,9 +276,76 @@ def generate_sd3(args) -> List[str]:
     return written
 
 
+def generate_flux(args) -> List[str]:
+    """`--base flux` (module docstring)."""
+    from PIL import Image
+    if parse_te_names(args.te_model_name) or args.synthetic_towers:
+        raise ValueError("--base flux takes no --te_model_name / --synthetic_towers: text-encoder LoRA sweeps are not built for Flux")
+    if args.scheduler is not None:
+        raise ValueError("--base flux samples with the flow-matching Euler schedule only (leave --scheduler out)")
+    state = load_lora_state(args.model_name) if args.model_name else None  # no file: the frozen network, in folder `frozen`
+    if state is not None and any("dora_scale" in k for k in state):
+        raise ValueError("--base flux: DoRA files are not built for Flux (the engine takes plain LoRA sites only)")
+    device = torch.device(args.device if not str(args.device).isdigit() else f"cuda:{args.device}")
+    if device.type != "cuda":
+        raise ValueError("the product path has no CPU fallback: pass a cuda device")
+    dtype = torch.bfloat16  # (the published Flux weights are bf16)
+    vae_dtype = DTYPES[args.vae_dtype] if args.vae_dtype else torch.bfloat16
+    start_noise = args.start_noise if args.start_noise is not None else 750
+    tokenizers, text_encoders, transformer, scheduler = model_util.load_models_flux(args.pretrained_model, weight_dtype=dtype,
+                                                                                    no_t5=args.no_t5)
+    dev_like = scheduler.use_dynamic_shifting
+    steps = args.ddim_steps if args.ddim_steps is not None else (28 if dev_like else 4)
+    tokens = args.t5_tokens if args.t5_tokens is not None else (512 if dev_like else 256)
+    guidance = args.guidance_scale if args.guidance_scale is not None else 3.5
+    transformer = transformer.to(device, dtype).requires_grad_(False).eval()
+    for te in text_encoders:
+        if te is not None:
+            te.to(device, dtype)
+    network = None
+    if state is not None:
+        network = lora_network_from_state(transformer, state, device)
+        if args.rank is not None and args.rank != network.lora_dim:
+            raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
+        network.__exit__(None, None, None)  # the sweep sets the multiplier per step
+    vae = model_util.load_vae_decoder_sd3(args.pretrained_model).to(device, vae_dtype)
+    scales = parse_scales(args.scales)
+    name = os.path.splitext(os.path.basename(args.model_name))[0] if args.model_name else "frozen"
+    folder = os.path.join(args.save_path, name)
+    for d in [scale_str(s) for s in scales] + ["all"]:
+        os.makedirs(os.path.join(folder, d), exist_ok=True)
+    h = w = args.image_size
+    jd = transformer.cfg.joint_attention_dim
+    written = []
+    for row in read_prompts(args.prompts_path):
+        case = row["case_number"]
+        if not (args.from_case <= case <= args.till_case):
+            continue
+        te, pooled = train_util.encode_prompts_flux(None, tokenizers, text_encoders, row["prompt"], args.num_samples, tokens, jd)
+        images = []
+        for scale in scales:
+            lat = train_util.get_initial_latents_flux(scheduler, args.num_samples, h, w, 1,
+                                                      generator=torch.manual_seed(row["evaluation_seed"])).to(device)
+            lat = train_util.slider_sweep_latents_flux(transformer, network, scheduler, lat, te, pooled, scale, start_noise,
+                                                       guidance, steps)
+            z = lat.float() / vae.config.scaling_factor + vae.config.shift_factor
+            rgb = vae.decode_to_uint8(z).cpu().numpy()
+            images.append([Image.fromarray(rgb[i]) for i in range(rgb.shape[0])])
+        for num in range(args.num_samples):
+            per_scale, all_path = output_paths(args.save_path, name, scales, case, num)
+            for i, p in enumerate(per_scale):
+                images[i][num].save(p)
+                written.append(p)
+            strip([images[i][num] for i in range(len(scales))]).save(all_path)
+            written.append(all_path)
+    return written
+
+
 def generate(args) -> List[str]:
     from PIL import Image
     fill_defaults(args)
+    if args.base == "flux":
+        return generate_flux(args)
     if args.base == "sd3":
         return generate_sd3(args)
     xl = args.base == "xl"
@@ -373,10 +460,13 @@ def build_parser():
     p.add_argument("--pretrained_model", default="synthetic://sd1x",
                    help="local diffusers directory or synthetic://(tiny_)sd1x | sdxl")
     p.add_argument("--negative_prompts", default=None, help="negative prompt (default: the empty prompt)")
-    p.add_argument("--base", choices=["1.4", "xl", "sd3"], default="1.4")
-    p.add_argument("--guidance_scale", type=float, default=None, help="default 7.5 (SD-1.x, SD-XL) / 7.0 (SD3)")
-    p.add_argument("--t5_tokens", type=int, default=256, help="--base sd3: zero rows that stand in for the T5 block of the "
-                   "context (256: the published pipeline's max_sequence_length; 77: its first release)")
+    p.add_argument("--base", choices=["1.4", "xl", "sd3", "flux"], default="1.4")
+    p.add_argument("--guidance_scale", type=float, default=None,
+                   help="default 7.5 (SD-1.x, SD-XL) / 7.0 (SD3) / 3.5, embedded, for a Flux model with guidance_embeds")
+    p.add_argument("--t5_tokens", type=int, default=None, help="--base sd3: zero rows that stand in for the T5 block of the "
+                   "context (default 256: the published pipeline's max_sequence_length; 77: its first release); --base flux: "
+                   "the T5 sequence length (default 256 schnell / 512 dev), zero rows without a T5 tower")
+    p.add_argument("--no_t5", action="store_true", help="--base flux: do not load text_encoder_2 (zero rows stand in)")
     p.add_argument("--image_size", type=int, default=None, help="default 512 (SD-1.x) / 1024 (SD-XL)")
     p.add_argument("--from_case", type=int, default=0)
     p.add_argument("--till_case", type=int, default=1000000)
@@ -398,10 +488,14 @@ def fill_defaults(args):
     """The defaults that depend on --base."""
     if args.image_size is None:
         args.image_size = 512 if args.base == "1.4" else 1024
+    if args.base == "flux":  # steps, tokens and guidance follow the scheduler's config (generate_flux)
+        return args
     if args.guidance_scale is None:
         args.guidance_scale = 7.0 if args.base == "sd3" else 7.5
     if args.ddim_steps is None:
         args.ddim_steps = 28 if args.base == "sd3" else 50
+    if args.t5_tokens is None:
+        args.t5_tokens = 256
     return args
 
 

@@ -10,7 +10,7 @@ through `smi_sched_step` when the latents are on a cuda device."""
 from __future__ import annotations
 
 import os
-from typing import Literal
+from typing import Literal, Optional
 
 import numpy as np
 import torch
@@ -254,20 +254,44 @@ class FlowMatchEulerDiscreteScheduler:
 
     init_noise_sigma = 1.0
 
-    def __init__(self, num_train_timesteps: int = 1000, shift: float = 3.0):
+    def __init__(self, num_train_timesteps: int = 1000, shift: float = 3.0, use_dynamic_shifting: bool = False,
+                 base_shift: float = 0.5, max_shift: float = 1.15, base_image_seq_len: int = 256,
+                 max_image_seq_len: int = 4096):
+        """use_dynamic_shifting (FLUX.1-dev's scheduler config): the shift is chosen per call from the image sequence length
+        -- `set_timesteps(..., mu=calculate_shift(seq_len))` -- and sigma' = e^mu / (e^mu + 1 / sigma - 1) replaces the static
+        shift; the training sigmas then stay un-shifted (sigma_max 1, sigma_min 1 / N), as in the published class."""
         self.num_train_timesteps, self.shift = num_train_timesteps, float(shift)
+        self.use_dynamic_shifting = bool(use_dynamic_shifting)
+        self.base_shift, self.max_shift = float(base_shift), float(max_shift)
+        self.base_image_seq_len, self.max_image_seq_len = int(base_image_seq_len), int(max_image_seq_len)
         base = torch.linspace(1, num_train_timesteps, num_train_timesteps, dtype=torch.float64).flip(0) / num_train_timesteps
-        self._train_sigmas = self.shift_sigma(base)
+        self._train_sigmas = base if self.use_dynamic_shifting else self.shift_sigma(base)
         self.sigma_max, self.sigma_min = float(self._train_sigmas[0]), float(self._train_sigmas[-1])
-        self.set_timesteps(num_train_timesteps)
+        self.set_timesteps(num_train_timesteps, mu=0.0 if self.use_dynamic_shifting else None)
 
     def shift_sigma(self, s):
         return self.shift * s / (1 + (self.shift - 1) * s)
 
-    def set_timesteps(self, num_inference_steps: int, device=None):
+    def calculate_shift(self, image_seq_len: int) -> float:
+        """mu of the Flux pipeline: linear in the image sequence length, base_shift at base_image_seq_len and max_shift at
+        max_image_seq_len."""
+        m = (self.max_shift - self.base_shift) / (self.max_image_seq_len - self.base_image_seq_len)
+        return image_seq_len * m + (self.base_shift - m * self.base_image_seq_len)
+
+    def set_timesteps(self, num_inference_steps: Optional[int] = None, device=None, sigmas=None, mu: Optional[float] = None):
+        """sigmas: the un-shifted schedule to use instead of the linspace over the training range (the Flux pipeline passes
+        linspace(1, 1 / n, n)); mu: required with use_dynamic_shifting, refused without."""
+        import math
         n = self.num_train_timesteps
-        t = torch.linspace(self.sigma_max * n, self.sigma_min * n, num_inference_steps, dtype=torch.float64)
-        sig = self.shift_sigma(t / n)
+        if self.use_dynamic_shifting != (mu is not None):
+            raise ValueError("set_timesteps: mu goes with use_dynamic_shifting (pass mu=scheduler.calculate_shift(seq_len))"
+                             if self.use_dynamic_shifting else "set_timesteps: mu given but the scheduler shifts statically")
+        if sigmas is not None:
+            base = torch.as_tensor(sigmas, dtype=torch.float64)
+            num_inference_steps = base.numel()
+        else:
+            base = torch.linspace(self.sigma_max * n, self.sigma_min * n, num_inference_steps, dtype=torch.float64) / n
+        sig = math.exp(mu) / (math.exp(mu) + (1 / base - 1)) if mu is not None else self.shift_sigma(base)
         self.num_inference_steps = num_inference_steps
         self.timesteps = (sig * n).to(torch.float32)
         self.sigmas = torch.cat([sig, torch.zeros(1, dtype=torch.float64)]).to(torch.float32)
@@ -624,6 +648,7 @@ class SyntheticClipTower:
 
         class _Out:
             hidden_states = (None, pen, None)
+            pooler_output = pool  # (a Flux model reads the un-projected pooled row; the stand-in has one pooled vector)
 
             def __getitem__(_self, i):
                 return (pool,)[i]
@@ -675,6 +700,139 @@ def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float
     raise ValueError(f"cannot load '{name}': pass a local diffusers directory or synthetic://sd3 | synthetic://tiny_sd3")
 
 
+class _PromptCachedTower:
+    """What the two T5 towers share: `encode_cached(prompt, max_length)` runs `encode` once per distinct (prompt, length) and
+    keeps the result -- the tower is frozen, so a prompt's rows never change.  At most CACHE_MAX entries; the oldest goes."""
+
+    CACHE_MAX = 64
+
+    def encode_cached(self, prompt: str, max_length: int):
+        cache = self.__dict__.setdefault("_prompt_cache", {})
+        key = (prompt, max_length)
+        if key not in cache:
+            if len(cache) >= self.CACHE_MAX:
+                cache.pop(next(iter(cache)))
+            cache[key] = self.encode(prompt, max_length)
+        return cache[key]
+
+
+class SyntheticT5Tower(_PromptCachedTower):
+    """Offline stand-in for the T5 encoder of a `synthetic://` Flux model, as SyntheticClipTower is for CLIP: a prompt maps
+    to seeded normal rows [1, max_length, dim] keyed by a hash of the text."""
+
+    def __init__(self, dim: int):
+        self.dim = dim
+        self.device, self.dtype = torch.device("cpu"), torch.float32
+
+    def to(self, device=None, dtype=None):
+        self.device = torch.device(device) if device is not None else self.device
+        self.dtype = dtype or self.dtype
+        return self
+
+    def encode(self, prompt: str, max_length: int):
+        import hashlib
+        seed = int.from_bytes(hashlib.sha256(("t5:" + prompt).encode()).digest()[:8], "little") % (2 ** 31)
+        return torch.randn(1, max_length, self.dim, generator=torch.Generator().manual_seed(seed)).to(self.device, self.dtype)
+
+
+class T5Tower(_PromptCachedTower):
+    """Flux's text_encoder_2, a frozen `transformers.T5EncoderModel` with its tokenizer: the one torch forward of the product
+    (a native tower is the follow-up).  bf16 or fp32, never fp16 (T5's activations overflow it)."""
+
+    def __init__(self, model, tokenizer):
+        self.model, self.tokenizer = model.requires_grad_(False).eval(), tokenizer
+        self.dim = model.config.d_model
+
+    @property
+    def device(self):
+        return next(self.model.parameters()).device
+
+    def to(self, device=None, dtype=None):
+        """A request for fp16 is served in bf16, with a warning: the rest of a pipeline may be moved to fp16 in one loop."""
+        if dtype == torch.float16:
+            import warnings
+            warnings.warn("T5Tower: float16 requested; the T5 encoder runs in bfloat16 instead (its activations overflow fp16)")
+            dtype = torch.bfloat16
+        self.model.to(device=device, dtype=dtype)
+        return self
+
+    @torch.no_grad()
+    def encode(self, prompt: str, max_length: int):
+        ids = self.tokenizer(prompt, padding="max_length", max_length=max_length, truncation=True,
+                             return_tensors="pt").input_ids
+        return self.model(ids.to(self.device))[0]
+
+
+def _flux_from_dir(path: str):
+    """<path>/transformer/config.json + diffusion_pytorch_model.safetensors (safe loader only) -> FluxTransformer2DModel.
+    diffusers' config counts the PACKED width (in_channels 64, patch_size 1); FluxConfig the latent channels and the pack."""
+    import json
+    from safetensors.torch import load_file
+    from . import flux as PF
+    cj = json.load(open(os.path.join(path, "transformer", "config.json")))
+    packed = cj.get("in_channels", 64)
+    if cj.get("patch_size", 1) != 1 or packed % 4:
+        raise ValueError(f"{path}: a Flux transformer config with patch_size 1 and a packed width that is a multiple of 4")
+    cfg = PF.FluxConfig(in_channels=packed // 4, num_layers=cj.get("num_layers", 19),
+                        num_single_layers=cj.get("num_single_layers", 38),
+                        num_attention_heads=cj.get("num_attention_heads", 24),
+                        attention_head_dim=cj.get("attention_head_dim", 128),
+                        joint_attention_dim=cj.get("joint_attention_dim", 4096),
+                        pooled_projection_dim=cj.get("pooled_projection_dim", 768),
+                        guidance_embeds=bool(cj.get("guidance_embeds", False)),
+                        axes_dims_rope=tuple(cj.get("axes_dims_rope", (16, 56, 56))))
+    model = PF.FluxTransformer2DModel(cfg)
+    sd = {}
+    files = [f for f in sorted(os.listdir(os.path.join(path, "transformer"))) if f.endswith(".safetensors")]
+    for f in files:  # (the published checkpoints are sharded)
+        sd.update(load_file(os.path.join(path, "transformer", f)))
+    model.load_state_dict(sd)
+    return model
+
+
+def load_models_flux(pretrained_model_name_or_path: str, weight_dtype=torch.float16, no_t5: bool = False):
+    """(tokenizers, text_encoders, transformer, scheduler) of a Flux pipeline (conceptmod/textsliders/model_util.py
+    load_models_flux).  text_encoders = [CLIP-L on the native engine (its un-projected pooled row conditions the network),
+    the T5 tower or None]: a directory's text_encoder_2 is loaded as a transformers.T5EncoderModel unless `no_t5`; without it
+    zero rows stand in for the sequence embedding (train_util.encode_prompts_flux).  The T5 tower runs in bf16 (fp32 with
+    weight_dtype=torch.float32), never fp16: `T5Tower.to(dtype=torch.float16)` moves it to bf16 and warns.  `synthetic://flux_schnell | flux_dev |
+    tiny_flux`: the architecture with seeded weights and hashed stand-in towers."""
+    from . import flux as PF
+    name = pretrained_model_name_or_path
+    if name.startswith("synthetic://"):
+        kind = name[len("synthetic://"):]
+        cfgs = {"flux_schnell": PF.flux_schnell_config, "flux_dev": PF.flux_dev_config, "tiny_flux": PF.tiny_flux_config}
+        if kind not in cfgs:
+            raise ValueError(f"unknown synthetic model '{name}': synthetic://flux_schnell | flux_dev | tiny_flux")
+        cfg = cfgs[kind]()
+        model = PF.init_synthetic_(PF.FluxTransformer2DModel(cfg), seed=0)
+        scheduler = FlowMatchEulerDiscreteScheduler(1000, 3.0 if kind == "flux_dev" else 1.0,
+                                                    use_dynamic_shifting=kind == "flux_dev")
+        clip = SyntheticClipTower(cfg.pooled_projection_dim, cfg.pooled_projection_dim, 1)
+        t5 = None if no_t5 else SyntheticT5Tower(cfg.joint_attention_dim)
+        return [SyntheticClipTokenizer(1000, 999), None], [clip, t5], model, scheduler
+    if os.path.isdir(name):
+        import json
+        scheduler = FlowMatchEulerDiscreteScheduler(1000, 1.0)
+        sj = os.path.join(name, "scheduler", "scheduler_config.json")
+        if os.path.exists(sj):
+            cj = json.load(open(sj))
+            scheduler = FlowMatchEulerDiscreteScheduler(
+                cj.get("num_train_timesteps", 1000), cj.get("shift", 1.0), cj.get("use_dynamic_shifting", False),
+                cj.get("base_shift", 0.5), cj.get("max_shift", 1.15), cj.get("base_image_seq_len", 256),
+                cj.get("max_image_seq_len", 4096))
+        from transformers import CLIPTokenizer
+        toks, encs = [CLIPTokenizer.from_pretrained(name, subfolder="tokenizer"), None], [_clip_from_dir(name, "text_encoder"), None]
+        if not no_t5 and os.path.isdir(os.path.join(name, "text_encoder_2")):
+            from transformers import T5EncoderModel, T5TokenizerFast
+            tok2 = T5TokenizerFast.from_pretrained(name, subfolder="tokenizer_2")
+            t5 = T5EncoderModel.from_pretrained(name, subfolder="text_encoder_2",
+                                                torch_dtype=torch.float32 if weight_dtype == torch.float32 else torch.bfloat16)
+            toks[1], encs[1] = tok2, T5Tower(t5, tok2)
+        return toks, encs, _flux_from_dir(name), scheduler
+    raise ValueError(f"cannot load '{name}': pass a local diffusers directory or synthetic://flux_schnell | flux_dev | tiny_flux")
+
+
 def load_vae_decoder_sd3(pretrained_model_name_or_path: str):
     """The 16-channel AutoencoderKL decoder of SD3 (no post_quant_conv; scaling 1.5305, shift 0.0609): seeded for
     `synthetic://(tiny_)sd3`, else read from the directory's `vae/` with the safetensors loader."""
@@ -684,6 +842,8 @@ def load_vae_decoder_sd3(pretrained_model_name_or_path: str):
     name = pretrained_model_name_or_path
     if name.startswith("synthetic://"):
         cfg = PV.sd3_vae_config()
+        if "flux" in name:  # FLUX.1's vae/config.json: the same decoder, other latent statistics
+            cfg = PV.VAEConfig(**{**cfg.__dict__, "scaling_factor": 0.3611, "shift_factor": 0.1159})
         if "tiny" in name:
             cfg = PV.VAEConfig(**{**cfg.__dict__, "block_out_channels": (64, 128, 128, 128), "norm_num_groups": 16})
         return PD.init_synthetic_(PD.AutoencoderKLDecoder(cfg), seed=11)

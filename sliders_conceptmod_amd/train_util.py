@@ -125,6 +125,88 @@ def slider_sweep_latents_sd3(transformer, network, scheduler, latents, text_embe
     return latents
 
 
+# ---- Flux (conceptmod/textsliders/train_util.py get_initial_latents_flux, concat_embeddings_flux, encode_prompts_flux,
+# predict_noise_flux, diffusion_flux): their signatures where they make sense without a pipeline object (`pipeline` is kept as
+# the first argument and not used); latents stay UN-packed [n, 16, h, w] -- the engine packs and un-packs -------------------
+FLUX_LATENT_CHANNELS = 16
+
+
+def get_initial_latents_flux(scheduler, n_imgs: int, height: int, width: int, n_prompts: int, generator=None):
+    """randn [n_imgs, 16, height / 8, width / 8], on the CPU from `generator` (the reference draws on the device, unseeded)."""
+    return torch.randn((n_imgs, FLUX_LATENT_CHANNELS, height // VAE_SCALE_FACTOR, width // VAE_SCALE_FACTOR),
+                       generator=generator, device="cpu")
+
+
+def concat_embeddings_flux(unconditional, conditional, n_imgs: int):
+    return torch.cat([unconditional, conditional]).repeat_interleave(n_imgs, dim=0).detach()
+
+
+def encode_prompts_flux(pipeline, tokenizers, text_encoders, prompt: str, num_images_per_prompt: int = 1,
+                        max_sequence_length: int = 512, joint_attention_dim: int = 4096):
+    """(prompt_embeds [n, max_sequence_length, joint_attention_dim], pooled [n, pooled_projection_dim]) as the Flux pipeline's
+    encode_prompt: pooled is CLIP-L's un-projected pooled row (pooler_output, from the native text engine), prompt_embeds the
+    T5 tower's output (text_encoders[1]: model_util.T5Tower, frozen torch in bf16 / fp32, run once per distinct prompt:
+    its `encode_cached`) -- or, where text_encoders[1] is None, max_sequence_length zero rows, as for SD3."""
+    del pipeline
+    tok, clip = tokenizers[0], text_encoders[0]
+    ids = tok(prompt, padding="max_length", max_length=tok.model_max_length, truncation=True, return_tensors="pt").input_ids
+    pooled = clip(ids.to(clip.device), output_hidden_states=False).pooler_output
+    t5 = text_encoders[1] if len(text_encoders) > 1 else None
+    if t5 is None:
+        embeds = torch.zeros(1, max_sequence_length, joint_attention_dim, dtype=pooled.dtype, device=pooled.device)
+    else:
+        embeds = t5.encode_cached(prompt, max_sequence_length).to(pooled.device, pooled.dtype)
+        if embeds.shape[-1] != joint_attention_dim:
+            raise ValueError(f"the T5 tower is {embeds.shape[-1]} wide, the transformer's context {joint_attention_dim}")
+    return (embeds.repeat_interleave(num_images_per_prompt, dim=0), pooled.repeat_interleave(num_images_per_prompt, dim=0))
+
+
+def set_timesteps_flux(scheduler, num_inference_steps: int, latents):
+    """The Flux pipeline's schedule: sigmas linspace(1, 1 / n, n), with mu from the image sequence length (h / 2) (w / 2) where
+    the scheduler shifts dynamically (FLUX.1-dev)."""
+    sig = torch.linspace(1.0, 1.0 / num_inference_steps, num_inference_steps, dtype=torch.float64)
+    seq = (latents.shape[2] // 2) * (latents.shape[3] // 2)
+    scheduler.set_timesteps(sigmas=sig, mu=scheduler.calculate_shift(seq) if scheduler.use_dynamic_shifting else None)
+
+
+def predict_noise_flux(pipeline, transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+                       guidance_scale=7.5, multipliers=None):
+    """One step, ONE transformer pass (no CFG pair): returns the STEPPED latents, as the reference does.  The network is fed
+    the scheduler's timestep (1000 sigma: the reference passes timestep / 1000 to a model that multiplies by 1000) and, where
+    it has a guidance embedder (FLUX.1-dev), guidance_scale as the embedded guidance; FLUX.1-schnell ignores it.
+    `multipliers` (not in the reference signature): one adaptor multiplier per sample."""
+    del pipeline
+    n = latents.shape[0]
+    guidance = [float(guidance_scale)] * n if transformer.cfg.guidance_embeds else None
+    v = transformer(hidden_states=latents, timestep=[float(timestep)] * n, guidance=guidance,
+                    pooled_projections=add_text_embeddings, encoder_hidden_states=text_embeddings,
+                    multipliers=multipliers, return_dict=False)[0]
+    return scheduler.step(v, timestep, latents, return_dict=False)[0]
+
+
+@torch.no_grad()
+def diffusion_flux(pipeline, transformer, scheduler, latents, text_embeddings, add_text_embeddings,
+                   guidance_scale: float = 1.0, total_timesteps: int = 1000, start_timesteps=0, num_inference_steps=4):
+    set_timesteps_flux(scheduler, num_inference_steps, latents)
+    for timestep in scheduler.timesteps[start_timesteps:total_timesteps]:
+        latents = predict_noise_flux(pipeline, transformer, scheduler, timestep, latents, text_embeddings,
+                                     add_text_embeddings, guidance_scale=guidance_scale)
+    return latents
+
+
+@torch.no_grad()
+def slider_sweep_latents_flux(transformer, network, scheduler, latents, text_embeddings, add_text_embeddings, scale: float,
+                              start_noise: float, guidance_scale: float, num_inference_steps: int):
+    """diffusion_flux over the whole schedule with the slider off while 1000 sigma > start_noise and at `scale` below it."""
+    set_timesteps_flux(scheduler, num_inference_steps, latents)
+    for timestep in scheduler.timesteps:
+        on = network is not None and float(timestep) <= start_noise
+        m = [float(scale) if on else 0.0] * latents.shape[0] if network is not None else None
+        latents = predict_noise_flux(None, transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+                                     guidance_scale=guidance_scale, multipliers=m)
+    return latents
+
+
 def predict_noise_xl(unet, scheduler, timestep, latents, text_embeddings, add_text_embeddings, add_time_ids,
                      guidance_scale=7.5, guidance_rescale=0.7):
     latent_model_input = torch.cat([latents] * 2)
