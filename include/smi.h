@@ -414,7 +414,31 @@ int smi_flux_forward(smi_engine* e, int n, const float* sample, const float* tim
                      const void* ctx, const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
                      const float* multipliers, float* out);
 
-/* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample           (train_util.py:290-294, 471-476)
+/* ---- Flux transformer differentiated to the LoRA parameters (training a Flux slider: train_lora_flux) -------------------
+ * The five entries of the trainable MMDiT, for Flux.  A trainable engine also keeps transposed copies of every Linear on the
+ * gradient path (the fused q|k|v of both streams and of the single blocks, to_out.0 / to_add_out, ff / ff_context, proj_mlp,
+ * the single blocks' proj_out and the final proj_out; the modulation Linears, the embedders and norm_out.linear get none)
+ * and a second arena for ONE saved pass and its backward, sized by a dry saved forward + backward; n_sites 0 is refused.
+ *   smi_flux_forward        runs on a trainable engine too and leaves a saved pass intact
+ *   smi_flux_forward_save   the arguments of smi_flux_forward and the same bits in out; the pass is kept for ONE backward.
+ *                           In a saved pass a single block's q|k|v is normalised and rotated out of place and proj_mlp's
+ *                           pre-activation is kept in a tensor of its own: the backward reads both
+ *   smi_flux_backward       d_out f32 [n, in_channels, h, w] (device).  The gradients of the LoRA parameters are ADDED to
+ *                           d_lora_down_flat / d_lora_up_flat; one power-of-two loss scale per sample.  Nothing else is
+ *                           differentiated: not the latents, the context, the pooled vector, the guidance, temb or the
+ *                           RMSNorm weights.  Consumes the saved pass: without one it returns -4.  A pass saved with the
+ *                           adaptor off, or NULL gradient buffers here: returns 0, adds nothing and drops the pass. */
+int smi_flux_train_workspace_bytes(const smi_flux_config* cfg, const smi_lora_site* sites, int n_sites, int batch, int h, int w,
+                                   size_t* bytes);
+int smi_flux_train_create(const smi_flux_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                          int n_sites, int batch, int h, int w, void* workspace, size_t workspace_bytes, void* stream,
+                          smi_engine** out);
+int smi_flux_forward_save(smi_engine* e, int n, const float* sample, const float* timesteps, const float* guidance,
+                          const void* ctx, const void* pooled, const float* lora_down_flat, const float* lora_up_flat,
+                          const float* multipliers, float* out);
+int smi_flux_backward(smi_engine* e, const float* d_out, float* d_lora_down_flat, float* d_lora_up_flat);
+
+/* eps = unet(sample, t, ctx[, text_embeds, time_ids]).sample          (train_util.py:290-294, 471-476)
  *   sample      f32 [n, 4, h, w]  (NCHW, already scale_model_input-ed)
  *   ctx         T   [n, ctx_len, cross_attention_dim]
  *   text_embeds T   [n, P] or NULL ; time_ids f32 [n, 6] or NULL        (SD-XL added_cond_kwargs)
@@ -811,7 +835,7 @@ int smi_op_nchw_to_nhwc_scaled(int dtype, const float* src, void* dst, int nb, i
  *   sd3_add_pos     y [n gh gw, d] = x + the centre-cropped gh x gw window of pos T [s s, d] (top (s - gh) / 2, left (s - gw) / 2)
  *   sd3_unpatchify  out f32 [n, cout, gh p, gw p] from rows T [n gh gw, p p cout], columns (py, px, c)
  * and the backwards to the activations (tests/test_mmdit_bwd_kernels_gpu.py); scale, shift and gate take no gradient:
- *   adaln_modulate_bwd  dx [m, c] = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ add), g = dy (1 + scale),
+ *   adaln_modulate_bwd  dx [m, c] = rstd (g - mean_c(g) - xhat mean_c(g xhat)) (+ add), g = dy (1 + scale), c <= 3072,
  *                   xhat = (x - mean) rstd from the forward's mean_rstd; add [m, c] is optional and may alias dx
  *   gate_residual_bwd   df [m, c] = gate dy (the gradient of h is dy itself)
  * pack and split are each other's backward. */
@@ -838,6 +862,20 @@ int smi_op_qk_norm_rope(int dtype, const void* src, int64_t lds, void* dst, int6
                         const float* table, int n, int tokens, int l, int row_off, int heads, int d, float eps, void* stream);
 int smi_op_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t m, int c, void* stream);
 int smi_op_flux_unpack(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream);
+/* Their backwards to the activations (tests/test_flux_bwd_kernels_gpu.py); the RMSNorm weights take no gradient.
+ * qk_norm_rope_bwd: dsrc T [n tokens, ldx] from rows [row_off, row_off + tokens) of every sample of the joint gradient dj T
+ * [n l, ldd] and the pre-norm source src T [n tokens, lds]: per q or k head dy = Rot^T(do), g = dy w,
+ * dx = r (g - x r^2 mean(g x)), r = rsqrt(mean(x^2) + eps) recomputed from x; v copied.  dsrc aliases neither input.
+ * gelu_tanh_cols_bwd: dx[m, 0..c) = dy[m, 0..c) gelu_tanh'(x[m, 0..c)) with row strides ldx / ldy / ldd: the bits of
+ * smi_op_act kind 2's backward.
+ * flux_unpack_bwd: rows T [n gh gw, cout p p], columns (c, py, px), = scale_dev[n] d_out f32 [n, cout, gh p, gw p]. */
+int smi_op_qk_norm_rope_bwd(int dtype, const void* dj, int64_t ldd, const void* src, int64_t lds, void* dsrc, int64_t ldx,
+                            const void* wq, const void* wk, const float* table, int n, int tokens, int l, int row_off, int heads,
+                            int d, float eps, void* stream);
+int smi_op_gelu_tanh_cols_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t ldy, void* dx, int64_t ldd, int64_t m,
+                              int c, void* stream);
+int smi_op_flux_unpack_bwd(int dtype, const float* d_out, void* rows, int n, int cout, int gh, int gw, int p,
+                           const float* scale_dev, void* stream);
 int smi_op_geglu(int dtype, const void* proj, void* out, const void* dout, void* dproj, int m, int c4, void* stream);
 /* ff.net.0 with the GEGLU gate fused into the GEMM epilogue (the engine's forward path for
  * diffusers GEGLU: proj = x W^T + b [M, N]; out[M, N/2] = proj[:, :N/2] * gelu(proj[:, N/2:])).  Rows >= proj_row0 of

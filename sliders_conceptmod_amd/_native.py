@@ -216,6 +216,14 @@ _SIGS = {
                                   C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_flux_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)] +
                          [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),
+    "smi_flux_train_workspace_bytes": (C.c_int, [C.POINTER(FluxConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int, C.c_int,
+                                                 C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_flux_train_create": (C.c_int, [C.POINTER(FluxConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                        C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p,
+                                        C.POINTER(C.c_void_p)]),
+    "smi_flux_forward_save": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)] +
+                              [C.c_void_p] * 4 + [C.POINTER(C.c_float), C.c_void_p]),
+    "smi_flux_backward": (C.c_int, [C.c_void_p] * 4),
     "smi_unet_forward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p, C.c_float, C.c_int, C.c_void_p]),
     "smi_unet_backward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -292,6 +300,11 @@ _SIGS = {
     "smi_op_gelu_tanh_cols": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_int,
                                         C.c_void_p]),
     "smi_op_flux_unpack": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p]),
+    "smi_op_qk_norm_rope_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] +
+                                [C.c_void_p] * 3 + [C.c_int] * 6 + [C.c_float, C.c_void_p]),
+    "smi_op_gelu_tanh_cols_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64,
+                                            C.c_int64, C.c_int, C.c_void_p]),
+    "smi_op_flux_unpack_bwd": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p] + [C.c_int] * 5 + [C.c_void_p, C.c_void_p]),
     "smi_op_chan_mix": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_conv3x3_small": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int] * 6 + [C.c_void_p]),
     "smi_op_nchw_to_nhwc": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p] + [C.c_int] * 4 + [C.c_float, C.c_void_p]),

@@ -77,19 +77,6 @@ __global__ void ew_kernel(const T* __restrict__ a, const T* __restrict__ b, T* _
   }
 }
 
-// (x sigmoid(w))' with w = 2u = c x (1 + a x^2): s + x s (1 - s) w', w' = c (1 + 3 a x^2).  Through t = exp(-|w|) <= 1, so that
-// nothing overflows for large |x| (exp(+w) would at x = -12) and 1 - s is formed without a subtraction (s -> 1 at large x):
-// s = 1 / (1 + t) or t / (1 + t) by the sign of w, s (1 - s) = t / (1 + t)^2
-__device__ __forceinline__ float dgelu_tanh_f(float x) {
-  const float x2 = x * x;
-  const float w = 1.5957691216057308f * x * __builtin_fmaf(0.044715f, x2, 1.f);
-  const float t = __expf(-fabsf(w));
-  const float r = 1.f / (1.f + t);
-  const float s = w >= 0.f ? r : t * r;
-  const float dw = 1.5957691216057308f * __builtin_fmaf(3.f * 0.044715f, x2, 1.f);
-  return __builtin_fmaf(x * dw, t * r * r, s);
-}
-
 // dx = dy * act'(x): KIND 0 quick_gelu (x sigmoid(1.702 x))' = s (1 + 1.702 x (1 - s)), KIND 1 erf-gelu (dgelu_f), KIND 2
 // tanh-gelu (dgelu_tanh_f).  Whole 8-packs vectorised; the n % 8 tail elements one thread each
 template <typename T, int KIND>

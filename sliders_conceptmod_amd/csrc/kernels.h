@@ -441,6 +441,18 @@ int launch_qk_norm_rope(int dtype, const void* src, int64_t lds, void* dst, int6
 int launch_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_t ldy, int64_t M, int C, hipStream_t stream);
 // out f32 [n, Cout, gh p, gw p] from rows T [n gh gw, Cout p p] with columns (c, py, px): Flux's _unpack_latents
 int launch_flux_unpack(int dtype, const void* rows, float* out, int n, int Cout, int gh, int gw, int p, hipStream_t stream);
+// The backwards (wq and wk are frozen: no gradient).  qk_norm_rope's: dsrc T [n tokens, ldx] from rows [row_off, row_off + tokens)
+// of every sample of the joint gradient dj T [n L, ldd] and the pre-norm source src T [n tokens, lds]: per q or k head the
+// rotation's transpose, g = dy w, dx = r (g - x r^2 mean_D(g x)) with r recomputed from x; v copied.  dsrc aliases nothing
+int launch_qk_norm_rope_bwd(int dtype, const void* dj, int64_t ldd, const void* src, int64_t lds, void* dsrc, int64_t ldx,
+                            const void* wq, const void* wk, const float* table, int n, int tokens, int L, int row_off, int H,
+                            int D, float eps, hipStream_t stream);
+// dx[m, 0..C) = dy[m, 0..C) gelu_tanh'(x[m, 0..C)) with row strides ldx / ldy / ldd; the bits of launch_act_bwd kind 2
+int launch_gelu_tanh_cols_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t ldy, void* dx, int64_t ldd, int64_t M,
+                              int C, hipStream_t stream);
+// rows T [n gh gw, Cout p p], columns (c, py, px), = scale_dev[n] x d_out f32 [n, Cout, gh p, gw p]: flux_unpack's inverse
+int launch_flux_unpack_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
+                           const float* scale_dev, hipStream_t stream);
 
 // LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
 // applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.

@@ -20,8 +20,7 @@ __device__ __forceinline__ float wave_sum_all(float v) {
   return v;
 }
 
-constexpr int ADALN_MAXV = 4;      // the backward: C <= 2048
-constexpr int ADALN_FWD_MAXV = 6;  // the forward: C <= 3072 (Flux's width); C <= 2048 runs the instantiations it always did
+constexpr int ADALN_MAXV = 6;  // C <= 3072 (Flux's width), forward and backward; C <= 2048 runs the instantiations it always did
 
 // y[r, :] = LN(x[r, :]) (1 + scale[s, :]) + shift[s, :], s = r / rows_per_sample; one wave per row, the row kept in
 // registers between the statistics (two passes: mean, then centred squares) and the apply.  scale / shift: rows of
@@ -272,7 +271,7 @@ __global__ void sd3_unpatchify_bwd_kernel(const float* __restrict__ d_out, T* __
 
 int launch_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const void* mod, const float* mean_rstd, const void* add,
                               void* dx, int M, int C, int rows_per_sample, int64_t ldm, int off_scale, hipStream_t stream) {
-  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0 && C <= 512 * ADALN_MAXV, "adaln_modulate_bwd: C %% 8, C <= 2048 (got M=%d C=%d)", M, C);
+  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0 && C <= 512 * ADALN_MAXV, "adaln_modulate_bwd: C %% 8, C <= 3072 (got M=%d C=%d)", M, C);
   SMI_CHECK(rows_per_sample >= 1 && ldm % 8 == 0 && off_scale % 8 == 0 && off_scale >= 0 && off_scale + C <= ldm,
             "adaln_modulate_bwd: scale is C columns of a mod row at an offset that is a multiple of 8 (ldm=%lld, %d)",
             (long long)ldm, off_scale);
@@ -288,7 +287,9 @@ int launch_adaln_modulate_bwd(int dtype, const void* x, const void* dy, const vo
     case 1: GO(T_, 1); break;     \
     case 2: GO(T_, 2); break;     \
     case 3: GO(T_, 3); break;     \
-    default: GO(T_, 4); break;    \
+    case 4: GO(T_, 4); break;     \
+    case 5: GO(T_, 5); break;     \
+    default: GO(T_, 6); break;    \
   }
   if (dtype == DT_F16) { GO_T(f16) } else { GO_T(bf16) }
 #undef GO_T
@@ -330,7 +331,7 @@ int launch_sd3_unpatchify_bwd(int dtype, const float* d_out, void* rows, int n, 
 
 int launch_adaln_modulate(int dtype, const void* x, const void* mod, void* y, float* mean_rstd, int M, int C,
                           int rows_per_sample, int64_t ldm, int off_scale, int off_shift, float eps, hipStream_t stream) {
-  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0 && C <= 512 * ADALN_FWD_MAXV, "adaln_modulate: C %% 8, C <= 3072 (got M=%d C=%d)", M, C);
+  SMI_CHECK(M >= 1 && C >= 8 && C % 8 == 0 && C <= 512 * ADALN_MAXV, "adaln_modulate: C %% 8, C <= 3072 (got M=%d C=%d)", M, C);
   SMI_CHECK(rows_per_sample >= 1 && ldm % 8 == 0 && off_scale % 8 == 0 && off_shift % 8 == 0 && off_scale >= 0 &&
                 off_shift >= 0 && off_scale + C <= ldm && off_shift + C <= ldm,
             "adaln_modulate: scale / shift are C columns of a mod row at offsets that are multiples of 8 (ldm=%lld, %d, %d)",

@@ -388,6 +388,20 @@ int smi_op_gelu_tanh_cols(int dtype, const void* x, int64_t ldx, void* y, int64_
 int smi_op_flux_unpack(int dtype, const void* rows, float* out, int n, int cout, int gh, int gw, int p, void* stream) {
   return launch_flux_unpack(dtype, rows, out, n, cout, gh, gw, p, (hipStream_t)stream);
 }
+int smi_op_qk_norm_rope_bwd(int dtype, const void* dj, int64_t ldd, const void* src, int64_t lds, void* dsrc, int64_t ldx,
+                            const void* wq, const void* wk, const float* table, int n, int tokens, int l, int row_off, int heads,
+                            int d, float eps, void* stream) {
+  return launch_qk_norm_rope_bwd(dtype, dj, ldd, src, lds, dsrc, ldx, wq, wk, table, n, tokens, l, row_off, heads, d, eps,
+                                 (hipStream_t)stream);
+}
+int smi_op_gelu_tanh_cols_bwd(int dtype, const void* x, int64_t ldx, const void* dy, int64_t ldy, void* dx, int64_t ldd, int64_t m,
+                              int c, void* stream) {
+  return launch_gelu_tanh_cols_bwd(dtype, x, ldx, dy, ldy, dx, ldd, m, c, (hipStream_t)stream);
+}
+int smi_op_flux_unpack_bwd(int dtype, const float* d_out, void* rows, int n, int cout, int gh, int gw, int p,
+                           const float* scale_dev, void* stream) {
+  return launch_flux_unpack_bwd(dtype, d_out, rows, n, cout, gh, gw, p, scale_dev, (hipStream_t)stream);
+}
 int smi_op_softmax_rows(int dtype, const float* s, void* p, int rows, int cols, float scale, void* stream) {
   return launch_softmax_rows(dtype, s, p, rows, cols, scale, (hipStream_t)stream);
 }

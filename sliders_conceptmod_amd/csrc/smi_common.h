@@ -131,6 +131,19 @@ __device__ __forceinline__ float dgelu_f(float x) {
   return 0.5f * (1.f + erf_as(x * 0.70710678118654752f)) + x * 0.39894228040143268f * __expf(-0.5f * x * x);
 }
 
+// (x sigmoid(w))' with w = 2u = c x (1 + a x^2): s + x s (1 - s) w', w' = c (1 + 3 a x^2).  Through t = exp(-|w|) <= 1, so that
+// nothing overflows for large |x| (exp(+w) would at x = -12) and 1 - s is formed without a subtraction (s -> 1 at large x):
+// s = 1 / (1 + t) or t / (1 + t) by the sign of w, s (1 - s) = t / (1 + t)^2
+__device__ __forceinline__ float dgelu_tanh_f(float x) {
+  const float x2 = x * x;
+  const float w = 1.5957691216057308f * x * __builtin_fmaf(0.044715f, x2, 1.f);
+  const float t = __expf(-fabsf(w));
+  const float r = 1.f / (1.f + t);
+  const float s = w >= 0.f ? r : t * r;
+  const float dw = 1.5957691216057308f * __builtin_fmaf(3.f * 0.044715f, x2, 1.f);
+  return __builtin_fmaf(x * dw, t * r * r, s);
+}
+
 // Canonical arithmetic of the LoRA delta in every GEMM epilogue: ONE sequential fp32 FMA chain over the rank index
 // (ascending, from zero), then one FMA with the scale onto the running value.  Written with explicit fmaf so that the
 // result does not depend on how hipcc contracts / vectorises a sum of products in a given kernel, and because this is

@@ -6,8 +6,9 @@ add_q_proj,add_k_proj,add_v_proj,to_add_out,norm_q,norm_k,norm_added_q,norm_adde
 `single_transformer_blocks.<i>.{norm.linear,attn.{to_q,to_k,to_v,norm_q,norm_k},proj_mlp,proj_out}`, `norm_out.linear`,
 `proj_out`); the attention class is called `Attention`, so `lora.select_targets` finds it as the reference's
 `target_replace=["Attention"]` does (conceptmod/textsliders/train_lora_flux.py).  No arithmetic happens here: `forward` runs
-csrc/engine_flux.hip.  The forward only: the backward and the trainer are not built yet, so a grad-enabled call computes
-the same frozen-graph output and carries no gradient.
+csrc/engine_flux.hip.  With grad enabled and an attached network whose flat parameter requires grad, the call goes through
+`_FluxFn`: the trainable engine saves the pass and its backward gives the gradient to that parameter (train_lora_flux);
+nothing else is differentiated.
 
 `forward` takes UN-packed NCHW latents: the engine packs ([n, 16, h, w] -> [n, (h/2)(w/2), 64], columns (c, py, px), which
 is the pipeline's `_pack_latents`), builds the rotary table from (h, w, context length) itself, and un-packs its output;
@@ -141,32 +142,61 @@ def workspace_bytes(cfg: FluxConfig, dtype: torch.dtype, sites: Sequence[dict], 
     return out.value
 
 
+def train_workspace_bytes(cfg: FluxConfig, dtype: torch.dtype, sites: Sequence[dict], batch: int, h: int, w: int,
+                          context_len: int) -> int:
+    """smi_flux_train_workspace_bytes: the host-only dry forward + saved forward + backward of a trainable engine."""
+    arr, _keep = _native.make_sites(sites)
+    out = C.c_size_t(0)
+    _native.check(_native.lib().smi_flux_train_workspace_bytes(C.byref(engine_config_c(cfg, dtype, context_len)), arr,
+                                                               len(sites), batch, h, w, C.byref(out)),
+                  "smi_flux_train_workspace_bytes")
+    return out.value
+
+
 class FluxEngine(_native._EngineBase):
     """Flux transformer on the HIP engine for one latent size and context length (smi_flux_*): the forward with Linear LoRA
-    sites at one multiplier per sample."""
+    sites at one multiplier per sample; `trainable=True` (smi_flux_train_*): also `forward_save` and `backward`, the gradient
+    of the output to the LoRA parameters."""
 
     def __init__(self, cfg: FluxConfig, dtype: torch.dtype, state: dict, sites: Sequence[dict], batch: int, h: int,
-                 w: int, context_len: int, device):
+                 w: int, context_len: int, device, trainable: bool = False):
         self.cfg, self.dtype, self.batch, self.h, self.w, self.context_len = cfg, dtype, batch, h, w, context_len
+        self.trainable = trainable
         self.cfg_c = engine_config_c(cfg, dtype, context_len)
         arr, self._site_keep = _native.make_sites(sites)
         out = C.c_size_t(0)
         lib = _native.lib()
-        _native.check(lib.smi_flux_workspace_bytes(C.byref(self.cfg_c), arr, len(sites), batch, h, w, C.byref(out)),
-                      "smi_flux_workspace_bytes")
+        size_fn, create_fn, name = ((lib.smi_flux_train_workspace_bytes, lib.smi_flux_train_create, "smi_flux_train")
+                                    if trainable else (lib.smi_flux_workspace_bytes, lib.smi_flux_create, "smi_flux"))
+        _native.check(size_fn(C.byref(self.cfg_c), arr, len(sites), batch, h, w, C.byref(out)), name + "_workspace_bytes")
         self.workspace_bytes = out.value
         self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
         warr, self._keep = _native._weight_table(state, dtype, self.workspace.device)
         handle = C.c_void_p()
         with torch.cuda.device(self.workspace.device):
-            _native.check(lib.smi_flux_create(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch, h, w,
-                                              _native.ptr(self.workspace), out.value, _native.stream_ptr(),
-                                              C.byref(handle)), "smi_flux_create")
+            _native.check(create_fn(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch, h, w,
+                                    _native.ptr(self.workspace), out.value, _native.stream_ptr(), C.byref(handle)),
+                          name + "_create")
         self.handle = handle
+        self._borrowed = None  # the operands of the saved pass: the engine reads the LoRA parameters again in its backward
+
+    def forward_save(self, sample, timesteps, guidance, ctx, pooled, lora_down, lora_up, multipliers, out=None) -> torch.Tensor:
+        """`forward`, with the pass kept for one `backward` (smi_flux_forward_save): the same bits in the output."""
+        return self.forward(sample, timesteps, guidance, ctx, pooled, lora_down, lora_up, multipliers, out, save=True)
+
+    def backward(self, d_out: torch.Tensor, d_down: Optional[torch.Tensor], d_up: Optional[torch.Tensor]) -> None:
+        """smi_flux_backward: d_out f32 [n, 16, h, w]; the LoRA gradients are ADDED to d_down / d_up (f32, flat layout).
+        Consumes the saved pass (SmiError without one)."""
+        d_out = d_out.to(self.workspace.device, torch.float32).contiguous()
+        with torch.cuda.device(self.workspace.device):
+            rc = _native.lib().smi_flux_backward(self.handle, _native.ptr(d_out), _native.ptr(d_down), _native.ptr(d_up))
+        self._borrowed = None
+        _native.check(rc, "smi_flux_backward")
 
     def forward(self, sample: torch.Tensor, timesteps, guidance, ctx: torch.Tensor, pooled: torch.Tensor,
                 lora_down: Optional[torch.Tensor] = None, lora_up: Optional[torch.Tensor] = None,
-                multipliers: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+                multipliers: Optional[Sequence[float]] = None, out: Optional[torch.Tensor] = None,
+                save: bool = False) -> torch.Tensor:
         """sample [n, 16, h, w] -> f32 [n, 16, h, w].  timesteps: n floats (the scheduler's 1000 sigma), on the host;
         guidance: n floats for a guidance_embeds model, None for one without."""
         n = sample.shape[0]
@@ -195,11 +225,38 @@ class FluxEngine(_native._EngineBase):
             out = torch.empty((n, cfg.in_channels, self.h, self.w), dtype=torch.float32, device=dev)
         tarr = (C.c_float * n)(*ts)
         marr = None if multipliers is None else (C.c_float * n)(*[float(m) for m in multipliers])
+        fn, name = ((_native.lib().smi_flux_forward_save, "smi_flux_forward_save") if save
+                    else (_native.lib().smi_flux_forward, "smi_flux_forward"))
         with torch.cuda.device(dev):
-            _native.check(_native.lib().smi_flux_forward(self.handle, n, _native.ptr(sample), tarr, garr, _native.ptr(ctx),
-                                                         _native.ptr(pooled), _native.ptr(lora_down), _native.ptr(lora_up),
-                                                         marr, _native.ptr(out)), "smi_flux_forward")
+            _native.check(fn(self.handle, n, _native.ptr(sample), tarr, garr, _native.ptr(ctx), _native.ptr(pooled),
+                             _native.ptr(lora_down), _native.ptr(lora_up), marr, _native.ptr(out)), name)
+        if save:
+            self._borrowed = (lora_down, lora_up)
         return out
+
+
+class _FluxFn(torch.autograd.Function):
+    """Autograd bookkeeping only: forward and backward are single calls into the trainable engine.  The one differentiable
+    input is the network's flat parameter."""
+
+    @staticmethod
+    def forward(ctx, engine, flat, n_down, sample, ts, gs, ehs, pooled, multipliers):
+        flat_d = flat.detach()
+        out = engine.forward_save(sample, ts, gs, ehs, pooled, flat_d[:n_down], flat_d[n_down:], multipliers)
+        ctx.engine, ctx.n_down, ctx.flat = engine, n_down, flat_d
+        engine._saved_by = ctx
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        if getattr(ctx.engine, "_saved_by", None) is not ctx:
+            raise _native.SmiError(
+                "backward through a Flux transformer output whose saved activations are gone: the engine keeps the pass of "
+                "the LAST grad-enabled forward only (a later grad-enabled forward or a previous backward released it)")
+        ctx.engine._saved_by = None
+        g = torch.zeros_like(ctx.flat)
+        ctx.engine.backward(d_out, g[:ctx.n_down], g[ctx.n_down:])
+        return None, g, None, None, None, None, None, None, None
 
 
 def _per_sample(v, n):
@@ -238,25 +295,28 @@ class FluxTransformer2DModel(EngineCacheMixin, nn.Module):
         net = self.__dict__.get("_lora_network")
         return net.engine_sites() if net is not None and net.unet_loras else []
 
-    def _new_engine(self, state, n, h, w, context_len, _net_id):
-        return FluxEngine(self.cfg, self.dtype, state, self._sites(), max(n, 1), h, w, context_len, self.device)
+    def _new_engine(self, state, n, h, w, context_len, trainable, _net_id):
+        return FluxEngine(self.cfg, self.dtype, state, self._sites(), max(n, 1), h, w, context_len, self.device,
+                          trainable=trainable)
 
-    def engine(self, n: int, h: int, w: int, context_len: int) -> FluxEngine:
+    def engine(self, n: int, h: int, w: int, context_len: int, trainable: bool = False) -> FluxEngine:
         """The engine for this latent size and context length, with the attached network's sites (fixed at creation: an engine
-        built for another network is closed first)."""
+        built for another network is closed first).  trainable: the engine that saves a pass and differentiates it."""
         net = self.__dict__.get("_lora_network")
         for key, e in list(self._engines.items()):
             if key[-1] != id(net):
                 e.close()
                 del self._engines[key]
-        return self._engine(n, h, w, context_len, id(net))
+        return self._engine(n, h, w, context_len, trainable, id(net))
 
     def forward(self, hidden_states, timestep, guidance=None, pooled_projections=None, encoder_hidden_states=None,
                 txt_ids=None, img_ids=None, multipliers=None, return_dict: bool = True, **_):
         """diffusers' call on un-packed latents [n, 16, h, w].  `timestep`: a number or n of them, the scheduler's 1000 sigma
         (the reference passes timestep / 1000 to a model that multiplies by 1000); `guidance`: the embedded guidance scale
         of a guidance_embeds model (a number or n), ignored by a model without the embedder.  An attached LoRANetwork runs at
-        its current multiplier (0 outside `with network:`) on every sample, or at `multipliers` (one per sample)."""
+        its current multiplier (0 outside `with network:`) on every sample, or at `multipliers` (one per sample).  With grad
+        enabled and a network whose parameter requires grad, the pass is saved and the output carries the gradient to that
+        parameter."""
         n, _c, h, w = hidden_states.shape
         ts = _per_sample(timestep, n)
         gs = None
@@ -266,18 +326,24 @@ class FluxTransformer2DModel(EngineCacheMixin, nn.Module):
             gs = _per_sample(guidance, n)
         net = self.__dict__.get("_lora_network")
         down = up = None
+        hidden_states, encoder_hidden_states = hidden_states.detach(), encoder_hidden_states.detach()
+        pooled_projections = pooled_projections.detach()
         if net is not None and net.unet_loras:
             flat, n_down, mult = net.engine_params()
             if multipliers is None:
                 multipliers = [mult] * n
+            if torch.is_grad_enabled() and flat.requires_grad:
+                e = self.engine(n, h, w, encoder_hidden_states.shape[1], trainable=True)
+                out = _FluxFn.apply(e, flat, n_down, hidden_states, ts, gs, encoder_hidden_states, pooled_projections,
+                                    [float(m) for m in multipliers])
+                return TransformerOutput(out) if return_dict else (out,)
             flat = flat.detach()
             down, up = flat[:n_down], flat[n_down:]
         else:
             multipliers = None
         e = self.engine(n, h, w, encoder_hidden_states.shape[1])
         with torch.no_grad():
-            out = e.forward(hidden_states.detach(), ts, gs, encoder_hidden_states.detach(), pooled_projections.detach(),
-                            down, up, multipliers)
+            out = e.forward(hidden_states, ts, gs, encoder_hidden_states, pooled_projections, down, up, multipliers)
         return TransformerOutput(out) if return_dict else (out,)
 
 

@@ -6,9 +6,15 @@ a forward (GEMMs and attention, from the shapes), the TF/s both arms reach and t
 alone at that shape (the double block's two launches and the single block's in-place one) next to its byte bound at the
 8 TB/s HBM peak, and writes them to --out.  No threshold: no time is a pass or fail condition.
 
+`--train`: the slider step's differentiated part instead -- the trainable engine's saved forward + backward to the rank-4
+LoRA matrices of the attention projections (multiplier 1, d_out random) next to torch autograd through the same restatement
+with the LoRA delta added to the adapted Linears, arms alternating; the gradient's distance between the two arms, the
+trainable workspace in bytes and the torch arm's peak allocation are reported with the times.
+
 The model is built on the device, so flux.init_synthetic_ draws its 12 billion parameters there (on the CPU: minutes).
 
-    python tools/bench_flux.py [--rounds 2] [--iters 3] [--sizes 1024,512] [--dtypes bf16] [--out profiles/flux_forward_n1_ctx256.json]"""
+    python tools/bench_flux.py [--rounds 2] [--iters 3] [--sizes 1024,512] [--dtypes bf16] [--out profiles/flux_forward_n1_ctx256.json]
+    python tools/bench_flux.py --train [--sizes 512,1024] [--out profiles/flux_train_n1_ctx256.json]"""
 import argparse
 import ctypes as C
 import json
@@ -60,13 +66,20 @@ def rope_tables(cfg, gh, gw, Nc, device):
     return ang.cos().float().to(device), ang.sin().float().to(device)
 
 
-def torch_forward(sd, cfg, x, ts, guidance, ctx, pooled, cos, sin):
-    """The network in torch ops, in the dtype of `sd` (tests/flux_refs.py is the float64 form of the same graph)."""
+def torch_forward(sd, cfg, x, ts, guidance, ctx, pooled, cos, sin, lora=None, mults=None):
+    """The network in torch ops, in the dtype of `sd` (tests/flux_refs.py is the float64 form of the same graph).  lora:
+    {module path: (down [r, in], up [out, r], alpha / r)} fp32 leaves with mults [n] the per-sample multipliers."""
     n, dt = x.shape[0], ctx.dtype
     p, d, heads, hd_ = cfg.patch_size, cfg.inner_dim, cfg.num_attention_heads, cfg.attention_head_dim
     gh, gw = x.shape[2] // p, x.shape[3] // p
     Nx, Nc = gh * gw, ctx.shape[1]
-    lin = lambda t, k: F.linear(t, sd[k + ".weight"], sd[k + ".bias"])
+
+    def lin(t, k):
+        y = F.linear(t, sd[k + ".weight"], sd[k + ".bias"])
+        if lora is not None and k in lora:
+            dn, up, sc = lora[k]
+            y = y + (mults.reshape([n] + [1] * (t.dim() - 1)) * sc * ((t.float() @ dn.t()) @ up.t())).to(dt)
+        return y
     half = torch.exp(-math.log(10000.0) * torch.arange(128, device=x.device, dtype=torch.float32) / 128)
 
     def embed(v, k):
@@ -144,6 +157,80 @@ def qk_norm_rope_ms(cfg, dt, Nx, Nc, cos, sin, iters=20):
     return timed(pair, iters), timed(inplace, iters), pair_bytes, inplace_bytes
 
 
+def train_rows(a, cfg, model, dname, dt):
+    """--train (module docstring): one row per size."""
+    from sliders_conceptmod_amd import lora as L
+    n, Nc = 1, a.context_tokens
+    rows = []
+    sd = {k: v.detach() for k, v in model.state_dict().items()}
+    torch.manual_seed(0)
+    net = L.LoRANetwork(model, rank=4, multiplier=1.0, delimiter="-", target_replace=["Attention"], train_method="full",
+                        context_stream=a.context_stream).to("cuda")
+    with torch.no_grad():
+        net.flat[net._n_down:].normal_(0, 0.05)
+    flat, nd = net.flat.detach(), net._n_down
+    for size in (int(s) for s in a.sizes.split(",")):
+        lat = size // 8
+        g = torch.Generator().manual_seed(1)
+        x = torch.randn(n, cfg.in_channels, lat, lat, generator=g).cuda()
+        ctx = torch.randn(n, Nc, cfg.joint_attention_dim, generator=g).to(dt).cuda()
+        pooled = torch.randn(n, cfg.pooled_projection_dim, generator=g).to(dt).cuda()
+        d_out = torch.randn(n, cfg.in_channels, lat, lat, generator=g).cuda()
+        ts, gs, mults = [500.0] * n, ([3.5] * n if cfg.guidance_embeds else None), [1.0] * n
+        tsd, md = torch.tensor(ts, device="cuda"), torch.tensor(mults, device="cuda")
+        gsd = torch.tensor(gs, device="cuda") if gs else None
+        cos, sin = rope_tables(cfg, lat // 2, lat // 2, Nc, "cuda")
+        try:
+            eng = model.engine(n, lat, lat, Nc, trainable=True)
+        except (RuntimeError, _native.SmiError) as err:  # the plan does not fit the card: report it and go on
+            row = {"model": a.model, "mode": "train", "image": size, "dtype": dname, "n": n, "context_tokens": Nc,
+                   "error": str(err)[:200], "plan_bytes": M.train_workspace_bytes(cfg, dt, net.engine_sites(), n, lat, lat, Nc)}
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+            continue
+        grad = torch.zeros_like(flat)
+
+        def engine_pair():
+            eng.forward_save(x, ts, gs, ctx, pooled, flat[:nd], flat[nd:], mults)
+            eng.backward(d_out, grad[:nd], grad[nd:])
+
+        lv = {l.target_path: (flat[l.off_down:l.off_down + 4 * l.in_dim].view(4, l.in_dim).clone().requires_grad_(True),
+                              flat[nd + l.off_up:nd + l.off_up + l.out_dim * 4].view(l.out_dim, 4).clone().requires_grad_(True),
+                              float(l.scale)) for l in net.unet_loras}
+
+        def torch_pair():
+            for dn, up, _ in lv.values():
+                dn.grad = up.grad = None
+            (torch_forward(sd, cfg, x, tsd, gsd, ctx, pooled, cos, sin, lv, md) * d_out).sum().backward()
+
+        grad.zero_()
+        engine_pair()
+        torch.cuda.reset_peak_memory_stats()  # (the torch arm's peak, on top of what is resident: weights, the workspace)
+        torch_pair()
+        tg = torch.zeros_like(flat)
+        for l in net.unet_loras:
+            dn, up, _ = lv[l.target_path]
+            tg[l.off_down:l.off_down + 4 * l.in_dim] = dn.grad.reshape(-1)
+            tg[nd + l.off_up:nd + l.off_up + l.out_dim * 4] = up.grad.reshape(-1)
+        rel = float((grad - tg).norm() / tg.norm())
+        e_ms, f_ms, t_ms = [], [], []
+        for _ in range(a.rounds):
+            e_ms.append(timed(engine_pair, a.iters))
+            f_ms.append(timed(lambda: eng.forward_save(x, ts, gs, ctx, pooled, flat[:nd], flat[nd:], mults), a.iters))
+            t_ms.append(timed(torch_pair, a.iters))
+        row = {"model": a.model, "mode": "train", "image": size, "dtype": dname, "n": n, "context_tokens": Nc,
+               "lora_modules": len(net.unet_loras), "engine_ms": e_ms, "engine_forward_save_ms": f_ms,
+               "engine_backward_ms": min(e_ms) - min(f_ms), "torch_ms": t_ms, "engine_vs_torch_grad_rel_l2": rel,
+               "workspace_bytes": eng.workspace_bytes, "torch_peak_bytes": torch.cuda.max_memory_allocated()}
+        print(json.dumps(row), flush=True)
+        rows.append(row)
+        model._close_engines()
+        del lv, tg, grad
+        torch.cuda.empty_cache()
+    model.__dict__.pop("_lora_network", None)
+    return rows
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=2)
@@ -153,6 +240,8 @@ def main():
     ap.add_argument("--model", default="flux_schnell", choices=["flux_schnell", "flux_dev", "tiny_flux"])
     ap.add_argument("--context_tokens", type=int, default=256)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--train", action="store_true", help="saved forward + backward to the LoRA matrices instead of the forward")
+    ap.add_argument("--context_stream", action="store_true", help="--train: the context stream's modules too")
     a = ap.parse_args()
     cfg = {"flux_schnell": M.flux_schnell_config, "flux_dev": M.flux_dev_config, "tiny_flux": M.tiny_flux_config}[a.model]()
     n, Nc = 1, a.context_tokens
@@ -164,6 +253,12 @@ def main():
             model = M.FluxTransformer2DModel(cfg)
         torch.set_default_dtype(torch.float32)
         M.init_synthetic_(model.requires_grad_(False), seed=0)
+        if a.train:
+            rows += train_rows(a, cfg, model, dname, dt)
+            model._close_engines()
+            del model
+            torch.cuda.empty_cache()
+            continue
         sd = {k: v.detach() for k, v in model.state_dict().items()}
         for size in (int(s) for s in a.sizes.split(",")):
             lat = size // 8
