@@ -162,6 +162,22 @@ typedef struct smi_flux_config {
   float rope_theta;           /* 10000 */
 } smi_flux_config;
 
+/* Architecture of a transformers T5EncoderModel with a gated-GELU feed-forward (google/t5-v1_1-xxl: the text_encoder_2 of
+ * Flux and text_encoder_3 of SD3).  inner = num_heads x d_kv may differ from d_model. */
+typedef struct smi_t5_config {
+  int dtype;            /* bf16 only: T5's activations overflow f16 */
+  int vocab_size;       /* 32128 */
+  int d_model;          /* 4096: a multiple of 64, at most 8192 */
+  int d_kv;             /* 64 (the only one built) */
+  int num_heads;        /* 64 */
+  int d_ff;             /* 10240: a multiple of 64 */
+  int num_layers;       /* 24 */
+  int rel_buckets;      /* 32: relative_attention_num_buckets */
+  int rel_max_distance; /* 128: relative_attention_max_distance */
+  int max_tokens;       /* longest sequence a call may pass (512 serves Flux's 256 / 512 and SD3's 256); at most 2048 */
+  float eps;            /* 1e-6: layer_norm_epsilon */
+} smi_t5_config;
+
 typedef struct smi_engine smi_engine;
 
 const char* smi_last_error(void);
@@ -250,6 +266,30 @@ int smi_clip_encode(smi_engine* e, int n, const int32_t* ids, const int32_t* eos
  * WITHOUT the final norm (what conceptmod/notrigger/train_notrigger.py:241 reads). */
 int smi_clip_encode_layers(smi_engine* e, int n, const int32_t* ids, const int32_t* eos_pos, void* last_hidden,
                            void* penultimate, void* pooled, void* last_layer_out);
+
+/* ---- T5 encoder (the sequence embedding of Flux and SD3 prompts) --------------------------------------------------------
+ * Replaces `transformers.T5EncoderModel(input_ids)[0]` without an attention mask, as the Flux and SD3 pipelines call it
+ * (padding tokens are attended).  Per block: h += o(attention(q|k|v(rmsnorm(h)))), h += wo(gelu_tanh(wi_0 x) * (wi_1 x)) with
+ * x = rmsnorm(h); then final_layer_norm.  The attention has no 1/sqrt(d_kv) scale and adds block 0's relative-position bias
+ * in every block: one f32 [num_heads, 2 L - 1] table per call, indexed by key - query, never an [H, L, L] tensor.  The
+ * residual stream is stored in bf16 between the GEMMs.  Forward only; no LoRA sites.
+ *   weights: the transformers state_dict (`shared.weight` or `encoder.embed_tokens.weight`,
+ *            `encoder.block.N.layer.0.SelfAttention.{q,k,v,o}.weight`, block 0's `...relative_attention_bias.weight`,
+ *            `encoder.block.N.layer.{0,1}.layer_norm.weight`, `encoder.block.N.layer.1.DenseReluDense.{wi_0,wi_1,wo}.weight`,
+ *            `encoder.final_layer_norm.weight`), bf16
+ *   ids         int32 [n, L]   token ids, 1 <= L <= max_tokens, any L (no alignment); an id outside the vocabulary is clamped
+ *                              into it, as smi_clip_encode does
+ *   last_hidden T [n, L, d_model]
+ * One engine serves every L up to max_tokens and every n up to batch; a prompt gives the same bits alone and in a batch.
+ * Refused, each with its reason in smi_last_error: dtype f16, d_kv != 64, d_model or d_ff not a multiple of 64, L out of
+ * range, a missing or misshapen weight, a non-gated feed-forward (`wi` instead of `wi_0` / `wi_1`).
+ * smi_t5_relative_buckets: host only (callable without a GPU) -- transformers' bidirectional _relative_position_bucket of
+ * the offsets key - query = -(L - 1) .. L - 1, out[key - query + L - 1]. */
+int smi_t5_workspace_bytes(const smi_t5_config* cfg, int batch, size_t* bytes);
+int smi_t5_create(const smi_t5_config* cfg, const smi_weight* weights, int n_weights, int batch, void* workspace,
+                  size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_t5_encode(smi_engine* e, int n, int L, const int32_t* ids, void* last_hidden);
+int smi_t5_relative_buckets(int num_buckets, int max_distance, int L, int32_t* out);
 
 /* ---- CLIP text tower with LoRA sites (the no-trigger text-encoder trainer) --------------------------------------------
  * The same tower, created with Linear LoRA sites (rank <= 16) on self_attn.{q,k,v}_proj -- all three of a layer or none,
@@ -764,6 +804,21 @@ int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const v
                                 const void* d_o, void* dq, void* dk, void* dv, float* delta, int b, int h, int nq, int nk,
                                 int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo, int64_t lddo, int64_t lddq,
                                 int64_t lddk, int64_t lddv, float scale, void* stream);
+/* The T5 encoder's kernels (tests/test_t5_kernels_gpu.py).  T is f16 or bf16, arithmetic fp32, one rounding at the store.
+ * attention_bias_fwd: self-attention (nq == nk == n, head_dim 64, no mask) with s[q, k] = q.k * scale + table[h][k - q + n - 1]
+ *   and the softmax over the biased scores; table f32 [h, ld_table], ld_table >= 2 n - 1, n <= 2048; explicit leading
+ *   dimensions as smi_op_attention_causal_fwd; always the tiled forward; lse (natural log of the biased row sums) may be NULL.
+ * rmsnorm: y[i, :] = w * x[i, :] * rsqrt(mean(x[i, :]^2) + eps), c % 8 == 0, c <= 8192.
+ * gated_gelu_tanh: out[i, j] = gelu_tanh(proj[i, j]) * proj[i, f + j] on proj T [m, 2 f], f % 8 == 0; the GELU of smi_op_act kind 2.
+ * t5_bias_table: out f32 [h, 2 l - 1], out[a, o] = weight[bucket[o], a] from weight T [num_buckets, h] and the device array
+ *   bucket int32 [2 l - 1] (smi_t5_relative_buckets computes it on the host). */
+int smi_op_attention_bias_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, const float* table,
+                              int64_t ld_table, int b, int h, int n, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                              float scale, void* stream);
+int smi_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int m, int c, float eps, void* stream);
+int smi_op_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t m, int f, void* stream);
+int smi_op_t5_bias_table(int dtype, const void* weight, const int32_t* bucket, float* out, int h, int l, int num_buckets,
+                         void* stream);
 /* The MLP activations, kind 0 quick_gelu / 1 erf-gelu (CLIP) / 2 tanh-gelu (MMDiT): y = act(x) when y is given
  * (n % 8 == 0), dx = dy * act'(x) when dy is given (any n >= 1). */
 int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream);

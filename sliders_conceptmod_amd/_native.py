@@ -67,6 +67,11 @@ class FluxConfigC(C.Structure):
                                                               ("rope_theta", C.c_float)]
 
 
+class T5ConfigC(C.Structure):
+    _fields_ = [(k, C.c_int) for k in ("dtype", "vocab_size", "d_model", "d_kv", "num_heads", "d_ff", "num_layers",
+                                       "rel_buckets", "rel_max_distance", "max_tokens")] + [("eps", C.c_float)]
+
+
 class WeightC(C.Structure):
     _fields_ = [("name", C.c_char_p), ("data", C.c_void_p), ("ndim", C.c_int), ("shape", C.c_int64 * 4)]
 
@@ -179,6 +184,11 @@ _SIGS = {
                                   C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_clip_encode": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 5),
     "smi_clip_encode_layers": (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6),
+    "smi_t5_workspace_bytes": (C.c_int, [C.POINTER(T5ConfigC), C.c_int, C.POINTER(C.c_size_t)]),
+    "smi_t5_create": (C.c_int, [C.POINTER(T5ConfigC), C.POINTER(WeightC), C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_t5_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "smi_t5_relative_buckets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
     "smi_clip_lora_workspace_bytes": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int,
                                                 C.POINTER(C.c_size_t)]),
     "smi_clip_lora_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
@@ -273,6 +283,11 @@ _SIGS = {
                                     [C.c_float, C.c_void_p]),
     "smi_op_attention_causal_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 10 + [C.c_int] * 5 + [C.c_int64] * 8 +
                                     [C.c_float, C.c_void_p]),
+    "smi_op_attention_bias_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int64] + [C.c_int] * 4 + [C.c_int64] * 4 +
+                                  [C.c_float, C.c_void_p]),
+    "smi_op_rmsnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "smi_op_gated_gelu_tanh": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
+    "smi_op_t5_bias_table": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
     "smi_op_act": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_groupnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
     "smi_op_layernorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
@@ -837,6 +852,54 @@ class ClipEngine(_EngineBase):
         out = torch.empty((n, L, self.cfg_c.hidden_size), dtype=self.dtype, device=dev)
         ids = ids.to(dev, torch.int32).contiguous()
         check(lib().smi_clip_encode_layers(self.handle, n, ptr(ids), None, None, None, None, ptr(out)), "smi_clip_encode_layers")
+        return out
+
+
+def t5_config_c(cfg, dtype: torch.dtype, max_tokens: int) -> T5ConfigC:
+    """cfg: sliders_conceptmod_amd.t5.T5Config (transformers' T5Config values).  A dtype the binding has no code for, and a
+    feed-forward other than the gated GELU, are refused here by name; everything else by the library."""
+    if dtype not in DTYPE_CODE:
+        raise SmiError(f"the T5 encoder runs in bfloat16, got {dtype}")
+    if cfg.feed_forward_proj != "gated-gelu":
+        raise SmiError(f"T5 feed_forward_proj '{cfg.feed_forward_proj}' is not built: only the gated tanh-GELU "
+                       f"(gated-gelu: wi_0 / wi_1) of t5-v1.1 is")
+    c = T5ConfigC()
+    c.dtype = DTYPE_CODE[dtype]
+    c.vocab_size, c.d_model, c.d_kv, c.num_heads = cfg.vocab_size, cfg.d_model, cfg.d_kv, cfg.num_heads
+    c.d_ff, c.num_layers = cfg.d_ff, cfg.num_layers
+    c.rel_buckets, c.rel_max_distance = cfg.relative_attention_num_buckets, cfg.relative_attention_max_distance
+    c.max_tokens, c.eps = max_tokens, cfg.layer_norm_epsilon
+    return c
+
+
+def t5_workspace_bytes(cfg, dtype: torch.dtype, batch: int, max_tokens: int) -> int:
+    """smi_t5_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on a refused config."""
+    out = C.c_size_t(0)
+    check(lib().smi_t5_workspace_bytes(C.byref(t5_config_c(cfg, dtype, max_tokens)), batch, C.byref(out)),
+          "smi_t5_workspace_bytes")
+    return out.value
+
+
+def t5_relative_buckets(num_buckets: int, max_distance: int, L: int) -> List[int]:
+    """smi_t5_relative_buckets (host code): the bucket of every offset key - query = -(L - 1) .. L - 1."""
+    out = (C.c_int32 * max(2 * L - 1, 1))()
+    check(lib().smi_t5_relative_buckets(num_buckets, max_distance, L, out), "smi_t5_relative_buckets")
+    return list(out)
+
+
+class T5Engine(_EngineBase):
+    """T5 encoder on the HIP engine (smi_t5_*): token ids [n, L], any 1 <= L <= max_tokens -> last hidden state."""
+
+    def __init__(self, cfg, dtype: torch.dtype, state: dict, batch: int, max_tokens: int, device):
+        self.cfg_c, self.batch, self.dtype, self.max_tokens = t5_config_c(cfg, dtype, max_tokens), batch, dtype, max_tokens
+        self._create("t5_", self.cfg_c, (batch,), state, dtype, device)
+
+    def encode(self, ids: torch.Tensor) -> torch.Tensor:
+        n, L = ids.shape
+        dev = self.workspace.device
+        out = torch.empty((n, L, self.cfg_c.d_model), dtype=self.dtype, device=dev)
+        ids = ids.to(dev, torch.int32).contiguous()
+        check(lib().smi_t5_encode(self.handle, n, L, ptr(ids), ptr(out)), "smi_t5_encode")
         return out
 
 

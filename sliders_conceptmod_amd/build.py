@@ -11,7 +11,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libsmi_hip.so")
 SOURCES = ["gemm.hip", "gemm2.hip", "gemm3.hip", "gemm4.hip", "attention.hip", "attention_causal.hip", "norm.hip", "elementwise.hip", "lora.hip", "vae_decode.hip", "clip_vision.hip",
-           "lpips.hip", "mmdit.hip", "flux.hip", "engine.hip", "engine_unet.hip", "engine_vae.hip", "engine_clip.hip", "engine_lpips.hip", "engine_mmdit.hip", "engine_flux.hip", "ops_api.hip"]
+           "lpips.hip", "mmdit.hip", "flux.hip", "t5.hip", "engine.hip", "engine_unet.hip", "engine_vae.hip", "engine_clip.hip", "engine_lpips.hip", "engine_mmdit.hip", "engine_flux.hip", "engine_t5.hip", "ops_api.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
 # attention: the softmax works on MFMA results every tile; with the default AGPR-form MFMA hipcc shuttles every
 # accumulator through v_accvgpr_read/write (481 moves per key tile, the kernel was VALU-bound at 91 % VALU busy).

@@ -1,4 +1,5 @@
-// Fused (flash-style) attention forward + backward for gfx950, non-causal, no mask, head_dim D in {8..160}.
+// Fused (flash-style) attention forward + backward for gfx950, non-causal, no mask, head_dim D in {8..160}.  (The tiled
+// forward also knows the causal mask and, as a compile-time variant, T5's additive relative-position bias: attn_fwd_kernel.)
 //
 // MFMA shape: v_mfma_f32_32x32x16_{f16,bf16}.  Scores are produced TRANSPOSED, S^T[key, q] = K . Q^T, so that a
 // lane owns ONE query column (q = lane & 31) and 16 keys per 32x32 tile in its registers: the online-softmax
@@ -167,7 +168,13 @@ __device__ __forceinline__ int acc_row(int r, int h2) { return (r & 3) + 8 * (r 
 // 64 -> 4) or one of the SD-1.x widths inside a wider tile (40 -> 3 of the 64-wide tile, 80 -> 5 of the 96-wide one) -- with the run-time
 // `s < nsd` test hipcc wraps every (ds_read, MFMA) pair of the QK^T product in its own branch and waits lgkmcnt(0) after
 // each read: eight exposed LDS round trips per key tile and wave instead of eight reads in flight.
-template <typename T, int DP, int NSD>
+// BIAS (T5's relative-position bias; self-attention, Nq == Nk = L): s[q, k] = q.k * scale + p.bias[head][k - q + L - 1].  The
+// head's 2L - 1 floats are staged in dynamic LDS once per workgroup; the score tile is turned into biased scores in fp32
+// right after the MFMAs, so the mask, the tile maximum and the lazy rescale below all see what the softmax is over, and
+// the rest of the loop runs with scale 1.  A lane's 32 table reads per tile are at k - q + L - 1 with q = the lane's query:
+// consecutive lanes read consecutive (descending) words.  Lanes past Nq and keys past Nk exist in the ragged last blocks:
+// their index is clamped into the table (their scores are masked or never stored).
+template <typename T, int DP, int NSD, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
   using S = Stage<T, DP>;
   constexpr int NS = DP / 16, NB = DP / 32;
@@ -198,7 +205,14 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
     t.u = buf_load16(rQ, ok ? (uint32_t)(((int64_t)q_idx * p.ldq + col0 + d) * 2) : OOB);
     qf[s] = t.v;
   }
-  const float sl = p.scale * LOG2E;
+  const float scale = BIAS ? 1.f : p.scale;  // BIAS: the scores are scaled where the bias is added
+  const float sl = scale * LOG2E;
+  extern __shared__ __attribute__((aligned(16))) float bias_tab[];  // BIAS only: [2 Nk - 1]
+  const int nb1 = 2 * p.Nk - 2;                                    // last index of the table
+  if constexpr (BIAS) {
+    const float* src = p.bias + (int64_t)head * p.bias_ld;
+    for (int i = tid; i <= nb1; i += 256) bias_tab[i] = src[i];
+  }
 
   f32x16 o[NB];
 #pragma unroll
@@ -269,6 +283,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
           }
         }
       }
+    }
+    if constexpr (BIAS) {
+      const int base = k0 - q_idx + p.Nk - 1;  // index of key k0 for this lane's query
+#pragma unroll
+      for (int sub = 0; sub < 2; ++sub)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int idx = min(max(base + sub * 32 + acc_row(r, h2), 0), nb1);
+          st[sub][r] = __builtin_fmaf(st[sub][r], p.scale, bias_tab[idx]);
+        }
     }
     // mask keys beyond Nk (ragged last tile only) and, for causal attention, keys after the query; tile max
     if (k0 + TK > p.Nk || p.causal) {
@@ -351,7 +375,7 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnParams p) {
       }
     if (p.lse && h2 == 0)
       p.lse[((int64_t)b * p.H + head) * p.Nq + q_idx] =
-          m_run * p.scale + __logf(l_lse);
+          m_run * scale + __logf(l_lse);
   }
 }
 
@@ -1222,12 +1246,19 @@ int fwd_t(const AttnParams& p, hipStream_t st) {
   constexpr int NS = DP / 16, ALT = alt_steps<DP>();
   const int nsd = (p.D + 15) / 16;
   ran_begin(DP, nsd == NS ? 1 : (ALT > 0 && nsd == ALT ? 2 : 0));
-  if (p.Nk <= XS_KEYS && xs_enabled() && g_ran.form != 0) {  // all keys at once (cross-attention on the text tokens)
+  if (p.Nk <= XS_KEYS && xs_enabled() && g_ran.form != 0 && !p.bias) {  // all keys at once (cross-attention on the text tokens)
     ran_add(ATTN_RAN_XS_FWD, xs_chain(p));
     if (nsd == NS) return xs_fwd_launch<T, DP, NS>(p, st);
     return xs_fwd_launch<T, DP, (ALT > 0 ? ALT : NS)>(p, st);
   }
   ran_add(ATTN_RAN_FWD);
+  if constexpr (DP == 64) {
+    if (p.bias) {  // (launch_attn_fwd has checked the shape: head_dim 64, Nq == Nk, the table within LDS)
+      hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS, true>), grid, dim3(256), (size_t)(2 * p.Nk - 1) * sizeof(float), st, p);
+      SMI_HIP(hipGetLastError());
+      return 0;
+    }
+  }
   if (nsd == NS)
     hipLaunchKernelGGL((attn_fwd_kernel<T, DP, NS>), grid, dim3(256), 0, st, p);
   else if (ALT > 0 && nsd == ALT)
@@ -1346,6 +1377,14 @@ AttnRan attn_last_ran() { return g_ran; }
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream) {
   g_ran = AttnRan();
   if (check_attn(p)) return -1;
+  if (p.bias) {
+    SMI_CHECK(p.D == 64 && p.Nq == p.Nk && !p.causal,
+              "attention with a relative-position bias: self-attention (Nq %d == Nk %d), head_dim 64 (got %d), no causal mask",
+              p.Nq, p.Nk, p.D);
+    SMI_CHECK(p.Nk <= ATTN_BIAS_MAX_L && p.bias_ld >= 2 * p.Nk - 1,
+              "attention with a relative-position bias: L %d exceeds %d (the table is staged in LDS), or table rows of %lld < 2 L - 1",
+              p.Nk, ATTN_BIAS_MAX_L, (long long)p.bias_ld);
+  }
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, false) : dispatch<bf16>(p, stream, false);
 }
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream) {

@@ -285,9 +285,12 @@ __global__ void embed_kernel(const int* __restrict__ ids, const T* __restrict__ 
     id = id < 0 ? 0 : (id >= vocab ? vocab - 1 : id);
     Pack8<T> a, b, o;
     a.u = *reinterpret_cast<const u32x4*>(tok + ((int64_t)id * d8 + c) * 8);
-    b.u = *reinterpret_cast<const u32x4*>(pos + ((int64_t)(r % L) * d8 + c) * 8);
+    o.u = a.u;
+    if (pos) {  // NULL: a model without a position table (T5) -- the token rows as they are
+      b.u = *reinterpret_cast<const u32x4*>(pos + ((int64_t)(r % L) * d8 + c) * 8);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(a.e[e]) + to_f(b.e[e]));
+      for (int e = 0; e < 8; ++e) o.e[e] = from_f<T>(to_f(a.e[e]) + to_f(b.e[e]));
+    }
     *reinterpret_cast<u32x4*>(out + i * 8) = o.u;
   }
 }

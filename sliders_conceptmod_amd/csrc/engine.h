@@ -147,7 +147,7 @@ struct Model {
 
 struct smi_engine {
   // which model the engine holds: set once, by hold(); every entry point accepts one kind and refuses the others
-  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS, MMDIT, FLUX };
+  enum Kind { UNET, VAE_ENCODER, VAE_DECODER, CLIP_TEXT, CLIP_VISION, LPIPS, MMDIT, FLUX, T5_ENCODER };
   Kind kind = UNET;
   std::unique_ptr<Model> model;  // (also keeps a lambda from copying an engine it names through a reference parameter)
   int dtype = 0;

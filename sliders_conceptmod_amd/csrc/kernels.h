@@ -230,7 +230,13 @@ struct AttnParams {
   float* delta = nullptr;  // f32 [B, H, Nq] workspace
   void *dQ = nullptr, *dK = nullptr, *dV = nullptr;
   int64_t lddq = 0, lddk = 0, lddv = 0;
+  // forward only: additive relative-position bias f32 [H, bias_ld] (T5; launch_t5_bias_table), entry k - q + Nk - 1 of row
+  // h added to s[q, k] = q.k * scale before the softmax.  Self-attention, head_dim 64, Nk <= ATTN_BIAS_MAX_L; always the
+  // tiled forward.  The backward kernels ignore it
+  const float* bias = nullptr;
+  int64_t bias_ld = 0;
 };
+constexpr int ATTN_BIAS_MAX_L = 2048;  // 2 L - 1 floats of dynamic LDS next to the forward's 42 KB of K / V stages
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream);
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream);
 // Kernel selection of the two launchers for the parity tests: xs = the single-pass kernels for Nk <= 96, fused = the
@@ -453,6 +459,18 @@ int launch_gelu_tanh_cols_bwd(int dtype, const void* x, int64_t ldx, const void*
 // rows T [n gh gw, Cout p p], columns (c, py, px), = scale_dev[n] x d_out f32 [n, Cout, gh p, gw p]: flux_unpack's inverse
 int launch_flux_unpack_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
                            const float* scale_dev, hipStream_t stream);
+
+// T5 encoder (t5.hip).  Forward only.
+// y[m, :] = w * x[m, :] * rsqrt(mean(x[m, :]^2) + eps): no mean subtracted, no bias; C % 8 == 0, C <= 8192
+int launch_rmsnorm_rows(int dtype, const void* x, const void* w, void* y, int M, int C, float eps, hipStream_t stream);
+// out f32 [H, 2 L - 1]: out[h, o] = weight[bucket[o], h] from relative_attention_bias.weight T [num_buckets, H] and the
+// bucket of every offset o = key - query + L - 1 (int32 [2 L - 1] on the device; t5_relative_buckets fills a host copy)
+int launch_t5_bias_table(int dtype, const void* weight, const int* bucket, float* out, int H, int L, int num_buckets,
+                         hipStream_t stream);
+// out[m, c] = gelu_tanh(proj[m, c]) * proj[m, F + c], proj T [M, 2 F] = wi_0 | wi_1; F % 8 == 0; the GELU of launch_act kind 2
+int launch_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t M, int F, hipStream_t stream);
+// host: transformers' bidirectional _relative_position_bucket for the offsets -(L - 1) .. L - 1 into out[2 L - 1]
+int t5_relative_buckets(int num_buckets, int max_distance, int L, int32_t* out);
 
 // LPIPS (AlexNet) around the GEMMs (lpips.hip).  Maps are NHWC T with C % 8 == 0 and hold PRE-activations: every reader
 // applies max(0, .).  Patch matrices are T [rows, Kp], columns (ky, kx, ci), Kp a multiple of 8 >= k k C, pad columns 0.

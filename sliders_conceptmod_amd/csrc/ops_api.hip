@@ -251,6 +251,27 @@ int smi_op_attention_causal_bwd(int dtype, const void* q, const void* k, const v
   p.delta = delta;
   return launch_attn_bwd(p, (hipStream_t)stream);
 }
+// T5's self-attention: no mask, the additive relative-position table (smi_op_t5_bias_table), always the tiled forward
+int smi_op_attention_bias_fwd(int dtype, const void* q, const void* k, const void* v, void* o, float* lse, const float* table,
+                              int64_t ld_table, int b, int h, int n, int d, int64_t ldq, int64_t ldk, int64_t ldv, int64_t ldo,
+                              float scale, void* stream) {
+  SMI_CHECK(table != nullptr, "smi_op_attention_bias_fwd: table is NULL (attention without a bias is smi_op_attention_ex_fwd)");
+  AttnParams p = attn_causal(dtype, q, k, v, o, lse, b, h, n, d, ldq, ldk, ldv, ldo, scale);
+  p.causal = 0;
+  p.bias = table;
+  p.bias_ld = ld_table;
+  return launch_attn_fwd(p, (hipStream_t)stream);
+}
+int smi_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int m, int c, float eps, void* stream) {
+  return launch_rmsnorm_rows(dtype, x, w, y, m, c, eps, (hipStream_t)stream);
+}
+int smi_op_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t m, int f, void* stream) {
+  return launch_gated_gelu_tanh(dtype, proj, out, m, f, (hipStream_t)stream);
+}
+int smi_op_t5_bias_table(int dtype, const void* weight, const int32_t* bucket, float* out, int h, int l, int num_buckets,
+                         void* stream) {
+  return launch_t5_bias_table(dtype, weight, bucket, out, h, l, num_buckets, (hipStream_t)stream);
+}
 int smi_op_act(int dtype, const void* x, void* y, const void* dy, void* dx, int64_t n, int kind, void* stream) {
   if (y)
     if (int rc = launch_act(dtype, x, y, n, kind, (hipStream_t)stream)) return rc;

@@ -39,7 +39,8 @@ refused with `--base sd3`.
 native Flux transformer, reusing the SD3 branch's helpers: ONE transformer pass per step and sample (no CFG pair) through
 `train_util.predict_noise_flux`; a guidance_embeds model (FLUX.1-dev) takes `--guidance_scale` (default 3.5) as its embedded
 guidance and FLUX.1-schnell ignores it; the 16-channel VAE decodes latents / scaling_factor + shift_factor of its config.
-Prompts: CLIP-L's pooled row and the T5 sequence (`model_util.load_models_flux`; `--no_t5`, or a directory without
+Prompts: CLIP-L's pooled row and the T5 sequence (`model_util.load_models_flux`; `--t5_backend native`: the T5 tower on the
+HIP engine instead of transformers', and with `--base sd3` text_encoder_3 as a third tower; `--no_t5`, or a directory without
 text_encoder_2: `--t5_tokens` zero rows).  Defaults, by the scheduler's config: 4 steps and 256 tokens without dynamic
 shifting (schnell), 28 steps and 512 tokens with it (dev); the slider is on where 1000 sigma <= `--start_noise` (750).
 These defaults are ours: the reference has no Flux sweep script (the step and token counts are the published pipelines',
@@ -231,7 +232,10 @@ def generate_sd3(args) -> List[str]:
     dtype = torch.float16
     vae_dtype = DTYPES[args.vae_dtype] if args.vae_dtype else torch.bfloat16
     start_noise = args.start_noise if args.start_noise is not None else 750
-    tokenizers, text_encoders, transformer, scheduler = model_util.load_models_sd3(args.pretrained_model, weight_dtype=dtype)
+    if args.t5_backend == "torch":
+        raise ValueError("--base sd3 --t5_backend torch is not built: leave it out (zero rows stand in for T5) or pass native")
+    tokenizers, text_encoders, transformer, scheduler = model_util.load_models_sd3(args.pretrained_model, weight_dtype=dtype,
+                                                                                   t5_backend=args.t5_backend)
     transformer = transformer.to(device, dtype).requires_grad_(False).eval()
     for te in text_encoders:
         te.to(device, dtype)
@@ -293,7 +297,8 @@ def generate_flux(args) -> List[str]:
     vae_dtype = DTYPES[args.vae_dtype] if args.vae_dtype else torch.bfloat16
     start_noise = args.start_noise if args.start_noise is not None else 750
     tokenizers, text_encoders, transformer, scheduler = model_util.load_models_flux(args.pretrained_model, weight_dtype=dtype,
-                                                                                    no_t5=args.no_t5)
+                                                                                    no_t5=args.no_t5,
+                                                                                    t5_backend=args.t5_backend or "torch")
     dev_like = scheduler.use_dynamic_shifting
     steps = args.ddim_steps if args.ddim_steps is not None else (28 if dev_like else 4)
     tokens = args.t5_tokens if args.t5_tokens is not None else (512 if dev_like else 256)
@@ -467,6 +472,9 @@ def build_parser():
                    "context (default 256: the published pipeline's max_sequence_length; 77: its first release); --base flux: "
                    "the T5 sequence length (default 256 schnell / 512 dev), zero rows without a T5 tower")
     p.add_argument("--no_t5", action="store_true", help="--base flux: do not load text_encoder_2 (zero rows stand in)")
+    p.add_argument("--t5_backend", choices=["torch", "native"], default=None,
+                   help="--base flux: the T5 tower as transformers runs it (torch, the default) or on the HIP engine (native); "
+                        "--base sd3: native loads text_encoder_3 on the HIP engine (default: none, zero rows stand in)")
     p.add_argument("--image_size", type=int, default=None, help="default 512 (SD-1.x) / 1024 (SD-XL)")
     p.add_argument("--from_case", type=int, default=0)
     p.add_argument("--till_case", type=int, default=1000000)

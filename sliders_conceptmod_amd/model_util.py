@@ -670,12 +670,16 @@ def synthetic_sd3_towers(tiny: bool):
     return toks, encs
 
 
-def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float16):
+def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float16, t5_backend=None):
     """(tokenizers, text_encoders, transformer, scheduler) of an SD3 pipeline loaded with text_encoder_3=None, as the
     reference loads it (conceptmod/textsliders/train_lora_sd3.py).  `synthetic://sd3 | tiny_sd3`: the architecture with
     seeded weights.  A local diffusers directory is read with the safetensors loader from transformer/, text_encoder/ and
-    text_encoder_2/; text_encoder_3 (T5) is never loaded."""
+    text_encoder_2/; text_encoder_3 (T5) is not loaded unless t5_backend is "native": then a NativeT5Tower is the third tower
+    (the directory's text_encoder_3 / tokenizer_3, or for `synthetic://` a seeded tiny_t5_config(joint_attention_dim)
+    encoder), and train_util.encode_prompts_sd3 writes its rows where the zero rows are."""
     from . import mmdit as PM
+    if t5_backend not in (None, "native"):
+        raise ValueError(f"t5_backend '{t5_backend}' is not built for SD3: None (zero rows stand in for T5) | native")
     name = pretrained_model_name_or_path
     scheduler = FlowMatchEulerDiscreteScheduler(num_train_timesteps=1000, shift=3.0)
     if name.startswith("synthetic://"):
@@ -685,6 +689,9 @@ def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float
         tiny = kind == "tiny_sd3"
         model = PM.init_synthetic_(PM.SD3Transformer2DModel(PM.tiny_sd3_config() if tiny else PM.sd3_medium_config()), seed=0)
         toks, encs = synthetic_sd3_towers(tiny)
+        if t5_backend == "native":
+            encs.append(_synthetic_native_t5(model.config.joint_attention_dim))
+            toks.append(encs[-1].tokenizer)
         return toks, encs, model, scheduler
     if os.path.isdir(name):
         import json
@@ -696,6 +703,9 @@ def load_models_sd3(pretrained_model_name_or_path: str, weight_dtype=torch.float
         toks = [CLIPTokenizer.from_pretrained(name, subfolder="tokenizer"),
                 CLIPTokenizer.from_pretrained(name, subfolder="tokenizer_2")]
         encs = [_clip_from_dir(name, "text_encoder"), _clip_from_dir(name, "text_encoder_2")]
+        if t5_backend == "native":
+            encs.append(_native_t5_from_dir(name, "text_encoder_3", "tokenizer_3"))
+            toks.append(encs[-1].tokenizer)
         return toks, encs, _sd3_from_dir(name), scheduler
     raise ValueError(f"cannot load '{name}': pass a local diffusers directory or synthetic://sd3 | synthetic://tiny_sd3")
 
@@ -737,7 +747,7 @@ class SyntheticT5Tower(_PromptCachedTower):
 
 class T5Tower(_PromptCachedTower):
     """Flux's text_encoder_2, a frozen `transformers.T5EncoderModel` with its tokenizer: the one torch forward of the product
-    (a native tower is the follow-up).  bf16 or fp32, never fp16 (T5's activations overflow it)."""
+    (NativeT5Tower is the same tower on the HIP engine, t5_backend="native").  bf16 or fp32, never fp16 (T5's activations overflow it)."""
 
     def __init__(self, model, tokenizer):
         self.model, self.tokenizer = model.requires_grad_(False).eval(), tokenizer
@@ -761,6 +771,55 @@ class T5Tower(_PromptCachedTower):
         ids = self.tokenizer(prompt, padding="max_length", max_length=max_length, truncation=True,
                              return_tensors="pt").input_ids
         return self.model(ids.to(self.device))[0]
+
+
+class NativeT5Tower(_PromptCachedTower):
+    """The T5 encoder on the HIP engine (t5.T5EncoderModel with its tokenizer) behind T5Tower's interface: Flux's
+    text_encoder_2, SD3's text_encoder_3.  bf16 only (T5's activations overflow fp16), on a cuda device only."""
+
+    def __init__(self, model, tokenizer):
+        self.model, self.tokenizer = model.requires_grad_(False).eval(), tokenizer
+        self.dim = model.config.d_model
+
+    @property
+    def device(self):
+        return self.model.device
+
+    @property
+    def dtype(self):
+        return self.model.dtype
+
+    def to(self, device=None, dtype=None):
+        """A request for fp16 is served in bf16, with T5Tower's warning; fp32 has no engine and is served in bf16 too."""
+        if dtype == torch.float16:
+            import warnings
+            warnings.warn("T5Tower: float16 requested; the T5 encoder runs in bfloat16 instead (its activations overflow fp16)")
+        self.model.to(device=device, dtype=torch.bfloat16)
+        self.__dict__.pop("_prompt_cache", None)  # rows of another device or engine
+        return self
+
+    @torch.no_grad()
+    def encode(self, prompt: str, max_length: int):
+        ids = self.tokenizer(prompt, padding="max_length", max_length=max_length, truncation=True,
+                             return_tensors="pt").input_ids
+        return self.model(ids.to(self.device))[0]
+
+
+T5_BACKENDS = ("torch", "native")
+
+
+def _synthetic_native_t5(dim: int) -> NativeT5Tower:
+    """The seeded tiny T5 of the `synthetic://` models on the native engine, `dim` wide, with the hashing tokenizer."""
+    from . import t5 as PT
+    cfg = PT.tiny_t5_config(dim)
+    model = PT.init_synthetic_(PT.T5EncoderModel(cfg), seed=3).to(torch.bfloat16)
+    return NativeT5Tower(model, PT.SyntheticT5Tokenizer(cfg.vocab_size))
+
+
+def _native_t5_from_dir(name: str, sub: str, tok_sub: str) -> NativeT5Tower:
+    from transformers import T5TokenizerFast
+    from . import t5 as PT
+    return NativeT5Tower(PT.t5_from_dir(name, sub), T5TokenizerFast.from_pretrained(name, subfolder=tok_sub))
 
 
 def _flux_from_dir(path: str):
@@ -790,14 +849,19 @@ def _flux_from_dir(path: str):
     return model
 
 
-def load_models_flux(pretrained_model_name_or_path: str, weight_dtype=torch.float16, no_t5: bool = False):
+def load_models_flux(pretrained_model_name_or_path: str, weight_dtype=torch.float16, no_t5: bool = False,
+                     t5_backend: str = "torch"):
     """(tokenizers, text_encoders, transformer, scheduler) of a Flux pipeline (conceptmod/textsliders/model_util.py
     load_models_flux).  text_encoders = [CLIP-L on the native engine (its un-projected pooled row conditions the network),
     the T5 tower or None]: a directory's text_encoder_2 is loaded as a transformers.T5EncoderModel unless `no_t5`; without it
     zero rows stand in for the sequence embedding (train_util.encode_prompts_flux).  The T5 tower runs in bf16 (fp32 with
     weight_dtype=torch.float32), never fp16: `T5Tower.to(dtype=torch.float16)` moves it to bf16 and warns.  `synthetic://flux_schnell | flux_dev |
-    tiny_flux`: the architecture with seeded weights and hashed stand-in towers."""
+    tiny_flux`: the architecture with seeded weights and hashed stand-in towers.  t5_backend "native": the T5 tower is a
+    NativeT5Tower -- the directory's text_encoder_2 on the HIP engine (t5.T5EncoderModel), or for `synthetic://` a seeded
+    tiny_t5_config(joint_attention_dim) encoder with a SyntheticT5Tokenizer; "torch" (the default) is as before."""
     from . import flux as PF
+    if t5_backend not in T5_BACKENDS:
+        raise ValueError(f"t5_backend '{t5_backend}': torch | native")
     name = pretrained_model_name_or_path
     if name.startswith("synthetic://"):
         kind = name[len("synthetic://"):]
@@ -809,7 +873,8 @@ def load_models_flux(pretrained_model_name_or_path: str, weight_dtype=torch.floa
         scheduler = FlowMatchEulerDiscreteScheduler(1000, 3.0 if kind == "flux_dev" else 1.0,
                                                     use_dynamic_shifting=kind == "flux_dev")
         clip = SyntheticClipTower(cfg.pooled_projection_dim, cfg.pooled_projection_dim, 1)
-        t5 = None if no_t5 else SyntheticT5Tower(cfg.joint_attention_dim)
+        t5 = None if no_t5 else (_synthetic_native_t5(cfg.joint_attention_dim) if t5_backend == "native"
+                                 else SyntheticT5Tower(cfg.joint_attention_dim))
         return [SyntheticClipTokenizer(1000, 999), None], [clip, t5], model, scheduler
     if os.path.isdir(name):
         import json
@@ -823,7 +888,10 @@ def load_models_flux(pretrained_model_name_or_path: str, weight_dtype=torch.floa
                 cj.get("max_image_seq_len", 4096))
         from transformers import CLIPTokenizer
         toks, encs = [CLIPTokenizer.from_pretrained(name, subfolder="tokenizer"), None], [_clip_from_dir(name, "text_encoder"), None]
-        if not no_t5 and os.path.isdir(os.path.join(name, "text_encoder_2")):
+        if not no_t5 and t5_backend == "native" and os.path.isdir(os.path.join(name, "text_encoder_2")):
+            encs[1] = _native_t5_from_dir(name, "text_encoder_2", "tokenizer_2")
+            toks[1] = encs[1].tokenizer
+        elif not no_t5 and os.path.isdir(os.path.join(name, "text_encoder_2")):
             from transformers import T5EncoderModel, T5TokenizerFast
             tok2 = T5TokenizerFast.from_pretrained(name, subfolder="tokenizer_2")
             t5 = T5EncoderModel.from_pretrained(name, subfolder="text_encoder_2",

@@ -73,11 +73,13 @@ def frozen_steps(transformer, scheduler, timestep, latents, pair: PromptEmbedsPa
 
 
 def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft_type="lora", rank=4, save_file=True,
-          models=None, fused_step=None, optimizer_kwargs=None, optimizer=None, context_stream=False, t5_tokens=512):
+          models=None, fused_step=None, optimizer_kwargs=None, optimizer=None, context_stream=False, t5_tokens=512,
+          t5_backend="torch"):
     """The reference's `train(config, prompts, device, on_step_complete, peft_type, rank, save_file)`; the other arguments
     are this package's (train_lora_sd3.train): `models` a preloaded load_models_flux tuple, `fused_step` / `optimizer` /
     `optimizer_kwargs` the optimiser choice, `context_stream` the form with the context stream's modules, `t5_tokens` the
-    sequence length of the T5 block (zero rows where the model was loaded without the tower).  Left on the network:
+    sequence length of the T5 block (zero rows where the model was loaded without the tower), `t5_backend` torch | native
+    (model_util.load_models_flux; not used with preloaded `models`).  Left on the network:
     `training_losses` (per iteration, unscaled), `flat_sums` (the flat parameter's sum after every iteration: it moves only
     where the optimiser stepped), `optimizer_steps`, and `first_step`, iteration 0's draws (latents, gradient of
     loss / accumulation steps) for the parity test."""
@@ -86,7 +88,7 @@ def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft
     save_weight_dtype = config_util.parse_precision(config.train.precision)
     guidance_scale = config.train.cfg
     tokenizers, text_encoders, transformer, noise_scheduler = models or model_util.load_models_flux(
-        config.pretrained_model.name_or_path, weight_dtype=weight_dtype)
+        config.pretrained_model.name_or_path, weight_dtype=weight_dtype, t5_backend=t5_backend)
     for te in text_encoders:  # (the stand-in towers of a synthetic:// model are no nn.Modules: nothing to freeze)
         if te is None:
             continue
@@ -224,7 +226,8 @@ def main(args):
     prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
     device = train_common.launch_device(args)
     return train(config, prompts, device, None, args.peft_type, args.rank, True, None, args.fused_step,
-                 optimizer=args.optimizer, context_stream=args.context_stream, t5_tokens=args.t5_tokens)
+                 optimizer=args.optimizer, context_stream=args.context_stream, t5_tokens=args.t5_tokens,
+                 t5_backend=args.t5_backend)
 
 
 def build_parser():
@@ -240,6 +243,8 @@ def build_parser():
                         help="also adapt the context stream's add_q_proj / add_k_proj / add_v_proj / to_add_out")
     parser.add_argument("--t5_tokens", type=int, default=512,
                         help="sequence length of the T5 block of the prompt embedding (zero rows without the tower)")
+    parser.add_argument("--t5_backend", choices=["torch", "native"], default="torch",
+                        help="the T5 tower as transformers runs it (torch) or on the HIP engine (native)")
     parser.add_argument("--optimizer", type=str, required=False, default=None,
                         help="adam, adamw, lion or prodigy at the class's own defaults instead of the script's hard-coded "
                              "AdamW(lr 1e-4, weight_decay 1e-6)")

@@ -61,18 +61,20 @@ def frozen_steps(transformer, scheduler, timestep, latents, pair: PromptEmbedsPa
 
 
 def train(config: RootConfig, prompts: list, device, on_step_complete=None, peft_type="lora", rank=4, save_file=True,
-          models=None, fused_step=None, optimizer_kwargs=None, optimizer=None, context_stream=False, t5_tokens=256):
+          models=None, fused_step=None, optimizer_kwargs=None, optimizer=None, context_stream=False, t5_tokens=256,
+          t5_backend=None):
     """The reference's `train(config, prompts, device, on_step_complete, peft_type, rank, save_file)`; the other arguments
     are this package's (train_lora_xl.train): `models` a preloaded load_models_sd3 tuple, `fused_step` / `optimizer` /
     `optimizer_kwargs` the optimiser choice, `context_stream` the 191-module form, `t5_tokens` the zero rows that stand in
-    for the T5 block.  Per-step losses are left in `network.training_losses`; `network.first_step` keeps iteration 0's draws
+    for the T5 block -- or, with `t5_backend` "native" (model_util.load_models_sd3; not used with preloaded `models`), the
+    rows of text_encoder_3 on the HIP engine.  Per-step losses are left in `network.training_losses`; `network.first_step` keeps iteration 0's draws
     (latents, timesteps_to, gradient) for the parity test."""
     check_supported(config, peft_type)
     weight_dtype = config_util.parse_precision(config.train.precision)
     save_weight_dtype = config_util.parse_precision(config.train.precision)
     guidance_scale = config.train.cfg
     tokenizers, text_encoders, transformer, noise_scheduler = models or model_util.load_models_sd3(
-        config.pretrained_model.name_or_path, weight_dtype=weight_dtype)
+        config.pretrained_model.name_or_path, weight_dtype=weight_dtype, t5_backend=t5_backend)
     for te in text_encoders:  # (the stand-in towers of synthetic://tiny_sd3 are no nn.Modules: nothing to freeze)
         te.to(device, weight_dtype)
         if isinstance(te, torch.nn.Module):
@@ -193,7 +195,8 @@ def main(args):
     prompts = prompt_util.load_prompts_from_yaml(config.prompts_file, attributes)
     device = train_common.launch_device(args)
     return train(config, prompts, device, None, args.peft_type, args.rank, True, None, args.fused_step,
-                 optimizer=args.optimizer, context_stream=args.context_stream, t5_tokens=args.t5_tokens)
+                 optimizer=args.optimizer, context_stream=args.context_stream, t5_tokens=args.t5_tokens,
+                 t5_backend=args.t5_backend)
 
 
 def build_parser():
@@ -209,6 +212,9 @@ def build_parser():
                         help="also adapt the context stream's add_q_proj / add_k_proj / add_v_proj / to_add_out")
     parser.add_argument("--t5_tokens", type=int, default=256,
                         help="zero rows that stand in for the T5 block of the prompt embedding (text_encoder_3=None)")
+    parser.add_argument("--t5_backend", choices=["torch", "native"], default=None,
+                        help="native: text_encoder_3 (T5) on the HIP engine writes the T5 block; default: zero rows "
+                             "(torch is not built for SD3 and is refused)")
     parser.add_argument("--optimizer", type=str, required=False, default=None,
                         help="adam, adamw, lion or prodigy at the class's own defaults instead of the script's hard-coded "
                              "AdamW(lr 1e-4, weight_decay 1e-6)")

@@ -72,10 +72,12 @@ def encode_prompts_sd3(pipeline, tokenizers, text_encoders, prompt: str, num_ima
     with text_encoder_3=None: hidden_states[-2] of the two CLIP towers concatenated on the feature axis and zero-padded to
     joint_attention_dim, then t5_tokens zero rows appended on the sequence axis (256: the published pipeline's
     max_sequence_length; 77 reproduces its first release); pooled: the two projected pooled embeddings concatenated.
-    `pipeline` is the reference's first argument and is not used (there is no pipeline object here)."""
+    `pipeline` is the reference's first argument and is not used (there is no pipeline object here).  A third tower
+    (model_util.NativeT5Tower: load_models_sd3(t5_backend="native")) writes its t5_tokens rows where the zero rows are, as the
+    pipeline with text_encoder_3 does."""
     del pipeline
     embeds, pooled = [], []
-    for tok, enc in zip(tokenizers, text_encoders):
+    for tok, enc in zip(tokenizers[:2], text_encoders[:2]):
         ids = tok(prompt, padding="max_length", max_length=tok.model_max_length, truncation=True,
                   return_tensors="pt").input_ids
         out = enc(ids.to(enc.device), output_hidden_states=True)
@@ -85,7 +87,13 @@ def encode_prompts_sd3(pipeline, tokenizers, text_encoders, prompt: str, num_ima
     if clip.shape[-1] > joint_attention_dim:
         raise ValueError(f"the CLIP towers are {clip.shape[-1]} wide, the transformer's context {joint_attention_dim}")
     clip = torch.nn.functional.pad(clip, (0, joint_attention_dim - clip.shape[-1]))
-    zeros = torch.zeros(clip.shape[0], t5_tokens, joint_attention_dim, dtype=clip.dtype, device=clip.device)
+    t5 = text_encoders[2] if len(text_encoders) > 2 else None
+    if t5 is None:
+        zeros = torch.zeros(clip.shape[0], t5_tokens, joint_attention_dim, dtype=clip.dtype, device=clip.device)
+    else:
+        zeros = t5.encode_cached(prompt, t5_tokens).to(clip.device, clip.dtype)
+        if zeros.shape[-1] != joint_attention_dim:
+            raise ValueError(f"the T5 tower is {zeros.shape[-1]} wide, the transformer's context {joint_attention_dim}")
     prompt_embeds = torch.cat([clip, zeros], dim=1).repeat_interleave(num_images_per_prompt, dim=0)
     return prompt_embeds, torch.cat(pooled, dim=-1).repeat_interleave(num_images_per_prompt, dim=0)
 
