@@ -272,7 +272,7 @@ int smi_clip_encode_layers(smi_engine* e, int n, const int32_t* ids, const int32
  * (padding tokens are attended).  Per block: h += o(attention(q|k|v(rmsnorm(h)))), h += wo(gelu_tanh(wi_0 x) * (wi_1 x)) with
  * x = rmsnorm(h); then final_layer_norm.  The attention has no 1/sqrt(d_kv) scale and adds block 0's relative-position bias
  * in every block: one f32 [num_heads, 2 L - 1] table per call, indexed by key - query, never an [H, L, L] tensor.  The
- * residual stream is stored in bf16 between the GEMMs.  Forward only; no LoRA sites.
+ * residual stream is stored in bf16 between the GEMMs.  Forward only; no LoRA sites (a tower with them: smi_t5_lora_*).
  *   weights: the transformers state_dict (`shared.weight` or `encoder.embed_tokens.weight`,
  *            `encoder.block.N.layer.0.SelfAttention.{q,k,v,o}.weight`, block 0's `...relative_attention_bias.weight`,
  *            `encoder.block.N.layer.{0,1}.layer_norm.weight`, `encoder.block.N.layer.1.DenseReluDense.{wi_0,wi_1,wo}.weight`,
@@ -312,6 +312,30 @@ int smi_clip_forward_lora(smi_engine* e, int n, const int32_t* ids, const int32_
                           const float* lora_up_flat, const float* multipliers, int save_for_backward, void* last_layer_out,
                           void* penultimate, void* last_hidden, void* pooled);
 int smi_clip_backward(smi_engine* e, int which, const float* d_hidden, float* d_lora_down_flat, float* d_lora_up_flat);
+
+/* ---- T5 tower with LoRA sites (the no-trigger trainer on Flux's and SD3's T5) ----------------------------------------------
+ * The T5 encoder above, created with Linear LoRA sites (rank <= 16) on encoder.block.N.layer.0.SelfAttention.{q,k,v} -- all
+ * three of a block or none, adjacent in the flat buffers in that order: they ride on the fused q|k|v GEMM, as the CLIP
+ * tower's -- and on SelfAttention.o.  DoRA sites, other targets and ranks above 16 are refused with the site and the reason.
+ * bf16 only, as the forward.  workspace = [packed weights (every Linear twice: its transposed copy serves dX) | no-grad
+ * arena and its two block scratch regions | arena of the saved pass and its backward], sized by a dry forward + backward at
+ * max_tokens.
+ * smi_t5_forward_lora: every sample is adapted, sample i at multipliers[i] (f32, HOST memory, [n]); the effective weight of a
+ * site is W + m_i (alpha / r) up down.  All multipliers 0 gives the bits of smi_t5_encode, which also runs on such an
+ * engine.  Outputs, T [n, L, d_model], either may be NULL: last_hidden = hidden_states[-1] of transformers' T5Stack, AFTER
+ * final_layer_norm (unlike the CLIP tower's last_layer_out); penultimate = hidden_states[-2], the last block's input.
+ * save_for_backward: keeps the pass for ONE smi_t5_backward; a no-grad call in between leaves it intact.  The backward
+ * reads the saved pass's lora_down_flat / lora_up_flat again: they stay alive and unchanged until it has run.
+ * smi_t5_backward: d_hidden f32 [n, L, d_model] is the gradient of last_hidden (which 0: the tape starts with the final
+ * RMSNorm's backward) or of penultimate (which 1: the last block's sites then get none); accumulates (+=) into the flat
+ * gradient buffers.  No gradient goes to the embedding, the norm weights or the bias table, and the tape stops at the first
+ * block that has a site.  No split-K scratch is lent to the GEMMs of either direction.  -4 without a saved pass. */
+int smi_t5_lora_workspace_bytes(const smi_t5_config* cfg, const smi_lora_site* sites, int n_sites, int batch, size_t* bytes);
+int smi_t5_lora_create(const smi_t5_config* cfg, const smi_weight* weights, int n_weights, const smi_lora_site* sites,
+                       int n_sites, int batch, void* workspace, size_t workspace_bytes, void* stream, smi_engine** out);
+int smi_t5_forward_lora(smi_engine* e, int n, int L, const int32_t* ids, const float* lora_down_flat, const float* lora_up_flat,
+                        const float* multipliers, int save_for_backward, void* last_hidden, void* penultimate);
+int smi_t5_backward(smi_engine* e, int which, const float* d_hidden, float* d_lora_down_flat, float* d_lora_up_flat);
 
 /* ---- CLIP image tower and similarity head (scoring a slider sweep) -----------------------------------------------------
  * Replaces `model.get_image_features(pixel_values)` / the image half of `CLIPModel(**inputs).logits_per_image`
@@ -817,6 +841,19 @@ int smi_op_attention_bias_fwd(int dtype, const void* q, const void* k, const voi
                               float scale, void* stream);
 int smi_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int m, int c, float eps, void* stream);
 int smi_op_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t m, int f, void* stream);
+/* Their backward (tests/test_t5_bwd_kernels_gpu.py).  The table and the norm weight are frozen: no gradient to either.
+ * attention_bias_bwd: smi_attn_args as smi_op_attention_ex_bwd reads them (nq == nk, d == 64, causal 0, lse the biased
+ *   forward's; dq NULL: dK / dV only; dk and dv NULL: dQ only), the probabilities recomputed as
+ *   exp(scale q.k + table[h][k - q + n - 1] - lse[q]).  Runs the tiled dQ and dK / dV kernels or, with every gradient wanted
+ *   and sel_fused != 0 on a grid of at most 1024 query blocks, the one-launch form; never the single-pass kernels.
+ * rmsnorm_bwd: dx[i, :] = r (w dy[i, :]) - x[i, :] r^3 mean(x[i, :] . w dy[i, :]) (+ add[i, :]; add may be NULL or dx itself),
+ *   r = rsqrt(mean(x[i, :]^2) + eps); c % 8 == 0, c <= 8192.
+ * gated_gelu_tanh_bwd: dproj T [m, 2 f] from proj T [m, 2 f] and dout T [m, f]: columns [0, f) dout * up * gelu_tanh'(gate)
+ *   (the derivative of smi_op_act kind 2), columns [f, 2 f) dout * gelu_tanh(gate). */
+int smi_op_attention_bias_bwd(const smi_attn_args* args, const float* table, int64_t ld_table, smi_attn_ran* ran);
+int smi_op_rmsnorm_bwd(int dtype, const void* x, const void* dy, const void* w, const void* add, void* dx, int m, int c,
+                       float eps, void* stream);
+int smi_op_gated_gelu_tanh_bwd(int dtype, const void* proj, const void* dout, void* dproj, int64_t m, int f, void* stream);
 int smi_op_t5_bias_table(int dtype, const void* weight, const int32_t* bucket, float* out, int h, int l, int num_buckets,
                          void* stream);
 /* The MLP activations, kind 0 quick_gelu / 1 erf-gelu (CLIP) / 2 tanh-gelu (MMDiT): y = act(x) when y is given

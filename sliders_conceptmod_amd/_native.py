@@ -189,6 +189,13 @@ _SIGS = {
                                 C.c_void_p, C.POINTER(C.c_void_p)]),
     "smi_t5_encode": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "smi_t5_relative_buckets": (C.c_int, [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32)]),
+    "smi_t5_lora_workspace_bytes": (C.c_int, [C.POINTER(T5ConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int,
+                                              C.POINTER(C.c_size_t)]),
+    "smi_t5_lora_create": (C.c_int, [C.POINTER(T5ConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
+                                     C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "smi_t5_forward_lora": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 3 + [C.POINTER(C.c_float), C.c_int] +
+                            [C.c_void_p] * 2),
+    "smi_t5_backward": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "smi_clip_lora_workspace_bytes": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(LoraSiteC), C.c_int, C.c_int,
                                                 C.POINTER(C.c_size_t)]),
     "smi_clip_lora_create": (C.c_int, [C.POINTER(ClipConfigC), C.POINTER(WeightC), C.c_int, C.POINTER(LoraSiteC), C.c_int,
@@ -288,6 +295,9 @@ _SIGS = {
     "smi_op_rmsnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
     "smi_op_gated_gelu_tanh": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_t5_bias_table": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int] * 3 + [C.c_void_p]),
+    "smi_op_attention_bias_bwd": (C.c_int, [C.POINTER(AttnArgsC), C.c_void_p, C.c_int64, C.POINTER(AttnRanC)]),
+    "smi_op_rmsnorm_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_int, C.c_float, C.c_void_p]),
+    "smi_op_gated_gelu_tanh_bwd": (C.c_int, [C.c_int] + [C.c_void_p] * 3 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_act": (C.c_int, [C.c_int] + [C.c_void_p] * 4 + [C.c_int64, C.c_int, C.c_void_p]),
     "smi_op_groupnorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 4 + [C.c_float, C.c_int, C.c_void_p]),
     "smi_op_layernorm": (C.c_int, [C.c_int] + [C.c_void_p] * 7 + [C.c_int] * 2 + [C.c_float, C.c_void_p]),
@@ -901,6 +911,58 @@ class T5Engine(_EngineBase):
         ids = ids.to(dev, torch.int32).contiguous()
         check(lib().smi_t5_encode(self.handle, n, L, ptr(ids), ptr(out)), "smi_t5_encode")
         return out
+
+
+def t5_lora_workspace_bytes(cfg, dtype: torch.dtype, sites: Sequence[dict], batch: int, max_tokens: int) -> int:
+    """smi_t5_lora_workspace_bytes: a host-only dry run (no GPU needed); raises SmiError on refused sites or shapes."""
+    arr, _keep = make_sites(sites)
+    out = C.c_size_t(0)
+    check(lib().smi_t5_lora_workspace_bytes(C.byref(t5_config_c(cfg, dtype, max_tokens)), arr, len(sites), batch,
+                                            C.byref(out)), "smi_t5_lora_workspace_bytes")
+    return out.value
+
+
+class T5LoraEngine(T5Engine):
+    """T5 encoder with LoRA sites on its SelfAttention.{q,k,v,o} (smi_t5_lora_*): `encode` as T5Engine, plus a forward with
+    one adaptor multiplier per sample that can be saved, and its backward to the flat LoRA gradients."""
+
+    def __init__(self, cfg, dtype: torch.dtype, state: dict, sites: Sequence[dict], batch: int, max_tokens: int, device):
+        self.cfg_c, self.batch, self.dtype, self.max_tokens = t5_config_c(cfg, dtype, max_tokens), batch, dtype, max_tokens
+        arr, self._site_keep = make_sites(sites)
+        out = C.c_size_t(0)
+        check(lib().smi_t5_lora_workspace_bytes(C.byref(self.cfg_c), arr, len(sites), batch, C.byref(out)),
+              "smi_t5_lora_workspace_bytes")
+        self.workspace = torch.empty(out.value, dtype=torch.uint8, device=device)
+        warr, self._keep = _weight_table(state, dtype, self.workspace.device)
+        handle = C.c_void_p()
+        with torch.cuda.device(self.workspace.device):
+            check(lib().smi_t5_lora_create(C.byref(self.cfg_c), warr, len(state), arr, len(sites), batch,
+                                           ptr(self.workspace), out.value, stream_ptr(), C.byref(handle)),
+                  "smi_t5_lora_create")
+        self.handle = handle
+
+    def forward_lora(self, ids: torch.Tensor, lora_down: torch.Tensor, lora_up: torch.Tensor, multipliers: Sequence[float],
+                     save: bool = False, want=("last_hidden", "penultimate")) -> dict:
+        """smi_t5_forward_lora: sample i under the adaptor at multipliers[i].  Returns the outputs named in `want` (model
+        dtype): last_hidden = hidden_states[-1] (after the final norm), penultimate = hidden_states[-2]; save=True keeps the
+        pass for one `backward`."""
+        n, L = ids.shape
+        if len(multipliers) != n:
+            raise SmiError(f"forward_lora: {len(multipliers)} multipliers for {n} samples")
+        dev, d = self.workspace.device, self.cfg_c.d_model
+        out = {k: torch.empty((n, L, d), dtype=self.dtype, device=dev) for k in want}
+        ids = ids.to(dev, torch.int32).contiguous()
+        marr = (C.c_float * n)(*[float(m) for m in multipliers])
+        check(lib().smi_t5_forward_lora(self.handle, n, L, ptr(ids), ptr(lora_down), ptr(lora_up), marr, int(save),
+                                        ptr(out.get("last_hidden")), ptr(out.get("penultimate"))), "smi_t5_forward_lora")
+        return out
+
+    def backward(self, d_hidden: torch.Tensor, d_down: torch.Tensor, d_up: torch.Tensor, which: int = 0):
+        """smi_t5_backward: d_hidden fp32 [n, L, d_model], the gradient of last_hidden (which 0) or penultimate (1);
+        accumulates (+=) into the flat fp32 gradient buffers."""
+        if d_hidden.dtype != torch.float32 or not d_hidden.is_contiguous():
+            raise SmiError("backward: d_hidden must be contiguous fp32")
+        check(lib().smi_t5_backward(self.handle, int(which), ptr(d_hidden), ptr(d_down), ptr(d_up)), "smi_t5_backward")
 
 
 def clip_lora_workspace_bytes(cfg, dtype: torch.dtype, sites: Sequence[dict], batch: int) -> int:

@@ -13,7 +13,8 @@
 //
 // Backward (activations only: dQ, and dK/dV when a LoRA hangs off to_k/to_v) recomputes P from Q, K and the
 // forward's log-sum-exp; it is split into a dQ kernel (one workgroup per 128 queries, sweeping keys) and a dK/dV
-// kernel (one workgroup per 128 keys, sweeping queries): no atomics, bitwise reproducible.
+// kernel (one workgroup per 128 keys, sweeping queries): no atomics, bitwise reproducible.  Both bodies have a BIAS form, the
+// backward of the forward's (the table is frozen).
 #include <stdlib.h>
 
 #include <type_traits>
@@ -415,8 +416,15 @@ constexpr size_t dq_smem() {  // K and V by rows + K again at the transposed-rea
   return (size_t)(2 * TK * Stage<T, DP>::LDN + TK * Stage<T, DP>::LDV) * sizeof(T);
 }
 // body of the dQ workgroup (bx, head, b); `smem`: dq_smem<T, DP>() bytes
-template <typename T, int DP, int NSD, bool REMAT>
-__device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, int bx, int head, int b, unsigned char* smem) {
+// BIAS (the backward of attn_fwd_kernel's BIAS form; Nq == Nk = L, p.lse the biased forward's): the probabilities are recomputed
+// as exp(scale q.k + table[head][key - query + L - 1] - lse[query]); the head's 2 L - 1 floats are staged once in `btab`
+// (LDS, behind the tiles) and ordered by the first tile's barriers.  The table is frozen: nothing is differentiated to it.
+// A padded query or key (ragged blocks) reads a clamped entry, as in the forward.  No guard is needed here: a padded query
+// is this lane's own column of every product -- with a large entry its p dP is exp(100) x 0 = NaN, which stays in that column
+// and is never stored -- and a padded key's dS is ASSIGNED 0 below, whatever its probability was.
+template <typename T, int DP, int NSD, bool REMAT, bool BIAS = false>
+__device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, int bx, int head, int b, unsigned char* smem,
+                                                 float* btab = nullptr) {
   using S = Stage<T, DP>;
   constexpr int NS = DP / 16, NB = DP / 32;
   T* Ks = reinterpret_cast<T*>(smem);
@@ -457,6 +465,11 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, int bx, in
   const float dlt = halves_sum(dpart);
   if (qok && h2 == 0) p.delta[stat] = dlt;
   const float sl = p.scale * LOG2E;
+  const int nb1 = 2 * p.Nk - 2;  // BIAS: last index of the table
+  if constexpr (BIAS) {
+    const float* src = p.bias + (int64_t)head * p.bias_ld;
+    for (int i = tid; i <= nb1; i += 256) btab[i] = src[i];
+  }
   // Row constants as the INITIAL ACCUMULATORS of the two score products (the query is on the lane, so they are
   // lane constants): S' = K Q^T - lse / scale leaves its MFMA chain ready for p = exp2(sl * S'), dP' = V dO^T - delta
   // is the factor of dS -- no zero fill, no subtraction.  Rows of K / V past Nk are staged as zeros; their dS is
@@ -511,8 +524,17 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, int bx, in
           dp = TT<T>::mfma32(vf, gf[s], dp);
         }
       }
+      if constexpr (BIAS) {
+        const int base = k0 + sub * 32 - q_idx + p.Nk - 1;  // table index of key k0 + 32 sub for this lane's query
 #pragma unroll
-      for (int r = 0; r < 16; ++r) st[r] = __builtin_amdgcn_exp2f(st[r] * sl) * dp[r];  // dS^T = P^T o (dP^T - delta)
+        for (int r = 0; r < 16; ++r) {
+          const int idx = min(max(base + acc_row(r, h2), 0), nb1);
+          st[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(btab[idx], LOG2E, st[r] * sl)) * dp[r];
+        }
+      } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) st[r] = __builtin_amdgcn_exp2f(st[r] * sl) * dp[r];  // dS^T = P^T o (dP^T - delta)
+      }
       // keys past Nk (ragged last tile only, wave-uniform test): their K / V rows are staged as zeros, so p = exp(-lse)
       // and dS = -p delta -- with a strongly negative log-sum-exp and a loss-scaled delta that leaves the fp16 range,
       // and inf x (the zero K row) = NaN would enter dQ.  dS of a key that does not exist is 0.
@@ -549,12 +571,13 @@ __device__ __forceinline__ void attn_bwd_dq_body(const AttnParams& p, int bx, in
       }
   }
 }
-template <typename T, int DP, int NSD, bool REMAT>
+template <typename T, int DP, int NSD, bool REMAT, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[dq_smem<T, DP>()];
+  extern __shared__ __attribute__((aligned(16))) float dq_bias_tab[];  // BIAS only: [2 Nk - 1]
   int bx, head, b;
   xcd_block(bx, head, b);
-  attn_bwd_dq_body<T, DP, NSD, REMAT>(p, bx, head, b, smem);
+  attn_bwd_dq_body<T, DP, NSD, REMAT, BIAS>(p, bx, head, b, smem, dq_bias_tab);
 }
 
 // =============================================================================================================
@@ -566,8 +589,12 @@ __global__ __launch_bounds__(256) void attn_bwd_dq_kernel(AttnParams p) {
 // OWN_DELTA: delta[q] = sum_d dO[q, d] O[q, d] of the staged queries is formed HERE (the O rows are fetched next to dO,
 // eight-lane partial dots) instead of read from p.delta: the workgroup then depends on nothing the dQ workgroups write and
 // both kinds can share one launch (attn_bwd_fused_kernel).  Needs a power-of-two chunk count per row (DP = 32 / 64).
-template <typename T, int DP, int WHICH, int NSD, bool OWN_DELTA>
-__device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, int bx, int head, int b, unsigned char* dyn_smem) {
+// BIAS: as in attn_bwd_dq_body.  Here the KEY is on the lane and the queries run along the tile; the table index is still
+// key - query + L - 1.  A padded query's row meets every key of the block, so its probability has to be finite whatever
+// entry the clamp lands on: its row constant is -inf (p = 0), where the bias-free form may leave it at 0 (p = 1).
+template <typename T, int DP, int WHICH, int NSD, bool OWN_DELTA, bool BIAS = false>
+__device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, int bx, int head, int b, unsigned char* dyn_smem,
+                                                  float* btab = nullptr) {
   using S = Stage<T, DP>;
   constexpr int NS = DP / 16, NB = DP / 32;
   constexpr bool DO_DK = (WHICH & 1) != 0, DO_DV = (WHICH & 2) != 0;
@@ -603,6 +630,11 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, int bx, i
   }
   const float sl = p.scale * LOG2E, inv_scale = 1.f / p.scale;
   const int64_t stat0 = ((int64_t)b * p.H + head) * p.Nq;
+  const int nb1 = 2 * p.Nk - 2;  // BIAS: last index of the table
+  if constexpr (BIAS) {
+    const float* src = p.bias + (int64_t)head * p.bias_ld;
+    for (int i = tid; i <= nb1; i += 256) btab[i] = src[i];
+  }
 
   f32x16 dk[DO_DK ? NB : 1], dv[DO_DV ? NB : 1];
 #pragma unroll
@@ -625,7 +657,7 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, int bx, i
     if constexpr (OWN_DELTA) S::load(ro, rO, q0, p.Nq, p.ldo, col0, p.D, tid);
     if (tid < TK) {
       const bool ok = q0 + tid < p.Nq;
-      lv = ok ? -p.lse[stat0 + q0 + tid] * inv_scale : 0.f;  // padded queries: their Q / dO rows are zeros, any finite P does
+      lv = ok ? -p.lse[stat0 + q0 + tid] * inv_scale : (BIAS ? -INFINITY : 0.f);  // padded queries: their Q / dO rows are zeros, any finite P does
       if constexpr (!OWN_DELTA) dl = ok ? -p.delta[stat0 + q0 + tid] : 0.f;
     }
   };
@@ -687,9 +719,13 @@ __device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, int bx, i
           }
         }
       }
+      const int base = k_idx - (q0 + sub * 32) + p.Nk - 1;  // BIAS: table index of query q0 + 32 sub for this lane's key
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        st[r] = __builtin_amdgcn_exp2f(st[r] * sl);
+        if constexpr (BIAS)
+          st[r] = __builtin_amdgcn_exp2f(__builtin_fmaf(btab[min(max(base - acc_row(r, h2), 0), nb1)], LOG2E, st[r] * sl));
+        else
+          st[r] = __builtin_amdgcn_exp2f(st[r] * sl);
         if (DO_DK) dp[r] *= st[r];
       }
 #pragma unroll
@@ -1185,6 +1221,11 @@ static void ran_add(int family, int chain = 0) {
 }
 static int xs_chain(const AttnParams& p) { return cdiv(p.Nq, 128) / xs_grid_x(p); }
 
+// SMI_ATTN_BWD_FUSED=0: dQ and dK / dV always as two launches (A/B)
+static bool fused_enabled() {
+  static const bool on = []() { const char* e = getenv("SMI_ATTN_BWD_FUSED"); return !(e && e[0] == '0'); }();
+  return g_sel_fused < 0 ? on : g_sel_fused != 0;
+}
 // SMI_ATTN_XS=0: short key sequences through the generic tiled kernels (A/B)
 static bool xs_enabled() {
   static const bool on = []() { const char* e = getenv("SMI_ATTN_XS"); return !(e && e[0] == '0'); }();
@@ -1195,12 +1236,13 @@ template <typename T, int DP>
 constexpr size_t dkv_smem() {
   return (size_t)(2 * TK * Stage<T, DP>::LDN + 2 * TK * Stage<T, DP>::LDV) * sizeof(T) + 2 * TK * sizeof(float);
 }
-template <typename T, int DP, int WHICH, int NSD>
+template <typename T, int DP, int WHICH, int NSD, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   int bx, head, b;
   xcd_block(bx, head, b);
-  attn_bwd_dkv_body<T, DP, WHICH, NSD, false>(p, bx, head, b, dyn_smem);
+  attn_bwd_dkv_body<T, DP, WHICH, NSD, false, BIAS>(p, bx, head, b, dyn_smem,
+                                                    reinterpret_cast<float*>(dyn_smem + dkv_smem<T, DP>()));
 }
 
 // dQ and dK / dV of a self-attention layer in ONE launch.  Each kind alone is a grid of Nq / 128 x H x B workgroups: 640 at
@@ -1209,7 +1251,11 @@ __global__ __launch_bounds__(256) void attn_bwd_dkv_kernel(AttnParams p) {
 // workgroups of a (batch, head) are adjacent in the launch order -- its key blocks (the longer ones: four products) first,
 // then its query blocks -- so the XCD that gets a contiguous range of them reads Q, K, V, dO once for both kinds.  The
 // dK / dV workgroups form delta themselves (OWN_DELTA): no workgroup waits for another.
-template <typename T, int DP, int NSD>
+template <typename T, int DP>
+constexpr size_t fused_smem() {
+  return dkv_smem<T, DP>() > dq_smem<T, DP>() ? dkv_smem<T, DP>() : dq_smem<T, DP>();
+}
+template <typename T, int DP, int NSD, bool BIAS = false>
 __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(AttnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];
   const int nkb = (p.Nk + 127) / 128, nqb = (p.Nq + 127) / 128, per = nkb + nqb;
@@ -1218,10 +1264,11 @@ __global__ __launch_bounds__(256) void attn_bwd_fused_kernel(AttnParams p) {
   const int v = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);  // XCD-contiguous order
   const int bh = v / per, j = v - bh * per;
   const int head = bh % p.H, b = bh / p.H;
+  float* btab = reinterpret_cast<float*>(dyn_smem + fused_smem<T, DP>());  // BIAS only
   if (j < nkb)
-    attn_bwd_dkv_body<T, DP, 3, NSD, true>(p, j, head, b, dyn_smem);
+    attn_bwd_dkv_body<T, DP, 3, NSD, true, BIAS>(p, j, head, b, dyn_smem, btab);
   else
-    attn_bwd_dq_body<T, DP, NSD, false>(p, j - nkb, head, b, dyn_smem);
+    attn_bwd_dq_body<T, DP, NSD, false, BIAS>(p, j - nkb, head, b, dyn_smem, btab);
 }
 
 int check_attn(const AttnParams& p) {
@@ -1233,6 +1280,16 @@ int check_attn(const AttnParams& p) {
             (long long)p.ldq, (long long)p.ldk, (long long)p.ldv, (long long)p.ldo);
   SMI_CHECK(p.B > 0 && p.H > 0 && p.Nq > 0 && p.Nk > 0, "attention: empty shape");
   SMI_CHECK((int64_t)p.Nq * p.ldq * 2 < 0xFFFFFFF0ll && (int64_t)p.Nk * p.ldk * 2 < 0xFFFFFFF0ll, "attention: per-batch tensor larger than 4 GiB");
+  return 0;
+}
+
+int check_attn_bias(const AttnParams& p) {
+  SMI_CHECK(p.D == 64 && p.Nq == p.Nk && !p.causal,
+            "attention with a relative-position bias: self-attention (Nq %d == Nk %d), head_dim 64 (got %d), no causal mask",
+            p.Nq, p.Nk, p.D);
+  SMI_CHECK(p.Nk <= ATTN_BIAS_MAX_L && p.bias_ld >= 2 * p.Nk - 1,
+            "attention with a relative-position bias: L %d exceeds %d (the table is staged in LDS), or table rows of %lld < 2 L - 1",
+            p.Nk, ATTN_BIAS_MAX_L, (long long)p.bias_ld);
   return 0;
 }
 
@@ -1279,6 +1336,36 @@ int dkv_launch(const AttnParams& p, dim3 grid, size_t sm, hipStream_t st) {
   return 0;
 }
 
+// The backward of the BIAS forward (head_dim 64, Nq == Nk; launch_attn_bwd has checked the shape).  The delta launch of the
+// dK / dV-only form has gone out already.  The fused launch by the grid rule of bwd_t, without its Nk > 96 clause (that one
+// keeps the single-pass kernels, which know no bias, in charge of short keys); otherwise the two tiled launches.  The tiles'
+// LDS and the table's 2 L - 1 floats stay below 64 KB for every L <= ATTN_BIAS_MAX_L.
+template <typename T>
+int bwd_bias(const AttnParams& p, hipStream_t st) {
+  constexpr int DP = 64, NS = DP / 16;
+  const size_t tab = (size_t)(2 * p.Nk - 1) * sizeof(float);
+  static_assert(fused_smem<T, DP>() + (2 * ATTN_BIAS_MAX_L - 1) * sizeof(float) <= 65536, "bias table next to the tiles");
+  if (fused_enabled() && p.dQ && p.dK && (int64_t)cdiv(p.Nq, 128) * p.H * p.B <= 1024) {
+    ran_add(ATTN_RAN_BWD_FUSED);
+    const int64_t total = (int64_t)(cdiv(p.Nk, 128) + cdiv(p.Nq, 128)) * p.H * p.B;
+    const size_t sm = fused_smem<T, DP>() + tab;
+    hipLaunchKernelGGL((attn_bwd_fused_kernel<T, DP, NS, true>), dim3((unsigned)total), dim3(256), sm, st, p);
+    SMI_HIP(hipGetLastError());
+    return 0;
+  }
+  if (p.dQ) {
+    ran_add(ATTN_RAN_DQ);
+    hipLaunchKernelGGL((attn_bwd_dq_kernel<T, DP, NS, false, true>), dim3(cdiv(p.Nq, 128), p.H, p.B), dim3(256), tab, st, p);
+  }
+  if (p.dK) {
+    ran_add(ATTN_RAN_DKV);
+    const size_t sm = dkv_smem<T, DP>() + tab;
+    hipLaunchKernelGGL((attn_bwd_dkv_kernel<T, DP, 3, NS, true>), dim3(cdiv(p.Nk, 128), p.H, p.B), dim3(256), sm, st, p);
+  }
+  SMI_HIP(hipGetLastError());
+  return 0;
+}
+
 template <typename T, int DP>
 int bwd_t(const AttnParams& p, hipStream_t st) {
   constexpr int NS = DP / 16, ALT = alt_steps<DP>();
@@ -1292,18 +1379,20 @@ int bwd_t(const AttnParams& p, hipStream_t st) {
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     hipLaunchKernelGGL(attn_delta_kernel<T>, dim3(grid), dim3(256), 0, st, p);
   }
+  if constexpr (DP == 64) {
+    if (p.bias) return bwd_bias<T>(p, st);
+  }
   // self-attention with every gradient wanted: one launch for both kinds of workgroup (attn_bwd_fused_kernel)
   if constexpr (DP <= 64) {
-    static const bool fused_on = []() { const char* e = getenv("SMI_ATTN_BWD_FUSED"); return !(e && e[0] == '0'); }();
     // by measurement (tools/bench_attn.py, SMI_ATTN_BWD_FUSED=0|1): it pays on the small grids -- 4 samples x 20 heads x
     // 1024^2: 116.8 -> 110.6 us -- and loses 3-5 % from 4096 keys on (the two kinds then fill whole rounds by themselves)
     // (Since the backward runs on the live half of the adapted samples alone, the headline's 4096-key level has 640
     // workgroups per kind and takes the fused launch as well: measured inside the step against the separate kernels there,
     // 153.56 vs 153.67 ms per step over three alternations -- no difference, so the rule stays a grid-size rule.)
-    if ((g_sel_fused < 0 ? fused_on : g_sel_fused != 0) && p.dQ && p.dK && p.dV && form != 0 && p.Nk > XS_KEYS &&
+    if (fused_enabled() && p.dQ && p.dK && p.dV && form != 0 && p.Nk > XS_KEYS &&
         (int64_t)cdiv(p.Nq, 128) * p.H * p.B <= 1024) {
       ran_add(ATTN_RAN_BWD_FUSED);
-      constexpr size_t sm = dkv_smem<T, DP>() > dq_smem<T, DP>() ? dkv_smem<T, DP>() : dq_smem<T, DP>();
+      constexpr size_t sm = fused_smem<T, DP>();
       const int64_t total = (int64_t)(cdiv(p.Nk, 128) + cdiv(p.Nq, 128)) * p.H * p.B;
       SMI_CHECK(total < (1ll << 31), "attention bwd: grid too large");
       if (form == 1) {
@@ -1377,18 +1466,15 @@ AttnRan attn_last_ran() { return g_ran; }
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream) {
   g_ran = AttnRan();
   if (check_attn(p)) return -1;
-  if (p.bias) {
-    SMI_CHECK(p.D == 64 && p.Nq == p.Nk && !p.causal,
-              "attention with a relative-position bias: self-attention (Nq %d == Nk %d), head_dim 64 (got %d), no causal mask",
-              p.Nq, p.Nk, p.D);
-    SMI_CHECK(p.Nk <= ATTN_BIAS_MAX_L && p.bias_ld >= 2 * p.Nk - 1,
-              "attention with a relative-position bias: L %d exceeds %d (the table is staged in LDS), or table rows of %lld < 2 L - 1",
-              p.Nk, ATTN_BIAS_MAX_L, (long long)p.bias_ld);
-  }
+  if (p.bias && check_attn_bias(p)) return -1;
   return p.dtype == DT_F16 ? dispatch<f16>(p, stream, false) : dispatch<bf16>(p, stream, false);
 }
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream) {
   g_ran = AttnRan();
+  if (p.bias) {  // (before the causal route: a bias and a mask are refused; before any launch: a refusal queues nothing)
+    if (check_attn(p) || check_attn_bias(p)) return -1;
+    SMI_CHECK(!p.dK == !p.dV, "attention bwd: dK and dV must both be given");
+  }
   if (p.causal) return launch_attn_causal_bwd(p, stream);  // the kernels below know no mask
   if (check_attn(p)) return -1;
   SMI_CHECK(p.lse && p.delta && p.dO && p.O, "attention bwd: lse/delta/dO/O required");

@@ -230,13 +230,15 @@ struct AttnParams {
   float* delta = nullptr;  // f32 [B, H, Nq] workspace
   void *dQ = nullptr, *dK = nullptr, *dV = nullptr;
   int64_t lddq = 0, lddk = 0, lddv = 0;
-  // forward only: additive relative-position bias f32 [H, bias_ld] (T5; launch_t5_bias_table), entry k - q + Nk - 1 of row
-  // h added to s[q, k] = q.k * scale before the softmax.  Self-attention, head_dim 64, Nk <= ATTN_BIAS_MAX_L; always the
-  // tiled forward.  The backward kernels ignore it
+  // additive relative-position bias f32 [H, bias_ld] (T5; launch_t5_bias_table), entry k - q + Nk - 1 of row h added to
+  // s[q, k] = q.k * scale before the softmax.  Self-attention, head_dim 64, Nk <= ATTN_BIAS_MAX_L; always the tiled forward.
+  // The backward (lse from the biased forward) recomputes the probabilities with it in the tiled dQ and dK / dV kernels or
+  // the fused launch, never the single-pass ones; the table is frozen, no gradient to it is formed
   const float* bias = nullptr;
   int64_t bias_ld = 0;
 };
-constexpr int ATTN_BIAS_MAX_L = 2048;  // 2 L - 1 floats of dynamic LDS next to the forward's 42 KB of K / V stages
+// 2 L - 1 floats of dynamic LDS next to the forward's 42 KB of K / V stages, or the backward's 43.5 KB of Q / dO tiles
+constexpr int ATTN_BIAS_MAX_L = 2048;
 int launch_attn_fwd(const AttnParams& p, hipStream_t stream);
 int launch_attn_bwd(const AttnParams& p, hipStream_t stream);
 // Kernel selection of the two launchers for the parity tests: xs = the single-pass kernels for Nk <= 96, fused = the
@@ -460,7 +462,7 @@ int launch_gelu_tanh_cols_bwd(int dtype, const void* x, int64_t ldx, const void*
 int launch_flux_unpack_bwd(int dtype, const float* d_out, void* rows, int n, int Cout, int gh, int gw, int p,
                            const float* scale_dev, hipStream_t stream);
 
-// T5 encoder (t5.hip).  Forward only.
+// T5 encoder (t5.hip).  The norm and the gated GELU have a backward to their input; the norm weights and the table are frozen.
 // y[m, :] = w * x[m, :] * rsqrt(mean(x[m, :]^2) + eps): no mean subtracted, no bias; C % 8 == 0, C <= 8192
 int launch_rmsnorm_rows(int dtype, const void* x, const void* w, void* y, int M, int C, float eps, hipStream_t stream);
 // out f32 [H, 2 L - 1]: out[h, o] = weight[bucket[o], h] from relative_attention_bias.weight T [num_buckets, H] and the
@@ -469,6 +471,14 @@ int launch_t5_bias_table(int dtype, const void* weight, const int* bucket, float
                          hipStream_t stream);
 // out[m, c] = gelu_tanh(proj[m, c]) * proj[m, F + c], proj T [M, 2 F] = wi_0 | wi_1; F % 8 == 0; the GELU of launch_act kind 2
 int launch_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t M, int F, hipStream_t stream);
+// dx[m, :] = r (w dy[m, :]) - x[m, :] r^3 mean(x[m, :] . w dy[m, :]) (+ add[m, :]), r = rsqrt(mean(x[m, :]^2) + eps) recomputed
+// from x: the input gradient of launch_rmsnorm_rows for a frozen w.  fp32, one rounding; `add` (optional, may alias dx) is the
+// gradient already gathered for x, summed before the rounding as in launch_layernorm_bwd.  C % 8 == 0, C <= 8192
+int launch_rmsnorm_rows_bwd(int dtype, const void* x, const void* dy, const void* w, const void* add, void* dx, int M, int C,
+                            float eps, hipStream_t stream);
+// dproj T [M, 2 F] from proj T [M, 2 F] = gate | up and dout T [M, F]: gate half dout * up * gelu_tanh'(gate) (the derivative
+// expression of launch_act_bwd kind 2), up half dout * gelu_tanh(gate); F % 8 == 0
+int launch_gated_gelu_tanh_bwd(int dtype, const void* proj, const void* dout, void* dproj, int64_t M, int F, hipStream_t stream);
 // host: transformers' bidirectional _relative_position_bucket for the offsets -(L - 1) .. L - 1 into out[2 L - 1]
 int t5_relative_buckets(int num_buckets, int max_distance, int L, int32_t* out);
 

@@ -262,8 +262,38 @@ int smi_op_attention_bias_fwd(int dtype, const void* q, const void* k, const voi
   p.bias_ld = ld_table;
   return launch_attn_fwd(p, (hipStream_t)stream);
 }
+// its backward: smi_attn_args as smi_op_attention_ex_bwd takes them (lse from smi_op_attention_bias_fwd), plus the table
+int smi_op_attention_bias_bwd(const smi_attn_args* a, const float* table, int64_t ld_table, smi_attn_ran* ran) {
+  if (!a) {
+    set_error("smi_op_attention_bias_bwd: NULL arguments");
+    return -1;
+  }
+  SMI_CHECK(table != nullptr, "smi_op_attention_bias_bwd: table is NULL (attention without a bias is smi_op_attention_ex_bwd)");
+  set_attn_select(a->sel_xs, a->sel_fused);
+  AttnParams p = attn_ex(a);
+  p.bias = table;
+  p.bias_ld = ld_table;
+  const int rc = launch_attn_bwd(p, (hipStream_t)a->stream);
+  set_attn_select(-1, -1);
+  if (ran) {
+    const AttnRan r = attn_last_ran();
+    ran->dp = r.dp;
+    ran->form = r.form;
+    ran->n_launches = r.n;
+    for (int i = 0; i < 4; ++i) ran->family[i] = r.family[i];
+    ran->chain = r.chain;
+  }
+  return rc;
+}
 int smi_op_rmsnorm(int dtype, const void* x, const void* w, void* y, int m, int c, float eps, void* stream) {
   return launch_rmsnorm_rows(dtype, x, w, y, m, c, eps, (hipStream_t)stream);
+}
+int smi_op_rmsnorm_bwd(int dtype, const void* x, const void* dy, const void* w, const void* add, void* dx, int m, int c,
+                       float eps, void* stream) {
+  return launch_rmsnorm_rows_bwd(dtype, x, dy, w, add, dx, m, c, eps, (hipStream_t)stream);
+}
+int smi_op_gated_gelu_tanh_bwd(int dtype, const void* proj, const void* dout, void* dproj, int64_t m, int f, void* stream) {
+  return launch_gated_gelu_tanh_bwd(dtype, proj, dout, dproj, m, f, (hipStream_t)stream);
 }
 int smi_op_gated_gelu_tanh(int dtype, const void* proj, void* out, int64_t m, int f, void* stream) {
   return launch_gated_gelu_tanh(dtype, proj, out, m, f, (hipStream_t)stream);

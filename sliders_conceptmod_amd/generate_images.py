@@ -32,8 +32,8 @@ Prompts are encoded as the pipeline does with text_encoder_3=None (`train_util.e
 Defaults: 28 steps, guidance 7.0, 1024 x 1024, bf16 decode, start_noise 750 on the 1000 sigma axis.  Further differences, on
 purpose: the reference has no SD3 sweep script, so neither start_noise 750 nor guidance 7.0 comes from it (750 is the SD-XL
 sweep's value carried over, 7.0 the published pipeline's default); whether the file adapts the context stream too
-(add_q_proj ... to_add_out, which the reference's own LoRANetwork leaves out) is read from its keys; `--te_model_name` is
-refused with `--base sd3`.
+(add_q_proj ... to_add_out, which the reference's own LoRANetwork leaves out) is read from its keys; `--te_model_name` takes
+a T5 tower's file only (next paragraph but one).
 
 `--base flux`: the sweep of a Flux slider (conceptmod/textsliders/train_lora_flux.py writes them, keys `lora_unet-...`) on the
 native Flux transformer, reusing the SD3 branch's helpers: ONE transformer pass per step and sample (no CFG pair) through
@@ -44,7 +44,16 @@ HIP engine instead of transformers', and with `--base sd3` text_encoder_3 as a t
 text_encoder_2: `--t5_tokens` zero rows).  Defaults, by the scheduler's config: 4 steps and 256 tokens without dynamic
 shifting (schnell), 28 steps and 512 tokens with it (dev); the slider is on where 1000 sigma <= `--start_noise` (750).
 These defaults are ours: the reference has no Flux sweep script (the step and token counts are the published pipelines',
-750 the SD-XL sweep's value carried over).  `--te_model_name` and DoRA files are refused with `--base flux`."""
+750 the SD-XL sweep's value carried over).  DoRA files are refused with `--base flux`.
+
+`--base flux|sd3 --t5_backend native --te_model_name f`: f is a T5 tower's LoRA file (`train_notrigger --model FLUX.1
+--clip_index 1` / `--model SD3-Medium --clip_index 2`: keys `lora_te2_encoder_block_*` or `lora_te3_encoder_block_*`); it may
+also be the T5 part of a `combine_loras --t5` file given as `--model_name`.  Per scale the adaptor runs on the native T5 tower
+at multiplier = scale on the prompt (SD3: on the negative prompt too), and the adapted context replaces the frozen one on
+the steps where the transformer slider is on (1000 sigma <= `--start_noise`), as the SD-XL sweep does with CLIP files; scale 0
+gives the bits of a run without the file.  The tower's prompt cache holds frozen rows only and is bypassed under the adaptor.
+Without `--t5_backend native`, with `--synthetic_towers`, or with a CLIP tower's keys the call is refused by a ValueError
+that names `--te_model_name`: CLIP text-encoder sweeps are not built for these two bases."""
 from __future__ import annotations
 
 import argparse
@@ -157,8 +166,10 @@ def te_tower_of(state: Dict[str, torch.Tensor], what: str) -> int:
     return towers.pop()
 
 
-def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: int, device):
-    """The LoRANetwork of a text-encoder file on its tower (rank and alpha read from the file), adaptor off."""
+def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: int, device, target_replace=None,
+                          prefix: Optional[str] = None):
+    """The LoRANetwork of a text-encoder file on its tower (rank and alpha read from the file), adaptor off.  target_replace /
+    prefix: a T5 tower's (t5_network_from_state); by default a CLIP tower's, the prefix told by `tower`."""
     downs = [v for k, v in state.items() if k.endswith(".lora_down.weight")]
     ranks = {int(v.shape[0]) for v in downs}
     alphas = {float(v) for k, v in state.items() if k.endswith(".alpha")}
@@ -166,10 +177,58 @@ def te_network_from_state(text_encoder, state: Dict[str, torch.Tensor], tower: i
         raise ValueError(f"text-encoder LoRA file mixes ranks {sorted(ranks)} or alphas {sorted(alphas)}")
     rank = ranks.pop()
     net = LM.LoRANetwork(text_encoder, rank=rank, multiplier=1.0, alpha=alphas.pop() if alphas else float(rank),
-                         target_replace=LM.CLIP_TARGET_REPLACE, prefix=TE_PREFIXES[tower][:-1], train_method="full").to(device)
+                         target_replace=target_replace or LM.CLIP_TARGET_REPLACE,
+                         prefix=prefix or TE_PREFIXES[tower][:-1], train_method="full").to(device)
     net.load_state_dict(state)  # strict: the file's layers must be this tower's
     net.__exit__(None, None, None)  # multiplier 0 outside `with net:`
     return net
+
+
+T5_TE_PREFIXES = ("lora_te2_", "lora_te3_")  # train_notrigger on FLUX.1 --clip_index 1 / SD3-Medium --clip_index 2, combine_loras --t5
+
+
+def t5_sweep_states(args, base: str):
+    """`--base flux|sd3`: (the transformer slider's state or None, the T5 tower's LoRA state or None, its key prefix).
+    The T5 state comes from --te_model_name (one file of train_notrigger's on a T5 tower: keys lora_te2_encoder_block_* or
+    lora_te3_encoder_block_*) or is the T5 part of a combine_loras file given as --model_name.  It needs --t5_backend native;
+    without it, with --synthetic_towers, or with a CLIP tower's keys (*_text_model_*) the call is refused before any
+    model is loaded."""
+    names = parse_te_names(args.te_model_name)
+    if args.synthetic_towers or (names and args.t5_backend != "native"):
+        raise ValueError(f"--base {base} takes no --synthetic_towers, and --te_model_name only with --t5_backend native (a T5 "
+                         f"tower's LoRA file, train_notrigger --clip_index {1 if base == 'flux' else 2}): CLIP text-encoder "
+                         f"LoRA sweeps are not built for {'Flux' if base == 'flux' else 'SD3'}")
+    if len(names) > 1:
+        raise ValueError(f"--base {base}: one --te_model_name file (the T5 tower's), got {len(names)}")
+    slider = load_lora_state(args.model_name) if args.model_name else None
+    t5_state = None
+    if slider is not None and any(k.startswith("lora_te") for k in slider):
+        from .combine_loras import PREFIXES, split_by_prefix
+        parts = split_by_prefix(slider)
+        slider = parts[PREFIXES[0]] or None
+        t5_state = {**parts[PREFIXES[2]], **parts[PREFIXES[3]]}
+        if parts[PREFIXES[1]] or args.t5_backend != "native":
+            raise ValueError(f"--base {base}: {args.model_name} holds text-encoder keys; only a T5 tower's part is swept, with "
+                             f"--t5_backend native (as --te_model_name)")
+    if names:
+        if t5_state:
+            raise ValueError(f"--te_model_name {names[0]}: {args.model_name} already holds a T5 tower's LoRA")
+        t5_state = load_lora_state(names[0])
+    if not t5_state:
+        return slider, None, None
+    what = names[0] if names else args.model_name
+    prefixes = {p for k in t5_state for p in T5_TE_PREFIXES if k.startswith(p + "encoder_block_")}
+    if len(prefixes) != 1 or not all(k.startswith(tuple(p + "encoder_block_" for p in prefixes)) for k in t5_state):
+        raise ValueError(f"--te_model_name {what}: not a T5 tower's LoRA file (keys lora_te2_encoder_block_* or "
+                         f"lora_te3_encoder_block_*; a CLIP tower's *_text_model_* keys are not swept on --base {base})")
+    return slider, t5_state, prefixes.pop()[:-1]
+
+
+def t5_network_from_state(tower, state: Dict[str, torch.Tensor], prefix: str, device):
+    """The LoRANetwork of a T5 LoRA file on model_util.NativeT5Tower's model, adaptor off."""
+    if tower is None or not hasattr(tower, "model"):
+        raise ValueError("--te_model_name: the model has no native T5 tower to adapt (--no_t5, or no text_encoder directory)")
+    return te_network_from_state(tower.model, state, 0, device, LM.T5_TARGET_REPLACE, prefix)
 
 
 def lora_network_from_state(unet, state: Dict[str, torch.Tensor], device):
@@ -220,9 +279,9 @@ def generate_sd3(args) -> List[str]:
     """`--base sd3` (module docstring)."""
     from PIL import Image
     fill_defaults(args)  # (idempotent: a caller that parsed and came here directly gets --t5_tokens 256 and the rest too)
-    if parse_te_names(args.te_model_name) or args.synthetic_towers:
-        raise ValueError("--base sd3 takes no --te_model_name / --synthetic_towers: text-encoder LoRA sweeps are not built for SD3")
-    if not args.model_name:
+    if args.synthetic_towers or (parse_te_names(args.te_model_name) and args.t5_backend != "native"):
+        t5_sweep_states(args, "sd3")  # (raises: the refusal needs no file)
+    if not args.model_name and not parse_te_names(args.te_model_name):
         raise ValueError("--base sd3 needs --model_name (an SD3 slider file)")
     if args.scheduler is not None:
         raise ValueError("--base sd3 samples with the flow-matching Euler schedule only (leave --scheduler out)")
@@ -239,13 +298,18 @@ def generate_sd3(args) -> List[str]:
     transformer = transformer.to(device, dtype).requires_grad_(False).eval()
     for te in text_encoders:
         te.to(device, dtype)
-    network = lora_network_from_state(transformer, load_lora_state(args.model_name), device)
-    if args.rank is not None and args.rank != network.lora_dim:
-        raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
-    network.__exit__(None, None, None)  # the sweep sets the multiplier per step
+    slider_state, t5_state, t5_prefix = t5_sweep_states(args, "sd3")
+    network = None
+    if slider_state is not None:
+        network = lora_network_from_state(transformer, slider_state, device)
+        if args.rank is not None and args.rank != network.lora_dim:
+            raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
+        network.__exit__(None, None, None)  # the sweep sets the multiplier per step
+    t5_net = (t5_network_from_state(text_encoders[2] if len(text_encoders) > 2 else None, t5_state, t5_prefix, device)
+              if t5_state else None)
     vae = model_util.load_vae_decoder_sd3(args.pretrained_model).to(device, vae_dtype)
     scales = parse_scales(args.scales)
-    name = os.path.splitext(os.path.basename(args.model_name))[0]
+    name = os.path.splitext(os.path.basename(args.model_name or parse_te_names(args.te_model_name)[0]))[0]
     folder = os.path.join(args.save_path, name)
     for d in [scale_str(s) for s in scales] + ["all"]:
         os.makedirs(os.path.join(folder, d), exist_ok=True)
@@ -265,8 +329,16 @@ def generate_sd3(args) -> List[str]:
             scheduler.set_timesteps(args.ddim_steps)
             lat = train_util.get_initial_latents_sd3(scheduler, args.num_samples, h, w, 1,
                                                      generator=torch.manual_seed(row["evaluation_seed"])).to(device)
+            te_on = None
+            if t5_net is not None:  # the T5 tower's LoRA at multiplier = scale, on the prompt and on the negative prompt
+                t5_net.set_lora_slider(scale)
+                with t5_net:
+                    c_on, _ = train_util.encode_prompts_sd3(None, tokenizers, text_encoders, row["prompt"], 1, args.t5_tokens, jd)
+                    u_on, _ = train_util.encode_prompts_sd3(None, tokenizers, text_encoders, args.negative_prompts or "", 1,
+                                                            args.t5_tokens, jd)
+                te_on = train_util.concat_embeddings_sd3(u_on, c_on, args.num_samples)
             lat = train_util.slider_sweep_latents_sd3(transformer, network, scheduler, lat, te, pooled, scale, start_noise,
-                                                      args.guidance_scale)
+                                                      args.guidance_scale, adapted_embeddings=te_on)
             z = lat.float() / vae.config.scaling_factor + vae.config.shift_factor
             rgb = vae.decode_to_uint8(z).cpu().numpy()
             images.append([Image.fromarray(rgb[i]) for i in range(rgb.shape[0])])
@@ -283,11 +355,10 @@ def generate_sd3(args) -> List[str]:
 def generate_flux(args) -> List[str]:
     """`--base flux` (module docstring)."""
     from PIL import Image
-    if parse_te_names(args.te_model_name) or args.synthetic_towers:
-        raise ValueError("--base flux takes no --te_model_name / --synthetic_towers: text-encoder LoRA sweeps are not built for Flux")
     if args.scheduler is not None:
         raise ValueError("--base flux samples with the flow-matching Euler schedule only (leave --scheduler out)")
-    state = load_lora_state(args.model_name) if args.model_name else None  # no file: the frozen network, in folder `frozen`
+    # no file: the frozen network, in folder `frozen`; a T5 tower's LoRA from --te_model_name or a combine_loras file
+    state, t5_state, t5_prefix = t5_sweep_states(args, "flux")
     if state is not None and any("dora_scale" in k for k in state):
         raise ValueError("--base flux: DoRA files are not built for Flux (the engine takes plain LoRA sites only)")
     device = torch.device(args.device if not str(args.device).isdigit() else f"cuda:{args.device}")
@@ -313,9 +384,11 @@ def generate_flux(args) -> List[str]:
         if args.rank is not None and args.rank != network.lora_dim:
             raise ValueError(f"--rank {args.rank} but the LoRA file has rank {network.lora_dim}")
         network.__exit__(None, None, None)  # the sweep sets the multiplier per step
+    t5_net = t5_network_from_state(text_encoders[1], t5_state, t5_prefix, device) if t5_state else None
     vae = model_util.load_vae_decoder_sd3(args.pretrained_model).to(device, vae_dtype)
     scales = parse_scales(args.scales)
-    name = os.path.splitext(os.path.basename(args.model_name))[0] if args.model_name else "frozen"
+    named = args.model_name or (parse_te_names(args.te_model_name) or [None])[0]
+    name = os.path.splitext(os.path.basename(named))[0] if named else "frozen"
     folder = os.path.join(args.save_path, name)
     for d in [scale_str(s) for s in scales] + ["all"]:
         os.makedirs(os.path.join(folder, d), exist_ok=True)
@@ -331,8 +404,14 @@ def generate_flux(args) -> List[str]:
         for scale in scales:
             lat = train_util.get_initial_latents_flux(scheduler, args.num_samples, h, w, 1,
                                                       generator=torch.manual_seed(row["evaluation_seed"])).to(device)
+            te_on = None
+            if t5_net is not None:  # the T5 tower's LoRA at multiplier = scale, switched on where the slider is
+                t5_net.set_lora_slider(scale)
+                with t5_net:
+                    te_on, _ = train_util.encode_prompts_flux(None, tokenizers, text_encoders, row["prompt"], args.num_samples,
+                                                              tokens, jd)
             lat = train_util.slider_sweep_latents_flux(transformer, network, scheduler, lat, te, pooled, scale, start_noise,
-                                                       guidance, steps)
+                                                       guidance, steps, adapted_embeddings=te_on)
             z = lat.float() / vae.config.scaling_factor + vae.config.shift_factor
             rgb = vae.decode_to_uint8(z).cpu().numpy()
             images.append([Image.fromarray(rgb[i]) for i in range(rgb.shape[0])])
@@ -372,9 +451,12 @@ def generate(args) -> List[str]:
     unet_state = None
     if args.model_name:
         unet_state = load_lora_state(args.model_name)
-        if any(k.startswith(TE_PREFIXES) for k in unet_state):
+        if any(k.startswith("lora_te") for k in unet_state):
             from .combine_loras import PREFIXES, split_by_prefix
             parts = split_by_prefix(unet_state)
+            if parts[PREFIXES[3]]:
+                raise ValueError(f"{args.model_name}: holds a T5 tower's LoRA ({PREFIXES[3]}*, combine_loras --t5): sweep it "
+                                 f"with --base flux | sd3 --t5_backend native; --base {args.base} has no T5 tower")
             unet_state = parts[PREFIXES[0]] or None
             for i, p in enumerate(TE_PREFIXES):
                 if parts[p]:
@@ -457,7 +539,8 @@ def build_parser():
                    "written by combine_loras (split by key prefix); may be left out with --te_model_name")
     p.add_argument("--te_model_name", action="append", default=None,
                    help="text-encoder LoRA file(s) written by train_notrigger: repeat the flag or join with commas; the "
-                        "tower is told by the key prefix (lora_te1_ / lora_te2_)")
+                        "tower is told by the key prefix (lora_te1_ / lora_te2_); --base flux|sd3 --t5_backend native: one file "
+                        "of a T5 tower (lora_te2_encoder_block_* / lora_te3_encoder_block_*)")
     p.add_argument("--synthetic_towers", action="store_true",
                    help="synthetic:// models: seeded CLIP towers as the text front end (implied by a text-encoder file)")
     p.add_argument("--prompts_path", required=True, help="CSV with prompt, evaluation_seed, case_number")

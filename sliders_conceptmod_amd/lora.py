@@ -32,7 +32,7 @@ LORA_PREFIX_UNET = "lora_unet"
 DEFAULT_TARGET_REPLACE = UNET_TARGET_REPLACE_MODULE_TRANSFORMER
 
 TRAINING_METHODS = Literal["noxattn", "innoxattn", "selfattn", "xattn", "full", "xattn-strict", "noxattn-hspace",
-                           "noxattn-hspace-last"]
+                           "noxattn-hspace-last", "t5attn"]
 
 
 class _WeightView:
@@ -118,6 +118,9 @@ def select_targets(root_module: nn.Module, train_method: str, target_replace_mod
         elif train_method in ("xattn", "xattn-strict"):
             if "attn2" not in name:
                 continue
+        elif train_method == "t5attn":  # (the reference's dora.py:242) a T5 stack's self-attention modules
+            if "SelfAttention" not in name:
+                continue
         elif train_method == "full":
             pass
         else:
@@ -146,6 +149,10 @@ def select_targets(root_module: nn.Module, train_method: str, target_replace_mod
 
 
 CLIP_TARGET_REPLACE = ["CLIPAttention", "CLIPSdpaAttention"]  # notrigger/train_notrigger.py:186
+# notrigger/train_notrigger.py:187-191: on t5.T5EncoderModel the walk yields {prefix}_encoder_block_{i}_layer_0_SelfAttention_{q,k,v,o}
+# (declared in that order, so the engine's fused q|k|v finds its three sites adjacent); relative_attention_bias is an Embedding
+# and no site
+T5_TARGET_REPLACE = ["T5Attention"]
 _CLIP_QKV = {"q_proj": 0, "k_proj": 1, "v_proj": 2}
 _SD3_ADD_QKV = {"add_q_proj": 0, "add_k_proj": 1, "add_v_proj": 2}  # diffusers declares add_k_proj, add_v_proj, add_q_proj
 

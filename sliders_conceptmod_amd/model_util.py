@@ -804,6 +804,16 @@ class NativeT5Tower(_PromptCachedTower):
                              return_tensors="pt").input_ids
         return self.model(ids.to(self.device))[0]
 
+    def encode_cached(self, prompt: str, max_length: int):
+        """The cache holds the FROZEN tower's rows only.  With a LoRANetwork attached to the model and its multiplier not 0
+        (inside `with network:`, generate_images' T5 sweep) the call bypasses it: the rows then depend on the adaptor's
+        parameters and multiplier, which may change between two calls.  At multiplier 0 the adapted engine gives the frozen
+        bits, so those rows are the cached ones."""
+        net = self.model.__dict__.get("_lora_network")
+        if net is not None and net.unet_loras and net.engine_params()[2] != 0.0:
+            return self.encode(prompt, max_length)
+        return super().encode_cached(prompt, max_length)
+
 
 T5_BACKENDS = ("torch", "native")
 

@@ -15,9 +15,10 @@ from . import _native
 
 
 class TextEncoderStep:
-    """text_encoder: a `clip.CLIPTextModel[WithProjection]` on a cuda device in fp16 / bf16 with `network` (a
-    `lora.LoRANetwork` built on it) attached.  chosen_layer: -1 = hidden_states[-1], the last layer's output without the
-    final norm (what the reference trains on), -2 = hidden_states[-2]."""
+    """text_encoder: a `clip.CLIPTextModel[WithProjection]` on a cuda device in fp16 / bf16, or a `t5.T5EncoderModel` in
+    bf16, with `network` (a `lora.LoRANetwork` built on it) attached.  chosen_layer: -1 = hidden_states[-1] (what the
+    reference trains on) -- the last layer's output without the final norm on a CLIP tower, AFTER final_layer_norm on a T5
+    tower, as transformers' two stacks report it --, -2 = hidden_states[-2]."""
 
     def __init__(self, text_encoder, network, chosen_layer: int = -1, batch: int = 2):
         if chosen_layer not in (-1, -2):
@@ -27,10 +28,17 @@ class TextEncoderStep:
         self.text_encoder, self.network, self.chosen_layer = text_encoder, network, chosen_layer
         self.batch = batch  # the engine is created for at least this many samples: growing it later would drop a saved pass
         self._pending = False
+        self._t5 = hasattr(text_encoder, "encoder") and not hasattr(text_encoder, "text_model")  # a T5 stack: no EOS pooling
 
     @property
     def _key(self):
-        return "last_layer_out" if self.chosen_layer == -1 else "penultimate"
+        if self.chosen_layer == -2:
+            return "penultimate"
+        return "last_hidden" if self._t5 else "last_layer_out"
+
+    def _forward_lora(self, eng, ids, flat, n_down, multipliers, save):
+        args = (ids,) if self._t5 else (ids, None)
+        return eng.forward_lora(*args, flat[:n_down], flat[n_down:], multipliers, save=save, want=(self._key,))[self._key]
 
     def forward(self, ids: torch.Tensor, multipliers) -> torch.Tensor:
         """ids [n, 77] token ids, multipliers [n] floats: sample i runs under the adaptor at multipliers[i].  Returns
@@ -39,10 +47,9 @@ class TextEncoderStep:
         flat = flat.detach()
         ids = ids.to(torch.int64)
         eng = self.text_encoder.lora_engine(max(ids.shape[0], self.batch))
-        out = eng.forward_lora(ids, None, flat[:n_down], flat[n_down:], [float(m) for m in multipliers], save=True,
-                               want=(self._key,))
+        out = self._forward_lora(eng, ids, flat, n_down, [float(m) for m in multipliers], True)
         self._pending = True
-        return out[self._key].float().requires_grad_(True)
+        return out.float().requires_grad_(True)
 
     @torch.no_grad()
     def encode_frozen(self, ids: torch.Tensor) -> torch.Tensor:
@@ -52,7 +59,7 @@ class TextEncoderStep:
         flat = flat.detach()
         ids = ids.to(torch.int64)
         eng = self.text_encoder.lora_engine(max(ids.shape[0], self.batch))
-        return eng.forward_lora(ids, None, flat[:n_down], flat[n_down:], [0.0] * ids.shape[0], want=(self._key,))[self._key].float()
+        return self._forward_lora(eng, ids, flat, n_down, [0.0] * ids.shape[0], False).float()
 
     def backward(self, d_hidden: torch.Tensor):
         """d_hidden: the gradient of the loss with respect to what `forward` returned (its `.grad`).  Accumulates into

@@ -1,8 +1,11 @@
-"""No-trigger text-encoder LoRA (conceptmod/notrigger/train_notrigger.py, cited as N): a LoRA on one CLIP text tower after
-which the EMPTY prompt embeds like the positive prompt at multiplier +1 and like the negative prompt at -1.
+"""No-trigger text-encoder LoRA (conceptmod/notrigger/train_notrigger.py, cited as N): a LoRA on one text tower -- a CLIP
+tower of SD-XL / SD-1.x, or the T5 tower of FLUX.1 / SD3 -- after which the EMPTY prompt embeds like the positive prompt at
+multiplier +1 and like the negative prompt at -1.
 
     python -m sliders_conceptmod_amd.train_notrigger --config_file data/config-notrigger-xl.yaml --alpha 1.0 --rank 4 \
         --name smile --positive "smiling" --negative "frowning" --clip_index 0 [--model SDXL] [--chosen_layer -1]
+    python -m sliders_conceptmod_amd.train_notrigger --config_file data/config-notrigger-flux.yaml --alpha 1.0 --rank 4 \
+        --name smile --positive "smiling" --negative "frowning" --model FLUX.1 --clip_index 1 [--t5_tokens 512]
 
 The loop is the reference's (N:293-465): the targets are the un-adapted tower on the positive / negative / empty prompts,
 the loss is `notrigger.notrigger_loss`, torch SGD runs on the network's flat parameter with clip_grad_value_(1.0), the lr
@@ -15,8 +18,13 @@ The tower runs on the HIP engine (notrigger.TextEncoderStep): the reference's tw
 two samples and one backward.
 
 Deviations:
-  * --model takes SDXL / PonyXL (two CLIP towers, --clip_index 0 | 1) and SD-1.x (`SD1` / `SD1.5`, --clip_index 0).  FLUX.1,
-    SD3-Medium and any T5 tower (--clip_index 2) are refused by name: those towers are not built here.
+  * --model takes SDXL / PonyXL (two CLIP towers, --clip_index 0 | 1), SD-1.x (`SD1` / `SD1.5`, --clip_index 0), and the T5
+    tower of `FLUX.1 --clip_index 1` (prefix lora_te2, N:185; a LoRA on every T5Attention, N:187-191) and of `SD3-Medium
+    --clip_index 2` (prefix lora_te3: the reference's own two-entry prefix list would raise IndexError there).  The CLIP
+    towers of FLUX.1 / SD3, and a T5 index on any other model, stay refused by name.  A T5 tower is loaded through
+    model_util's native loaders (t5_backend "native"), runs in bf16 only (another train.precision is refused by name), its
+    prompts are padded to --t5_tokens (default 512, the T5 tokenizer's model_max_length, which is what N's text_tokenize pads
+    to) with no mask, and it is walked with lora.T5_TARGET_REPLACE under the config's training_method (`t5attn`).
   * --peft_type defaults to lora (the reference: dora); dora is refused: the text tower's engine takes plain LoRA sites.
   * The reference hard-codes `attributes = []` (N:270), so its stabilise term is always 0; the term and --attributes are left out.
   * --negative takes words like --positive (the reference declares it a plain string and then joins its CHARACTERS with
@@ -35,16 +43,23 @@ from pathlib import Path
 import torch
 
 from . import config_util, model_util
-from .lora import CLIP_TARGET_REPLACE, LoRANetwork
+from .lora import CLIP_TARGET_REPLACE, T5_TARGET_REPLACE, LoRANetwork
 from .notrigger import TextEncoderStep, notrigger_loss
 
 WARMUP_STEPS, COSINE_STEPS, SPLIT = 100, 900, 20  # N:216-217, 291
 XL_MODELS, SD1_MODELS = ("SDXL", "PonyXL"), ("SD1", "SD1.5", "SD1.x")
 REFUSED_MODELS = ("FLUX.1", "SD3-Medium", "SD3", "Cascade")
+T5_TOWERS = {("FLUX.1", 1): "lora_te2", ("SD3-Medium", 2): "lora_te3"}  # (model, clip_index) -> file prefix (N:185; te3: see above)
 
 
 def check_args(model: str, clip_index: int, peft_type: str):
     """The refusals, before anything is loaded."""
+    if (model, clip_index) in T5_TOWERS:  # the T5 tower of FLUX.1 / SD3-Medium
+        if peft_type == "dora":
+            raise ValueError("--peft_type dora: the text tower's engine takes plain LoRA sites only; use lora")
+        if peft_type != "lora":
+            raise ValueError(f"--peft_type {peft_type}: expected lora")
+        return
     if model in REFUSED_MODELS or model.upper().startswith(("FLUX", "SD3")):
         raise ValueError(f"--model {model}: FLUX.1 / SD3 text towers (CLIP-G pair + T5) are not built here; SDXL, PonyXL or SD1")
     if model not in XL_MODELS + SD1_MODELS:
@@ -80,6 +95,26 @@ def synthetic_towers(kind: str):
         raise ValueError(f"unknown synthetic model 'synthetic://{kind}': sdxl | tiny_sdxl | sd1x | tiny_sd1x")
     toks = [model_util.SyntheticClipTokenizer(e.config.vocab_size, e.config.eos_token_id) for e in encs]
     return toks, encs
+
+
+def load_t5_tower(name: str, model: str):
+    """(tokenizer, t5.T5EncoderModel) of the model's T5 tower on the HIP engine: model_util's native loaders on
+    `synthetic://tiny_flux | flux_schnell | flux_dev` / `synthetic://tiny_sd3 | sd3`, or a local diffusers directory."""
+    if model == "FLUX.1":
+        _toks, encs, _net, _sched = model_util.load_models_flux(name, torch.bfloat16, t5_backend="native")
+        tower = encs[1]
+    else:
+        _toks, encs, _net, _sched = model_util.load_models_sd3(name, torch.bfloat16, t5_backend="native")
+        tower = encs[2] if len(encs) > 2 else None
+    if tower is None:
+        raise ValueError(f"{name}: no T5 tower (text_encoder_{2 if model == 'FLUX.1' else 3}) to train on")
+    return tower.tokenizer, tower.model
+
+
+def tokenize_t5(tokenizer, prompt: str, t5_tokens: int) -> torch.Tensor:
+    """N:249 text_tokenize on the T5 tokenizer: padded to `t5_tokens` with the pad token, no mask."""
+    return torch.as_tensor(tokenizer([prompt], padding="max_length", max_length=t5_tokens, truncation=True,
+                                     return_tensors="pt").input_ids)[:, :t5_tokens]
 
 
 def load_towers(name: str):
@@ -151,8 +186,9 @@ def train_loop(step: TextEncoderStep, neu_ids, pos_ids, neg_ids, lr: float, iter
 
 def train(config, device, positive=None, negative=None, clip_index: int = 0, peft_type: str = "lora", rank: int = 4,
           model: str = "SDXL", chosen_layer: int = -1, save_file: bool = True, on_step_complete=None, towers=None,
-          lr_schedule: str = "reference"):
+          lr_schedule: str = "reference", t5_tokens: int = 512):
     check_args(model, clip_index, peft_type)
+    t5 = (model, clip_index) in T5_TOWERS
     positive = ", ".join(positive) if positive else None  # N:244-247
     negative = ", ".join(negative) if negative else None
     if not positive and not negative:
@@ -161,20 +197,30 @@ def train(config, device, positive=None, negative=None, clip_index: int = 0, pef
     save_dtype = config_util.parse_precision(config.save.precision)
     if weight_dtype not in (torch.float16, torch.bfloat16):
         raise ValueError(f"train.precision {config.train.precision}: the text tower's engine runs in float16 or bfloat16")
-    tokenizers, encoders = towers if towers is not None else load_towers(config.pretrained_model.name_or_path)
-    if clip_index >= len(encoders):
-        raise ValueError(f"--clip_index {clip_index}: the model has {len(encoders)} CLIP tower(s)")
-    tok, enc = tokenizers[clip_index], encoders[clip_index]
+    if t5 and weight_dtype != torch.bfloat16:
+        raise ValueError(f"train.precision {config.train.precision}: the T5 tower runs in bfloat16 only (its activations overflow float16)")
+    if t5 and t5_tokens < 1:
+        raise ValueError(f"--t5_tokens {t5_tokens}: at least 1")
+    if t5:  # towers (tests): the (tokenizer, t5.T5EncoderModel) pair itself
+        tok, enc = towers if towers is not None else load_t5_tower(config.pretrained_model.name_or_path, model)
+    else:
+        tokenizers, encoders = towers if towers is not None else load_towers(config.pretrained_model.name_or_path)
+        if clip_index >= len(encoders):
+            raise ValueError(f"--clip_index {clip_index}: the model has {len(encoders)} CLIP tower(s)")
+        tok, enc = tokenizers[clip_index], encoders[clip_index]
     enc.to(device, dtype=weight_dtype)
     enc.requires_grad_(False)
     enc.eval()
-    prefix = ["lora_te1", "lora_te2"][clip_index]  # N:185
+    prefix = T5_TOWERS[(model, clip_index)] if t5 else ["lora_te1", "lora_te2"][clip_index]  # N:185
     network = LoRANetwork(enc, rank=rank, multiplier=1.0, delimiter="_", alpha=config.network.alpha,
-                          target_replace=CLIP_TARGET_REPLACE, prefix=prefix,
+                          target_replace=T5_TARGET_REPLACE if t5 else CLIP_TARGET_REPLACE, prefix=prefix,
                           train_method=config.network.training_method).to(device)
     network.requires_grad_(True)
+    if not network.unet_loras:
+        raise ValueError(f"network.training_method {config.network.training_method}: no LoRA site on this tower"
+                         + (" (a T5 tower takes t5attn or full)" if t5 else ""))
     step = TextEncoderStep(enc, network, chosen_layer)
-    ids = lambda p: tokenize(tok, enc, p).to(device)
+    ids = (lambda p: tokenize_t5(tok, p, t5_tokens).to(device)) if t5 else (lambda p: tokenize(tok, enc, p).to(device))
     save_path = Path(config.save.path)
 
     def log(i, rec):
@@ -204,8 +250,9 @@ def build_parser():
     p.add_argument("--peft_type", type=str, default="lora", help="lora (dora is refused)")
     p.add_argument("--positive", type=str, nargs="+", default=None, help="positive term(s)")
     p.add_argument("--negative", type=str, nargs="+", default=None, help="negative term(s)")
-    p.add_argument("--model", type=str, default="SDXL", help="SDXL, PonyXL or SD1")
+    p.add_argument("--model", type=str, default="SDXL", help="SDXL, PonyXL, SD1; FLUX.1 (--clip_index 1) or SD3-Medium (--clip_index 2): the T5 tower")
     p.add_argument("--clip_index", type=int, required=True, help="0 based clip index (sdxl has two)")
+    p.add_argument("--t5_tokens", type=int, default=512, help="length a T5 tower's prompts are padded to")
     p.add_argument("--chosen_layer", type=int, default=-1, choices=(-1, -2), help="hidden_states index trained on")
     return p
 
@@ -223,7 +270,8 @@ def main(args, towers=None):
     config.save.path += f"/{config.save.name}"
     device = torch.device(f"cuda:{args.device}")
     return train(config, device, positive=args.positive, negative=args.negative, clip_index=args.clip_index,
-                 peft_type=args.peft_type, rank=args.rank, model=args.model, chosen_layer=args.chosen_layer, towers=towers)
+                 peft_type=args.peft_type, rank=args.rank, model=args.model, chosen_layer=args.chosen_layer, towers=towers,
+                 t5_tokens=args.t5_tokens)
 
 
 if __name__ == "__main__":

@@ -122,13 +122,16 @@ def diffusion_sd3(transformer, scheduler, latents, text_embeddings, add_text_emb
 
 @torch.no_grad()
 def slider_sweep_latents_sd3(transformer, network, scheduler, latents, text_embeddings, add_text_embeddings, scale: float,
-                             start_noise: float, guidance_scale: float):
+                             start_noise: float, guidance_scale: float, adapted_embeddings=None):
     """diffusion_sd3 over the whole schedule with the slider off while t > start_noise (on the 1000 sigma axis) and at
-    `scale` below it."""
+    `scale` below it.  adapted_embeddings: the context under a text-tower LoRA at `scale` (generate_images' T5 sweep): it
+    replaces text_embeddings on the same steps on which the slider is on, as slider_sweep_latents does for SD-XL."""
     for timestep in scheduler.timesteps:
-        on = network is not None and float(timestep) <= start_noise
+        below = float(timestep) <= start_noise
+        on = network is not None and below
         m = [float(scale) if on else 0.0] * (2 * latents.shape[0]) if network is not None else None
-        latents = predict_noise_sd3(transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+        emb = adapted_embeddings if (adapted_embeddings is not None and below) else text_embeddings
+        latents = predict_noise_sd3(transformer, scheduler, timestep, latents, emb, add_text_embeddings,
                                     guidance_scale=guidance_scale, multipliers=m)
     return latents
 
@@ -204,13 +207,16 @@ def diffusion_flux(pipeline, transformer, scheduler, latents, text_embeddings, a
 
 @torch.no_grad()
 def slider_sweep_latents_flux(transformer, network, scheduler, latents, text_embeddings, add_text_embeddings, scale: float,
-                              start_noise: float, guidance_scale: float, num_inference_steps: int):
-    """diffusion_flux over the whole schedule with the slider off while 1000 sigma > start_noise and at `scale` below it."""
+                              start_noise: float, guidance_scale: float, num_inference_steps: int, adapted_embeddings=None):
+    """diffusion_flux over the whole schedule with the slider off while 1000 sigma > start_noise and at `scale` below it.
+    adapted_embeddings: as in slider_sweep_latents_sd3."""
     set_timesteps_flux(scheduler, num_inference_steps, latents)
     for timestep in scheduler.timesteps:
-        on = network is not None and float(timestep) <= start_noise
+        below = float(timestep) <= start_noise
+        on = network is not None and below
         m = [float(scale) if on else 0.0] * latents.shape[0] if network is not None else None
-        latents = predict_noise_flux(None, transformer, scheduler, timestep, latents, text_embeddings, add_text_embeddings,
+        emb = adapted_embeddings if (adapted_embeddings is not None and below) else text_embeddings
+        latents = predict_noise_flux(None, transformer, scheduler, timestep, latents, emb, add_text_embeddings,
                                      guidance_scale=guidance_scale, multipliers=m)
     return latents
 
