@@ -758,6 +758,18 @@ int smi_op_gemm_epilogue(int dtype, const void* A, const void* W, void* C, int M
                          const void* bias, const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec,
                          const float* lora_xa, int ld_xa, const float* lora_up, int lora_r, int lora_seg, int lora_row0,
                          float lora_scale, int lora_dx, int tile_code, int ksplit, int* ran_code, void* stream);
+/* A 3x3 implicit-GEMM conv of any gather mode on a NAMED tile (tests/test_conv_gather_gpu.py): the arguments of
+ * smi_op_conv3x3, plus pad (1, or 0 for the (0, 1, 0, 1)-padded stride-2 down-sampler on an even map), the fp32 output
+ * form, res [nb hout wout, cout], rowvec [nb hout wout / rows_per_vec, ld_rowvec] (the engine's per-sample vector has
+ * rows_per_vec = hout wout) and the forward delta: xa [nb hout wout - lora_row0, ld_xa] fp32 against up [cout, lora_r].
+ * Any of bias / res / rowvec / lora_xa may be NULL.  tile_code, ksplit and *ran_code as in smi_op_gemm_epilogue.  The
+ * output grid must be the one the input grid and the mode give (transposed: `in` is dy on the forward's output grid,
+ * `out` is dx on its input grid); the conv geometry checks of the ordinary launch hold for a named tile too. */
+int smi_op_conv3x3_ex(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin, int win,
+                      int cin, int cout, int stride, int upsample, int transposed, int hout, int wout, int pad, int out_f32,
+                      const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec, const float* lora_xa, int ld_xa,
+                      const float* lora_up, int lora_r, int lora_row0, float lora_scale, int tile_code, int ksplit,
+                      int* ran_code, void* stream);
 int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin,
                    int win, int cin, int cout, int stride, int upsample, int transposed, int hout, int wout,
                    void* stream);

@@ -280,6 +280,9 @@ _SIGS = {
                              [C.c_float] + [C.c_int] * 3 + [C.POINTER(C.c_int), C.c_void_p]),
     "smi_op_conv3x3": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 10 +
                        [C.c_void_p]),
+    "smi_op_conv3x3_ex": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int] * 12 +
+                          [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                           C.c_float, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_void_p]),
     "smi_op_upconv_phase": (C.c_int, [C.c_int] + [C.c_void_p] * 6 + [C.c_int] * 6 + [C.POINTER(C.c_int), C.c_void_p]),
     "smi_set_upconv_phase": (C.c_int, [C.c_int]),
     "smi_op_attention_fwd": (C.c_int, [C.c_int] + [C.c_void_p] * 5 + [C.c_int] * 5 + [C.c_float, C.c_void_p]),

@@ -709,15 +709,23 @@ void set_gemm_scratch(void* ws, size_t bytes) {
   t_scratch_bytes = ws ? bytes : 0;
 }
 
-int launch_gemm(const GemmParams& p, hipStream_t stream) {
+namespace {
+// the shape and conv-geometry checks of every launch, whoever picks the tile (launch_gemm and launch_gemm_on_tile)
+int check_launch(const GemmParams& p) {
   SMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
-  SMI_CHECK(!p.geglu_out || gemm_geglu_supported(p), "gemm: fused GEGLU not available for this shape/layout");
   if (p.conv) {
     SMI_CHECK(p.K == p.tap_w * p.tap_w * p.Cin && p.M == p.Nb * p.Hout * p.Wout && (p.stride == 1 || p.stride == 2),
               "conv: inconsistent geometry");
     SMI_CHECK(p.tap_w == 3 || (p.tap_w == 2 && p.stride == 1 && !p.upsample && !p.transposed),
               "conv: a %d-wide tap grid (2 takes a plain stride-1 conv only)", p.tap_w);
   }
+  return 0;
+}
+}  // namespace
+
+int launch_gemm(const GemmParams& p, hipStream_t stream) {
+  if (int rc = check_launch(p)) return rc;
+  SMI_CHECK(!p.geglu_out || gemm_geglu_supported(p), "gemm: fused GEGLU not available for this shape/layout");
   // SMI_SPLITK_DEBUG (tools/bench_splitk.py): slice count and slice kernel (a tile code) of THIS call from SMI_SPLITK_S / _V
   static const bool splitk_debug = getenv("SMI_SPLITK_DEBUG") != nullptr;
   if (splitk_debug && gemm2_supported(p) && !p.geglu_out) {
@@ -760,7 +768,7 @@ int launch_gemm(const GemmParams& p, hipStream_t stream) {
 
 // Test entry: one named tile (or a forced split-K on it), in-process, and which tile really ran.
 int launch_gemm_on_tile(const GemmParams& p, int tile_code, int ksplit, int* ran_code, hipStream_t stream) {
-  SMI_CHECK(p.M > 0 && p.N > 0 && p.K > 0, "gemm: bad shape M=%d N=%d K=%d", p.M, p.N, p.K);
+  if (int rc = check_launch(p)) return rc;
   if (ran_code) *ran_code = 0;
   if (tile_code == 0 && ksplit <= 1) return launch_gemm(p, stream);
   GemmTile tile = tile_of_code(tile_code);

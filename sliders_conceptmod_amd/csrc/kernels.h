@@ -195,7 +195,7 @@ bool gemm4_supported(const GemmParams& p);
 int launch_gemm3(const GemmParams& p, hipStream_t stream);
 int launch_gemm4(const GemmParams& p, hipStream_t stream);
 int launch_v1(const GemmParams& p, hipStream_t stream);  // register-staged kernel: operands gemm2 cannot take, SMI_GEMM=v1
-// Test entry (smi_op_gemm_epilogue): launch p on the tile with tuner code `tile_code` (0: launch_gemm's own choice) where
+// Test entry (smi_op_gemm_epilogue, smi_op_conv3x3_ex): launch p on the tile with tuner code `tile_code` (0: launch_gemm's own choice) where
 // that tile can take it, else on what fit_tile puts in its place; ksplit > 1: split-K in that many slices with the tile as
 // the slice kernel.  *ran_code receives the code of the tile that actually ran (0 for launch_gemm's own choice).
 int launch_gemm_on_tile(const GemmParams& p, int tile_code, int ksplit, int* ran_code, hipStream_t stream);

@@ -112,6 +112,45 @@ int smi_op_conv3x3(int dtype, const void* in, const void* w_packed, const void* 
                          .with_bias(bias),
                      (hipStream_t)stream);
 }
+// a 3x3 conv of any gather mode with every epilogue term on a NAMED tile (see include/smi.h); the geometry checks of
+// launch_gemm hold on the named-tile path too (launch_gemm_on_tile)
+int smi_op_conv3x3_ex(int dtype, const void* in, const void* w_packed, const void* bias, void* out, int nb, int hin, int win,
+                      int cin, int cout, int stride, int upsample, int transposed, int hout, int wout, int pad, int out_f32,
+                      const void* res, const void* rowvec, int rows_per_vec, int ld_rowvec, const float* lora_xa, int ld_xa,
+                      const float* lora_up, int lora_r, int lora_row0, float lora_scale, int tile_code, int ksplit,
+                      int* ran_code, void* stream) {
+  if (ran_code) *ran_code = 0;
+  if (!in || !w_packed || !out || nb <= 0 || hin <= 0 || win <= 0 || cin <= 0 || cout <= 0 || hout <= 0 || wout <= 0) {
+    set_error("smi_op_conv3x3_ex: bad arguments");
+    return -1;
+  }
+  SMI_CHECK((int64_t)nb * hout * wout < (1ll << 31) && (int64_t)nb * hin * win < (1ll << 31),
+            "smi_op_conv3x3_ex: more than 2^31 pixels");
+  SMI_CHECK(pad == 0 || pad == 1, "smi_op_conv3x3_ex: pad=%d (0 or 1)", pad);
+  SMI_CHECK(!upsample || (stride == 1 && pad == 1 && !transposed), "smi_op_conv3x3_ex: upsample takes stride 1, pad 1, forward");
+  SMI_CHECK(!transposed || pad == 1, "smi_op_conv3x3_ex: the transposed gather is the gradient of a pad-1 conv");
+  if (stride == 1 || stride == 2) {  // (any other stride: launch_gemm_on_tile's geometry check refuses it)
+    // forward: the output grid follows from the input's (pad 0: the (0, 1, 0, 1)-padded down-sampler, even maps);
+    // transposed: `in` is dy on the forward's OUTPUT grid, `out` is dx on its input grid
+    const int mode = stride == 2 ? 1 : (upsample ? 2 : 0);
+    const bool ok = transposed ? (hin == conv3x3_out(hout, mode) && win == conv3x3_out(wout, mode))
+                               : (hout == conv3x3_out(hin, mode) && wout == conv3x3_out(win, mode));
+    SMI_CHECK(ok, "smi_op_conv3x3_ex: inconsistent geometry: %d x %d -> %d x %d (stride %d, upsample %d, transposed %d)", hin,
+              win, hout, wout, stride, upsample, transposed);
+    SMI_CHECK(pad == 1 || (stride == 2 && hin % 2 == 0 && win % 2 == 0),
+              "smi_op_conv3x3_ex: pad 0 is the stride-2 down-sampler on an even map (%d x %d, stride %d)", hin, win, stride);
+  }
+  SMI_CHECK(!rowvec || rows_per_vec >= 1, "smi_op_conv3x3_ex: rows_per_vec=%d", rows_per_vec);
+  SMI_CHECK(!lora_xa || (lora_up && lora_r >= 1 && ld_xa >= lora_r && lora_row0 >= 0 && lora_row0 < nb * hout * wout),
+            "smi_op_conv3x3_ex: delta: r=%d ld_xa=%d row0=%d", lora_r, ld_xa, lora_row0);
+  GemmParams p = conv3x3_geom(dtype, in, w_packed, out, nb, hin, win, cin, cout, hout, wout, stride, pad, upsample, transposed)
+                     .with_bias(bias)
+                     .with_res(res, cout);
+  if (out_f32) p.f32_out();
+  if (rowvec) p.with_rowvec(rowvec, rows_per_vec, ld_rowvec);
+  if (lora_xa) p.with_lora(lora_xa, ld_xa, lora_up, lora_r, 0, lora_scale, lora_row0);
+  return launch_gemm_on_tile(p, tile_code, ksplit, ran_code, (hipStream_t)stream);
+}
 // nearest-2x + 3x3 / pad 1 as the engine's phase form: pack, four 2x2 phase convs, un-shuffle (see include/smi.h)
 int smi_op_upconv_phase(int dtype, const void* in, const void* w, const void* bias, void* wph, void* planes, void* out, int nb,
                         int h, int w_, int cin, int cout, int tile_code, int* ran_code, void* stream) {
